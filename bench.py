@@ -10,6 +10,15 @@ A step = one pass of the hot path over one batch of 64 synthetic crops per GPU (
 with N > 1 every step's per-frame SMPL-parameter record is all-gathered over RCCL on a side stream.
 Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the K steps once and prints the headline (`value`, `ms_per_step`).  Everything
+else the line can carry (repeated regions, lanes overlap, the one-batch rate, the conv / SMPL rooflines, other_configs,
+the CPU baseline, the N>1 gather check and per-step comm times) is measured only with --full:
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+--dump-outputs DIR writes what the last timed step computed (every array pipeline.FramePipeline returns, float32, or
+float64 where the path computes in double) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+
     configs[3]'s per-GPU workload (2048 frames on 8 GPUs = 256 per GPU):  ... bench.py --gpus N --batch 256 --lanes 2
     configs[2] (bf16 encoder):                                            python bench.py --precision bf16 --batch 256 --lanes 2
 """
@@ -123,6 +132,28 @@ def measure_other_config(precision, B, lanes, steps, warmup, dev, sd, sm, info, 
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """The arrays a caller of the timed path receives from its last step (FramePipeline's dict, fenced), one
+    DIR/<name>.npy each: float64 stays float64, everything else (float32 results, int32 scores and status) is written as
+    float32, exactly.  Above DUMP_LIMIT_BYTES in all, every array keeps the same seeded, sorted sample of frames."""
+    arrays = {}
+    for name, t in sorted(out.items()):
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frames = len(next(iter(arrays.values())))
+        keep = max(1, frames * DUMP_LIMIT_BYTES // total)
+        idx = np.sort(np.random.default_rng(0).choice(frames, size=keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -131,8 +162,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step")
-    ap.add_argument("--cpu-frames", type=int, default=1024, help="frames in the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (the options marked [--full] below); "
+                         "a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--cpu-frames", type=int, default=1024, help="[--full] frames in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="[--full] skip the conv and SMPL roofline passes")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal of the N>1 path)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
     ap.add_argument("--streams", type=int, default=0, help="encoder sub-batch streams inside one batch (0 = library default 1)")
@@ -140,22 +176,24 @@ def main():
                     help="encoder precision: fp32 = configs[1] (headline), bf16 = configs[2] (use --batch 256)")
     ap.add_argument("--lanes", type=int, default=3, help="whole batches in flight on separate HIP streams")
     ap.add_argument("--check-gather", dest="check_gather", action="store_true", default=None,
-                    help="N>1 (default ON there): after the timed steps, check on every rank that the gathered tensor holds "
+                    help="[--full] N>1 (default ON there): after the timed steps, check on every rank that the gathered tensor holds "
                          "each rank's own last record (second route: all_gather_object of host copies) -> gather_verified")
     ap.add_argument("--no-check-gather", dest="check_gather", action="store_false")
     ap.add_argument("--graph", action="store_true",
                     help="every lane replays its batch from a hipGraph (one host call per batch instead of ~90 launches): the "
                          "per-rank host budget when eight ranks share one host; same bits")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false", default=True,
-                    help="skip the two extra configurations measured behind the headline in the same process "
+                    help="[--full] skip the two extra configurations measured behind the headline in the same process "
                          "(configs[2]: bf16 encoder, B=256; configs[3]'s per-GPU slice: fp32, B=256) -> `other_configs`")
     ap.add_argument("--force-exchange", action="store_true",
                     help="one rank only: initialise the process group anyway (RCCL with world size 1) and run the per-step "
                          "record exchange as the N>1 path does -- comm stream, ring of records, all_gather_into_tensor, "
                          "release_after -- so that the RCCL branch executes on a single MI355X (comm_ms_per_step, gather_verified)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="K-step regions timed in all (the first is `value`; all of them give value_spread)")
+                    help="[--full] K-step regions timed in all (the first is `value`; all of them give value_spread)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.check_gather is None:
         args.check_gather = int(os.environ.get("WORLD_SIZE", "1")) > 1
@@ -230,35 +268,40 @@ def main():
         step()
     fence()
     def timed_region(timed_comm=False):
-        """EXACTLY K steps between fences; returns (max over ranks, every rank's own seconds)."""
+        """EXACTLY K steps between fences; returns (max over ranks, every rank's own seconds, the last step's outputs)."""
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step(timed=timed_comm)
+            out = step(timed=timed_comm)
         fence()
         mine = time.perf_counter() - t0
         if world == 1:
-            return mine, [mine]
+            return mine, [mine], out
         t = torch.zeros(world, dtype=torch.float64, device=dev)
         t[rank] = mine
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         per_rank = [float(v) for v in t.cpu()]
-        return max(per_rank), per_rank
+        return max(per_rank), per_rank, out
 
-    elapsed, per_rank_s = timed_region(timed_comm=True)      # THE measurement: `value`, `ms_per_step`
+    # THE measurement: `value`, `ms_per_step` (with --full its comm-stream events ride along, N>1)
+    elapsed, per_rank_s, last_out = timed_region(timed_comm=args.full)
+    if args.dump_outputs and rank == 0:
+        # before any later step reuses the lane's buffers; fenced above
+        dump_outputs(args.dump_outputs, last_out)
+    del last_out
     comm_ms_per_step = None
     if dist_on and comm_events:
         torch.cuda.synchronize(dev)
         comm_ms_per_step = sum(a.elapsed_time(b) for a, b in comm_events) / len(comm_events)
     # the same region again: how much a K-step region moves from one repeat to the next (box noise, clocks)
     region_values = [args.steps * B * world / elapsed]
-    for _ in range(max(args.repeats, 1) - 1):
-        e, _unused = timed_region()
+    for _ in range(max(args.repeats, 1) - 1 if args.full else 0):
+        e, _unused, _out = timed_region()
         region_values.append(args.steps * B * world / e)
 
     # How the batches in flight overlap on the GPU, from HIP events on each lane's own stream (a kernel trace under
     # rocprofv3 cannot show it for the fp32 step: tracing ~90 short launches per batch makes the host the limit).
     lanes_overlap = None
-    if world == 1 and args.lanes > 1:
+    if args.full and world == 1 and args.lanes > 1:
         base = torch.cuda.Event(enable_timing=True)
         fence()
         base.record(torch.cuda.current_stream(dev))
@@ -289,7 +332,7 @@ def main():
                                  "a new one completes every ms_per_step"}
 
     gather_verified = None
-    if dist_on and args.check_gather:
+    if args.full and dist_on and args.check_gather:
         # one more step, fenced, then every rank's record by a second route; rows [r*B, (r+1)*B) must be rank r's
         last_out = step()
         fence()
@@ -307,7 +350,7 @@ def main():
     # Transparency: the same K steps with ONE batch in flight (each step waits for the previous one on the
     # same stream), so the gain from overlapping whole batches is visible next to `value`.
     serial_fps = None
-    if world == 1 and args.lanes > 1:
+    if args.full and world == 1 and args.lanes > 1:
         one = pl.FramePipeline(model, layer, info, with_verts=True, lanes=1)
         for _ in range(3):
             one(crops)
@@ -319,7 +362,7 @@ def main():
         serial_fps = args.steps * B / (time.perf_counter() - t1)
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # Same K steps again with every conv launch bracketed by hipEvents on the launch stream
         # (kept out of the timed region so the events do not perturb `value`; in this pass one batch
         # is in flight at a time so that each bracket times one kernel alone).
@@ -388,7 +431,7 @@ def main():
                     "batches_in_flight": 1,
                     "ms_per_step_same_mode": round(B / serial_fps * 1e3, 4) if serial_fps else round(elapsed / args.steps * 1e3, 4)}
     smpl_lbs = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # SURVEY.md 8d also asks for the SMPL forward's achieved HBM rate: flags + pose + skin kernels of one
         # batch (mesh + joints), timed with events on the stream they are launched on (torch's current one).
         def smpl_rate(lay, n):
@@ -432,7 +475,7 @@ def main():
             smpl_lbs["at_b256"] = smpl_roofline(us2, nb2, 256)
             del big
     other_configs = None
-    if rank == 0 and world == 1 and args.other_configs and args.precision == "fp32" and B == 64:
+    if args.full and rank == 0 and world == 1 and args.other_configs and args.precision == "fp32" and B == 64:
         # configs[2] and configs[3]'s per-GPU slice, driver-observed: same process, fresh handles (the headline's are
         # released first), the driver's own --steps / --warmup
         del pipe
@@ -445,7 +488,7 @@ def main():
                                  "configs[3]'s per-GPU slice: batch=256 (2048 frames over 8 GPUs), ResNet-50+SMPL fp32, 1 GPU"),
         ]
     dist_info = None
-    if dist_on:
+    if args.full and dist_on:
         # did the backend see N ranks on N devices?  answered by the record itself
         me = {"rank": rank, "device": str(dev), "device_name": torch.cuda.get_device_name(dev),
               "pci_bus_id": getattr(torch.cuda.get_device_properties(dev), "pci_bus_id", None)}
@@ -458,6 +501,7 @@ def main():
         dist_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                      "rccl_version (torch.cuda.nccl.version)": ver, "ranks": seen,
                      "distinct_devices": len({(d["device"], d["pci_bus_id"]) for d in seen})}
+    if dist_on:
         dist.barrier()
 
     if rank == 0:
@@ -482,18 +526,20 @@ def main():
         if args.precision != "fp32":
             line["conv_roofline_frames_per_s_per_gpu"] = round(PEAK_BF16_MFMA_TFLOPS * 1e3 / CONV_GFLOP_PER_FRAME, 1)
             line["frac_of_conv_roofline"] = round(value / world / line["conv_roofline_frames_per_s_per_gpu"], 4)
-        rv = sorted(region_values)
-        line["value_spread"] = {"regions": len(rv), "min": round(rv[0], 1), "median": round(rv[len(rv) // 2], 1),
-                                "max": round(rv[-1], 1),
-                                "note": "frames/s of each timed K-step region; `value` is the first one"}
+        if args.full:
+            rv = sorted(region_values)
+            line["value_spread"] = {"regions": len(rv), "min": round(rv[0], 1), "median": round(rv[len(rv) // 2], 1),
+                                    "max": round(rv[-1], 1),
+                                    "note": "frames/s of each timed K-step region; `value` is the first one"}
         if dist_on:
             ms_rank = [t / args.steps * 1e3 for t in per_rank_s]
             line["per_rank_ms_per_step"] = {"min": round(min(ms_rank), 4), "max": round(max(ms_rank), 4),
                                             "all": [round(v, 4) for v in ms_rank]}
-            line["comm_ms_per_step"] = None if comm_ms_per_step is None else round(comm_ms_per_step, 4)
-            line["comm_note"] = ("events on rank 0's side stream around pack + all_gather_into_tensor of one step "
-                                 "(overlaps the next batch; not on the critical path unless it exceeds ms_per_step)")
-            line["dist"] = dist_info
+            if args.full:
+                line["comm_ms_per_step"] = None if comm_ms_per_step is None else round(comm_ms_per_step, 4)
+                line["comm_note"] = ("events on rank 0's side stream around pack + all_gather_into_tensor of one step "
+                                     "(overlaps the next batch; not on the critical path unless it exceeds ms_per_step)")
+                line["dist"] = dist_info
         if gather_verified is not None:
             line["gather_verified"] = gather_verified
         if serial_fps is not None:
@@ -509,7 +555,7 @@ def main():
         from poserisk_release_amd import _lib
         line["library"] = {"path": os.path.relpath(_lib.LIB_PATH, REPO), "build": _lib.load().pr_build_info().decode(),
                            "abi": _lib.load().pr_abi_version()}
-        if world == 1 and args.cpu_frames > 0:
+        if args.full and world == 1 and args.cpu_frames > 0:
             line["cpu_baseline"] = cpu_baseline(sd, sm, info, args.cpu_frames)
         print(json.dumps(line), flush=True)
     if dist_on:

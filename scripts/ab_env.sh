@@ -4,12 +4,13 @@
 # each argument is one configuration (space-separated VAR=value pairs, "" = defaults); the list is run twice, in order.
 set -eo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
+BENCH_OUT=${BENCH_OUT:-bench_out}; export BENCH_OUT; mkdir -p "$BENCH_OUT"
 for round in 1 2; do
   for cfg in "$@"; do
-    env $cfg timeout -k 10 200 python3 bench.py --precision bf16 --batch 256 --lanes 2 --cpu-frames 0 --no-roofline --steps 30 --repeats 3 > gpurun_out/ab_env.json
+    env $cfg timeout -k 10 200 python3 bench.py --full --precision bf16 --batch 256 --lanes 2 --cpu-frames 0 --no-roofline --steps 30 --repeats 3 > "$BENCH_OUT/ab_env.json"
     python3 - "$cfg" <<'PY'
-import json, sys
-d = json.loads(open("gpurun_out/ab_env.json").read().strip().splitlines()[-1])
+import json, os, sys
+d = json.loads(open(os.path.join(os.environ["BENCH_OUT"], "ab_env.json")).read().strip().splitlines()[-1])
 s = d["value_spread"]
 print(f"[{sys.argv[1]:40s}] {d['value']:9.1f} frames/s  ({s['min']:.0f} - {s['max']:.0f})")
 PY

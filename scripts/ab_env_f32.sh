@@ -5,13 +5,13 @@
 # BATCH / LANES / EXTRA in the environment change the workload (defaults 64 / 3 / "").
 set -eo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+BENCH_OUT=${BENCH_OUT:-bench_out}; export BENCH_OUT; mkdir -p "$BENCH_OUT"
 for round in 1 2; do
   for cfg in "$@"; do
-    env $cfg timeout -k 10 200 python3 bench.py --batch ${BATCH:-64} --lanes ${LANES:-3} --cpu-frames 0 --steps 30 --repeats 3 $EXTRA > gpurun_out/ab_env.json
+    env $cfg timeout -k 10 200 python3 bench.py --batch ${BATCH:-64} --lanes ${LANES:-3} --cpu-frames 0 --steps 30 --repeats 3 --full $EXTRA > "$BENCH_OUT/ab_env.json"
     python3 - "$cfg" <<'PY'
-import json, sys
-d = json.loads(open("gpurun_out/ab_env.json").read().strip().splitlines()[-1])
+import json, os, sys
+d = json.loads(open(os.path.join(os.environ["BENCH_OUT"], "ab_env.json")).read().strip().splitlines()[-1])
 s = d["value_spread"]
 r = d.get("roofline") or {}
 print(f"[{sys.argv[1]:44s}] {d['value']:9.1f} frames/s ({s['min']:.0f} - {s['max']:.0f})  one batch {d.get('frames_per_s_one_batch_in_flight', 0):9.1f}"

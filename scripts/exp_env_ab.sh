@@ -5,7 +5,7 @@ set -eo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out
 SW="$1"; shift || true
-ARGS="--steps 100 --warmup 10 --no-other-configs --cpu-frames 0 --repeats 3 $*"
+ARGS="--full --steps 100 --warmup 10 --no-other-configs --cpu-frames 0 --repeats 3 $*"
 show() { python3 - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d.get("roofline") or {}

@@ -4,7 +4,7 @@
 set -eo pipefail
 cd "${GRAFT_REPO_ROOT:-.}"
 mkdir -p gpurun_out
-ARGS="--precision bf16 --batch 256 --lanes 2 --steps 60 --warmup 10 --no-other-configs --cpu-frames 0 --repeats 3"
+ARGS="--full --precision bf16 --batch 256 --lanes 2 --steps 60 --warmup 10 --no-other-configs --cpu-frames 0 --repeats 3"
 show() { python3 - "$1" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]

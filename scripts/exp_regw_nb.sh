@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 run() {
   echo "== $*"
-  env "$@" python3 bench.py --no-other-configs --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --no-other-configs --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -8,7 +8,7 @@ for v in "2 1 2 1" "1 2 2 1" "2 1 1 2" "2 1 2 2" "1 2 1 2"; do
 done
 run() {
   echo "== $*"
-  env "$@" python3 bench.py --no-other-configs --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --no-other-configs --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

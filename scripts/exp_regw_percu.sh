@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 run() {
   echo "== $*"
   L=$1; shift
-  env "$@" python3 bench.py --lanes $L --no-other-configs --no-roofline --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
+  env "$@" python3 bench.py --full --lanes $L --no-other-configs --no-roofline --cpu-frames 0 --steps 100 --warmup 10 --repeats 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value', d['value'], 'spread', d['value_spread']['min'], d['value_spread']['max'], 'one-lane', d.get('frames_per_s_one_batch_in_flight'))"

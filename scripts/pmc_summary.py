@@ -106,7 +106,7 @@ for f in glob.glob(os.path.join(root, f"{tag}_ktrace_lanes_{SFX}", "**", "*kerne
     for r in csv.DictReader(open(f)):
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", r.get("Stream_Id", "?"))))
     ev.sort()
-    # the timed region of `bench.py --warmup 5 --steps 30 --repeats 1`: from the 6th to the 36th layout-change launch
+    # the timed region of `bench.py --full --warmup 5 --steps 30 --repeats 1`: from the 6th to the 36th layout-change launch
     # (one per step, the first kernel of a step); what follows in the trace is bench.py's one-batch-in-flight pass
     firsts = [e for e in ev if "nchw3_to" in e[2]]
     t_lo = firsts[5][0] if len(firsts) > 35 else ev[0][0]
@@ -177,7 +177,7 @@ for cdir in ("FETCH_SIZE", "WRITE_SIZE"):
             pkn[short(r["Kernel_Name"])][r["Counter_Name"]].add(r["Dispatch_Id"])
 out = {
     "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, scripts/profile_round.sh) on "
-              f"`bench.py --lanes 1 --steps 4 --warmup 2` (all its timed regions), B={BATCH} {mode}",
+              f"`bench.py --full --lanes 1 --steps 4 --warmup 2` (all its timed regions), B={BATCH} {mode}",
     "correction": "FETCH_SIZE x2 (gfx950 reports half of coalesced reads; calibrated with scripts/micro/t_traffic.hip: "
                   "1 GiB read by 16-B LDS-DMA and by dword loads both report 524 300 KiB), WRITE_SIZE x1 (1 GiB of dword "
                   "or dwordx4 stores reports 1 048 576 KiB); the counters sit on the L2's memory side, so Infinity-Cache "
@@ -274,7 +274,7 @@ lines = []
 for name in sorted(by, key=lambda n: -sum(d["ns"] for d in by[n])):
     b, c, t = ratio(by[name])
     lines.append(f"  {name:<58s} {len(by[name]) / msteps:6.2f} launches/step {t / msteps / 1e3:9.1f} us/step  busy {b / (c * 1024):.3f}")
-txt = (f"rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE on `bench.py --lanes 1 --steps 4 --warmup 2`, B={BATCH} {mode} "
+txt = (f"rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE on `bench.py --full --lanes 1 --steps 4 --warmup 2`, B={BATCH} {mode} "
        f"(kernels serialised by the counter collection); {msteps} steps\n"
        f"conv-family launches per step: {len(per) / msteps:g} = {len(gemm) / msteps:g} multiplying launches + "
        f"{(len(per) - len(gemm)) / msteps:g} Winograd transform passes; the library reports {want} "

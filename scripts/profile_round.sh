@@ -12,9 +12,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 export TMPDIR=/tmp
 if [ "$MODE" = bf16 ]; then
-  ARGS="--precision bf16 --batch 256"; LANES=2; SFX=b256_bf16
+  ARGS="--full --precision bf16 --batch 256"; LANES=2; SFX=b256_bf16
 else
-  ARGS=""; LANES=3; SFX=b64
+  ARGS="--full"; LANES=3; SFX=b64
 fi
 cd "$ROOT"
 timeout -k 10 400 python3 bench.py $ARGS --lanes $LANES > "$OUT/${TAG}_bench_${SFX}_default.json"

@@ -15,7 +15,23 @@ def pytest_configure(config):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """The arrays of tests/golden/<name>; an array stored in row chunks beside it (<stem>.<key>.<i>.npz, so that no
+    committed file exceeds 1 MiB) is joined back in chunk order."""
+    with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as z:
+        arrays = {k: z[k] for k in z.files}
+    stem = name[:-len(".npz")]
+    chunks = {}
+    for f in os.listdir(GOLDEN):
+        parts = f.split(".")
+        if len(parts) == 4 and parts[0] == stem and parts[3] == "npz" and parts[2].isdigit():
+            chunks.setdefault(parts[1], []).append((int(parts[2]), f))
+    for key, files in chunks.items():
+        pieces = []
+        for _, f in sorted(files):
+            with np.load(os.path.join(GOLDEN, f), allow_pickle=False) as z:
+                pieces.append(z[key])
+        arrays[key] = np.concatenate(pieces)
+    return arrays
 
 
 @pytest.fixture(scope="session")

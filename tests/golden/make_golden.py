@@ -202,7 +202,12 @@ def gen_scores():
     # action levels (reba.py:83-104, rula.py:100-118)
     out["reba_action"] = np.array([REBA().action_level(s)[0] or 0 for s in range(1, 16)], np.int32)
     out["rula_action"] = np.array([RULA().action_level(s)[0] or 0 for s in range(1, 10)], np.int32)
+    # every committed file stays under 1 MiB: the poses (3.5 MB of float64) go in row chunks beside scores.npz, which
+    # tests/conftest.py's golden() joins again
+    pose = out.pop("pose")
     np.savez_compressed(os.path.join(HERE, "scores.npz"), **out)
+    for i, s in enumerate(range(0, len(pose), 1500)):
+        np.savez_compressed(os.path.join(HERE, f"scores.pose.{i}.npz"), pose=pose[s:s + 1500])
 
 
 def _import_reference_core_base():

@@ -14,7 +14,7 @@ from conftest import REPO
 def _launch(extra, port, timeout=900, ranks=2):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-           "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--cpu-frames", "0", "--no-roofline"] + extra
+           "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--full", "--cpu-frames", "0", "--no-roofline"] + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     return subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
 
@@ -81,9 +81,9 @@ def test_bench_refuses_a_world_size_mismatch(gpu_device):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_carries_the_contract(gpu_device):
-    """The default (N = 1) run: one JSON line with the driver's fields, the `roofline` of the dominant kernel and the
+    """The --full (N = 1) run: one JSON line with the driver's fields, the `roofline` of the dominant kernel and the
     `cpu_baseline` of a bounded oracle sample (here 16 frames so that the test stays short)."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-frames", "16"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--cpu-frames", "16"],
                        cwd=REPO, capture_output=True, text=True, timeout=900,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -121,3 +121,33 @@ def test_bench_single_gpu_line_carries_the_contract(gpu_device):
     assert oc[0]["roofline"]["peak"] == 2500.0 and oc[1]["roofline"]["peak"] == 157.3
     assert line["library"]["build"] == "gfx950 release" and line["library"]["path"].endswith("libposerisk_hip.so")
     assert cpu["kind"] == "port" and cpu["unit"] == "frames/s" and cpu["cores"] >= 1 and cpu["value"] > 0 and "16 frames" in cpu["sample"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(gpu_device, tmp_path):
+    """A plain run: the headline fields and nothing that needs runs of its own; --dump-outputs writes every array the
+    timed path returns for its last step (float32, or float64 where the path computes in double), one file per name."""
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)],
+                       cwd=REPO, capture_output=True, text=True, timeout=600,
+                       env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in line, key
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert abs(line["value"] - 4 * 64 / (line["ms_per_step"] * 4 * 1e-3)) / line["value"] < 1e-3
+    for key in ("value_spread", "lanes_overlap", "frames_per_s_one_batch_in_flight", "roofline", "smpl_lbs",
+                "other_configs", "cpu_baseline"):
+        assert key not in line, key
+    import numpy as np
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    for name in ("rotmat", "betas", "cam", "axis_angle", "euler", "joint_cam", "verts", "reba", "rula", "status"):
+        assert name in got, name
+        assert got[name].shape[0] == 64 and np.isfinite(got[name]).all(), name
+    assert got["euler"].dtype == np.float64 and got["rotmat"].dtype == np.float32 and got["reba"].dtype == np.float32
+    assert got["rotmat"].shape == (64, 24, 3, 3) and got["verts"].shape == (64, 6890, 3)
+    assert (got["reba"] == np.round(got["reba"])).all() and (got["reba"][:, 0] >= 1).all()
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

@@ -49,7 +49,7 @@ def test_bench_force_exchange_runs_the_rccl_branch(gpu_device):
     with a barrier, the second-route gather check, the `dist` object) on one rank."""
     env = {k: v for k, v in os.environ.items() if k not in ENV_DROP}
     env["MASTER_PORT"] = str(29550 + os.getpid() % 100)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-exchange", "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-exchange", "--steps", "5", "--warmup", "2", "--full",
                         "--cpu-frames", "0", "--no-roofline", "--no-other-configs", "--repeats", "2"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
