@@ -149,6 +149,14 @@ int pr_hmr_num_conv_layers(void);
  * average pool = conv_launches + 2 * winograd_layers: scripts/pmc_summary.py refuses to summarise counter passes whose
  * dispatch count differs (round 4's summary silently missed a new kernel).  No reference counterpart (measurement). */
 int pr_hmr_plan_counts(pr_hmr_t* h, int B, int* conv_launches, int* winograd_layers);
+/* Encoder tap (ABI 11; a test entry): the encoder of pr_hmr_forward -- the same sub-batch split, streams, concurrency hint and
+ * kernel routing -- stopped after `block` and that block's output copied to act_dev, NHWC with the real channels in the
+ * handle's precision (fp32, or bf16 bits): block 0 = the stem + max-pool [B,56,56,64], 1..16 = the outputs of the 16
+ * Bottlenecks ([B,56,56,256] x3, [B,28,28,512] x4, [B,14,14,1024] x6, [B,7,7,2048] x3).  Asynchronous on `stream`;
+ * refused (PR_ERR_INVALID) while `stream` is being captured, and when B is outside 1..max_batch or block outside 0..16.
+ * tests/test_encoder_blocks.py checks every block of the production plan against an fp64 reference from this tap.
+ * No reference counterpart (testing). */
+int pr_hmr_encode_until(pr_hmr_t* h, const float* x_dev, int B, int block, void* act_dev, void* stream);
 /* The conv form this handle really runs (what PR_CONV_FORM_DEFAULT resolved to at create time: the built-in default,
  * or POSERISK_WINOGRAD's value): 0, 2, 4, 5 or three digits.  scripts/validate_checkpoint.py bases its exit status on it. */
 int pr_hmr_conv_form(pr_hmr_t* h);

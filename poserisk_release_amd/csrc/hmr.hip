@@ -161,12 +161,22 @@ struct ChunkRun {
   int b;
   float* xf_out;
   hipStream_t s;
+  void* tap = nullptr;   // encode_until: where this sub-batch's frames of the tapped block go
 };
+
+// Elements per frame of block k's output (pr_hmr_encode_until): the stem + max-pool, then layer1..layer4's blocks.
+size_t block_frame_elems(int k) {
+  if (k == 0) return (size_t)56 * 56 * 64;
+  const int L = k <= 3 ? 0 : k <= 7 ? 1 : k <= 13 ? 2 : 3, hw = 56 >> L;
+  return (size_t)hw * hw * (256 << L);
+}
 
 // Encoder over n sub-batches: layout change, 53 convs, max-pool, global average pool -> xf[b,2048].
 // Launches are issued layer by layer across the sub-batches so that all streams advance together
 // (issuing one whole sub-batch after another would stagger them by the host's enqueue time).
-int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n) {
+// stop_block >= 0 (pr_hmr_encode_until): after the plan entry that completes that block, each sub-batch's copy of it goes to
+// its run's `tap` and nothing further is launched.
+int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
   const bool bf = h->precision == 1;
   for (int i = 0; i < n; ++i) {
     if (h->stem_s2d) {
@@ -249,6 +259,13 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n) {
         if (bf) PR_TRY(launch_maxpool_bf16(h->act[r.chunk][1], h->act[r.chunk][2], r.b, 112, 112, 64, r.s));
         else PR_TRY(launch_maxpool(h->act[r.chunk][1], h->act[r.chunk][2], r.b, 112, 112, 64, r.s));
       }
+    }
+    if (stop_block >= 0 && ci == (size_t)h->block_last[stop_block]) {
+      const size_t frame_bytes = block_frame_elems(stop_block) * (bf ? 2 : 4);
+      for (int i = 0; i < n; ++i)
+        PR_HIP(hipMemcpyAsync(runs[i].tap, h->act[runs[i].chunk][h->block_buf[stop_block]], runs[i].b * frame_bytes,
+                              hipMemcpyDeviceToDevice, runs[i].s));
+      return PR_OK;
     }
   }
   for (int i = 0; i < n; ++i) {
@@ -343,6 +360,47 @@ int pr_hmr_set_streams(pr_hmr_t* h, int n_streams) {
   return pr::set_chunks(h, std::min(n_streams, h->max_batch));
 }
 
+}  // extern "C"
+
+namespace pr {
+namespace {
+// The encoder of pr_hmr_forward (stop_block < 0) or its early exit of pr_hmr_encode_until, on the same sub-batch split.
+int encode_batch(pr_hmr_t* h, const float* x_dev, int B, hipStream_t s, int stop_block, void* tap) {
+  // Profiling runs serially on the caller's stream so that each conv's event bracket is its own time.  The split is
+  // hmr_split_batch's (host_plan.cc), which pr_hmr_plan_counts walks too.
+  int sizes[4096];
+  bool concurrent = false;
+  const int nsub = hmr_split_batch(B, h->chunk_cap, h->n_chunks, h->profile != 0, sizes, 4096, &concurrent);
+  const size_t frame = (size_t)3 * kImg * kImg;
+  const size_t tap_frame = stop_block >= 0 ? block_frame_elems(stop_block) * (h->precision == 1 ? 2 : 4) : 0;
+  auto tap_at = [&](int b0) { return tap ? (void*)((char*)tap + (size_t)b0 * tap_frame) : nullptr; };
+  if (!concurrent) {
+    // one sub-batch at a time on the caller's stream (more than one pass if B exceeds a chunk's buffers)
+    for (int i = 0, b0 = 0; i < nsub; b0 += sizes[i], ++i) {
+      ChunkRun r{0, x_dev + b0 * frame, sizes[i], h->xf + (size_t)b0 * 2048, s, tap_at(b0)};
+      PR_TRY(encode_chunks(h, &r, 1, stop_block));
+    }
+  } else {
+    const int nch = nsub;
+    ChunkRun runs[pr_hmr::kMaxChunks];
+    PR_HIP(hipEventRecord(h->ev_fork, s));
+    for (int c = 0, b0 = 0; c < nch; b0 += sizes[c], ++c) {
+      runs[c] = ChunkRun{c, x_dev + b0 * frame, sizes[c], h->xf + (size_t)b0 * 2048, h->streams[c], tap_at(b0)};
+      PR_HIP(hipStreamWaitEvent(h->streams[c], h->ev_fork, 0));
+    }
+    PR_TRY(encode_chunks(h, runs, nch, stop_block));
+    for (int c = 0; c < nch; ++c) {
+      PR_HIP(hipEventRecord(h->ev_join[c], h->streams[c]));
+      PR_HIP(hipStreamWaitEvent(s, h->ev_join[c], 0));
+    }
+  }
+  return PR_OK;
+}
+}  // namespace
+}  // namespace pr
+
+extern "C" {
+
 int pr_hmr_forward(pr_hmr_t* h, const float* x_dev, int B, float* rotmat_dev, float* betas_dev,
                    float* cam_dev, float* xf_dev, float* pose6d_dev, void* stream) {
   using namespace pr;
@@ -355,32 +413,7 @@ int pr_hmr_forward(pr_hmr_t* h, const float* x_dev, int B, float* rotmat_dev, fl
   }
   if (B == 0) return PR_OK;
   hipStream_t s = (hipStream_t)stream;
-  // Profiling runs serially on the caller's stream so that each conv's event bracket is its own time.  The split is
-  // hmr_split_batch's (host_plan.cc), which pr_hmr_plan_counts walks too.
-  int sizes[4096];
-  bool concurrent = false;
-  const int nsub = hmr_split_batch(B, h->chunk_cap, h->n_chunks, h->profile != 0, sizes, 4096, &concurrent);
-  const size_t frame = (size_t)3 * kImg * kImg;
-  if (!concurrent) {
-    // one sub-batch at a time on the caller's stream (more than one pass if B exceeds a chunk's buffers)
-    for (int i = 0, b0 = 0; i < nsub; b0 += sizes[i], ++i) {
-      ChunkRun r{0, x_dev + b0 * frame, sizes[i], h->xf + (size_t)b0 * 2048, s};
-      PR_TRY(encode_chunks(h, &r, 1));
-    }
-  } else {
-    const int nch = nsub;
-    ChunkRun runs[pr_hmr::kMaxChunks];
-    PR_HIP(hipEventRecord(h->ev_fork, s));
-    for (int c = 0, b0 = 0; c < nch; b0 += sizes[c], ++c) {
-      runs[c] = ChunkRun{c, x_dev + b0 * frame, sizes[c], h->xf + (size_t)b0 * 2048, h->streams[c]};
-      PR_HIP(hipStreamWaitEvent(h->streams[c], h->ev_fork, 0));
-    }
-    PR_TRY(encode_chunks(h, runs, nch));
-    for (int c = 0; c < nch; ++c) {
-      PR_HIP(hipEventRecord(h->ev_join[c], h->streams[c]));
-      PR_HIP(hipStreamWaitEvent(s, h->ev_join[c], 0));
-    }
-  }
+  PR_TRY(encode_batch(h, x_dev, B, s, -1, nullptr));
   if (xf_dev) PR_HIP(hipMemcpyAsync(xf_dev, h->xf, (size_t)B * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (!rotmat_dev && !betas_dev && !cam_dev && !pose6d_dev) return PR_OK;
   // regressor: h_static = xf*W1x^T + b1 once; 3 x { h1 = state*W1s^T + h_static; h2 = h1*W2^T + b2;
@@ -394,6 +427,18 @@ int pr_hmr_forward(pr_hmr_t* h, const float* x_dev, int B, float* rotmat_dev, fl
   }
   PR_TRY(launch_regressor_finalize(h->state, rotmat_dev, betas_dev, cam_dev, pose6d_dev, B, s));
   return PR_OK;
+}
+
+int pr_hmr_encode_until(pr_hmr_t* h, const float* x_dev, int B, int block, void* act_dev, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(B >= 1, "pr_hmr_encode_until: batch %d out of range", B);
+  PR_REQUIRE(block >= 0 && block < HmrPlan::kBlocks, "pr_hmr_encode_until: block %d out of range 0..%d", block,
+             HmrPlan::kBlocks - 1);
+  PR_REQUIRE(h && x_dev && act_dev, "pr_hmr_encode_until: null argument");
+  PR_REQUIRE(B <= h->max_batch, "pr_hmr_encode_until: batch %d out of range 1..%d", B, h->max_batch);
+  hipStream_t s = (hipStream_t)stream;
+  PR_TRY(refuse_if_capturing(s, "pr_hmr_encode_until"));   // a test entry: never part of a captured forward
+  return encode_batch(h, x_dev, B, s, block, act_dev);
 }
 
 int pr_hmr_conv_form(pr_hmr_t* h) { return h ? h->conv_form : PR_ERR_INVALID; }

@@ -335,7 +335,9 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
     c1.macs_fixed = (double)(kImg / 2) * (kImg / 2) * 64 * 3 * 49;
   }
   PR_TRY(add_conv(cx, br, c1));
-  int cur = 2, H = 56, inpl = 64, layer = 1;
+  h->block_last[0] = 0;
+  h->block_buf[0] = 2;
+  int cur = 2, H = 56, inpl = 64, layer = 1, blk_no = 1;
   const int planes[4] = {64, 128, 256, 512}, blocks[4] = {3, 4, 6, 3};
   for (int L = 0; L < 4; ++L)
     for (int b = 0; b < blocks[L]; ++b) {
@@ -403,6 +405,8 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
         layer += first ? 3 : 2;  // conv1, conv2 (and the downsample branch) report no launch of their own
         blk.layer = layer++;
         h->convs.push_back(blk);
+        h->block_last[blk_no] = (int)h->convs.size() - 1;
+        h->block_buf[blk_no++] = outb;
         cur = outb;
         H = Ho;
         inpl = pl * 4;
@@ -494,11 +498,15 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
         PR_REQUIRE(h->convs.size() == h->fused3.back().first + 3, "hmr: a plain layer3 block is three launches of the plan");
         h->fused3.back().blk.layer = h->convs.back().layer;   // reported under conv3's index, as the other whole-block kernels
       }
+      // every form of the block ends with the entry just added writing outb (conv3, conv3 + downsample, or conv2 carrying conv3)
+      h->block_last[blk_no] = (int)h->convs.size() - 1;
+      h->block_buf[blk_no++] = outb;
       cur = outb;
       H = Ho;
       inpl = pl * 4;
     }
   h->final_buf = cur;
+  PR_REQUIRE(blk_no == HmrPlan::kBlocks, "hmr: planned %d blocks", blk_no);
   PR_REQUIRE(layer == kNumConv && (int)h->convs.size() ==
                                       kNumConv - (h->fuse_downsample ? 4 : 0) -
                                           (h->precision == 1 && h->fuse_bottleneck ? (h->fuse_downsample ? 6 : 4) : h->fuse_conv3 ? 2 : 0) -

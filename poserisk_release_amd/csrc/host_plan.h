@@ -175,6 +175,12 @@ struct HmrPlan {
     ConvSpec blk;
   };
   std::vector<FusedBlock> fused3;
+  // Where each block's output is complete (pr_hmr_encode_until): block 0 = the stem + max-pool, 1..16 = the Bottlenecks.
+  // block_last[k] is the plan entry after which it is written (a whole-block spec, the last of a block's launches -- also
+  // for the fused3 alternate, which spans the same three entries -- or a conv2 carrying conv3), block_buf[k] the buffer.
+  static constexpr int kBlocks = 17;
+  int block_last[kBlocks] = {};
+  int block_buf[kBlocks] = {};
   // regressor workspaces (device, zero-filled)
   float* xf = nullptr;       // [B,2048]
   float* h_static = nullptr; // [B,1024]

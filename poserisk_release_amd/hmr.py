@@ -153,6 +153,27 @@ class HMR:
 
     __call__ = forward
 
+    # (H = W, channels) of the encoder tap's blocks: the stem + max-pool, then layer1..layer4's Bottlenecks
+    BLOCK_SHAPES = [(56, 64)] + [(56, 256)] * 3 + [(28, 512)] * 4 + [(14, 1024)] * 6 + [(7, 2048)] * 3
+
+    def encode_until(self, x, block):
+        """Test entry: the encoder of forward() -- same sub-batches, streams and kernel routing -- stopped after `block`
+        (0 = stem + max-pool, 1..16 = the Bottlenecks) -> that block's output, NHWC [B,H,W,C] in the handle's dtype
+        (torch.float32, or torch.bfloat16 for the bf16 encoder) (pr_hmr_encode_until)."""
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224):
+            raise ValueError(f"expected [B,3,224,224], got {tuple(x.shape)}")
+        if x.device.type != "cuda":
+            raise _lib.PoseRiskHipError("input batch must be on the GPU")
+        x = x.contiguous().float()
+        B = x.shape[0]
+        self._ensure(B)
+        hw, c = self.BLOCK_SHAPES[block] if 0 <= block < len(self.BLOCK_SHAPES) else (1, 1)
+        out = torch.empty((B, hw, hw, c), dtype=torch.bfloat16 if self._precision == 1 else torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.load().pr_hmr_encode_until(self._handle, x.data_ptr(), B, int(block), out.data_ptr(), stream),
+                   "pr_hmr_encode_until")
+        return out
+
     def set_streams(self, n):
         """Number of concurrent sub-batch streams inside the encoder (1..8); results do not depend on it."""
         self._streams = int(n)

@@ -103,7 +103,9 @@ static void check_dataflow(const HmrPlan& pl, const char* tag) {
     CHECK(layers.insert(l).second, "%s: layer index %d carried twice", tag, l);
   };
   auto buf_ok = [&](int b, bool input) { return b >= (input ? 0 : 1) && b <= 5; };
-  int inpl = 64, H = 56;
+  int inpl = 64, H = 56, blk_no = 1;
+  // the encoder tap (pr_hmr_encode_until): block 0 is the max-pooled stem, written by launch 0 into buffer 2
+  CHECK(pl.block_last[0] == 0 && pl.block_buf[0] == 2, "%s: block 0 tapped after launch %d from buffer %d", tag, pl.block_last[0], pl.block_buf[0]);
   for (int L = 0; L < 4; ++L)
     for (int b = 0; b < kBlocks[L]; ++b) {
       char xin[32], xout[32];
@@ -181,6 +183,11 @@ static void check_dataflow(const HmrPlan& pl, const char* tag) {
           ++ci;
         }
       }
+      // ... and every Bottleneck's output is complete after the last launch of the block, in the buffer that holds it
+      CHECK(pl.block_last[blk_no] == (int)ci - 1 && holds[pl.block_buf[blk_no]] == xout,
+            "%s: block %d tapped after launch %d from buffer %d ('%s'); it ends at launch %zu", tag, blk_no, pl.block_last[blk_no],
+            pl.block_buf[blk_no], holds[pl.block_buf[blk_no]].c_str(), ci - 1);
+      ++blk_no;
       inpl = 4 * pln;
       H = Ho;
     }

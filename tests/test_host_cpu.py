@@ -302,6 +302,14 @@ def test_c_abi_error_behaviour():
     assert lib.pr_hmr_forward(None, None, -1, None, None, None, None, None, None) == -1 and "negative" in msg()
     assert lib.pr_hmr_forward(None, None, 0, None, None, None, None, None, None) == 0  # an empty batch is legal
     assert lib.pr_hmr_forward(None, None, 4, None, None, None, None, None, None) == -1
+    # the encoder tap (ABI 11): a null handle, a batch below 1, a block outside 0..16
+    buf = np.zeros(4, np.float32)
+    assert lib.pr_hmr_encode_until(None, buf.ctypes.data, 4, 3, buf.ctypes.data, None) == -1 and "null" in msg()
+    assert lib.pr_hmr_encode_until(None, buf.ctypes.data, -1, 3, buf.ctypes.data, None) == -1 and "batch -1" in msg()
+    assert lib.pr_hmr_encode_until(None, buf.ctypes.data, 0, 3, buf.ctypes.data, None) == -1 and "batch 0" in msg()
+    for block in (-1, 17):
+        assert lib.pr_hmr_encode_until(None, buf.ctypes.data, 4, block, buf.ctypes.data, None) == -1
+        assert f"block {block} out of range 0..16" in msg()
     info = _lib.reba_info_struct(synth.EXAMPLE_INFO["REBA"])
     assert lib.pr_reba(None, 4, C.byref(info), None, None) == -1 and "pr_reba" in msg()
     assert lib.pr_rot6d_to_rotmat(None, 1, None, None) == -1
