@@ -356,6 +356,69 @@ int pr_frames_forward(pr_hmr_t* hmr, pr_smpl_t* smpl, const float* x_dev, int B,
                       const pr_reba_info* reba_info, const pr_rula_info* rula_info,
                       const pr_frames_out* out, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* r1  mesh overlay (ABI 12): the fitted mesh of every crop drawn over its video frame   */
+/* extends: the --debug_frame reporting lib/core/base.py:273-327 (one frame's OBJ and    */
+/*          skeleton plot, root forced to (3.14, 0, 0), zero betas, no image)            */
+/* ------------------------------------------------------------------------------------ */
+/* Raster contract.  Integer-exact, so that tests/raster_ref.py (numpy) reproduces face_id bit for bit.
+ *
+ * Projection.  Crop n has vertices (X, Y, Z) in metres in SPIN's camera axes (x right, y down, z away from the camera),
+ *   cam[n] = (s, tx, ty), its box (cx, cy, w, h) and `scale` (cfg.DATASET.bbox_scale).  Image point, pixel centres at
+ *   integer coordinates:
+ *     x = cx + s (X + tx) w scale / 2,   y = cy + s (Y + ty) h scale / 2,   depth = Z.
+ *   This is SPIN's crop pixel u = 112 (1 + s (X + tx)) taken back through the inverse of the crop's affine
+ *   (_img_utils.py:53-86, rot = 0; the affine pr_crop_frames applies).  It is weak perspective, which is what the camera
+ *   parameters are; against SPIN's f = 5000 perspective the difference is about |Z| / 50 m of the offset from the box centre.
+ * Fixed point.  xf = rint(16 x), yf = rint(16 y), zf = rint(4096 Z) + 2^20, int32, rounding half to even.  A vertex is
+ *   invalid if a coordinate is non-finite, if x or y lies 4096 px or more outside the frame (x <= -4096 or x >= W - 1 + 4096,
+ *   likewise y), or if |Z| >= 256 m; faces that touch an invalid vertex are skipped.  H, W <= 4096.  These bounds keep every
+ *   product below inside int64.
+ * Coverage.  A = orient2d(a, b, c) = (b - a) x (c - a) in int64; A = 0: the face is skipped; A < 0: b and c are swapped (no
+ *   back-face culling: the result depends neither on winding nor on the mesh being closed).  Pixel (row i, col j) samples
+ *   p = (16 j, 16 i): w0 = orient2d(b, c, p), w1 = orient2d(c, a, p), w2 = orient2d(a, b, p).  Covered when every wk >= 0,
+ *   where a tie (wk == 0) counts only if that weight's edge P->Q (w0: b->c, w1: c->a, w2: a->b, after the swap) has dy > 0,
+ *   or dy == 0 and dx < 0: no sample of a split-quad grid is covered twice or missed.
+ * Visibility.  depth = (w0 zf_a + w1 zf_b + w2 zf_c) / A in int64 (every term non-negative: truncation = floor);
+ *   key = (uint64)depth << 32 | face index; the smallest key wins (depth ties go to the lower face index); empty = ~0.
+ * Shading.  Flat per face: n = normalised (v_b - v_a) x (v_c - v_a) of the float 3-D vertices in the face's own order,
+ *   I = 0.35 + 0.65 |n_z| (two-sided, light along the view axis), c = part_rgb[n, face_part[f]] I, kept in quarter steps;
+ *   out = rint((1 - alpha) frame + alpha c) clamped to [0, 255].  A pixel with no visible face is copied unchanged.
+ *   frames and out share one channel order; part_rgb is RGB and is swapped when bgr != 0.
+ *
+ * Arguments (device pointers):
+ *   verts f32[N,V,3], faces int32[F,3], cam f32[N,3], bboxes f32[N,4] (cx, cy, w, h), scale;
+ *   frames u8[n_frames,H,W,3], bgr, frame_idx int32[N] or NULL (crop n over frame n);
+ *   face_part int32[F] (values outside [0, P) are clamped), part_rgb u8[N,P,3], P, alpha in [0, 1];
+ *   out u8[N,H,W,3]; face_id int32[N,H,W] or NULL (the visible face, -1 where none); vert_fx int32[N,V,4] or NULL (xf, yf,
+ *   zf, valid; all zero when invalid); status int32[N] or NULL:
+ *     bit 0  frame index outside [0, n_frames): that crop's out is zero-filled (as pr_crop_frames does), face_id -1
+ *     bit 1  an invalid vertex
+ *     bit 2  a face index outside [0, V) (that face is skipped)
+ * workspace: device memory of at least pr_render_workspace_bytes(N, V, F, H, W) bytes (z-buffer, projected vertices, face
+ * colours, big-face queue), owned by the caller.  Argument errors return PR_ERR_INVALID before any device work; N = 0 returns
+ * PR_OK.  Asynchronous on `stream`, no allocation, no synchronisation. */
+typedef struct pr_render_args {
+  const float* verts;
+  const int32_t* faces;
+  const float* cam;
+  const float* bboxes;
+  const uint8_t* frames;
+  const int32_t* frame_idx;
+  const int32_t* face_part;
+  const uint8_t* part_rgb;
+  uint8_t* out;
+  int32_t* face_id;
+  int32_t* vert_fx;
+  int32_t* status;
+  int N, V, F, P;
+  int n_frames, H, W, bgr;
+  float scale, alpha;
+} pr_render_args;
+
+size_t pr_render_workspace_bytes(int N, int V, int F, int H, int W);
+int pr_render_overlay(const pr_render_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # pr_build_info() -- printed by bench.py as `library` -- says which build a record came from.
 LIB_PATH = os.environ.get("POSERISK_LIB_PATH") or os.path.join(HERE, "libposerisk_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class PoseRiskHipError(RuntimeError):
@@ -28,6 +28,14 @@ class RebaInfo(C.Structure):
 class RulaInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("arm_supported_l", "arm_supported_r", "a_muscle_l", "a_muscle_r",
                                           "a_load_l", "a_load_r", "legs_bilateral", "b_muscle", "b_load")]
+
+
+class RenderArgs(C.Structure):
+    """pr_render_args (include/poserisk_hip.h, the mesh overlay)."""
+    _fields_ = [(n, C.c_void_p) for n in ("verts", "faces", "cam", "bboxes", "frames", "frame_idx", "face_part", "part_rgb",
+                                           "out", "face_id", "vert_fx", "status")] + \
+               [(n, C.c_int) for n in ("N", "V", "F", "P", "n_frames", "H", "W", "bgr")] + \
+               [("scale", C.c_float), ("alpha", C.c_float)]
 
 
 class FramesOut(C.Structure):
@@ -76,6 +84,8 @@ SIGNATURES = {
     "pr_rula": (_I, [_P, _I, C.POINTER(RulaInfo), _P, _P]),
     "pr_frames_forward": (_I, [_P, _P, _P, _I, C.POINTER(RebaInfo), C.POINTER(RulaInfo),
                                C.POINTER(FramesOut), _P]),
+    "pr_render_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "pr_render_overlay": (_I, [C.POINTER(RenderArgs), _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -133,6 +133,9 @@ class Predictor:
         self.run_rula = 'RULA' in scores
         self.debugging = debug
         self.debug_frame = getattr(args, 'debug_frame', -1)
+        # the mesh overlay (render_overlay): args.render_mesh, else cfg.DATASET.render_mesh (False; $POSERISK_CFG can set it)
+        knob = getattr(args, 'render_mesh', None)
+        self.render_mesh = bool(knob if knob is not None else cfg.DATASET.get('render_mesh', False))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
             self.debug_joints = None
@@ -183,9 +186,11 @@ class Predictor:
         return dist.get_world_size()
 
     # ---- base.py:211-240 -------------------------------------------------------------------------
-    def get_pose_estimation_results(self, crop_dataloader, keep_images=True, n_total=None):
+    def get_pose_estimation_results(self, crop_dataloader, keep_images=True, n_total=None, smpl_params=None):
         """Iterable of f32[b,3,224,224] batches -> (result f64[N,24,3] Euler deg, joint_cam f32[N,24,3] mm,
         images f32[N,3,224,224], debug_result f32[N,24,3] axis-angle with root rows = 3.14,0,0).
+        `smpl_params`: a dict that receives the network's rotmat f32[N,24,3,3], betas f32[N,10] and cam f32[N,3] (host
+        arrays, gathered like the others; the mesh overlay draws from them), or None: the return value is the same.
 
         `n_total` (multi-GPU): the loader holds only this rank's contiguous shard
         `pipeline.shard_bounds(n_total, world, rank)`; the per-frame results of all ranks are all-gathered
@@ -197,6 +202,7 @@ class Predictor:
             self._pipe = pl.FramePipeline(self.spin_model, self.smpl_model.layer['neutral'], None, lanes=self.lanes)
         pipe = self._pipe
         eul, jc, aa, st, images = [], [], [], [], []
+        params = {'rotmat': [], 'betas': [], 'cam': []} if smpl_params is not None else None
         # host batches cross PCIe from PINNED staging buffers (one per batch in flight + 1): a `.to(device, non_blocking=True)`
         # from pageable memory -- what a DataLoader without pin_memory yields -- is a synchronous copy that stalls the loop
         stage, n_stage, uploads = [], self.lanes + 1, 0
@@ -223,14 +229,24 @@ class Predictor:
                 pl.FramePipeline.wait(out)      # the copies below queue behind this batch; the next one overlaps
                 eul.append(out['euler'].clone()); jc.append(out['joint_cam'].clone())
                 aa.append(out['axis_angle'].clone()); st.append(out['status'].clone())
+                if params is not None:
+                    for k in params:
+                        params[k].append(out[k].clone())
                 if keep_images:
                     images.append(batch.cpu().numpy())
         dev = self.device
         cat = lambda parts, shape, dt: torch.cat(parts) if parts else torch.empty((0,) + shape, dtype=dt, device=dev)
         eul, jc = cat(eul, (24, 3), torch.float64), cat(jc, (24, 3), torch.float32)
         aa, st = cat(aa, (24, 3), torch.float32), cat(st, (), torch.int32)
+        if params is not None:
+            for k, shape in (('rotmat', (24, 3, 3)), ('betas', (10,)), ('cam', (3,))):
+                params[k] = cat(params[k], shape, torch.float32)
         if n_total is not None:
             eul, jc, aa, st = (pl.gather_padded(t, n_total) for t in (eul, jc, aa, st))
+            if params is not None:
+                params = {k: pl.gather_padded(t, n_total) for k, t in params.items()}
+        if params is not None:
+            smpl_params.update({k: t.cpu().numpy() for k, t in params.items()})
         status = st.cpu().numpy()
         if np.any(status != 0):     # coord_utils.py:70,91: the reference aborts on these
             raise AssertionError(f"invalid rotation in frames {np.nonzero(status)[0].tolist()}")
@@ -247,17 +263,21 @@ class Predictor:
         return aggregate(scores), np.copy(scores), logs
 
     # ---- the accelerated half of __call__ (base.py:126-182 without tracking / reporting) ------------
-    def score_crops(self, crop_batches, add_info=None, n_total=None):
+    def score_crops(self, crop_batches, add_info=None, n_total=None, with_smpl_params=False):
         """crops -> dict(result, joint_cam, reba=(final, scores, logs, level), rula=(...)).
-        `n_total`: see get_pose_estimation_results (the batches are this rank's shard of n_total frames)."""
+        `n_total`: see get_pose_estimation_results (the batches are this rank's shard of n_total frames).
+        `with_smpl_params`: the dict also holds rotmat, betas, cam and the add_info used (what render_overlay needs)."""
         if add_info is None:
             add_info = default_information()
         elif isinstance(add_info, str):
             with open(add_info, 'r') as f:
                 add_info = json.load(f)
+        params = {} if with_smpl_params else None
         result, joint_cam, _, debug_result = self.get_pose_estimation_results(crop_batches, keep_images=False,
-                                                                              n_total=n_total)
+                                                                              n_total=n_total, smpl_params=params)
         out = dict(result=result, joint_cam=joint_cam, debug_result=debug_result)
+        if with_smpl_params:
+            out.update(params, add_info=add_info)
         if self.run_reba:
             final, scores, logs = self.post_processing(self.reba(result, joint_cam, add_info))
             out['reba'] = (final, scores, logs, self.reba.action_level(final[4]))
@@ -266,8 +286,10 @@ class Predictor:
             out['rula'] = (final, scores, logs, self.rula.action_level(final[4]))
         return out
 
-    def score_frames(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None):
+    def score_frames(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None):
         """Decoded frames + tracker output -> scores, all on the GPU (BASELINE config 5 without the detector).
+        `with_smpl_params` (default: the render_mesh knob): also return the network's rotmat, betas and cam per track frame
+        (and the add_info used), which render_overlay draws from.
 
         frames: uint8[F,H,W,3] (torch CUDA tensor or numpy); tracking_results: multi_person_tracker's dict
         {id: {'bbox': [n,4] (cx,cy,w,h), 'frames': [n]}}.  Does what base.py:53-73 (track filter + target
@@ -303,10 +325,80 @@ class Predictor:
             for i in range(lo, hi, self.batch_size):
                 j = min(i + self.batch_size, hi)
                 yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
-        out = self.score_crops(batches(), add_info, n_total=len(fidx) if world > 1 else None)
+        if with_smpl_params is None:
+            with_smpl_params = self.render_mesh
+        out = self.score_crops(batches(), add_info, n_total=len(fidx) if world > 1 else None,
+                               with_smpl_params=with_smpl_params)
         out['frames'] = fidx
         out['bboxes'] = bboxes
+        if with_smpl_params:
+            out['bbox_scale'] = float(bbox_scale)
         return out
+
+    # ---- the mesh overlay (extends the --debug_frame mesh of base.py:273-282 to every track frame) -----------------
+    def render_overlay(self, out, frames, title='REBA', bgr=False, alpha=0.6):
+        """Yield (track frame numbers int[b], overlaid frames u8[b,H,W,3] CUDA) batch by batch: the fitted mesh of every
+        track frame drawn over its video frame (poserisk_release_amd.render), parts coloured by the `title` scheme's
+        risk levels ('REBA' / 'RULA'; None: one neutral colour).  `out` is what score_frames returned with the SMPL
+        parameters.  The pose is rebuilt from the returned rotmat (ops.pose_to_euler's axis-angle: the root keeps the
+        network's rotation, it is NOT overwritten as the scores' pose is), betas from the prediction, vertices from
+        smpl_model.layer['neutral']; `frames` and the output share one channel order (`bgr`)."""
+        from poserisk_release_amd import ops, render
+        if 'rotmat' not in out:
+            raise ValueError("render_overlay needs score_frames(..., with_smpl_params=True) (or the render_mesh knob)")
+        layer = self.smpl_model.layer['neutral']
+        faces = np.asarray(self.smpl_model.face)
+        if faces.ndim != 2 or faces.shape[0] == 0:
+            raise ValueError("the SMPL model has no faces to draw")
+        scheme = None if title is None else str(title).upper()
+        face_part = render.face_parts(layer.th_weights.numpy(), faces, scheme)
+        frames = torch.as_tensor(frames)
+        if frames.device.type != 'cuda':
+            frames = frames.to(self.device)
+        dev = frames.device
+        faces_dev = torch.as_tensor(faces.astype(np.int32), device=dev)
+        fidx, n = np.asarray(out['frames']), len(out['frames'])
+        info = out.get('add_info') or default_information()
+        for i in range(0, n, self.batch_size):
+            j = min(i + self.batch_size, n)
+            rotmat = torch.as_tensor(out['rotmat'][i:j], device=dev)
+            aa, eul, _ = ops.pose_to_euler(rotmat)
+            betas = torch.as_tensor(out['betas'][i:j], device=dev)
+            verts, _ = layer(aa.reshape(j - i, 72), betas)
+            if scheme is None:
+                rgb = render.part_colours(np.zeros((j - i, 1)), None)
+            else:
+                packed = (ops.reba if scheme == 'REBA' else ops.rula)(eul, info[scheme]).cpu().numpy()
+                rgb = render.part_colours(packed, scheme)
+            img = render.overlay(frames, verts, faces_dev, out['cam'][i:j], out['bboxes'][i:j],
+                                 scale=out.get('bbox_scale', cfg.DATASET.bbox_scale), frame_idx=fidx[i:j].astype(np.int32),
+                                 face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
+            yield fidx[i:j], img
+
+    def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
+        """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
+        frame.  Returns the path written."""
+        import os
+        try:
+            import cv2
+        except ImportError:
+            cv2 = None
+        name = f"{title if title is not None else 'MESH'}_mesh"
+        if cv2 is not None:
+            path = osp.join(output_path, name + '.mp4')
+            H, W = int(frames.shape[1]), int(frames.shape[2])
+            vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*'mp4v'), float(fps), (W, H))
+            for _, img in self.render_overlay(out, frames, title, bgr):
+                for im in img.cpu().numpy():
+                    vw.write(im if bgr else im[..., ::-1])
+            vw.release()
+            return path
+        path = osp.join(output_path, name)
+        os.makedirs(path, exist_ok=True)
+        for fr, img in self.render_overlay(out, frames, title, bgr):
+            for f, im in zip(fr, img.cpu().numpy()):
+                _save_png(osp.join(path, '{0:09d}.png'.format(int(f))), im[..., ::-1] if bgr else im)
+        return path
 
     # ---- base.py:273-282 ------------------------------------------------------------------------------------
     def visualize_joint_cam_mesh(self, debug_result, joint_cam, frames, output_path):
@@ -435,6 +527,14 @@ class Predictor:
         if self.debugging and self.debug_frame is not None and self.debug_frame >= 0:
             # base.py:128-135: the --debug_frame branch dumps that frame's mesh and 3-D skeleton and stops there
             self.visualize_joint_cam_mesh(out['debug_result'], out['joint_cam'], fidx, debug_path)
+            if self.render_mesh:
+                idx = int(np.where(np.asarray(fidx) == self.debug_frame)[0][0])
+                one = dict(out, frames=fidx[idx:idx + 1], bboxes=out['bboxes'][idx:idx + 1], rotmat=out['rotmat'][idx:idx + 1],
+                           betas=out['betas'][idx:idx + 1], cam=out['cam'][idx:idx + 1])
+                title = 'REBA' if 'reba' in out else ('RULA' if 'rula' in out else None)
+                for _, img in self.render_overlay(one, frames, title, bgr):
+                    im = img[0].cpu().numpy()
+                    _save_png(osp.join(debug_path, 'mesh_overlay.png'), im[..., ::-1] if bgr else im)
             print("\n Debug files are saved in : ", debug_path)
             return out
         pose_str = reports.pose_to_str(out['result'])
@@ -453,6 +553,18 @@ class Predictor:
                     print("OpenCV (cv2) is not importable: the annotated mp4 is skipped, all other outputs are written")
                     self._warned_no_cv2 = True
             reports.write_result_txt(output_path, title, final, level, name)
+            if self.render_mesh:
+                self.write_mesh_overlay(out, frames, output_path, title, bgr, fps)
             if self.debugging:
                 reports.save_score_csv(debug_path, title, timestamp, scores, scorer.eval_items, logs, scorer.log)
         return out
+
+
+def _save_png(path, rgb):
+    """u8[H,W,3] RGB -> PNG with Pillow, else matplotlib."""
+    try:
+        from PIL import Image
+        Image.fromarray(np.ascontiguousarray(rgb)).save(path)
+    except ImportError:
+        import matplotlib.image
+        matplotlib.image.imsave(path, np.ascontiguousarray(rgb))

@@ -19,6 +19,8 @@ absent from the reference and all optional:
     cfg.DATASET.hip_lanes     whole batches in flight on separate HIP streams (2)
     cfg.DATASET.hip_world_size  0 = whatever the launcher says ($WORLD_SIZE of torch.distributed.run, else 1); N > 1 insists
                               on N ranks, one per GPU, frames sharded and gathered once over RCCL
+    cfg.DATASET.render_mesh   False | True: Predictor.__call__ also draws the fitted mesh over every track frame
+                              (<TITLE>_mesh.mp4, or <TITLE>_mesh/%09d.png without cv2; args.render_mesh overrides it)
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -77,7 +79,8 @@ def _defaults(root):
         'smpl_dir': osp.join(root, 'smplpytorch'),
         'DATASET': {'workers': 16, 'batch_size': 8, 'min_frame_ratio': 0.33, 'bbox_scale': 1.2,
                     'default_information': osp.join(core_dir, 'default_information.json'),
-                    'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0},
+                    'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
+                    'render_mesh': False},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

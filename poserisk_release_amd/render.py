@@ -1,0 +1,125 @@
+"""Mesh overlay: the fitted SMPL mesh of every scored crop drawn over its video frame, one colour per body part by risk
+level (include/poserisk_hip.h, pr_render_overlay; the kernels are csrc/render.hip).
+
+`overlay` is the torch wrapper of the kernel.  `face_parts` and `part_colours` turn SMPL's skinning weights and the REBA /
+RULA logs into the kernel's face_part and part_rgb tables.  The Predictor's `render_overlay` (dropin/core/base.py) chains
+them on the arrays `score_frames` returns."""
+import numpy as np
+import torch
+
+from . import _lib
+
+# The parts a face can belong to, in this order for both schemes (face_part values index it).
+PARTS = ("trunk", "neck", "leg", "upper_arm_l", "upper_arm_r", "lower_arm_l", "lower_arm_r", "wrist_l", "wrist_r")
+# SMPL joint -> part: the joint whose rotation moves that segment (csrc/frame_kernels.hip reads L_SHOULDER = 16 for upper
+# arm L, L_ELBOW = 18 for lower arm L, L_WRIST = 20 for wrist L; the hands 22 / 23 follow their wrists).
+_JOINT_PART = {0: 0, 3: 0, 6: 0, 9: 0, 13: 0, 14: 0,
+               12: 1, 15: 1,
+               1: 2, 2: 2, 4: 2, 5: 2, 7: 2, 8: 2, 10: 2, 11: 2,
+               16: 3, 17: 4, 18: 5, 19: 6, 20: 7, 22: 7, 21: 8, 23: 8}
+JOINT_PART = np.array([_JOINT_PART[j] for j in range(24)], np.int32)
+# the log column of each part: REBA int32[N,10] score, trunk, neck, leg, upper_arm L,R, lower_arm L,R, wrist L,R;
+# RULA int32[N,12] score, upper_arm L,R, lower_arm L,R, wrist L,R, wrist_twist L,R, neck, trunk, leg.  RULA's wrist-twist
+# columns (7, 8) have no segment of their own and are not drawn.
+LOG_COLUMNS = {"REBA": (1, 2, 3, 4, 5, 6, 7, 8, 9), "RULA": (10, 9, 11, 1, 2, 3, 4, 5, 6)}
+# risk level clip(sub_score - 1, 0, 3): green, yellow, orange, red (RGB)
+LEVEL_RGB = np.array([[40, 200, 60], [250, 220, 40], [250, 140, 20], [230, 30, 30]], np.uint8)
+NEUTRAL_RGB = np.array([200, 200, 210], np.uint8)
+
+
+def _scheme(scheme):
+    if scheme is None:
+        return None
+    s = str(scheme).upper()
+    if s not in LOG_COLUMNS:
+        raise ValueError(f"scheme must be 'REBA', 'RULA' or None, got {scheme!r}")
+    return s
+
+
+def face_parts(weights, faces, scheme=None):
+    """Skinning weights f32[V,24] + faces int[F,3] -> int32[F] part index into PARTS: the joint with the largest sum of the
+    face's three vertices' weights, mapped by JOINT_PART.  scheme None: one neutral part (all zeros)."""
+    faces = np.asarray(faces, np.int64)
+    if _scheme(scheme) is None:
+        return np.zeros(faces.shape[0], np.int32)
+    w = np.asarray(weights, np.float64)
+    joint = np.argmax(w[faces[:, 0]] + w[faces[:, 1]] + w[faces[:, 2]], axis=1)
+    return JOINT_PART[joint]
+
+
+def part_colours(logs, scheme=None):
+    """REBA int32[N,10] / RULA int32[N,12] logs -> part_rgb u8[N,len(PARTS),3] by risk level; scheme None: u8[N,1,3]
+    neutral grey."""
+    logs = np.asarray(logs)
+    s = _scheme(scheme)
+    if s is None:
+        return np.broadcast_to(NEUTRAL_RGB, (logs.shape[0], 1, 3)).copy()
+    want = 10 if s == "REBA" else 12
+    if logs.ndim != 2 or logs.shape[1] != want:
+        raise ValueError(f"{s} logs must be int[N,{want}], got shape {logs.shape}")
+    level = np.clip(logs[:, list(LOG_COLUMNS[s])].astype(np.int64) - 1, 0, 3)
+    return LEVEL_RGB[level]
+
+
+def _dev_tensor(x, dtype, dev, shape=None, what=""):
+    t = torch.as_tensor(x).to(device=dev, dtype=dtype).contiguous()
+    if shape is not None and (t.dim() != len(shape) or any(s is not None and t.shape[i] != s for i, s in enumerate(shape))):
+        raise ValueError(f"{what} must have shape {shape}, got {tuple(t.shape)}")
+    return t
+
+
+def overlay(frames, verts, faces, cam, bboxes, scale=1.2, frame_idx=None, face_part=None, part_rgb=None, alpha=0.6,
+            bgr=False, out=None, return_face_id=False, return_vert_fx=False, return_status=False):
+    """Draw the meshes over their frames on the GPU.
+
+    frames u8[n_frames,H,W,3] CUDA; verts f32[N,V,3] (SPIN camera axes, metres); faces int[F,3]; cam f32[N,3] (s, tx, ty);
+    bboxes f32[N,4] (cx, cy, w, h); scale = cfg.DATASET.bbox_scale; frame_idx int[N] or None (crop n over frame n);
+    face_part int[F] or None (all part 0); part_rgb u8[N,P,3] or u8[P,3] (RGB) or None (neutral grey); alpha in [0, 1];
+    bgr: the frames' channel order.  Returns out u8[N,H,W,3], followed by face_id int32[N,H,W], vert_fx int32[N,V,4] and
+    status int32[N] as asked for.  Face indices are checked here, once, on the host."""
+    if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
+        raise _lib.PoseRiskHipError("overlay: frames must be a CUDA tensor (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError("frames must be uint8 [n_frames,H,W,3]")
+    dev = frames.device
+    frames = frames.contiguous()
+    n_frames, H, W, _ = frames.shape
+    v = _dev_tensor(verts, torch.float32, dev, (None, None, 3), "verts")
+    N, V = v.shape[0], v.shape[1]
+    faces_host = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if faces_host.ndim != 2 or faces_host.shape[1] != 3 or faces_host.shape[0] == 0:
+        raise ValueError(f"faces must be int [F,3], got shape {faces_host.shape}")
+    if int(faces_host.min()) < 0 or int(faces_host.max()) >= V:
+        raise ValueError(f"face indices {int(faces_host.min())}..{int(faces_host.max())} outside [0, {V})")
+    F = faces_host.shape[0]
+    f = _dev_tensor(faces if isinstance(faces, torch.Tensor) else faces_host, torch.int32, dev)
+    c = _dev_tensor(cam, torch.float32, dev, (N, 3), "cam")
+    bb = _dev_tensor(bboxes, torch.float32, dev, (N, 4), "bboxes")
+    fp = _dev_tensor(np.zeros(F, np.int32) if face_part is None else face_part, torch.int32, dev, (F,), "face_part")
+    rgb = _dev_tensor(NEUTRAL_RGB[None] if part_rgb is None else part_rgb, torch.uint8, dev)
+    if rgb.dim() == 2:
+        rgb = rgb[None].expand(N, -1, -1).contiguous()
+    if rgb.dim() != 3 or rgb.shape[0] != N or rgb.shape[2] != 3:
+        raise ValueError(f"part_rgb must be u8[N,P,3] or u8[P,3], got {tuple(rgb.shape)}")
+    P = rgb.shape[1]
+    idx = None
+    if frame_idx is not None:
+        idx = _dev_tensor(frame_idx, torch.int32, dev, (N,), "frame_idx")
+    if out is None:
+        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
+    elif out.shape != (N, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous uint8 [N,H,W,3] tensor on the frames' device")
+    fid = torch.empty((N, H, W), dtype=torch.int32, device=dev) if return_face_id else None
+    vfx = torch.empty((N, V, 4), dtype=torch.int32, device=dev) if return_vert_fx else None
+    st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    lib = _lib.load()
+    nbytes = lib.pr_render_workspace_bytes(N, V, F, H, W)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    args = _lib.RenderArgs(v.data_ptr(), f.data_ptr(), c.data_ptr(), bb.data_ptr(), frames.data_ptr(), ptr(idx),
+                           fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), ptr(fid), ptr(vfx), ptr(st),
+                           N, V, F, P, n_frames, H, W, int(bool(bgr)), float(scale), float(alpha))
+    _lib.check(lib.pr_render_overlay(args, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+               "pr_render_overlay")
+    extra = [t for t, want in ((fid, return_face_id), (vfx, return_vert_fx), (st, return_status)) if want]
+    return (out, *extra) if extra else out

@@ -123,6 +123,48 @@ def rotmats(n, seed=5, scale=0.8):
     return np.stack([b1, b2, b3], axis=-1).reshape(n, 24, 3, 3).astype(np.float32)
 
 
+def genus0_mesh(V):
+    """A closed genus-0 triangulation of exactly V >= 66 vertices on the unit sphere: the largest UV sphere (two poles,
+    rings of 64) with at most V vertices, then each remaining vertex inserted into one face (+1 vertex, +2 faces), so
+    F = 2 V - 4.  Synthetic SMPL models have no faces; this gives them a closed mesh with SMPL's counts (V = 6890 ->
+    F = 13776).  Returns (vertices f32[V,3], faces int32[F,3])."""
+    n_lon = 64
+    n_lat = (V - 2) // n_lon
+    th = np.pi * (np.arange(n_lat) + 1) / (n_lat + 1)
+    ph = 2 * np.pi * np.arange(n_lon) / n_lon
+    ring = np.stack([np.sin(th)[:, None] * np.cos(ph)[None], np.cos(th)[:, None] * np.ones_like(ph)[None],
+                     np.sin(th)[:, None] * np.sin(ph)[None]], -1).reshape(-1, 3)
+    nv = 2 + n_lat * n_lon
+    verts = [np.array([0.0, 1.0, 0.0])] + list(ring) + [np.array([0.0, -1.0, 0.0])]
+    rid = lambda i, j: 1 + i * n_lon + (j % n_lon)
+    faces = [(0, rid(0, j + 1), rid(0, j)) for j in range(n_lon)]
+    for i in range(n_lat - 1):
+        for j in range(n_lon):
+            a, b, c, d = rid(i, j), rid(i, j + 1), rid(i + 1, j), rid(i + 1, j + 1)
+            faces += [(a, b, d), (a, d, c)]
+    faces += [(nv - 1, rid(n_lat - 1, j), rid(n_lat - 1, j + 1)) for j in range(n_lon)]
+    k = 0
+    while nv < V:   # split face k into three around a new vertex at its (projected) centroid
+        a, b, c = faces[k]
+        m = verts[a] + verts[b] + verts[c]
+        verts.append(m / np.linalg.norm(m))
+        faces[k] = (a, b, nv)
+        faces += [(b, c, nv), (c, a, nv)]
+        nv += 1
+        k += 2
+    return np.array(verts, np.float32), np.array(faces, np.int32)
+
+
+def closed_body(V=6890, seed=7):
+    """A closed person-sized mesh with SMPL's counts (V = 6890, F = 13776): the genus-0 sphere stretched to a 1.7 m tall,
+    0.5 m wide, 0.3 m deep body with a little surface noise, in SPIN's camera axes (y down), metres, centred on the
+    origin.  Returns (vertices f32[V,3], faces int32[F,3])."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    v, f = genus0_mesh(V)
+    v = v * np.array([0.25, 0.85, 0.15], np.float32) * (1 + 0.03 * rng.standard_normal((V, 1))).astype(np.float32)
+    return v.astype(np.float32), f
+
+
 DEFAULT_INFO = {  # main/default_information.json
     "REBA": {"Legs_bilateral_weight_bearing/walking": 0, "Sitting": 0, "Load/Force Score": 0,
              "Arm_supported_leaning_L": 0, "Arm_supported_leaning_R": 0, "Coupling": 0, "Activity_Score": 0},
