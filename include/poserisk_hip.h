@@ -157,6 +157,15 @@ int pr_hmr_plan_counts(pr_hmr_t* h, int B, int* conv_launches, int* winograd_lay
  * tests/test_encoder_blocks.py checks every block of the production plan against an fp64 reference from this tap.
  * No reference counterpart (testing). */
 int pr_hmr_encode_until(pr_hmr_t* h, const float* x_dev, int B, int block, void* act_dev, void* stream);
+/* Regressor tap (ABI 13; a test entry): the regressor of pr_hmr_forward -- the same launches on the same workspaces with the
+ * handle's GEMM kernel and tile shape -- run on the caller's pooled features xf_dev f32[B,2048], stopped after launch `step` and
+ * what that launch wrote copied to out_dev: step 0 = the initial state [B,192] (pose6d 144 | betas 10 | cam 3 | zero pad),
+ * 1 = h_static = fc1's feature columns + bias [B,1024]; for iteration i = 0..2: 2 + 3 i = h1 = fc1's state columns +
+ * h_static [B,1024], 3 + 3 i = h2 = fc2 [B,1024], 4 + 3 i = the state after decpose | decshape | deccam were added in place
+ * [B,192].  Asynchronous on `stream`; refused (PR_ERR_INVALID) while `stream` is being captured, and when B is outside
+ * 1..max_batch or step outside 0..10.  tests/test_regressor_steps.py checks every launch against an fp64 reference of it
+ * computed from the tap before.  No reference counterpart (testing). */
+int pr_hmr_regress_until(pr_hmr_t* h, const float* xf_dev, int B, int step, float* out_dev, void* stream);
 /* The conv form this handle really runs (what PR_CONV_FORM_DEFAULT resolved to at create time: the built-in default,
  * or POSERISK_WINOGRAD's value): 0, 2, 4, 5 or three digits.  scripts/validate_checkpoint.py bases its exit status on it. */
 int pr_hmr_conv_form(pr_hmr_t* h);

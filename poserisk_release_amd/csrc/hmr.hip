@@ -396,6 +396,25 @@ int encode_batch(pr_hmr_t* h, const float* x_dev, int B, hipStream_t s, int stop
   }
   return PR_OK;
 }
+
+// The regressor of pr_hmr_forward, launch by launch, stopped after launch `last` (10 = all of it; pr_hmr_regress_until
+// stops earlier): h_static = xf*W1x^T + b1 once; 3 x { h1 = state*W1s^T + h_static; h2 = h1*W2^T + b2;
+// state += h2*Wdec^T + bdec }.  Launch 0 = the state's initial value, 1 = fc1x, 2 + 3 i / 3 + 3 i / 4 + 3 i = iteration i's
+// fc1s / fc2 / dec.
+int regress_steps(pr_hmr_t* h, const float* xf, int B, int last, hipStream_t s) {
+  PR_TRY(launch_state_init(h->init157, h->state, B, s));
+  if (last < 1) return PR_OK;
+  PR_TRY(fc_launch(h, h->fc1x, xf, nullptr, h->h_static, B, true, s));
+  for (int it = 0; it < 3; ++it) {
+    if (last < 2 + 3 * it) return PR_OK;
+    PR_TRY(fc_launch(h, h->fc1s, h->state, h->h_static, h->h1, B, false, s));
+    if (last < 3 + 3 * it) return PR_OK;
+    PR_TRY(fc_launch(h, h->fc2, h->h1, nullptr, h->h2, B, true, s));
+    if (last < 4 + 3 * it) return PR_OK;
+    PR_TRY(fc_launch(h, h->dec, h->h2, h->state, h->state, B, true, s));
+  }
+  return PR_OK;
+}
 }  // namespace
 }  // namespace pr
 
@@ -416,15 +435,7 @@ int pr_hmr_forward(pr_hmr_t* h, const float* x_dev, int B, float* rotmat_dev, fl
   PR_TRY(encode_batch(h, x_dev, B, s, -1, nullptr));
   if (xf_dev) PR_HIP(hipMemcpyAsync(xf_dev, h->xf, (size_t)B * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (!rotmat_dev && !betas_dev && !cam_dev && !pose6d_dev) return PR_OK;
-  // regressor: h_static = xf*W1x^T + b1 once; 3 x { h1 = state*W1s^T + h_static; h2 = h1*W2^T + b2;
-  //                                               state += h2*Wdec^T + bdec }
-  PR_TRY(launch_state_init(h->init157, h->state, B, s));
-  PR_TRY(fc_launch(h, h->fc1x, h->xf, nullptr, h->h_static, B, true, s));
-  for (int it = 0; it < 3; ++it) {
-    PR_TRY(fc_launch(h, h->fc1s, h->state, h->h_static, h->h1, B, false, s));
-    PR_TRY(fc_launch(h, h->fc2, h->h1, nullptr, h->h2, B, true, s));
-    PR_TRY(fc_launch(h, h->dec, h->h2, h->state, h->state, B, true, s));
-  }
+  PR_TRY(regress_steps(h, h->xf, B, 10, s));
   PR_TRY(launch_regressor_finalize(h->state, rotmat_dev, betas_dev, cam_dev, pose6d_dev, B, s));
   return PR_OK;
 }
@@ -439,6 +450,23 @@ int pr_hmr_encode_until(pr_hmr_t* h, const float* x_dev, int B, int block, void*
   hipStream_t s = (hipStream_t)stream;
   PR_TRY(refuse_if_capturing(s, "pr_hmr_encode_until"));   // a test entry: never part of a captured forward
   return encode_batch(h, x_dev, B, s, block, act_dev);
+}
+
+int pr_hmr_regress_until(pr_hmr_t* h, const float* xf_dev, int B, int step, float* out_dev, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(B >= 1, "pr_hmr_regress_until: batch %d out of range", B);
+  PR_REQUIRE(step >= 0 && step <= 10, "pr_hmr_regress_until: step %d out of range 0..10", step);
+  PR_REQUIRE(h && xf_dev && out_dev, "pr_hmr_regress_until: null argument");
+  PR_REQUIRE(B <= h->max_batch, "pr_hmr_regress_until: batch %d out of range 1..%d", B, h->max_batch);
+  hipStream_t s = (hipStream_t)stream;
+  PR_TRY(refuse_if_capturing(s, "pr_hmr_regress_until"));   // a test entry: never part of a captured forward
+  PR_TRY(regress_steps(h, xf_dev, B, step, s));
+  // what launch `step` wrote: the state (init, dec), h_static (fc1x), h1 (fc1s) or h2 (fc2)
+  const int phase = step < 2 ? step : 2 + (step - 2) % 3;
+  const float* src = phase == 0 || phase == 4 ? h->state : phase == 1 ? h->h_static : phase == 2 ? h->h1 : h->h2;
+  const size_t cols = phase == 0 || phase == 4 ? kStateStride : 1024;
+  PR_HIP(hipMemcpyAsync(out_dev, src, (size_t)B * cols * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return PR_OK;
 }
 
 int pr_hmr_conv_form(pr_hmr_t* h) { return h ? h->conv_form : PR_ERR_INVALID; }

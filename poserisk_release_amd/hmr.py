@@ -174,6 +174,32 @@ class HMR:
                    "pr_hmr_encode_until")
         return out
 
+    # columns of the regressor tap's steps: the state (pose6d 144 | betas 10 | cam 3 | zero pad) or a hidden layer
+    STEP_COLS = [192, 1024] + [1024, 1024, 192] * 3
+
+    def regress_until(self, xf, step, out=None):
+        """Test entry: the regressor of forward() -- same launches, workspaces and GEMM tile shape -- on the pooled features
+        xf [B,2048], stopped after launch `step` (0 = initial state, 1 = fc1x, 2 + 3 i / 3 + 3 i / 4 + 3 i = iteration i's
+        fc1s / fc2 / dec) -> what that launch wrote, float32 [B,192] (a state) or [B,1024] (pr_hmr_regress_until).  out: a
+        contiguous float32 tensor of at least B rows to write into (its first B rows are returned)."""
+        if xf.dim() != 2 or xf.shape[1] != 2048:
+            raise ValueError(f"expected [B,2048], got {tuple(xf.shape)}")
+        if xf.device.type != "cuda":
+            raise _lib.PoseRiskHipError("features must be on the GPU")
+        xf = xf.contiguous().float()
+        B = xf.shape[0]
+        self._ensure(B)
+        cols = self.STEP_COLS[step] if 0 <= step < len(self.STEP_COLS) else 1
+        if out is None:
+            out = torch.empty((B, cols), dtype=torch.float32, device=xf.device)
+        elif (out.dtype != torch.float32 or out.device != xf.device or not out.is_contiguous() or out.dim() != 2
+              or out.shape[0] < B or out.shape[1] != cols):
+            raise ValueError(f"out must be a contiguous float32 [>= {B}, {cols}] tensor on {xf.device}")
+        stream = torch.cuda.current_stream(xf.device).cuda_stream
+        _lib.check(_lib.load().pr_hmr_regress_until(self._handle, xf.data_ptr(), B, int(step), out.data_ptr(), stream),
+                   "pr_hmr_regress_until")
+        return out[:B]
+
     def set_streams(self, n):
         """Number of concurrent sub-batch streams inside the encoder (1..8); results do not depend on it."""
         self._streams = int(n)

@@ -310,6 +310,13 @@ def test_c_abi_error_behaviour():
     for block in (-1, 17):
         assert lib.pr_hmr_encode_until(None, buf.ctypes.data, 4, block, buf.ctypes.data, None) == -1
         assert f"block {block} out of range 0..16" in msg()
+    # the regressor tap (ABI 13): a null handle, a batch below 1, a step outside 0..10
+    assert lib.pr_hmr_regress_until(None, buf.ctypes.data, 4, 3, buf.ctypes.data, None) == -1 and "null" in msg()
+    assert lib.pr_hmr_regress_until(None, buf.ctypes.data, -1, 3, buf.ctypes.data, None) == -1 and "batch -1" in msg()
+    assert lib.pr_hmr_regress_until(None, buf.ctypes.data, 0, 3, buf.ctypes.data, None) == -1 and "batch 0" in msg()
+    for step in (-1, 11):
+        assert lib.pr_hmr_regress_until(None, buf.ctypes.data, 4, step, buf.ctypes.data, None) == -1
+        assert f"step {step} out of range 0..10" in msg()
     info = _lib.reba_info_struct(synth.EXAMPLE_INFO["REBA"])
     assert lib.pr_reba(None, 4, C.byref(info), None, None) == -1 and "pr_reba" in msg()
     assert lib.pr_rot6d_to_rotmat(None, 1, None, None) == -1

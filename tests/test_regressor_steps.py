@@ -1,0 +1,107 @@
+"""Every launch of the regressor as pr_hmr_forward issues it (fc_rows16_f32, ten per batch), at the pipeline's batch sizes,
+against an fp64 reference computed from that launch's own GPU input (tests/regressor_ref.py): the tap pr_hmr_regress_until
+gives launch k's output; its reference starts from the GPU's taps of the launches before it, so errors do not compound.
+Per launch: (a) every element within the bound E, (b) no 16-frame x 16-output tile's RMS of r = |gpu - ref| / E above
+encoder_ref.RHO times the launch's, (c) the launch's RMS of r within regressor_ref.LEVEL times that of the kernel's
+arithmetic emulated in fp32 on the same input.  The features are the GPU encoder's own for synth.crops (|xf| reaches several
+hundred), and once more with frame 0 zeroed and frame 1 scaled by 2^10: rows must not leak into each other."""
+import pytest
+import torch
+
+import encoder_ref as er
+import regressor_ref as rr
+from conftest import measured
+from poserisk_release_amd import synth
+from poserisk_release_amd.hmr import HMR
+
+pytestmark = pytest.mark.gpu
+
+# name -> (precision of the encoder that makes the features, B = max_batch, POSERISK_FC_SHAPE or None)
+CONFIGS = {f"fp32_B{B}": ("fp32", B, None) for B in (1, 15, 16, 17, 64, 217, 256, 600)}
+CONFIGS.update({f"fp32_B{B}_shape{s}": ("fp32", B, s) for B in (256, 217) for s in ("42", "22")})
+CONFIGS["bf16_B256"] = ("bf16", 256, None)
+
+CANARY = -12345.0
+_NET = {}
+
+
+def _net(dev):
+    if not _NET:
+        sd = synth.hmr_state_dict(seed=1)
+        _NET["sd"] = sd
+        _NET["layers"], _NET["init"] = rr.layers(sd, dev)
+    return _NET["sd"], _NET["layers"], _NET["init"]
+
+
+def _taps(m, xf):
+    """All eleven taps of one input, each into a buffer with three canary rows behind the batch, each run twice."""
+    B = xf.shape[0]
+    taps = {}
+    for step in range(11):
+        buf = torch.full((B + 3, HMR.STEP_COLS[step]), CANARY, device=xf.device)
+        tap = m.regress_until(xf, step, out=buf)
+        assert tap.shape == (B, HMR.STEP_COLS[step]) and tap.dtype == torch.float32
+        assert bool((buf[B:] == CANARY).all()), f"step {step}: rows behind the batch were written"
+        assert torch.equal(tap, m.regress_until(xf, step)), f"step {step}: two runs differ"
+        taps[step] = tap.clone()
+    return taps
+
+
+def _check_launches(name, tag, layers, xf, taps, report):
+    worst = {"r": 0.0, "tile": 0.0, "level": 0.0}
+    for step in range(1, 11):
+        lname, src, rs = rr.STEPS[step]
+        a = xf if src is None else taps[src]
+        res = None if rs is None else taps[rs]
+        layer = layers[lname]
+        z, E = rr.reference(layer, a, res)
+        s, e, bad = rr.check(taps[step], rr.emulate(layer, a, res), z, E, layer.real)
+        level = s.rms / e.rms if e.rms > 0 else (0.0 if s.rms == 0 else float("inf"))
+        worst = {"r": max(worst["r"], s.max_r), "tile": max(worst["tile"], s.tile_ratio), "level": max(worst["level"], level)}
+        if report:
+            key = f"{name} step {step} {lname}"
+            measured(f"{key}: max |gpu - ref| / E", s.max_r, 1.0)
+            measured(f"{key}: max tile RMS of r / launch RMS", s.tile_ratio, er.RHO)
+            measured(f"{key}: RMS of r, kernel", s.rms)
+            measured(f"{key}: RMS of r, four-chain emulation", e.rms)
+            measured(f"{key}: kernel RMS / emulation RMS", level, rr.LEVEL)
+        assert not bad, (tag, step, lname, bad, s.max_r, s.tile_ratio, s.rms, e.rms)
+        assert s.pad_max == 0.0, (tag, step, "pad columns 157..191 are not zero")
+    return worst
+
+
+@pytest.mark.parametrize("name", list(CONFIGS))
+def test_regressor_launches_match_fp64_reference(gpu_device, monkeypatch, name):
+    precision, B, shape = CONFIGS[name]
+    sd, layers, init = _net(gpu_device)
+    if shape:
+        monkeypatch.setenv("POSERISK_FC_SHAPE", shape)      # read when the handle is created
+    m = HMR(max_batch=B, precision=precision).to(gpu_device)
+    m.load_state_dict(sd)
+    x = torch.from_numpy(synth.crops(B, seed=33)).to(gpu_device)
+    with torch.no_grad():
+        rotmat, betas, cam, xf, p6 = [t.clone() for t in m(x, return_features=True)]
+        del x
+        measured(f"{name}: max |xf|", xf.abs().max())
+        assert float(xf.abs().max()) > 100          # real magnitudes
+        taps = _taps(m, xf)
+        assert torch.equal(taps[0], init.expand(B, -1))
+        # the tap is the forward: same bits at the end
+        assert torch.equal(taps[10][:, :144], p6) and torch.equal(taps[10][:, 144:154], betas)
+        assert torch.equal(taps[10][:, 154:157], cam)
+        _check_launches(name, "features", layers, xf, taps, report=True)
+
+        # the same features with frame 0 zeroed and frame 1 scaled by 2^10
+        xq = xf.clone()
+        xq[0] = 0
+        if B > 1:
+            xq[1] *= 1024.0
+        tq = _taps(m, xq)
+        w = _check_launches(name, "frame 0 zeroed, frame 1 x 2^10", layers, xq, tq, report=False)
+        measured(f"{name} rows: max |gpu - ref| / E over the launches", w["r"], 1.0)
+        measured(f"{name} rows: max tile ratio over the launches", w["tile"], er.RHO)
+        measured(f"{name} rows: max kernel RMS / emulation RMS over the launches", w["level"], rr.LEVEL)
+        for step in range(11):      # a frame's bits depend on its own features only
+            assert torch.equal(tq[step][2:], taps[step][2:]), f"step {step}: frames 2.. changed with frames 0 and 1"
+        if B > 1:
+            assert torch.isfinite(tq[10]).all()
