@@ -86,7 +86,9 @@ size_t pr_hmr_weight_floats(void);
  * precision: 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32; products and sums are exact-fp32 fmaf chains),
  * 1 = bf16 MFMA encoder with fp32 accumulate (regressor stays fp32).
  * conv_form (fp32 encoder only; a property of the handle, so one process may hold several): how the ten 3x3 /
- * stride-1 layers with >= 128 channels are computed on that kernel -- PR_CONV_FORM_DIRECT (implicit GEMM, the
+ * stride-1 layers with >= 128 channels are computed on that kernel (and, where layer2's form is an F(4x4,3x3) one, layer1.0's
+ * 64-channel conv2 on the one-launch kernel of csrc/conv_wino64.hip with the same points; POSERISK_WINO_LAYER1=0 / 2 at create
+ * time: none / all three of layer1's) -- PR_CONV_FORM_DIRECT (implicit GEMM, the
  * reference's arithmetic up to summation order), PR_CONV_FORM_WINOGRAD_2X2 / _4X4 (F(2x2,3x3) / F(4x4,3x3) on Lavin &
  * Gray's points 0, +-1, +-2: 2.25x / 4x fewer multiplies, a different rounding pattern), PR_CONV_FORM_WINOGRAD_4X4_B
  * (F(4x4,3x3) on the points 0, +-11/16, +-3/2: the same cost as _4X4 with half its per-layer rounding error, every
@@ -210,6 +212,18 @@ int pr_conv1x1_dual_nhwc(int device, const void* x1_dev, const float* w1_host, c
 int pr_conv3x3_conv1x1_nhwc(int device, const void* x_dev, const float* w2_host, const float* b2_host,
                             const float* w3_host, const float* b3_host, const void* res_dev, void* y_dev,
                             int B, int H, int W, int Cin, int N3, int relu3, int precision, void* stream);
+
+/* A layer1 Bottleneck's conv2 as Winograd F(4x4,3x3) in ONE launch (ABI 14; csrc/conv_wino64.hip: input transform, 36 small
+ * GEMMs and output transform inside a workgroup), alone or with conv3 behind it as pr_conv3x3_conv1x1_nhwc: exported for
+ * parity tests (allocates, synchronises).  fp32 only.  x_dev [B,H,W,Cin], w2_host f32[Cout,Cin,3,3] OIHW, b2_host f32[Cout];
+ * Cin and Cout must both be 64, anything else is refused by name with PR_ERR_INVALID.  Any H, W >= 1: tiles that overhang the
+ * map are computed and dropped.  form: 4 (Lavin & Gray's points 0, +-1, +-2) or 5 (0, +-11/16, +-3/2).
+ *   w3_host == NULL: y_dev [B,H,W,64] = act(conv3x3(x, w2) + b2), act = ReLU if relu2 (b3_host, res_dev, N3, relu3 unused);
+ *   else w3_host f32[N3,64], b3_host f32[N3], res_dev [B,H,W,N3] or NULL:
+ *        y_dev [B,H,W,N3] = act(relu(conv3x3(x, w2) + b2) * w3^T + b3 + res), act = ReLU if relu3 (N3 % 64 == 0). */
+int pr_conv3x3_wino64_nhwc(int device, const void* x_dev, const float* w2_host, const float* b2_host,
+                           const float* w3_host, const float* b3_host, const void* res_dev, void* y_dev, int B, int H,
+                           int W, int Cin, int Cout, int N3, int relu2, int relu3, int form, void* stream);
 
 /* A whole layer1 Bottleneck (SPIN models/hmr.py Bottleneck.forward: conv1 1x1 -> conv2 3x3 64->64 -> conv3 1x1 64->256,
  * BatchNorm folded by the caller, + identity, ReLU) as ONE persistent bf16 kernel (csrc/bottleneck_bf16.hip): exported for

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # pr_build_info() -- printed by bench.py as `library` -- says which build a record came from.
 LIB_PATH = os.environ.get("POSERISK_LIB_PATH") or os.path.join(HERE, "libposerisk_hip.so")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class PoseRiskHipError(RuntimeError):
@@ -68,6 +68,7 @@ SIGNATURES = {
     "pr_conv2d_nhwc": (_I, [_I, _P, _P, _P, _P, _P] + [_I] * 14 + [_P, _P]),
     "pr_conv1x1_dual_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P] + [_I] * 12 + [_P]),
     "pr_conv3x3_conv1x1_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P, _P] + [_I] * 7 + [_P]),
+    "pr_conv3x3_wino64_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P, _P] + [_I] * 9 + [_P]),
     "pr_bottleneck_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pr_bottleneck128_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "pr_bottleneck256_nhwc": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),

@@ -31,7 +31,7 @@ void set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* pr_last_error(void) { return pr::g_last_error.c_str(); }
-int pr_abi_version(void) { return 13; }
+int pr_abi_version(void) { return 14; }
 
 int pr_declare_stream(void* stream, int declared) {
   pr::g_stream_declared = declared != 0;
@@ -296,6 +296,49 @@ int pr_conv3x3_conv1x1_nhwc(int device, const void* x_dev, const float* w2_host,
   p.res3 = (const float*)res_dev; p.y3 = (float*)y_dev;
   p.N3 = N3; p.relu3 = relu3;
   const int st = conv_launch(p, 8, s);
+  const hipError_t e = hipStreamSynchronize(s);
+  if (st != PR_OK) return st;
+  PR_HIP(e);
+  return PR_OK;
+}
+
+int pr_conv3x3_wino64_nhwc(int device, const void* x_dev, const float* w2_host, const float* b2_host, const float* w3_host,
+                           const float* b3_host, const void* res_dev, void* y_dev, int B, int H, int W, int Cin, int Cout, int N3,
+                           int relu2, int relu3, int form, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(x_dev && w2_host && b2_host && y_dev, "pr_conv3x3_wino64_nhwc: null argument");
+  PR_REQUIRE(Cin == 64 && Cout == 64, "pr_conv3x3_wino64_nhwc: Cin = Cout = 64 only (got %d -> %d)", Cin, Cout);
+  PR_REQUIRE(form == 4 || form == 5, "pr_conv3x3_wino64_nhwc: form %d is not 4 or 5", form);
+  PR_REQUIRE(B >= 0 && H > 0 && W > 0, "pr_conv3x3_wino64_nhwc: bad geometry");
+  PR_REQUIRE(!w3_host || (b3_host && N3 > 0 && N3 % 64 == 0), "pr_conv3x3_wino64_nhwc: conv3 needs a bias and N3 %% 64 == 0 (%d)", N3);
+  DeviceGuard g(device);
+  hipStream_t s = (hipStream_t)stream;
+  PR_TRY(refuse_if_capturing(s, "stand-alone test entry"));   // allocates and synchronises: never inside a capture
+  struct Scratch {
+    float* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Scratch() {
+      for (float* q : p)
+        if (q) (void)hipFree(q);
+    }
+  } sc;
+  std::vector<float> u((size_t)36 * 64 * 64), up(u.size());
+  conv_winograd_pack_weights(w2_host, nullptr, 64, 64, form, u.data());
+  conv_wino64_pack_u(u.data(), up.data());
+  const size_t sizes[4] = {up.size(), 64, w3_host ? (size_t)N3 * 64 : 0, w3_host ? (size_t)N3 : 0};
+  const float* src[4] = {up.data(), b2_host, w3_host, b3_host};
+  for (int i = 0; i < 4; ++i) {
+    if (!sizes[i]) continue;
+    PR_HIP(hipMalloc(&sc.p[i], sizes[i] * sizeof(float)));
+    PR_HIP(hipMemcpy(sc.p[i], src[i], sizes[i] * sizeof(float), hipMemcpyHostToDevice));
+  }
+  ConvProblem p;
+  p.B = B; p.H = p.Ho = H; p.W = p.Wo = W; p.Cin = 64; p.Cout = 64; p.KH = p.KW = 3; p.stride = 1; p.pad = 1; p.relu = relu2;
+  p.precision = 0;
+  p.x = (const float*)x_dev; p.w = nullptr; p.bias = sc.p[1]; p.res = nullptr; p.y = w3_host ? nullptr : (float*)y_dev;
+  if (w3_host) {
+    p.w3 = sc.p[2]; p.bias3 = sc.p[3]; p.res3 = (const float*)res_dev; p.y3 = (float*)y_dev; p.N3 = N3; p.relu3 = relu3;
+  }
+  const int st = conv_wino64_launch(p, sc.p[0], form, s);
   const hipError_t e = hipStreamSynchronize(s);
   if (st != PR_OK) return st;
   PR_HIP(e);

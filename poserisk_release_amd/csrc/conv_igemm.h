@@ -105,6 +105,12 @@ int conv_tile_dims(int cfg, int* BM, int* BN);
 size_t conv_winograd_work_floats(const ConvProblem& p, int form);
 int conv_winograd_launch(const ConvProblem& p, const float* u, float* work, int form, hipStream_t stream);
 
+// F(4x4,3x3) of a 64 -> 64 channel 3x3 / stride 1 / pad 1 fp32 convolution in ONE launch (conv_wino64.hip): input transform,
+// 36 small GEMMs and output transform + bias + ReLU inside a workgroup; with p.w3 set, the 1x1 convolution behind it as in
+// conv_fused3_launch (y3 = act(relu(y) * w3^T + bias3 + res3), y itself not written).  `u` = conv_winograd_pack_weights'
+// U of `form` (4 or 5) through conv_wino64_pack_u.  Any H, W: tiles that overhang the map are computed and dropped.
+int conv_wino64_launch(const ConvProblem& p, const float* u, int form, hipStream_t stream);
+
 // A whole layer1 Bottleneck (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + residual, 64 planes, stride 1) as one persistent
 // bf16 kernel (bottleneck_bf16.hip).  x, y: [B,H,W,256] bf16; w1 [64][256], w2 [64][576] (k = tap * 64 + c), w3 [256][64]
 // bf16 with BatchNorm folded and rows permuted by bottleneck_pack_rows_bf16; biases fp32 in channel order.

@@ -241,6 +241,7 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
           bp.lead_tiles = h->b128_lead;
           return bottleneck_bf16_launch(bp, r.s);
         }
+        if (c.u1) return conv_wino64_launch(p, c.u1, h->stage_form[0], r.s);      // layer1's conv2 (+ conv3) as one-launch F(4x4,3x3)
         return c.u ? conv_winograd_launch(p, c.u, h->wino_work[r.chunk], c.wino_form, r.s) : conv_launch(p, cfg, r.s);
       };
       if (h->profile) {

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <utility>
 #include <vector>
 
 namespace pr {
@@ -86,6 +87,12 @@ void conv_winograd_pack_weights(const float* w, const double* scale, int Cout, i
           out[((size_t)(n * i + j) * Cout + o) * Cin + ci] = (float)u;
         }
     }
+}
+
+void conv_wino64_pack_u(const float* u, float* out) {
+  for (int k = 0; k < 36; ++k)
+    for (int co = 0; co < 64; ++co)
+      for (int ci = 0; ci < 64; ++ci) out[(((size_t)k * 4 + (ci >> 4)) * 64 + co) * 16 + (ci & 15)] = u[((size_t)k * 64 + co) * 64 + ci];
 }
 
 // Packed weight rows for the transposed MFMAs: row 32 T + i of the packed matrix is output channel 32 T + sigma(i),
@@ -168,6 +175,9 @@ size_t hmr_weight_floats_impl() {
 struct Ctx {
   HmrPlan* h;
   PlanSink* sink;
+  // U of layer1's one-launch Winograd layers, by plan entry: uploaded behind the last convolution's weights (build)
+  std::vector<std::pair<size_t, std::vector<float>>> u1_pending;
+  int block = 0;      // index of the Bottleneck being planned within its stage (the switch routes layer1 by block)
 };
 
 int upload(Ctx& cx, const std::vector<float>& host, float** out) {
@@ -259,11 +269,21 @@ int add_conv(Ctx& cx, BlobReader& br, ConvSpec spec, bool second = false) {
   PR_TRY(upload(cx, bias, &spec.bias));
   const float* w = f1.w;
   const std::vector<double>& scale = f1.scale;
-  // 3x3 / stride 1 with >= 128 channels (layer2..layer4): Winograd F(2x2,3x3).  layer1 (64 channels at 56x56)
-  // stays direct: its 16 GEMMs would have K = 64 and the V/M passes cost more than the MFMAs they save.
+  // 3x3 / stride 1 with >= 128 channels (layer2..layer4): the handle's Winograd form as three launches (input transform,
+  // grouped GEMMs, output transform).  layer1 (64 channels at 56x56) cannot take that form: V and M would be 115.6 MB each
+  // per layer at B = 64, written once and read once, and the passes cost more than the MFMAs they save.  Its conv2 runs as
+  // F(4x4,3x3) inside ONE kernel instead (conv_wino64.hip: V and M never leave the CU), on layer2's points when layer2's
+  // form is 4 or 5 (stage_form[0], hmr_plan_configure); it is no `wino_m` layer: one launch, no workspace.
   // The form is a property of the handle (pr_hmr_create's conv_form), so one process can hold several.
   const int use_wino = h->stage_form[spec.stage];
-  if (use_wino && h->precision == 0 && spec.k == 3 && spec.stride == 1 && spec.pad == 1 && spec.Cin >= h->wino_min_c &&
+  if (spec.stage == 0 && use_wino && (h->wino_layer1 >= 2 || cx.block == 0) && h->precision == 0 && spec.k == 3 && spec.stride == 1 && spec.pad == 1 && spec.Cin == 64 &&
+      spec.Cout == 64 && spec.Cin == spec.Cin_real) {
+    std::vector<float> u((size_t)36 * 64 * 64), packed(u.size());
+    conv_winograd_pack_weights(w, scale.data(), 64, 64, use_wino, u.data());
+    conv_wino64_pack_u(u.data(), packed.data());
+    cx.u1_pending.emplace_back(h->convs.size(), std::move(packed));
+  }
+  if (spec.stage > 0 && use_wino && h->precision == 0 && spec.k == 3 && spec.stride == 1 && spec.pad == 1 && spec.Cin >= h->wino_min_c &&
       spec.Cin == spec.Cin_real) {
     const int m = conv_winograd_tile(use_wino), n2 = (m + 2) * (m + 2);
     std::vector<float> u((size_t)n2 * spec.Cout * spec.Cin);
@@ -343,6 +363,7 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
     for (int b = 0; b < blocks[L]; ++b) {
       const int pl = planes[L];
       const int stride = (b == 0 && L > 0) ? 2 : 1;
+      cx.block = b;
       // pick 4 free buffers among 1..5 other than cur
       int fr[4], nf = 0;
       for (int i = 1; i <= 5 && nf < 4; ++i)
@@ -506,6 +527,7 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
       inpl = pl * 4;
     }
   h->final_buf = cur;
+  for (const auto& pu : cx.u1_pending) PR_TRY(upload(cx, pu.second, &h->convs[pu.first].u1));
   PR_REQUIRE(blk_no == HmrPlan::kBlocks, "hmr: planned %d blocks", blk_no);
   PR_REQUIRE(layer == kNumConv && (int)h->convs.size() ==
                                       kNumConv - (h->fuse_downsample ? 4 : 0) -
@@ -606,6 +628,9 @@ void hmr_plan_configure(HmrPlan* h, int precision, int conv_form, int max_batch)
   if (const char* e = getenv("POSERISK_PANEL_MAX_K")) h->panel_max_k = atoi(e);                // A/B timing only (0 = off)
   if (const char* e = getenv("POSERISK_REGW")) h->regw = atoi(e) != 0;                         // A/B timing only
   if (const char* e = getenv("POSERISK_SPLITK")) h->splitk = std::max(1, std::min(atoi(e), 8));    // A/B timing only (1 = off)
+  if (const char* e = getenv("POSERISK_WINO_LAYER1")) h->wino_layer1 = std::max(0, std::min(atoi(e), 2));   // 0 | 1 | 2 (changes layer1's rounding)
+  // layer1 follows layer2's form where that is an F(4x4,3x3) one (the one-launch kernel has no F(2x2) form)
+  h->stage_form[0] = precision == 0 && h->wino_layer1 && (h->stage_form[1] == 4 || h->stage_form[1] == 5) ? h->stage_form[1] : 0;
 }
 
 int hmr_plan_build(HmrPlan* plan, const float* blob, size_t n_floats, PlanSink& sink) {

@@ -60,6 +60,11 @@ unsigned short f32_to_bf16_host(float f);
 constexpr float kWa = 11.f / 16.f, kWb = 3.f / 2.f;
 inline int conv_winograd_tile(int form) { return form == 2 ? 2 : 4; }
 void conv_winograd_pack_weights(const float* w_oihw, const double* scale, int Cout, int Cin, int form, float* out_u);
+// The one-launch F(4x4,3x3) kernel of the 64 -> 64 channel layers (conv_wino64.hip) walks the input channels in four slices
+// of 16: U [36][64 co][64 ci] as conv_winograd_pack_weights leaves it -> [36][4 slices][64 co][16 ci], a wave's fragment of a
+// plane and slice one contiguous KB.  kWino64Tiles: tiles per workgroup = the B columns of its MFMA.
+constexpr int kWino64Tiles = 16;
+void conv_wino64_pack_u(const float* u, float* out);
 
 // Packed weight rows for the transposed MFMAs of the whole-Bottleneck kernels: row 32 T + i of the packed matrix is output
 // channel 32 T + sigma(i), sigma(i) = 16 ((i >> 2) & 1) + 4 (i >> 3) + (i & 3).  `src` is [rows][K] (rows % 32 == 0).
@@ -83,6 +88,10 @@ struct ConvSpec {
   float* u = nullptr;            // device, Winograd-domain weights [(m+2)^2][Cout][Cin] (3x3 stride-1 layers of layer2..4)
   int wino_m = 0;                // Winograd output tile (2 or 4), 0 = direct form
   int wino_form = 0;             // ... and the form it belongs to (2, 4, or 5 = F(4x4) on the points 0, +-11/16, +-3/2)
+  // A 64 -> 64 channel 3x3 / stride-1 layer (layer1's conv2) as F(4x4,3x3) inside ONE kernel (conv_wino64.hip), with or
+  // without the conv3 of `w3` behind it: U in conv_wino64_pack_u's layout, built on the form of HmrPlan::stage_form[0] (4 or
+  // 5).  Not a `wino_m` layer: one launch, no V / M workspace.
+  float* u1 = nullptr;
   int cfg = -1;
   int layer = 0;                 // index among the 53 convolutions of the network (execution order), for the profile
   int stage = 0;                 // ResNet stage 0..3 (layer1..layer4); the stem counts as stage 0
@@ -118,6 +127,10 @@ struct ConvSpec {
   // (m+2)^2 products per m x m output tile for a Winograd layer.
   double mfma_macs_per_frame(int k_step) const {
     if (bneck_planes) return macs_per_frame();
+    if (u1) {      // 36 products per 4x4 tile, the idle B columns of a unit's last MFMA included, + conv3 as it stands
+      const int cols = ((W + 3) / 4 + kWino64Tiles - 1) / kWino64Tiles * kWino64Tiles;      // rounded up in integers
+      return (double)((H + 3) / 4) * cols * 36 * Cin * Cout + (double)Ho() * Wo() * N3 * Cout;
+    }
     if (wino_m) {
       const double tiles = (double)((H + wino_m - 1) / wino_m) * ((W + wino_m - 1) / wino_m);
       return tiles * (wino_m + 2) * (wino_m + 2) * Cin * Cout;
@@ -145,8 +158,11 @@ struct HmrPlan {
   int max_batch = 0;
   int precision = 0;  // 0 = fp32 encoder, 1 = bf16 encoder (fp32 accumulate); the regressor is always fp32
   int conv_form = PR_CONV_FORM_BUILTIN_DEFAULT;  // fp32 encoder: 0 = every conv direct, 2 / 4 / 5 = a Winograd form, or a digit per stage
-  int stage_form[4] = {0, 5, 5, 5};  // the form per ResNet stage (layer1 stays direct: 64 channels)
+  int stage_form[4] = {0, 5, 5, 5};  // the form per ResNet stage (layer1: 0 = direct, or layer2's 4 / 5 on the one-launch kernel; hmr_plan_configure)
   int wino_min_c = 128;
+  // layer1's conv2 (64 channels) on the one-launch F(4x4,3x3) kernel when layer2's form is 4 or 5: 0 = none, 1 = block
+  // layer1.0's only, 2 = also layer1.1's and layer1.2's, with or without conv3 behind them (POSERISK_WINO_LAYER1)
+  int wino_layer1 = 1;
   bool fuse_downsample = true;  // first Bottlenecks: conv3 and the downsample branch as one dual-source GEMM
   bool fuse_conv3 = true;       // layer1 blocks 1, 2: conv2 (3x3, 64 channels) and conv3 in one kernel
   bool expand_regs = true;      // bf16 encoder: layer2's / layer3's conv3 + residual with the weights in registers (expand_res_bf16.hip)

@@ -153,6 +153,32 @@ def conv3x3_conv1x1_nhwc(x, w2, b2, w3, b3, residual=None, relu=True, precision=
     return y
 
 
+def conv3x3_wino64_nhwc(x, w2, b2, w3=None, b3=None, residual=None, relu=True, form=5, out=None):
+    """A layer1 conv2 (64 -> 64, 3x3 / stride 1 / pad 1, fp32) as Winograd F(4x4,3x3) in one launch, alone --
+    relu?(conv3x3(x, w2) + b2) -> [B,H,W,64] -- or, with w3 [N3,64] / b3, with conv3 behind it as conv3x3_conv1x1_nhwc:
+    relu?(relu(conv3x3(x, w2) + b2) * w3^T + b3 + residual) -> [B,H,W,N3].  form 4 or 5 (the interpolation points).
+    Other channel counts are refused by the library."""
+    _need_cuda(x, "conv3x3_wino64_nhwc")
+    x = x.contiguous().float()
+    B, H, W, Cin = x.shape
+    w2 = np.ascontiguousarray(w2, dtype=np.float32)
+    b2 = np.ascontiguousarray(b2, dtype=np.float32)
+    Cout = w2.shape[0]
+    fused = w3 is not None
+    if fused:
+        w3 = np.ascontiguousarray(w3, dtype=np.float32).reshape(-1, 64)
+        b3 = np.ascontiguousarray(b3, dtype=np.float32)
+    N3 = w3.shape[0] if fused else 0
+    res = residual.contiguous().float() if residual is not None else None
+    y = _out(out, (B, H, W, N3 if fused else Cout), torch.float32, x.device)
+    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.load().pr_conv3x3_wino64_nhwc(
+        idx, x.data_ptr(), w2.ctypes.data, b2.ctypes.data, w3.ctypes.data if fused else None,
+        b3.ctypes.data if fused else None, res.data_ptr() if res is not None else None, y.data_ptr(), B, H, W, Cin, Cout,
+        N3, int(relu), int(relu), form, _stream(x.device)), "pr_conv3x3_wino64_nhwc")
+    return y
+
+
 def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0):
     """A whole layer1 Bottleneck (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + identity, ReLU after each; BatchNorm folded by
     the caller) in one persistent bf16 kernel.  Without `wd`: x bf16 [B,H,W,256] CUDA, w1 [64,256], identity = x.  With
