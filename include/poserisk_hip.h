@@ -442,6 +442,67 @@ typedef struct pr_render_args {
 size_t pr_render_workspace_bytes(int N, int V, int F, int H, int W);
 int pr_render_overlay(const pr_render_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* r2  annotated score video (ABI 15): frame + track box + score panel, one call a batch */
+/* replaces: the per-frame OpenCV loop of lib/core/base.py:284-327 (cv2.resize INTER_AREA, */
+/*           cv2.putText) and visualize_box lib/utils/vis_utils.py:278-294 (cv2.line)     */
+/* ------------------------------------------------------------------------------------ */
+/* Compose contract.  Integer-exact, so that tests/video_ref.py (numpy) reproduces every byte.
+ *
+ * Canvas.  out u8[N, dst_h, dst_w + panel_w, 3].  The host passes dst_w, dst_h and panel_w (the reference: 720,
+ *   int(H * 720 / W) and 280, base.py:287-290).  Columns [0, dst_w) of canvas n are the image region: source frame src_idx[n]
+ *   (canvas n shows frame n when src_idx is NULL) of frames u8[n_frames,H,W,3] with the box drawn on it, resampled.  Columns
+ *   [dst_w, dst_w + panel_w) are the panel: black with the text lines.  A frame index outside [0, n_frames) zero-fills the
+ *   image region and sets status bit 0 (as pr_crop_frames and pr_render_overlay do); the panel is drawn all the same.  frames
+ *   may be the plain video or what pr_render_overlay wrote.  frames and out share one channel order; the box and line colours
+ *   are three bytes for channels 0, 1, 2 of that order.  1 <= H, W, dst_w, dst_h <= 4096, 0 <= panel_w <= 4096.
+ * Box, on the source BEFORE resampling (vis_utils.py:278-294 draws on the full-size frame, base.py:326 resizes afterwards).
+ *   box int32[N,4] = (x_min, y_min, x_max, y_max), the corners the reference's integer arithmetic gives; x_max < x_min (or a
+ *   NULL box) means no box.  Source pixel (x, y) takes box_rgb when it lies within Chebyshev distance 1 of the rectangle's
+ *   outline: inside [x_min-1, x_max+1] x [y_min-1, y_max+1] and not inside [x_min+2, x_max-2] x [y_min+2, y_max-2]; clipped to
+ *   the frame.  By a reading of OpenCV's thick-line code this differs from the reference's four cv2.line(..., thickness 2)
+ *   calls in at most the four outer corner pixels; that is UNVERIFIED (OpenCV was not available to compare against).
+ * Area resample, any ratio up or down.  On axis x, source cell k covers [k dst_w, (k+1) dst_w) and destination cell i covers
+ *   [i W, (i+1) W) in units of 1 / (W dst_w); ox[i][k] is the integer length of their overlap.  Axis y likewise with H and
+ *   dst_h.  S = sum_j sum_k oy[r][j] ox[i][k] src[j][k][c] is an exact integer, at most 255 H W <= 255 * 2^24 < 2^32: the
+ *   accumulator is uint32 and never wraps (the column sums sum_j oy src <= 255 H < 2^20 are uint32 too).  out = S / (H W)
+ *   rounded half to even.  This is the mathematical box filter that cv2.resize(..., INTER_AREA) (base.py:326) approximates
+ *   in float; OpenCV's bits are not reproduced.
+ * Panel text.  L <= 16 lines per canvas.  lines int32[N,L,5] = (x0, yb, size class s, length, colour c0 | c1 << 8 | c2 << 16):
+ *   an origin (x0, baseline yb) in canvas coordinates as cv2.putText takes it (base.py:296-323).  text u8[N,L,C] holds the
+ *   codes (1 <= C <= 4096; length is clamped to C).  x0 and yb may be any int32, as may the box corners: a line or a box
+ *   edge too far away to reach the canvas or the frame simply draws nothing there.  atlas u8[S,96,CH,CW] is a monospace coverage atlas for codes 32..127 with per-class
+ *   advance adv[s] (1 <= adv[s] <= CW) and ascent[s]; it is the caller's data.  For panel pixel (y, x) and line l:
+ *     k = floor((x - x0) / adv), counted when 0 <= k < length;  u = (x - x0) - k adv;  v = y - (yb - ascent);
+ *     cov = atlas[s][code - 32][v][u] when 0 <= v < CH, else the line leaves the pixel alone;
+ *     out_c = (2 (bg_c (255 - cov) + col_c cov) + 255) div 510       (bg: black, then what earlier lines left)
+ *   Lines apply in index order, later over earlier.  Codes outside 32..127, lengths <= 0 and size classes outside [0, S) draw
+ *   nothing.  Text is clipped to the panel: the image region always shows the image (base.py:326 pastes it over the canvas).
+ *
+ * status int32[N] or NULL: bit 0 as above, else 0.  Argument errors return PR_ERR_INVALID before any device work; N = 0
+ * returns PR_OK.  Asynchronous on `stream`, one launch, no workspace, no allocation, no synchronisation (capturable).  A
+ * canvas depends on no other canvas of the batch. */
+#define PR_VIDEO_MAX_LINES 16
+#define PR_VIDEO_MAX_CLASSES 4
+#define PR_VIDEO_LINE_INTS 5
+typedef struct pr_compose_args {
+  const uint8_t* frames;    /* u8[n_frames,H,W,3] */
+  const int32_t* src_idx;   /* int32[N] or NULL */
+  const int32_t* box;       /* int32[N,4] or NULL */
+  const int32_t* lines;     /* int32[N,L,5]  (may be NULL when L = 0, like text and atlas) */
+  const uint8_t* text;      /* u8[N,L,C] */
+  const uint8_t* atlas;     /* u8[S,96,CH,CW] */
+  uint8_t* out;             /* u8[N,dst_h,dst_w+panel_w,3] */
+  int32_t* status;          /* int32[N] or NULL */
+  int N, n_frames, H, W;
+  int dst_h, dst_w, panel_w;
+  int L, C, S, CH, CW;
+  int adv[PR_VIDEO_MAX_CLASSES], ascent[PR_VIDEO_MAX_CLASSES];
+  uint8_t box_rgb[4];       /* channels 0, 1, 2; [3] unused */
+} pr_compose_args;
+
+int pr_compose_video(const pr_compose_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # pr_build_info() -- printed by bench.py as `library` -- says which build a record came from.
 LIB_PATH = os.environ.get("POSERISK_LIB_PATH") or os.path.join(HERE, "libposerisk_hip.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class PoseRiskHipError(RuntimeError):
@@ -36,6 +36,13 @@ class RenderArgs(C.Structure):
                                            "out", "face_id", "vert_fx", "status")] + \
                [(n, C.c_int) for n in ("N", "V", "F", "P", "n_frames", "H", "W", "bgr")] + \
                [("scale", C.c_float), ("alpha", C.c_float)]
+
+
+class ComposeArgs(C.Structure):
+    """pr_compose_args (include/poserisk_hip.h, the annotated score video)."""
+    _fields_ = [(n, C.c_void_p) for n in ("frames", "src_idx", "box", "lines", "text", "atlas", "out", "status")] + \
+               [(n, C.c_int) for n in ("N", "n_frames", "H", "W", "dst_h", "dst_w", "panel_w", "L", "C", "S", "CH", "CW")] + \
+               [("adv", C.c_int * 4), ("ascent", C.c_int * 4), ("box_rgb", C.c_uint8 * 4)]
 
 
 class FramesOut(C.Structure):
@@ -88,6 +95,7 @@ SIGNATURES = {
                                C.POINTER(FramesOut), _P]),
     "pr_render_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_render_overlay": (_I, [C.POINTER(RenderArgs), _P, C.c_size_t, _P]),
+    "pr_compose_video": (_I, [C.POINTER(ComposeArgs), _P]),
 }
 
 _lib = None

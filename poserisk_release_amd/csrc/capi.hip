@@ -31,7 +31,7 @@ void set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* pr_last_error(void) { return pr::g_last_error.c_str(); }
-int pr_abi_version(void) { return 14; }
+int pr_abi_version(void) { return 15; }
 
 int pr_declare_stream(void* stream, int declared) {
   pr::g_stream_declared = declared != 0;

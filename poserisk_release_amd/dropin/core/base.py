@@ -11,7 +11,8 @@ end of the loop, and with `torch.distributed` initialised every rank takes a con
 the per-frame records are all-gathered once.  Video decoding and tracking (base.py:47-74) are outside the
 accelerated path: `__call__` takes decoded frames + the tracker's dict, finds them in a
 directory, or runs the reference's own front end when cv2 and multi_person_tracker are importable; it writes the
-result text files, the score plots, the debug CSVs and (where cv2 is importable) the annotated mp4.
+result text files, the score plots, the debug CSVs and the annotated video (drawn by OpenCV where cv2 is importable, or
+composed on the GPU with the gpu_video knob).
 """
 import json
 import os.path as osp
@@ -136,6 +137,9 @@ class Predictor:
         # the mesh overlay (render_overlay): args.render_mesh, else cfg.DATASET.render_mesh (False; $POSERISK_CFG can set it)
         knob = getattr(args, 'render_mesh', None)
         self.render_mesh = bool(knob if knob is not None else cfg.DATASET.get('render_mesh', False))
+        # the annotated score video composed on the GPU (write_gpu_video): args.gpu_video, else cfg.DATASET.gpu_video (False)
+        knob = getattr(args, 'gpu_video', None)
+        self.gpu_video = bool(knob if knob is not None else cfg.DATASET.get('gpu_video', False))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
             self.debug_joints = None
@@ -375,9 +379,9 @@ class Predictor:
                                  face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
             yield fidx[i:j], img
 
-    def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
-        """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
-        frame.  Returns the path written."""
+    def _mesh_writer(self, frames, output_path, title, bgr, fps):
+        """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): <output>/<TITLE>_mesh.mp4 where cv2 is importable,
+        else <output>/<TITLE>_mesh/%09d.png (frame number)."""
         import os
         try:
             import cv2
@@ -388,16 +392,79 @@ class Predictor:
             path = osp.join(output_path, name + '.mp4')
             H, W = int(frames.shape[1]), int(frames.shape[2])
             vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*'mp4v'), float(fps), (W, H))
-            for _, img in self.render_overlay(out, frames, title, bgr):
+
+            def write(fr, img):
                 for im in img.cpu().numpy():
                     vw.write(im if bgr else im[..., ::-1])
-            vw.release()
-            return path
+            return write, lambda: (vw.release(), path)[1]
         path = osp.join(output_path, name)
         os.makedirs(path, exist_ok=True)
-        for fr, img in self.render_overlay(out, frames, title, bgr):
+
+        def write(fr, img):
             for f, im in zip(fr, img.cpu().numpy()):
                 _save_png(osp.join(path, '{0:09d}.png'.format(int(f))), im[..., ::-1] if bgr else im)
+        return write, lambda: path
+
+    def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
+        """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
+        frame.  Returns the path written."""
+        write, close = self._mesh_writer(frames, output_path, title, bgr, fps)
+        for fr, img in self.render_overlay(out, frames, title, bgr):
+            write(fr, img)
+        return close()
+
+    # ---- base.py:284-327 on the GPU (the gpu_video knob) ---------------------------------------------------------
+    def write_gpu_video(self, out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
+        """`<TITLE>_video`: every frame of the video at 720 px wide with the target's box, beside the score panel, composed by
+        poserisk_release_amd.video (pr_compose_video) from the arrays score_frames returned.  <output>/<TITLE>_video.mp4 where
+        cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame.  With
+        the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
+        parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
+        that the mesh output is written from the same rendering.  Returns the path written."""
+        import os
+        from poserisk_release_amd import video
+        frames = torch.as_tensor(frames)
+        if frames.device.type != 'cuda':
+            frames = frames.to(self.device)
+        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        _, scores, logs, _ = out[title.lower()]
+        items = (self.reba if title.upper() == 'REBA' else self.rula).eval_items
+        fidx = np.asarray(out['frames'])
+        canvas_h, resize_w, panel_w = video.canvas_size(H, W)
+        draw = video.draw_list(title, n_frames, out['bboxes'], (0, fidx, n_frames), scores, items, logs, canvas_h)
+        overlay = None
+        if self.render_mesh:
+            def overlay(lo, hi):
+                sel = np.nonzero((fidx >= lo) & (fidx < hi))[0]
+                if not sel.size:
+                    return [], None
+                some = dict(out, frames=fidx[sel], bboxes=out['bboxes'][sel])
+                some.update({k: out[k][sel] for k in ('rotmat', 'betas', 'cam') if k in out})
+                parts = list(self.render_overlay(some, frames, title, bgr))      # raises by name without the SMPL parameters
+                numbers, images = np.concatenate([f for f, _ in parts]), torch.cat([img for _, img in parts])
+                if mesh_sink is not None:
+                    mesh_sink(numbers, images)
+                return numbers, images
+        batches = video.annotated_frames(frames, draw, self.batch_size, overlay=overlay)
+        try:
+            import cv2
+        except ImportError:
+            cv2 = None
+        if cv2 is not None:
+            path = osp.join(output_path, title + '_video.mp4')
+            vw = cv2.VideoWriter(path, 0x7634706d, float(fps), (resize_w + panel_w, canvas_h))
+            for canvases in batches:
+                for im in canvases.cpu().numpy():
+                    vw.write(im if bgr else np.ascontiguousarray(im[..., ::-1]))
+            vw.release()
+            return path
+        path = osp.join(output_path, title + '_video')
+        os.makedirs(path, exist_ok=True)
+        i = 0
+        for canvases in batches:
+            for im in canvases.cpu().numpy():
+                _save_png(osp.join(path, '{0:09d}.png'.format(i)), im[..., ::-1] if bgr else im)
+                i += 1
         return path
 
     # ---- base.py:273-282 ------------------------------------------------------------------------------------
@@ -497,8 +564,8 @@ class Predictor:
     def __call__(self, input_path, info_path, output_path, frames=None, tracking_results=None, fps=30.0, bgr=False):
         """The reference's entry point (base.py:126-209) around the accelerated path: front end (given, found or
         the reference's own: `load_front_end`) -> crops, pose, scores on the GPU -> `reba_result.txt` /
-        `rula_result.txt`, `<TITLE>_score.png`, `<TITLE>_video.mp4` (OpenCV drawing: only where cv2 is importable) and
-        with `args.debug` the CSV logs under <output>/debug.  Returns the dict of `score_frames` plus `fps`."""
+        `rula_result.txt`, `<TITLE>_score.png`, `<TITLE>_video.mp4` (OpenCV drawing: only where cv2 is importable; with
+        the gpu_video knob composed on the GPU instead, see write_gpu_video) and with `args.debug` the CSV logs under <output>/debug.  Returns the dict of `score_frames` plus `fps`."""
         import os
         from poserisk_release_amd import reports
         os.makedirs(output_path, exist_ok=True)
@@ -540,12 +607,23 @@ class Predictor:
         pose_str = reports.pose_to_str(out['result'])
         if self.debugging and self.debug_joints is not None:
             reports.save_pose_log_csv(debug_path, timestamp, pose_str, self.debug_joints, self.smpl_model.joints_name_upper)
+        if self.gpu_video and getattr(self, 'visualize', True):
+            frames = torch.as_tensor(frames).to(self.device)       # one upload for both titles' videos (and the mesh)
         for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
             if title.lower() not in out:
                 continue
             final, scores, logs, (level, name) = out[title.lower()]
+            mesh_written = False
             reports.save_score_plot(output_path, title, timestamp, scores)      # base.py:254-262
-            if getattr(self, 'visualize', True):                                # base.py:156,173 (OpenCV only)
+            if getattr(self, 'visualize', True) and self.gpu_video:            # base.py:156,173 on the GPU
+                if self.render_mesh:                # one rendering of the mesh feeds both outputs
+                    sink, close = self._mesh_writer(frames, output_path, title, bgr, fps)
+                    self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=sink)
+                    close()
+                    mesh_written = True
+                else:
+                    self.write_gpu_video(out, frames, output_path, title, bgr, fps)
+            elif getattr(self, 'visualize', True):                              # base.py:156,173 (OpenCV only)
                 fr = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)   # once, host side
                 video = reports.write_annotated_video(output_path, title, fr if bgr else fr[..., ::-1], out['bboxes'],
                                                       timestamp, fps, scores, scorer.eval_items, logs)
@@ -553,7 +631,7 @@ class Predictor:
                     print("OpenCV (cv2) is not importable: the annotated mp4 is skipped, all other outputs are written")
                     self._warned_no_cv2 = True
             reports.write_result_txt(output_path, title, final, level, name)
-            if self.render_mesh:
+            if self.render_mesh and not mesh_written:
                 self.write_mesh_overlay(out, frames, output_path, title, bgr, fps)
             if self.debugging:
                 reports.save_score_csv(debug_path, title, timestamp, scores, scorer.eval_items, logs, scorer.log)

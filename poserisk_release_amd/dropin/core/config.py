@@ -21,6 +21,9 @@ absent from the reference and all optional:
                               on N ranks, one per GPU, frames sharded and gathered once over RCCL
     cfg.DATASET.render_mesh   False | True: Predictor.__call__ also draws the fitted mesh over every track frame
                               (<TITLE>_mesh.mp4, or <TITLE>_mesh/%09d.png without cv2; args.render_mesh overrides it)
+    cfg.DATASET.gpu_video     False | True: Predictor.__call__ composes <TITLE>_video on the GPU (pr_compose_video) instead of
+                              drawing it with OpenCV (<TITLE>_video.mp4, or <TITLE>_video/%09d.png without cv2;
+                              args.gpu_video overrides it)
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -80,7 +83,7 @@ def _defaults(root):
         'DATASET': {'workers': 16, 'batch_size': 8, 'min_frame_ratio': 0.33, 'bbox_scale': 1.2,
                     'default_information': osp.join(core_dir, 'default_information.json'),
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
-                    'render_mesh': False},
+                    'render_mesh': False, 'gpu_video': False},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),
