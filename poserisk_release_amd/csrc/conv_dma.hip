@@ -757,17 +757,16 @@ int conv_dma_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, in
   }
   // Tile quantisation (256 CUs): the tiles beyond the last whole round of 256 run as quarter tiles when that
   // shortens the launch (conv_tail_quarter; same bits).  ConvTuning::tail = 0 turns it off for A/B timing.
-  if (p.tune.tail && BM == 64 && BN == 64 && threads == 256 && da.splitk == 1) {
+  {
     // A quarter block needs as many K-steps as a whole tile and each of them costs it a DMA round trip, so it
     // only disappears behind the whole tiles when they run for at least two rounds (measured: 784 tiles
     // 152 -> 137 us, 392 tiles 154 -> 175 us); with at most 64 tiles every quarter gets a CU to itself.
-    const int min_rounds = p.tune.tail_min_rounds, max_rem = p.tune.tail_max_rem;
-    const int rem = grid % 256, rounds = grid / 256;
-    if ((rounds >= min_rounds && rem > 0 && rem <= max_rem) || grid <= 64) {
-      da.n_full = grid - rem;
-      da.n_tail = 4 * rem;
-      grid = da.n_full + ceil_div(da.n_tail, 8) * 8;
-    }
+    // The rule itself: conv_tail_split (host_plan.h).
+    const bool eligible = p.tune.tail && BM == 64 && BN == 64 && threads == 256 && da.splitk == 1;
+    const ConvTailSplit ts = conv_tail_split(grid, eligible, p.tune.tail_min_rounds, p.tune.tail_max_rem);
+    da.n_full = ts.n_full;
+    da.n_tail = ts.n_tail;
+    grid = ts.grid;
   }
   da.stamps = nullptr;
 #ifdef PR_TIMING_HOOKS

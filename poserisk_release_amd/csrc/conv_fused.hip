@@ -768,8 +768,7 @@ int conv_panel_launch(const ConvProblem& p, hipStream_t stream) {
     pb.relu = p.relu;
     if (pb.M == 0) return PR_OK;
     const int panels = ceil_div(pb.M, 64), nchunks = p.Cout / 64;
-    int nsplit = 1;
-    while (nsplit * 2 <= nchunks && nchunks % (nsplit * 2) == 0 && panels * nsplit < 1536) nsplit *= 2;
+    const int nsplit = conv_panel_nsplit(panels, nchunks);
     pb.nsplit = nsplit;
     pb.chunks = nchunks / nsplit;
     // the attribute is set once per device to what the LARGEST admissible K needs (the launch itself asks for its own K's)
@@ -794,8 +793,7 @@ int conv_panel_launch(const ConvProblem& p, hipStream_t stream) {
   if (pa.M == 0) return PR_OK;
   // work items: row panels x column parts, enough of them to balance the 256 CUs (about 6 per CU where the layer allows)
   const int panels = ceil_div(pa.M, 64), nchunks = p.Cout / 64;
-  int nsplit = 1;
-  while (nsplit * 2 <= nchunks && nchunks % (nsplit * 2) == 0 && panels * nsplit < 1536) nsplit *= 2;
+  const int nsplit = conv_panel_nsplit(panels, nchunks);      // host_plan.h
   pa.nsplit = nsplit;
   pa.chunks = nchunks / nsplit;
   const size_t lds = (size_t)pa.nk * 8192 + 16384, lds_max = (size_t)(kmax / bk) * 8192 + 16384;

@@ -14,23 +14,7 @@ namespace pr {
 
 // kConvBK (floats of K per LDS stage) and the host-side weight packers: host_plan.h
 
-// A/B switches of the conv launches.  Defaults are the measured best.  They are read from the environment ONCE per handle
-// (conv_tuning_from_env, at pr_hmr_create; the stand-alone test entries read them per call) and travel in the
-// ConvProblem, so two handles of one process can differ and nothing is latched per process.
-struct ConvTuning {
-  int force_cfg = -1;        // POSERISK_CONV_CFG=<index>: one tile configuration wherever it fits
-  int tail = 1;              // POSERISK_CONV_TAIL=0: no quarter tiles for the remainder of a launch
-  int tail_min_rounds = 2;   // POSERISK_TAIL_MIN_ROUNDS
-  int tail_max_rem = 128;    // POSERISK_TAIL_MAX_REM
-  int wino_vec = 2;          // POSERISK_WINO_VEC: channels per thread of the F(4x4) transform passes (2 or 4; same bits)
-  int wino_bm = 64, wino_bn = 64;   // POSERISK_WINO_TILE=<BM>x<BN>: tile of the Winograd forms' grouped GEMM (A/B timing)
-  int wino_regw = 1;         // POSERISK_WINO_REGW=0: the grouped GEMM of a Winograd layer with K = 128 / 256 on the tile kernel
-                             // instead of the register-resident-weights kernel (conv_regw_f32.hip)
-  int regw_per_cu = 2;       // POSERISK_REGW_PER_CU: persistent workgroups per CU of conv1x1_regw_f32 (A/B timing)
-  int regw_wt = 0, regw_wnb = 0; // POSERISK_REGW_WT / POSERISK_REGW_WNB: the same for the grouped GEMMs of a Winograd layer
-  int regw_t = 0, regw_nb = 0;   // POSERISK_REGW_T / POSERISK_REGW_NB: 16-pixel tiles and 64-channel blocks per unit of that kernel (0 = its defaults; same bits)
-  int bal_stages = 4;        // POSERISK_BAL_STAGES=5: conv_bal_bf16's LDS ring of 5 stages (all 160 KB) instead of 4 (128 KB)
-};
+// struct ConvTuning (the A/B switches of the conv launches): host_plan.h
 ConvTuning conv_tuning_from_env();
 
 struct ConvProblem {

@@ -92,9 +92,8 @@ int conv_pick_tile_cfg(const ConvProblem& p) {
     // every layer with >= 128 output channels (4.18 ms of conv per step against 4.49 with 256x64) except layer2's short-K
     // expansions with residual, where 128x64 wins (125 vs 140 us); 64-channel 1x1 layers take 128x64, the stem and
     // layer1's 3x3 keep 256x64 (all tiles within 1 %).
-    if (p.Cout % 128 == 0 && p.M() >= 128) return (p.KH == 1 && !p.x2 && p.res && p.Cin <= 128) ? 13 : 12;
-    if (p.M() >= 256) return p.KH == 1 ? 13 : 11;
-    return 8;
+    // The rule itself: conv_tile_cfg_bf16 (host_plan.h).
+    return conv_tile_cfg_bf16(p.M(), p.Cin, p.Cout, p.KH, p.x2 != nullptr, p.res != nullptr);
   }
   // fp32: the 4-wave 64x64 LDS-DMA tile (5 workgroups per CU, quarter tiles for the remainder).  Sweeps of all 23
   // ResNet-50 shapes at B=64 and B=256 (profiles/r01_conv_tile_sweep_b64.txt, ..._b256_fp32.txt): it is the fastest or

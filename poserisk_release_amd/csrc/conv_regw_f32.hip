@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void conv1x1_regw_f32(const RArgs a) {
   // y [groups * M][N]) weight row = 64 NB cb + .., output column = 64 NB (cb % nblk) + .., first row = group * M + kPx pg, and
   // rows >= group * M + M are not this group's.
   const long G = gridDim.x;
-  const int u0 = (int)((long)blockIdx.x * a.units / G), u1 = (int)((long)(blockIdx.x + 1) * a.units / G);
+  const int u0 = conv_regw_run_begin(blockIdx.x, a.units, G), u1 = conv_regw_run_begin((long)(blockIdx.x + 1), a.units, G);
   if (u0 >= u1) return;
 
   const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
@@ -290,21 +290,18 @@ int conv_regw_f32_launch(const ConvProblem& p, hipStream_t stream) {
   // T = 1.  The 36 GEMMs of a Winograd layer keep T = 2, NB = 1: NB = 2 costs layer3's 72 -> 77 us (T = 1) / 82 us (T = 2)
   // with one batch in flight and is level with three.  POSERISK_REGW_T / _NB (plain) and POSERISK_REGW_WT / _WNB (Winograd
   // GEMMs) move them for A/B runs.  Never chosen from the batch, and every (T, NB) gives the same bits anyway.
-  const int nblk64 = p.Cout / 64;
+  // The arithmetic itself: conv_regw_geometry (host_plan.h).
   const bool grouped = p.groups > 1;       // the 36 GEMMs of a Winograd layer: their own pair of knobs
-  int NB = grouped ? (p.tune.regw_wnb > 0 ? p.tune.regw_wnb : 1) : (p.tune.regw_nb > 0 ? p.tune.regw_nb : 2);
-  while (NB > 1 && (nblk64 % NB != 0 || (p.Cin == 256 && NB > 2))) NB >>= 1;
-  int T = grouped ? (p.tune.regw_wt > 0 ? p.tune.regw_wt : 2) : (p.tune.regw_t > 0 ? p.tune.regw_t : 1);
-  if (T != 1 && T != 2) T = 2;
-  const int px = 16 * T;
-  a.pp = ceil_div(a.M, px);
-  a.nblk = nblk64 / NB;
-  a.units = a.pp * a.nblk * p.groups;
   int cus = 256;
   PR_TRY(current_device_cus(&cus));
-  const size_t lds = (size_t)2 * px * p.Cin * 4;
   // two workgroups per CU (64 KB of LDS each at K = 256, T = 2), every one with an equal share of the units
-  const int grid = std::min(a.units, p.tune.regw_per_cu * cus);
+  const RegwGeometry geo = conv_regw_geometry(a.M, p.Cin, p.Cout, p.groups, grouped ? p.tune.regw_wt : p.tune.regw_t,
+                                              grouped ? p.tune.regw_wnb : p.tune.regw_nb, p.tune.regw_per_cu, cus);
+  const int T = geo.T, NB = geo.NB, px = 16 * T, grid = geo.grid;
+  a.pp = geo.pp;
+  a.nblk = geo.nblk;
+  a.units = geo.units;
+  const size_t lds = (size_t)2 * px * p.Cin * 4;
   a.stamps = nullptr;
   a.exp = 0;
 #ifdef PR_TIMING_HOOKS

@@ -238,4 +238,97 @@ void hmr_plan_counts(const HmrPlan& plan, int B, int chunk_cap, int n_chunks, bo
 // in `sizes` (frames; room for max(n_chunks, ceil(B / chunk_cap)) entries), *concurrent = whether they run side by side.
 int hmr_split_batch(int B, int chunk_cap, int n_chunks, bool serial, int* sizes, int max_sizes, bool* concurrent);
 
+// ---- launch geometry -------------------------------------------------------------------------------------------
+// What the launchers decide from a problem's SIZE alone -- the decisions that change with the batch -- as pure functions
+// the launchers call, so that tests/native/launch_geometry.cc can enumerate them per batch size without a device
+// (tests/test_launch_geometry.py: every geometry class that occurs up to 256 frames is run by a committed batch size).
+// A/B switches of the conv launches.  Defaults are the measured best.  They are read from the environment ONCE per handle
+// (conv_tuning_from_env, at pr_hmr_create; the stand-alone test entries read them per call) and travel in the
+// ConvProblem, so two handles of one process can differ and nothing is latched per process.
+struct ConvTuning {
+  int force_cfg = -1;        // POSERISK_CONV_CFG=<index>: one tile configuration wherever it fits
+  int tail = 1;              // POSERISK_CONV_TAIL=0: no quarter tiles for the remainder of a launch
+  int tail_min_rounds = 2;   // POSERISK_TAIL_MIN_ROUNDS
+  int tail_max_rem = 128;    // POSERISK_TAIL_MAX_REM
+  int wino_vec = 2;          // POSERISK_WINO_VEC: channels per thread of the F(4x4) transform passes (2 or 4; same bits)
+  int wino_bm = 64, wino_bn = 64;   // POSERISK_WINO_TILE=<BM>x<BN>: tile of the Winograd forms' grouped GEMM (A/B timing)
+  int wino_regw = 1;         // POSERISK_WINO_REGW=0: the grouped GEMM of a Winograd layer with K = 128 / 256 on the tile kernel
+                             // instead of the register-resident-weights kernel (conv_regw_f32.hip)
+  int regw_per_cu = 2;       // POSERISK_REGW_PER_CU: persistent workgroups per CU of conv1x1_regw_f32 (A/B timing)
+  int regw_wt = 0, regw_wnb = 0; // POSERISK_REGW_WT / POSERISK_REGW_WNB: the same for the grouped GEMMs of a Winograd layer
+  int regw_t = 0, regw_nb = 0;   // POSERISK_REGW_T / POSERISK_REGW_NB: 16-pixel tiles and 64-channel blocks per unit of that kernel (0 = its defaults; same bits)
+  int bal_stages = 4;        // POSERISK_BAL_STAGES=5: conv_bal_bf16's LDS ring of 5 stages (all 160 KB) instead of 4 (128 KB)
+};
+
+#if defined(__HIP__)
+#define PR_HOST_DEVICE __host__ __device__
+#else
+#define PR_HOST_DEVICE
+#endif
+
+// conv_dma_launch's tile quantisation on 256 CUs: of `tiles` 64x64 tiles (split-K parts included) the ones beyond the last
+// whole round of 256 run as quarter tiles -- four 32x32 work items each -- when the whole tiles run for at least
+// `min_rounds` rounds and at most `max_rem` tiles remain, or when there are at most 64 tiles at all (every quarter then has a
+// CU to itself).  grid = workgroups launched: n_full whole tiles, then the n_tail quarters padded to a multiple of 8 (one
+// share per XCD).  `eligible`: the 64x64 / 4-wave tile without split-K, ConvTuning::tail on.
+struct ConvTailSplit {
+  int grid, n_full, n_tail;
+};
+inline ConvTailSplit conv_tail_split(int tiles, bool eligible, int min_rounds, int max_rem) {
+  ConvTailSplit s{tiles, tiles, 0};
+  if (!eligible) return s;
+  const int rem = tiles % 256, rounds = tiles / 256;
+  if ((rounds >= min_rounds && rem > 0 && rem <= max_rem) || tiles <= 64) {
+    s.n_full = tiles - rem;
+    s.n_tail = 4 * rem;
+    s.grid = s.n_full + ceil_div(s.n_tail, 8) * 8;
+  }
+  return s;
+}
+
+// conv_regw_f32_launch: a unit is (NB blocks of 64 output channels, T tiles of 16 pixels) of one of `groups` GEMMs of M rows,
+// unit u = (group * nblk + channel-block group) * pp + pixel group; `grid` persistent workgroups (at most per_cu per CU) take
+// the contiguous runs [conv_regw_run_begin(wg), conv_regw_run_begin(wg + 1)).  t_knob / nb_knob: ConvTuning's pair for the
+// problem's kind (regw_wt / regw_wnb when grouped, regw_t / regw_nb otherwise; 0 = the measured default).
+struct RegwGeometry {
+  int T, NB, pp, nblk, units, grid;
+};
+inline RegwGeometry conv_regw_geometry(int M, int Cin, int Cout, int groups, int t_knob, int nb_knob, int per_cu, int cus) {
+  RegwGeometry g;
+  const int nblk64 = Cout / 64;
+  const bool grouped = groups > 1;       // the 36 GEMMs of a Winograd layer: their own pair of knobs
+  g.NB = nb_knob > 0 ? nb_knob : (grouped ? 1 : 2);
+  while (g.NB > 1 && (nblk64 % g.NB != 0 || (Cin == 256 && g.NB > 2))) g.NB >>= 1;
+  g.T = t_knob > 0 ? t_knob : (grouped ? 2 : 1);
+  if (g.T != 1 && g.T != 2) g.T = 2;
+  g.pp = ceil_div(M, 16 * g.T);
+  g.nblk = nblk64 / g.NB;
+  g.units = g.pp * g.nblk * groups;
+  g.grid = std::min(g.units, per_cu * cus);      // every workgroup an equal share of the units
+  return g;
+}
+PR_HOST_DEVICE inline int conv_regw_run_begin(long wg, int units, long grid) { return (int)(wg * units / grid); }
+// Whether some workgroup's run spans two channel blocks (u / pp changes inside it): it reloads its weights mid-run.
+inline bool conv_regw_run_crosses(const RegwGeometry& g) {
+  for (int wg = 0; wg < g.grid; ++wg) {
+    const int u0 = conv_regw_run_begin(wg, g.units, g.grid), u1 = conv_regw_run_begin(wg + 1, g.units, g.grid);
+    if (u1 > u0 && (u1 - 1) / g.pp != u0 / g.pp) return true;
+  }
+  return false;
+}
+
+// conv_panel_launch: column parts per 64-row panel -- enough work items to balance 256 CUs (about 6 per CU where the layer allows)
+inline int conv_panel_nsplit(int panels, int nchunks) {
+  int nsplit = 1;
+  while (nsplit * 2 <= nchunks && nchunks % (nsplit * 2) == 0 && panels * nsplit < 1536) nsplit *= 2;
+  return nsplit;
+}
+
+// conv_pick_tile_cfg's bf16 half (conv_igemm.hip has the measurements): the tile index by the rows of the launch
+inline int conv_tile_cfg_bf16(int M, int Cin, int Cout, int KH, bool second_source, bool residual) {
+  if (Cout % 128 == 0 && M >= 128) return (KH == 1 && !second_source && residual && Cin <= 128) ? 13 : 12;
+  if (M >= 256) return KH == 1 ? 13 : 11;
+  return 8;
+}
+
 }  // namespace pr

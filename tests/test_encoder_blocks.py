@@ -29,6 +29,11 @@ CONFIGS = {
     "fp32_B64_wino": ("fp32", 64, 64, 1, "default", (47, 10)),
     "fp32_B64_direct": ("fp32", 64, 64, 1, "direct", (47, 0)),
     "fp32_B1": ("fp32", 1, 1, 1, "default", (47, 10)),
+    # one sub-batch each (fp32 has no batch-dependent routing: 47 launches, 10 Winograd layers): 37 frames = whole rounds + a
+    # quarter tail + a ragged last tile in layer2.0's and layer3.0's conv3 + downsample, layer3.0's conv1 and layer4's Winograd GEMMs
+    # (tests/test_launch_geometry.py); 256 = the configs[3] slice
+    "fp32_B37": ("fp32", 37, 37, 1, "default", (47, 10)),
+    "fp32_B256": ("fp32", 256, 256, 1, "default", (47, 10)),
 }
 
 _REFS = {}

@@ -79,10 +79,15 @@ def test_conv_no_bias_no_residual_no_relu(gpu_device):
     # (B, H, Cin_real, Cin, Cout, k, stride, pad): tile counts 40 (all quarters, ragged last tile), 392 (136 tail
     # tiles, per-lane tap decode), 784 (16 tail tiles, scalar tap decode), 3136 (64 tail tiles, 1x1)
     (3, 14, 1024, 1024, 256, 1, 1, 0), (2, 224, 3, 4, 64, 7, 2, 3), (64, 14, 256, 256, 256, 3, 1, 1),
-    (64, 14, 256, 256, 1024, 1, 1, 0)], ids=lambda c: "x".join(map(str, c)))
+    (64, 14, 256, 256, 1024, 1, 1, 0),
+    # whole rounds + a quarter tail + a ragged last tile (M % 64 != 0), which no batch of 64 frames has: 1x1, 114 x 16 = 1824
+    # tiles = 7 rounds + 32 (7252 rows); 3x3 / stride 2, 138 x 4 = 552 = 2 rounds + 40 (8820 rows); the 7x7 stem on a 222 x 222
+    # image, 578 = 2 rounds + 66 (36 963 rows, per-lane tap decode)
+    (37, 14, 256, 256, 1024, 1, 1, 0), (45, 28, 256, 256, 256, 3, 2, 1), (3, 222, 3, 4, 64, 7, 2, 3)],
+    ids=lambda c: "x".join(map(str, c)))
 def test_conv_quarter_tiles_have_the_same_bits(gpu_device, case):
     """The 64x64 kernel computes the tiles beyond the last whole round of 256 CUs as 16x16-MFMA quarter tiles;
-    they must equal, bit for bit, what a whole-tile kernel (128x64: no quarter path) produces."""
+    they must equal, bit for bit, what a whole-tile kernel (128x64: no quarter path) produces -- and both an fp64 conv2d."""
     B, H, Cr, Cin, Cout, k, s, p = case
     g = torch.Generator(device=gpu_device).manual_seed(11)
     x = torch.randn((B, H, H, Cin), generator=g, device=gpu_device)
@@ -95,6 +100,11 @@ def test_conv_quarter_tiles_have_the_same_bits(gpu_device, case):
     y64, _ = ops.conv2d_nhwc(x, w, bias, res, stride=s, pad=p, relu=True, tile_cfg=8)
     y128, _ = ops.conv2d_nhwc(x, w, bias, res, stride=s, pad=p, relu=True, tile_cfg=7)
     assert torch.equal(y64, y128)
+    ref = torch.nn.functional.conv2d(x[..., :Cr].cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
+                                     torch.from_numpy(bias).double(), stride=s, padding=p).permute(0, 2, 3, 1)
+    ref = torch.relu(ref + res.cpu().double())
+    err = float((y64.cpu().double() - ref).abs().max())
+    assert err < 2e-5 * max(1.0, float(ref.abs().max())), err
     y64, _ = ops.conv2d_nhwc(x, w, None, None, stride=s, pad=p, relu=False, tile_cfg=8)
     y128, _ = ops.conv2d_nhwc(x, w, None, None, stride=s, pad=p, relu=False, tile_cfg=7)
     assert torch.equal(y64, y128)
@@ -136,7 +146,11 @@ def test_conv_split_k(gpu_device, case):
 
 
 @pytest.mark.parametrize("m", [2, 4, 5])
-@pytest.mark.parametrize("case", [(3, 28, 128, 128), (5, 14, 256, 256), (6, 7, 512, 512), (2, 9, 64, 192)],
+@pytest.mark.parametrize("case", [(3, 28, 128, 128), (5, 14, 256, 256), (6, 7, 512, 512), (2, 9, 64, 192),
+                                  # tile counts that are no multiple of 64 in every form: 37 frames of 14 x 14 (1813 / 592 tiles; the
+                                  # grouped GEMM's runs of units cross channel blocks and GEMMs), 33 frames of 7 x 7 with 512 channels
+                                  # (528 / 132 tiles: the tile kernel's grouped grid, 4 rounds + 128 / 3 rounds + 96, takes the quarter tail)
+                                  (37, 14, 256, 256), (33, 7, 512, 512)],
                          ids=lambda c: "x".join(map(str, c)))
 def test_conv_winograd_matches_torch_and_direct(gpu_device, case, m):
     """Winograd forms (tile_cfg = -form: 2 = F(2x2,3x3), 4 = F(4x4,3x3) on Lavin & Gray's points, 5 = F(4x4,3x3) on the
@@ -164,7 +178,9 @@ def test_conv_winograd_matches_torch_and_direct(gpu_device, case, m):
 @pytest.mark.parametrize("case", [
     # (B, Ho, C1, H2, C2, stride2, Cout): the four first-Bottleneck tails of ResNet-50 (small batches) + a ragged one
     (2, 56, 64, 56, 64, 1, 256), (2, 28, 128, 56, 256, 2, 512), (3, 14, 256, 28, 512, 2, 1024), (5, 7, 512, 14, 1024, 2, 2048),
-    (1, 5, 64, 9, 128, 2, 64)], ids=lambda c: "x".join(map(str, c)))
+    (1, 5, 64, 9, 128, 2, 64),
+    # fp32: 114 x 16 = 1824 tiles = 7 whole rounds + 32 as quarter blocks, the last of 7252 rows' tiles ragged
+    (37, 14, 256, 28, 512, 2, 1024)], ids=lambda c: "x".join(map(str, c)))
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
 def test_conv_dual_source_matches_torch(gpu_device, case, precision):
     """relu(conv3(t) + downsample(x) + bias) as one GEMM over K = [t's channels | x's channels] (a first Bottleneck's
@@ -1912,7 +1928,10 @@ def test_conv_register_weights_unit_shapes_have_the_same_bits(gpu_device, case, 
 
 @pytest.mark.parametrize("case", [
     # (B, H, Cin, Cout, residual): layer3's conv3, layer2's conv3, layer1's conv1, ragged pixel counts (M % 32 != 0)
-    (4, 14, 256, 1024, True), (3, 28, 128, 512, True), (2, 56, 256, 64, False), (3, 7, 256, 64, True), (1, 5, 128, 192, False)],
+    (4, 14, 256, 1024, True), (3, 28, 128, 512, True), (2, 56, 256, 64, False), (3, 7, 256, 64, True), (1, 5, 128, 192, False),
+    # 454 pixel groups x 8 channel-block pairs = 3632 units on 512 workgroups: runs of 7 or 8 units cross channel blocks
+    # mid-run, and each block's last unit is ragged (7252 rows, % 16 = 4)
+    (37, 14, 256, 1024, True)],
     ids=lambda c: "x".join(map(str, c)))
 def test_conv_register_weights_matches_torch(gpu_device, case):
     """tile_cfg 400 = conv1x1_regw_f32: a wave's 16 x K weight slice stays in registers, only the activations stream through
