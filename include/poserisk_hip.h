@@ -503,6 +503,151 @@ typedef struct pr_compose_args {
 
 int pr_compose_video(const pr_compose_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j1  baseline JPEG frames -> u8[F,H,W,3] on the device, bit-exact with libjpeg         */
+/* replaces: cv2.imread in CropDataset.__getitem__ data/demo_dataset.py:58-59 on the      */
+/*           <output>/tmp/%09d.jpg files the front end writes (lib/core/base.py:47-56)    */
+/* ------------------------------------------------------------------------------------ */
+/* The host half (pr_jpeg_parse, csrc/jpeg_host.cc, no device) reads markers and fills descriptors; the device half
+ * (pr_jpeg_decode, csrc/jpeg.hip) does everything else: nothing is decoded on the host.  No ABI bump: functions were added,
+ * no signature changed.
+ *
+ * Accepted: 8-bit baseline (SOF0), Huffman coded, one component or three with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1,
+ *   ONE interleaved scan, with or without a restart interval, 16 <= width, height <= 4096, 8-bit quantisation tables, Huffman
+ *   table ids 0 and 1.  APPn and COM segments are skipped: the EXIF orientation tag is IGNORED (as cv2.imread with
+ *   IMREAD_IGNORE_ORIENTATION and Pillow's Image.open do; plain cv2.imread would rotate), and an Adobe APP14 colour transform
+ *   flag is not looked at (three components are YCbCr).  Everything else is refused per frame with one of the codes below,
+ *   never guessed at.  A single-component frame's sampling factors mean nothing (one block per MCU) and are stored as 1x1.
+ *
+ * Arithmetic contract.  Integer-exact, so that tests/jpeg_ref.py (numpy) and libjpeg's default decode path (jpeg_idct_islow,
+ *   fancy upsampling, the 16-bit fixed-point YCbCr conversion: what cv2.imread and Pillow run) agree with it byte for byte on
+ *   valid streams.  All shifts are arithmetic; DESCALE(x, n) = (x + (1 << (n-1))) >> n.
+ * Entropy decoding.  Baseline Huffman decoding, receive-and-extend, DC prediction reset to 0 at the start of every restart
+ *   segment, zig-zag order mapped to natural order; coefficients are kept as int16.
+ * IDCT.  jpeg_idct_islow of jpeg-6b (CONST_BITS 13, PASS1_BITS 2) on the dequantised block d = coefficient * quantiser
+ *   (natural order): pass 1 down the columns with DESCALE(., 11), pass 2 along the rows with DESCALE(., 18).  One 1-D pass on
+ *   i0..i7:
+ *     z1=(i2+i6)*4433; t2=z1-i6*15137; t3=z1+i2*6270
+ *     t0=(i0+i4)<<13;  t1=(i0-i4)<<13
+ *     t10=t0+t3; t13=t0-t3; t11=t1+t2; t12=t1-t2
+ *     a0=i7; a1=i5; a2=i3; a3=i1
+ *     z1=a0+a3; z2=a1+a2; z3=a0+a2; z4=a1+a3; z5=(z3+z4)*9633
+ *     a0*=2446; a1*=16819; a2*=25172; a3*=12299
+ *     z1*=-7373; z2*=-20995; z3=z3*-16069+z5; z4=z4*-3196+z5
+ *     a0+=z1+z3; a1+=z2+z4; a2+=z2+z3; a3+=z1+z4
+ *     out0..7 = t10+a3, t11+a2, t12+a1, t13+a0, t13-a0, t12-a1, t11-a2, t10-a3      (each DESCALEd)
+ *   sample = x = (out + 128) & 1023, then 0..255 -> x, 256..511 -> 255, 512..1023 -> 0 (libjpeg's range-limit table, its wrap
+ *   included).  libjpeg's shortcuts for all-zero AC terms give the same values and do not exist here.
+ *   32-bit evaluation.  libjpeg computes in `long`; the kernel computes in 32-bit two's-complement (unsigned arithmetic, one
+ *   arithmetic shift at the end).  A pass is +, -, * by constants and <<: ring operations, so the 32-bit value of an output
+ *   before DESCALE equals the 64-bit one whenever the latter fits int32, whatever the intermediates did.  Each output is
+ *   sum_k c_k i_k with sum_k |c_k| <= 61214 (the largest row of the pass as a matrix; 8192 + 11363 + 10703 + 9633 + 8192 +
+ *   6437 + 4433 + 2260 = 61213 for out0, 61214 for out2 and out5), so with every input of a pass at most
+ *   PR_JPEG_IDCT_BOUND = 35079 in magnitude, |out| + 2^17 <= 61214 * 35079 + 131072 = 2 147 457 978 < 2^31: exact.  The kernel
+ *   checks exactly that -- every dequantised coefficient AND every pass-1 result within +-35079 -- and sets
+ *   PR_JPEG_ST_IDCT_RANGE for a frame with a block outside; such a block is computed the same way (wrapped), not differently.
+ *   In terms of the dequantised coefficients alone: all |d| <= 1173 suffices (then every pass-1 result is at most
+ *   (61214 * 1173 + 1024) >> 11 = 35061).  An 8-bit image's DCT has |d| <= 1024 plus half a quantiser step, and pass 1 is
+ *   the column transform scaled by 4: valid streams are far inside the bound.  The golden streams, saturating noise at
+ *   quality 100 among them, reach |d| = 680 and |pass-1 result| = 3619.
+ * Upsampling (libjpeg's "fancy" upsampling).  A component's own size is dw = ceil(W h / hmax), dh = ceil(H v / vmax); the
+ *   block padding beyond it is never read.  s = the component's samples, r = source row, i = source column:
+ *     1x1   copy.
+ *     h2v1  out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2, except out[0] = s[0] and
+ *           out[2dw-1] = s[dw-1].
+ *     h2v2  vertical: c[i] = 3 s[r][i] + s[r'][i] with r' = r-1 for the even output row 2r and r+1 for the odd one, clamped
+ *           to 0..dh-1 (libjpeg's duplicated context rows at the image's top and bottom, not at block boundaries);
+ *           horizontal: out[2i] = (3 c[i] + c[i-1] + 8) >> 4, out[2i+1] = (3 c[i] + c[i+1] + 7) >> 4, with
+ *           out[0] = (4 c[0] + 8) >> 4 and out[2dw-1] = (4 c[dw-1] + 7) >> 4.
+ *   The result is cropped to H x W.
+ * Colour.  With cb and cr minus 128: R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb + 32768 - 46802 cr) >> 16),
+ *   B = y + ((116130 cb + 32768) >> 16), each clamped to 0..255.  One component gives gray in all three channels.  out is
+ *   RGB, or BGR (cv2.imread's order) when bgr != 0: the layout pr_crop_frames, pr_render_overlay and pr_compose_video take.
+ *
+ * Memory safety (on ANY bytes, valid or not).  Every byte the device reads from `data` lies inside its segment's
+ *   [begin, end), itself checked against data_bytes; past the end (or at a marker) the bit reader yields zero bits and, once
+ *   such a bit is consumed, sets PR_JPEG_ST_TRUNCATED; a run that would push a coefficient index past 63 ends the block with
+ *   PR_JPEG_ST_BAD_RUN; a code no table holds ends the segment with PR_JPEG_ST_BAD_CODE; a DC value that
+ *   leaves int16 (no 8-bit image has one beyond +-2048) is stored truncated with PR_JPEG_ST_COEF_RANGE; blocks never written stay zero;
+ *   every descriptor field that forms an address (frame and table-set indices, sizes, sampling, selectors) is checked on the
+ *   device and a frame whose descriptor fails gets PR_JPEG_ST_REFUSED and zero pixels.  A frame's workspace and pixels are its
+ *   own: a bad frame never touches another frame's.  Parity with libjpeg on corrupt streams is NOT promised, only bounds and
+ *   a non-zero status. */
+#define PR_JPEG_IDCT_BOUND 35079
+#define PR_JPEG_LOOK_BITS 9
+enum { /* bits of pr_jpeg_decode's status[f] */
+  PR_JPEG_ST_REFUSED = 1, PR_JPEG_ST_TRUNCATED = 2, PR_JPEG_ST_BAD_RUN = 4, PR_JPEG_ST_BAD_CODE = 8, PR_JPEG_ST_IDCT_RANGE = 16,
+  PR_JPEG_ST_COEF_RANGE = 32
+};
+enum { /* pr_jpeg_parse's parse_status[f]; pr_jpeg_refusal_name gives the words */
+  PR_JPEG_OK = 0, PR_JPEG_E_NOT_JPEG = 1, PR_JPEG_E_TRUNCATED = 2, PR_JPEG_E_PROGRESSIVE = 3, PR_JPEG_E_EXTENDED = 4,
+  PR_JPEG_E_ARITHMETIC = 5, PR_JPEG_E_PRECISION = 6, PR_JPEG_E_COMPONENTS = 7, PR_JPEG_E_SAMPLING = 8, PR_JPEG_E_SCANS = 9,
+  PR_JPEG_E_QUANT16 = 10, PR_JPEG_E_DIMENSIONS = 11, PR_JPEG_E_SIZE_DIFFERS = 12, PR_JPEG_E_TABLE = 13, PR_JPEG_E_MARKER = 14,
+  PR_JPEG_E_RESTARTS = 15, PR_JPEG_E_COUNT = 16
+};
+typedef struct pr_jpeg_hufftab { /* one Huffman table as the device decodes it */
+  uint16_t look[1 << PR_JPEG_LOOK_BITS]; /* next 9 bits -> length << 8 | symbol for codes of <= 9 bits, else 0 */
+  int32_t maxcode[17];                   /* [l], l = 1..16: the largest code of length l, -1 when there is none */
+  int32_t valoff[17];                    /* [l]: index into vals of length l's first code, minus that code */
+  uint8_t vals[256];                     /* symbols in code order */
+  int32_t defined;
+} pr_jpeg_hufftab;
+typedef struct pr_jpeg_huff { /* the tables in force at a frame's SOS: DC 0, DC 1, AC 0, AC 1 */
+  pr_jpeg_hufftab tab[4];
+} pr_jpeg_huff;
+typedef struct pr_jpeg_frame {
+  int32_t width, height;
+  int32_t ncomp;                     /* 1 or 3; 0 = refused by the parser (the device zero-fills the frame) */
+  int32_t hs, vs;                    /* luma sampling: 1x1, 2x1 or 2x2 (chroma is 1x1) */
+  int32_t restart_interval;          /* MCUs per restart segment, 0 = none */
+  int32_t first_segment, n_segments; /* this frame's run of the segment array */
+  int32_t huff_set;                  /* index into the pr_jpeg_huff array (identical sets of a call are stored once) */
+  int32_t dc_sel[3], ac_sel[3];      /* per component: 0 or 1 */
+  uint16_t quant[3][64];             /* per component, natural order */
+} pr_jpeg_frame;
+typedef struct pr_jpeg_segment { /* one entropy-coded segment = one unit of device parallelism */
+  int64_t begin, end;            /* byte range in `data`; end is where the marker behind it starts */
+  int32_t frame, first_mcu;
+} pr_jpeg_segment;
+
+/* data_host: the files of the call back to back; file f is bytes [offsets_host[f], offsets_host[f+1]) (int64[F+1], ascending,
+ * offsets_host[0] >= 0).  H, W: the size every frame must have, or 0, 0 to adopt the first accepted frame's.  Fills
+ * frames_host[F], parse_status_host[F] (PR_JPEG_OK or a refusal; a refused frame has ncomp = 0), up to segment_capacity
+ * segments and huff_capacity table sets, and counts_host[4] = segments used, table sets used, H, W.  Returns PR_OK also when
+ * frames were refused (the last refusal is named in pr_last_error with its frame index), PR_ERR_CAPACITY when a capacity
+ * was too small (counts_host then holds what is needed; nothing else is valid), PR_ERR_INVALID for a null pointer, F < 0 or
+ * offsets out of order, before anything is dereferenced.  F = 0 is legal.  Segment ranges are absolute offsets in data_host
+ * and always lie inside their file.  Never reads outside [offsets_host[0], offsets_host[F]). */
+int pr_jpeg_parse(const uint8_t* data_host, const int64_t* offsets_host, int F, int H, int W, pr_jpeg_frame* frames_host,
+                  pr_jpeg_segment* segments_host, int segment_capacity, pr_jpeg_huff* huff_host, int huff_capacity,
+                  int32_t* parse_status_host, int32_t* counts_host);
+const char* pr_jpeg_refusal_name(int code);
+
+/* Device memory pr_jpeg_decode needs for F frames of H x W: int16 coefficients and u8 component planes at block-padded size. */
+size_t pr_jpeg_workspace_bytes(int F, int H, int W);
+
+/* All device pointers: data u8[data_bytes] (what pr_jpeg_parse read, uploaded), frames / segments / huff its descriptors
+ * uploaded unchanged, out u8[F,H,W,3] (4-byte aligned for dword stores; any other address is written byte by byte), status
+ * int32[F] (required; bits PR_JPEG_ST_*).  The workspace must be 16-byte aligned.  Three kernels (entropy decode: one lane per segment; dequantise + IDCT: one lane per block;
+ * upsample + colour: one lane per four pixels) behind one asynchronous clear of the coefficients and the status words.
+ * Argument errors (null pointers, sizes outside 16..4096, a workspace below pr_jpeg_workspace_bytes or misaligned, negative
+ * counts, segments without data or tables) return
+ * PR_ERR_INVALID by name before any device work; F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no blocking
+ * copy, no synchronisation (capturable). */
+typedef struct pr_jpeg_args {
+  const uint8_t* data;
+  const pr_jpeg_frame* frames;
+  const pr_jpeg_segment* segments;
+  const pr_jpeg_huff* huff;
+  uint8_t* out;
+  int32_t* status;
+  int64_t data_bytes;
+  int F, H, W;
+  int n_segments, n_huff;
+  int bgr;
+} pr_jpeg_args;
+int pr_jpeg_decode(const pr_jpeg_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -487,7 +487,12 @@ class Predictor:
         Video decoding and multi-person tracking are outside the accelerated path; this only finds them:
           1. a directory with `frames.npy` (uint8 [F,H,W,3] RGB) and `tracking.pkl` (multi_person_tracker's
              dict {id: {'bbox': [n,4] (cx,cy,w,h), 'frames': [n]}}), optional `fps.txt`;
-          2. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
+          2. a directory without `frames.npy` but with JPEG frames (`*.jpg` / `*.jpeg`, sorted by name: what the reference's
+             front end leaves under <output>/tmp, what `ffmpeg -i video %09d.jpg` or a camera writes) and `tracking.pkl`,
+             optional `fps.txt`: the files are decoded on the GPU, bit-exact with cv2.imread's pixels
+             (poserisk_release_amd/jpeg.py), and the frames come back as a device tensor, RGB.  A frame that is not
+             baseline JPEG, has another size than the first or is damaged raises, naming the file and the reason;
+          3. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
              frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
              written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
              the same JPEG-decoded pixels as the reference's CropDataset."""
@@ -499,12 +504,28 @@ class Predictor:
             fps_file = osp.join(input_path, 'fps.txt')
             fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
             return frames, False, fps, tracking
+        if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'tracking.pkl')):
+            from poserisk_release_amd import jpeg
+            names = jpeg.list_frames(input_path)
+            if names:
+                paths = [osp.join(input_path, n) for n in names]
+                frames, status = jpeg.decode_files(paths, self.device)
+                bad = jpeg.bad_frames(paths, status)
+                if bad:
+                    raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
+                                       + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+                with open(osp.join(input_path, 'tracking.pkl'), 'rb') as f:
+                    tracking = pickle.load(f)
+                fps_file = osp.join(input_path, 'fps.txt')
+                fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
+                return frames, False, fps, tracking
         try:
             import cv2
             from multi_person_tracker import MPT
         except ImportError as e:
             raise RuntimeError(
-                f"{input_path!r} is not a directory with frames.npy + tracking.pkl, and the reference's front end "
+                f"{input_path!r} is neither a directory with frames.npy + tracking.pkl nor one with JPEG frames "
+                f"(*.jpg, decoded on the GPU) + tracking.pkl, and the reference's front end "
                 f"(cv2 video decoding, multi_person_tracker) is not importable here ({e}); decode and track outside, "
                 "then call Predictor.score_frames(frames, tracking_results, info)") from e
         import os
@@ -545,7 +566,8 @@ class Predictor:
         if rank == 0:
             try:
                 frames, bgr, fps, tracking = self.load_front_end(input_path, output_path)
-                frames = torch.as_tensor(np.ascontiguousarray(frames))
+                # a device tensor (the JPEG folder case) stays where it is; arrays become one contiguous host tensor
+                frames = frames.contiguous() if isinstance(frames, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(frames))
                 meta = [dict(shape=tuple(frames.shape), bgr=bool(bgr), fps=float(fps), tracking=tracking)]
             except Exception as e:               # the other ranks are waiting in the broadcast: tell them, then raise
                 meta, err = [dict(error=f"{type(e).__name__}: {e}")], e
@@ -558,6 +580,8 @@ class Predictor:
             frames = torch.empty(m['shape'], dtype=torch.uint8, device=self.device if on_gpu else 'cpu')
         elif on_gpu:
             frames = frames.to(self.device)
+        else:
+            frames = frames.cpu()                    # gloo broadcasts host memory
         dist.broadcast(frames, src=0)
         return frames, m['bgr'], m['fps'], m['tracking']
 

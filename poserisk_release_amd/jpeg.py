@@ -1,0 +1,211 @@
+"""Baseline JPEG frames decoded on the GPU, bit-exact with libjpeg's default path (what cv2.imread and Pillow run): the front
+of the accelerated path for a folder of frames as the reference's front end writes it (`<output>/tmp/%09d.jpg`,
+lib/core/base.py:47-56, read back by CropDataset with cv2.imread).  The contract is in include/poserisk_hip.h (section j1);
+the marker parser is csrc/jpeg_host.cc (host, no device), everything else csrc/jpeg.hip.
+
+`list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
+go through ONE pinned buffer and ONE upload, then pr_jpeg_decode."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# pr_jpeg_frame, pr_jpeg_segment, pr_jpeg_hufftab / pr_jpeg_huff as numpy records (tests compare them with the C structs)
+FRAME_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"),
+                        ("restart_interval", "<i4"), ("first_segment", "<i4"), ("n_segments", "<i4"), ("huff_set", "<i4"),
+                        ("dc_sel", "<i4", (3,)), ("ac_sel", "<i4", (3,)), ("quant", "<u2", (3, 64))])
+SEGMENT_DTYPE = np.dtype([("begin", "<i8"), ("end", "<i8"), ("frame", "<i4"), ("first_mcu", "<i4")])
+HUFFTAB_DTYPE = np.dtype([("look", "<u2", (512,)), ("maxcode", "<i4", (17,)), ("valoff", "<i4", (17,)), ("vals", "u1", (256,)),
+                          ("defined", "<i4")])
+HUFF_DTYPE = np.dtype([("tab", HUFFTAB_DTYPE, (4,))])
+ST_REFUSED, ST_TRUNCATED, ST_BAD_RUN, ST_BAD_CODE, ST_IDCT_RANGE, ST_COEF_RANGE = 1, 2, 4, 8, 16, 32
+_ST_NAMES = ((ST_REFUSED, "refused (descriptor or segment range invalid)"), (ST_TRUNCATED, "entropy-coded data ends early"),
+             (ST_BAD_RUN, "a zero run leaves the block"), (ST_BAD_CODE, "a Huffman code no table holds"),
+             (ST_IDCT_RANGE, "coefficients outside the 32-bit IDCT bound"), (ST_COEF_RANGE, "a DC value outside int16"))
+# Frames per pr_jpeg_decode call, from profiles/jpeg_decode.json (MI355X, 800x450 4:2:0 quality 95, scripts/bench_jpeg.py).  A frame
+# without restart markers -- what cv2.imwrite writes -- is one serial chain on one lane and takes 112 ms whether 64 or 256 of
+# them are in flight, so the rate is the chunk: decode_files gives 571 / 2220 / 5142 frames/s at 64 / 256 / 1024 (Pillow on 16
+# threads: 2033).  Frames with a restart marker per MCU row peak at 256 (18.9 k, 13.3 k at 1024, where one chunk is the whole
+# measured list and nothing overlaps), far above the CPU either way: the restart-free case decides.  Workspace 3.3 MB a frame.
+DEFAULT_CHUNK = 1024
+_EXT = (".jpg", ".jpeg")
+
+
+def status_text(st):
+    """The words for a pr_jpeg_decode status."""
+    return "; ".join(t for bit, t in _ST_NAMES if st & bit) or "ok"
+
+
+def refusal_name(code):
+    return _lib.load().pr_jpeg_refusal_name(int(code)).decode()
+
+
+def list_frames(directory):
+    """The frame files of `directory`: names ending in .jpg / .jpeg (any case), sorted -- position in that order is the frame
+    index, as in the reference's sorted(os.listdir) (multi_person_tracker's ImageFolder, CropDataset).  A .png among them is
+    refused by name: there is no PNG decoder here.  Other files (tracking.pkl, fps.txt) are ignored."""
+    names = sorted(os.listdir(directory))
+    png = [n for n in names if n.lower().endswith(".png")]
+    if png:
+        raise ValueError(f"{os.path.join(directory, png[0])!r}: PNG frames are not supported (there is no PNG decoder here); "
+                         "convert the frames to baseline JPEG or pass frames.npy")
+    return [n for n in names if n.lower().endswith(_EXT)]
+
+
+def _packed(blobs):
+    offsets = np.zeros(len(blobs) + 1, np.int64)
+    np.cumsum([len(b) for b in blobs], out=offsets[1:])
+    return offsets
+
+
+def _parse_into(data, offsets, H, W, frames, segs, huff, pstatus):
+    """pr_jpeg_parse into caller-owned numpy arrays -> (status code, counts int32[4] = segments, table sets, H, W)."""
+    counts = np.zeros(4, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = _lib.load().pr_jpeg_parse(ptr(data), ptr(offsets), len(offsets) - 1, int(H), int(W), ptr(frames), ptr(segs), len(segs),
+                                   ptr(huff), len(huff), ptr(pstatus), ptr(counts))
+    return rc, counts
+
+
+def parse(blobs, H=0, W=0):
+    """Host half on a list of bytes objects: (frames FRAME_DTYPE[F], segments SEGMENT_DTYPE[S], huff HUFF_DTYPE[T],
+    parse_status int32[F], H, W, offsets int64[F+1]).  Refused frames have parse_status != 0 (refusal_name gives the words)."""
+    offsets = _packed(blobs)
+    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    F = len(blobs)
+    frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
+    seg_cap, huff_cap = 64 + 2 * F, 4
+    while True:
+        segs, huff = np.zeros(seg_cap, SEGMENT_DTYPE), np.zeros(huff_cap, HUFF_DTYPE)
+        rc, counts = _parse_into(data, offsets, H, W, frames, segs, huff, pstatus)
+        if rc != -4:                                             # PR_ERR_CAPACITY: counts says what is needed
+            _lib.check(rc, "pr_jpeg_parse")
+            return frames, segs[:counts[0]], huff[:counts[1]], pstatus, int(counts[2]), int(counts[3]), offsets
+        seg_cap, huff_cap = max(seg_cap, int(counts[0])), max(huff_cap, int(counts[1]))
+
+
+def workspace_bytes(F, H, W):
+    return int(_lib.load().pr_jpeg_workspace_bytes(int(F), int(H), int(W)))
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None):
+    """Decode F baseline JPEG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread
+    gives with bgr=True).  Returns (frames, status int32[F] on the device): status[f] != 0 marks a frame that was refused
+    (bit 0; its pixels are zero) or whose stream was damaged; `bad_frames` puts the reasons into words.  Per chunk of `chunk`
+    files the bytes are read into ONE pinned host buffer, the parser writes its descriptors behind them in the same buffer, and
+    ONE asynchronous copy uploads it; the decode neither allocates nor synchronises (include/poserisk_hip.h, pr_jpeg_decode).
+    The host waits for chunk k's upload (not its decode) before it reads chunk k + 1 into the buffer."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PoseRiskHipError("decode_files: the decoder runs on the GPU only (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    items = list(paths_or_bytes)
+    F, chunk = len(items), max(int(chunk), 1)
+    lib = _lib.load()
+    H, W, seg_per_frame = 0, 0, 2
+    frames_out = status = pinned = ws = uploaded = first_refusal = None
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        for lo in range(0, F, chunk):
+            part = items[lo:lo + chunk]
+            n = len(part)
+            sizes = [os.path.getsize(p) if isinstance(p, (str, os.PathLike)) else len(p) for p in part]
+            offsets = np.zeros(n + 1, np.int64)
+            np.cumsum(sizes, out=offsets[1:])
+            total, seg_room = int(offsets[-1]), 64 + seg_per_frame * n
+            # [file bytes | frames | segments | table sets]: the parser reads the bytes where they lie and writes beside them
+            o_fr = _align(max(total, 1))
+            o_seg = _align(o_fr + n * FRAME_DTYPE.itemsize)
+            o_huff = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
+            room = o_huff + n * HUFF_DTYPE.itemsize
+            if uploaded is not None:
+                uploaded.synchronize()                           # the previous chunk has left the buffer
+                uploaded = None
+            if pinned is None or pinned.numel() < room:
+                pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
+            host = pinned.numpy()
+            for p, a, b in zip(part, offsets[:-1], offsets[1:]):
+                if isinstance(p, (str, os.PathLike)):
+                    with open(p, "rb") as f:
+                        got = f.readinto(memoryview(host[a:b]))
+                    if got != b - a:
+                        raise OSError(f"{p!r} changed size while it was read")
+                else:
+                    host[a:b] = np.frombuffer(bytes(p), np.uint8)
+            pst = np.zeros(n, np.int32)
+            while True:
+                fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
+                segs = host[o_seg:o_seg + seg_room * SEGMENT_DTYPE.itemsize].view(SEGMENT_DTYPE)
+                huff = host[o_huff:o_huff + n * HUFF_DTYPE.itemsize].view(HUFF_DTYPE)
+                rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, segs, huff, pst)
+                if rc != -4:                                     # PR_ERR_CAPACITY: more restart segments than guessed
+                    _lib.check(rc, "pr_jpeg_parse")
+                    break
+                # parse again where the bytes lie, with the room the parser asked for; later chunks start from what this one
+                # needed a frame (a folder one encoder wrote has one restart interval)
+                seg_room = int(counts[0])
+                seg_per_frame = max(seg_per_frame, -(-seg_room // n))
+                o_huff = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
+                room = o_huff + n * HUFF_DTYPE.itemsize
+                if pinned.numel() < room:
+                    bigger = torch.empty(room, dtype=torch.uint8).pin_memory()
+                    bigger[:total] = pinned[:total]
+                    pinned, host = bigger, bigger.numpy()
+            n_segs, n_huff = int(counts[0]), int(counts[1])
+            if H == 0 and pst.any() and first_refusal is None:
+                first_refusal = (lo + int(np.nonzero(pst)[0][0]), refusal_name(pst[np.nonzero(pst)[0][0]]))
+            if H == 0 and counts[2]:
+                H, W = int(counts[2]), int(counts[3])
+                frames_out = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
+                if tuple(frames_out.shape) != (F, H, W, 3) or frames_out.dtype != torch.uint8 or not frames_out.is_contiguous() \
+                        or frames_out.device != device:
+                    raise ValueError(f"out must be a contiguous uint8 {[F, H, W, 3]} tensor on {device}")
+                status = torch.full((F,), ST_REFUSED, dtype=torch.int32, device=device)   # chunks before the first size
+                frames_out[:lo].zero_()
+            if H == 0:
+                continue                                         # nothing accepted so far: no size to decode at
+            used = o_huff + n_huff * HUFF_DTYPE.itemsize
+            dev = torch.empty(used, dtype=torch.uint8, device=device)
+            dev.copy_(pinned[:used], non_blocking=True)          # the chunk's one upload
+            uploaded = torch.cuda.Event()
+            uploaded.record(stream)
+            need = workspace_bytes(n, H, W)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=device)
+            base = dev.data_ptr()
+            args = _lib.JpegArgs(base, base + o_fr, base + o_seg, base + o_huff, frames_out[lo:lo + n].data_ptr(),
+                                 status[lo:lo + n].data_ptr(), total, n, H, W, n_segs, n_huff, int(bool(bgr)))
+            _lib.check(lib.pr_jpeg_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode")
+            dev.record_stream(stream)
+            ws.record_stream(stream)
+        if uploaded is not None:
+            uploaded.synchronize()
+    if frames_out is None:
+        if first_refusal:
+            raise _lib.PoseRiskHipError(f"decode_files: no frame was accepted; frame {first_refusal[0]}: {first_refusal[1]}")
+        frames_out = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
+        status = torch.zeros(0, dtype=torch.int32, device=device)
+    return frames_out, status
+
+
+def bad_frames(paths_or_bytes, status):
+    """[(frame index, reason)] for every frame of a decode_files call whose status is non-zero (one device -> host copy; a
+    refused frame's file is parsed again on its own to name the parser's reason)."""
+    items, st, out = list(paths_or_bytes), status.cpu().numpy(), []
+    for i in np.nonzero(st)[0]:
+        why = status_text(int(st[i]))
+        if st[i] & ST_REFUSED:
+            p = items[i]
+            blob = open(p, "rb").read() if isinstance(p, (str, os.PathLike)) else bytes(p)
+            _, _, _, pst, h, w, _ = parse([blob])
+            why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
+        out.append((int(i), why))
+    return out
