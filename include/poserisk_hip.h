@@ -177,8 +177,9 @@ int pr_hmr_conv_form(pr_hmr_t* h);
  *   x_dev f32[B,H,W,Cin] (Cin % 4 == 0), w_host f32[Cout,Cin_real,KH,KW] (PyTorch OIHW;
  *   Cin_real <= Cin, extra input channels are treated as zero), bias_host f32[Cout] or NULL,
  *   res_dev f32[B,Ho,Wo,Cout] or NULL, y_dev f32[B,Ho,Wo,Cout].  Cout % 64 == 0.
- * tile_cfg -1 selects the built-in heuristic, >= 6 a tile configuration index (pr_conv_num_tile_cfgs(); 0..5 are reserved:
- * the first-generation kernel they selected was retired and they return PR_ERR_INVALID),
+ * tile_cfg -1 selects the built-in heuristic, >= 6 a tile configuration index (pr_conv_num_tile_cfgs(); 0..5 and 18 are
+ * reserved: the first-generation kernel and the 256x256 bf16 tile they selected were retired, they return PR_ERR_INVALID and
+ * the message says "retired"),
  * -2 / -4 the Winograd F(2x2,3x3) / F(4x4,3x3) form (the encoder runs its 3x3 / stride-1 layers with >= 128
  * channels as F(4x4,3x3); fp32, pad 1, no residual, Cin % 32 == 0: input transform, 16 / 36 grouped GEMMs in one
  * launch, output transform), 100 the row-panel form of a short-K 1x1 convolution, 300 (bf16, 1x1, Cin 128 -> Cout 512, with bias

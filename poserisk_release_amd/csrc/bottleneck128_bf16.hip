@@ -24,23 +24,14 @@
 // those launches store them: bit-identical (tests/test_hip_parity.py::test_bottleneck128_bf16_*).  25 % of conv1 is
 // recomputed in the halo tiles.
 #include <algorithm>
-#include <cstdio>
-#include <vector>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 constexpr int kC = 512, kP = 128;           // block channels, planes
 constexpr int kCT = 8;                      // pixel tiles (32 pixels) per chunk
 constexpr int kRowT = 272;                  // bytes of a t1 / t2 row: 128 channels + 16 bytes of padding
@@ -65,18 +56,6 @@ struct Bn2Args {
   unsigned long long* stamps;   // timing builds only (-DPR_TIMING_HOOKS, POSERISK_B128_STAMPS): s_memtime at the phase boundaries of chunk 1
 };
 
-__device__ inline unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-// Two values of an epilogue at once: the sums as one v_pk_add_f32 each, the ReLU on the ROUNDED pair as one v_pk_max_i16
-// (a bf16 is negative exactly when its bits are a negative int16, and rounding keeps the sign: round(relu(v)) == relu(round(v))
-// for every finite v and both infinities, -0 included).  6 VALU operations per pair instead of 9.
-using i16x2 = __attribute__((ext_vector_type(2))) short;
-__device__ inline unsigned relu_pack2(f32x2 v) {
-  const i16x2 r = __builtin_bit_cast(i16x2, __builtin_convertvector(v, bf16x2));
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(r, i16x2{0, 0}));
-}
-
 __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -97,10 +76,10 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
   const int ct = wave & 3, hw = wave >> 2;   // conv1 / conv2: channel tile, parity of the pixel tiles this wave takes
   const int i = lane & 31, h = lane >> 5;
 
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto w1src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w1), 0, kP * kC * 2, 0x00020000);
-  const auto w2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w2), 0, kP * 9 * kP * 2, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto w1src = make_rsrc(a.w1, kP * kC * 2);
+  const auto w2src = make_rsrc(a.w2, kP * 9 * kP * 2);
+  const auto ysrc = make_rsrc(a.y, (int)a.x_bytes);
 
   // zero row, biases (visible after the first barrier)
   if (tid < 32) *reinterpret_cast<u32x4*>(smem + kOffZ + tid * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -123,7 +102,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // nothing of the set-up is counted among the rings' operations
 
   // DMA geometry: a piece is 8 LDS rows of 128 bytes; lane l writes row l >> 3, slot l & 7, which holds logical slot dq
-  const int dq = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+  const int dq = PR_DMA_SWIZZLE_SLOT(lane, wave);
   // fragment reads of a swizzled [rows][128 B] stage: lane reads row (tile base + i), logical slot 2 ks + h
   int foff[4];
 #pragma unroll
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
 #pragma unroll
         for (int q = 0; q < N1; ++q) {
           const bf16x8 xf = *reinterpret_cast<const bf16x8*>(st + (hw + 2 * q) * 4096 + foff[ks]);
-          acc1[q] = mfma_bf16_step(wf, xf, acc1[q], ks);
+          acc1[q] = mfma_bf16_step(wf, xf, acc1[q]);
         }
       }
     }
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
         unsigned pk[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          pk[e] = relu_pack2(f32x2{acc1[q][2 * e], acc1[q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
+          pk[e] = relu_pack_bf16x2(f32x2{acc1[q][2 * e], acc1[q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
         char* dst = smem + kOffT + (32 * (hw + 2 * q) + i) * kRowT + (32 * ct + 16 * h) * 2;
         *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
         *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -318,7 +297,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
 #pragma unroll
           for (int q = 0; q < N2; ++q) {
             const bf16x8 tf = *reinterpret_cast<const bf16x8*>(smem + ta[q] + ks * 32);
-            acc2[q] = mfma_bf16_step(wf, tf, acc2[q], ks);
+            acc2[q] = mfma_bf16_step(wf, tf, acc2[q]);
           }
         }
       }
@@ -336,7 +315,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
         unsigned pk[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          pk[e] = relu_pack2(f32x2{acc2[q][2 * e], acc2[q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
+          pk[e] = relu_pack_bf16x2(f32x2{acc2[q][2 * e], acc2[q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
         char* dst = smem + kOffT + (32 * (hw + 2 * q) + i) * kRowT + (32 * ct + 16 * h) * 2;
         *reinterpret_cast<u32x4*>(dst) = u32x4{pk[0], pk[1], pk[2], pk[3]};
         *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -375,7 +354,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
 #pragma unroll
       for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) acc[nn] = mfma_bf16_step(w3f[nn][ks], tf[ks], acc[nn], ks);
+        for (int ks = 0; ks < 8; ++ks) acc[nn] = mfma_bf16_step(w3f[nn][ks], tf[ks], acc[nn]);
       // the tile's residual has landed when at most the operations issued behind its DMA are outstanding: the previous
       // tile's 4 stores (none before the first tile) and the next tile's 4 DMA instructions (none behind the last tile's)
       const int younger = (pt > 0 ? 4 : 0) + (pt + 1 < n ? 4 : 0);
@@ -394,7 +373,7 @@ __global__ __launch_bounds__(512) void bottleneck128_bf16(const Bn2Args a) {
           const unsigned r2 = e < 4 ? r0[e & 3] : r1[e & 3];
           f32x2 v = f32x2{acc[nn][2 * e], acc[nn][2 * e + 1]} + b3r[nn][e];
           v += f32x2{__uint_as_float(r2 << 16), __uint_as_float(r2 & 0xffff0000u)};
-          pk[e] = relu_pack2(v);
+          pk[e] = relu_pack_bf16x2(v);
         }
         *reinterpret_cast<u32x4*>(p0) = u32x4{pk[0], pk[1], pk[2], pk[3]};
         *reinterpret_cast<u32x4*>(p1) = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -455,27 +434,11 @@ int bottleneck128_bf16_launch(const BottleneckProblem& p, hipStream_t stream) {
   static std::atomic<uint64_t> done{0};
   PR_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck128_bf16), kLds, done));
 #ifdef PR_TIMING_HOOKS
-  static unsigned long long* stamp_buf = nullptr;
-  static int stamp_calls = 0;
   if (const char* e = getenv("POSERISK_B128_DBG")) a.dbg = atoi(e);
   if (a.dbg & 64) a.runs = std::max(a.runs / 2, 1);
-  if (const char* path = getenv("POSERISK_B128_STAMPS")) {
-    const size_t n = (size_t)256 * 8 * 4 * 8;
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, n * 8));
-    a.stamps = stamp_buf;
-    if (++stamp_calls == 20) {
-      PR_HIP(hipMemsetAsync(stamp_buf, 0, n * 8, stream));
-      hipLaunchKernelGGL(bottleneck128_bf16, dim3(a.runs), dim3(512), kLds, stream, a);
-      std::vector<unsigned long long> host(n);
-      PR_HIP(hipStreamSynchronize(stream));
-      PR_HIP(hipMemcpy(host.data(), stamp_buf, n * 8, hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(path, "wb")) {
-        fwrite(host.data(), 8, n, f);
-        fclose(f);
-      }
-      return check_launch("bottleneck128_bf16");
-    }
-  }
+  static int stamp_calls = 0;
+  StampRecorder stamp_rec("POSERISK_B128_STAMPS", (size_t)256 * 8 * 4 * 8, 20, stamp_calls, stream);
+  a.stamps = stamp_rec.stamps();
 #endif
   hipLaunchKernelGGL(bottleneck128_bf16, dim3(a.runs), dim3(512), kLds, stream, a);
   return check_launch("bottleneck128_bf16");

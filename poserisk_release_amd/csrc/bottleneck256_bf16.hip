@@ -24,23 +24,14 @@
 // conv_k_index_bf16), t1 and t2 rounded to bf16 where those launches store them: bit-identical
 // (tests/test_hip_parity.py::test_bottleneck256_bf16_*).
 #include <algorithm>
-#include <cstdio>
-#include <vector>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using i16x2 = __attribute__((ext_vector_type(2))) short;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 constexpr int kC = 1024, kP = 256;
 constexpr int kPT = 7;                                     // pixel tiles of 32 per frame at most
 constexpr int kMaxPix = 32 * kPT;
@@ -65,15 +56,6 @@ struct Bn3Args {
   unsigned long long* stamps;   // timing builds only (-DPR_TIMING_HOOKS, POSERISK_B256_STAMPS): s_memtime at the phase boundaries of every workgroup's first frame
 };
 
-// Two values of an epilogue at once: sums as v_pk_add_f32, the ReLU on the ROUNDED pair as one v_pk_max_i16 (a bf16 is
-// negative exactly when its bits are a negative int16 and rounding keeps the sign: round(relu(v)) == relu(round(v))).
-__device__ inline unsigned relu_pack2(f32x2 v) {
-  const i16x2 r = __builtin_bit_cast(i16x2, __builtin_convertvector(v, bf16x2));
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(r, i16x2{0, 0}));
-}
-
-
-
 __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -83,9 +65,9 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
   const int i = lane & 31, h = lane >> 5;
   const int nt = (a.HW + 31) >> 5;           // pixel tiles of a frame
 
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto w1src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w1), 0, kP * kC * 2, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto w1src = make_rsrc(a.w1, kP * kC * 2);
+  const auto ysrc = make_rsrc(a.y, (int)a.x_bytes);
 
   // zero row, biases (visible after the first barrier)
   if (tid < 64) *reinterpret_cast<u32x4*>(smem + kOffZ + tid * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -101,7 +83,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
   // DMA geometry: a piece is 8 LDS rows of 128 bytes; lane l writes row l >> 3, slot l & 7, which holds logical slot dq
-  const int dq = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+  const int dq = PR_DMA_SWIZZLE_SLOT(lane, wave);
   // fragment reads of a swizzled [rows][128 B] stage: lane reads row (tile base + i), logical slot 2 ks + h
   int foff[4];
 #pragma unroll
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
         for (int q = 0; q < N; ++q) {
           const bf16x8 xf = *reinterpret_cast<const bf16x8*>(st + (4 * ph + q) * 4096 + foff[ks]);
 #pragma unroll
-          for (int c = 0; c < 2; ++c) acc1[c][q] = mfma_bf16_step(wf[c], xf, acc1[c][q], ks);
+          for (int c = 0; c < 2; ++c) acc1[c][q] = mfma_bf16_step(wf[c], xf, acc1[c][q]);
         }
       }
     }
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
       for (int q = 0; q < N; ++q) {
         unsigned pk[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pk[e] = relu_pack2(f32x2{acc1[c][q][2 * e], acc1[c][q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
+        for (int e = 0; e < 8; ++e) pk[e] = relu_pack_bf16x2(f32x2{acc1[c][q][2 * e], acc1[c][q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
         const int r = 32 * (4 * ph + q) + i;
         if (r < a.HW) {
           char* dst = smem + kOffT + r * kRowT + (32 * (2 * cp + c) + 16 * h) * 2;
@@ -251,7 +233,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
         for (int q = 0; q < N; ++q) {
           const bf16x8 tf = *reinterpret_cast<const bf16x8*>(smem + ta[q] + k * 32);
 #pragma unroll
-          for (int c = 0; c < 2; ++c) acc2[c][q] = mfma_bf16_step(wf[c][k], tf, acc2[c][q], k);
+          for (int c = 0; c < 2; ++c) acc2[c][q] = mfma_bf16_step(wf[c][k], tf, acc2[c][q]);
         }
     };
 #pragma unroll 1
@@ -274,7 +256,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
       for (int q = 0; q < N; ++q) {
         unsigned pk[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) pk[e] = relu_pack2(f32x2{acc2[c][q][2 * e], acc2[c][q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
+        for (int e = 0; e < 8; ++e) pk[e] = relu_pack_bf16x2(f32x2{acc2[c][q][2 * e], acc2[c][q][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]});
         const int r = 32 * (4 * ph + q) + i;
         if (r < a.HW) {
           char* dst = smem + kOffT + r * kRowT + (32 * (2 * cp + c) + 16 * h) * 2;
@@ -327,7 +309,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
 #pragma unroll
           for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[c] = mfma_bf16_step(w3f[c][4 * g + k], tf[k], acc[c], k);
+            for (int k = 0; k < 4; ++k) acc[c] = mfma_bf16_step(w3f[c][4 * g + k], tf[k], acc[c]);
         }
         // the tile's residual has landed when at most the previous tile's 4 stores, issued behind its DMA, are outstanding
         if (pt > 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(512) void bottleneck256_bf16(const Bn3Args a) {
             const unsigned r2 = e < 4 ? r0[e & 3] : r1[e & 3];
             f32x2 v = f32x2{acc[c][2 * e], acc[c][2 * e + 1]} + f32x2{bp[2 * e], bp[2 * e + 1]};
             v += f32x2{__uint_as_float(r2 << 16), __uint_as_float(r2 & 0xffff0000u)};
-            pk[e] = relu_pack2(v);
+            pk[e] = relu_pack_bf16x2(v);
           }
           *reinterpret_cast<u32x4*>(p0) = u32x4{pk[0], pk[1], pk[2], pk[3]};
           *reinterpret_cast<u32x4*>(p1) = u32x4{pk[4], pk[5], pk[6], pk[7]};
@@ -405,25 +387,9 @@ int bottleneck256_bf16_launch(const BottleneckProblem& p, hipStream_t stream) {
   PR_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck256_bf16), kLds, done));
   a.stamps = nullptr;
 #ifdef PR_TIMING_HOOKS
-  static unsigned long long* stamp_buf = nullptr;
   static int stamp_calls = 0;
-  if (const char* path = getenv("POSERISK_B256_STAMPS")) {
-    const size_t n = (size_t)256 * 8 * 8;
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, n * 8));
-    a.stamps = stamp_buf;
-    if (++stamp_calls == 20) {
-      PR_HIP(hipMemsetAsync(stamp_buf, 0, n * 8, stream));
-      hipLaunchKernelGGL(bottleneck256_bf16, dim3(std::min(p.B, cus)), dim3(512), kLds, stream, a);
-      std::vector<unsigned long long> host(n);
-      PR_HIP(hipStreamSynchronize(stream));
-      PR_HIP(hipMemcpy(host.data(), stamp_buf, n * 8, hipMemcpyDeviceToHost));
-      if (FILE* fo = fopen(path, "wb")) {
-        fwrite(host.data(), 8, n, fo);
-        fclose(fo);
-      }
-      return check_launch("bottleneck256_bf16");
-    }
-  }
+  StampRecorder stamp_rec("POSERISK_B256_STAMPS", (size_t)256 * 8 * 8, 20, stamp_calls, stream);
+  a.stamps = stamp_rec.stamps();
 #endif
   hipLaunchKernelGGL(bottleneck256_bf16, dim3(std::min(p.B, cus)), dim3(512), kLds, stream, a);
   return check_launch("bottleneck256_bf16");

@@ -24,20 +24,13 @@
 //     exactly where the separate launches store them.
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 
 constexpr int kRing = 192;                         // t1 ring: three 64-pixel blocks
 constexpr int kXSlots = 6;                         // x ring: six 8 KB slices
@@ -68,12 +61,6 @@ struct BnArgs {
 };
 constexpr int kStampJ0 = 8, kStampNJ = 16, kStampK = 6;
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-__device__ inline unsigned pack_bf16x2(float lo, float hi) {   // one v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
-
 #define PR_BARRIER()                                         \
   do {                                                       \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
@@ -90,12 +77,12 @@ template <int DBG, bool FIRST>
 __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  auto MFMA = [](const bf16x8& wa, const bf16x8& xb, const f32x16& c, int sel = 0) -> f32x16 {
+  auto MFMA = [](const bf16x8& wa, const bf16x8& xb, const f32x16& c) -> f32x16 {
     if (DBG & 4) {                                   // keep the operands live so nothing upstream is removed
       asm volatile("" ::"v"(wa), "v"(xb));
       return c;
     }
-    return mfma_bf16_step(wa, xb, c, sel);
+    return mfma_bf16_step(wa, xb, c);
   };
   // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the instruction takes an immediate)
   auto wait_vm = [](int n) {
@@ -139,10 +126,10 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
     // W2 -> LDS: 9 taps x [64 rows][128 B], 16-byte chunks XOR-swizzled on the source side (conv_dma_bf16.hip); the 72
     // the
     // 1 KB groups of 8 rows are dealt to the eight waves
-    const auto w2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w2), 0, 64 * 576 * 2, 0x00020000);
+    const auto w2src = make_rsrc(a.w2, 64 * 576 * 2);
     for (int idx = wave; idx < 72; idx += 8) {
       const int tap = idx >> 3, grp = idx & 7;
-      const int q = (lane & 7) ^ ((4 * (grp & 1) + (lane >> 4)) & 7);
+      const int q = PR_DMA_SWIZZLE_SLOT(lane, grp);
       const unsigned voff = (unsigned)(((8 * grp + (lane >> 3)) * 576 + q * 8) * 2);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(w2src, (lds_void*)(smem + kOffW2 + tap * 8192 + grp * 1024), 16, voff,
                                                tap * 128, 0, 0);
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
     // =================================================================================================================
     // group A (waves 0-3, one per SIMD): the x ring's LDS-DMA, conv2 of block t, then conv1 of block t+2 -- the matrix half
     // =================================================================================================================
-    const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
     bf16x8 w1f[4 * SPB];     // W1 rows of this wave's output tile as MFMA A fragments (row i, k = 16 ks + 8 h .. + 7)
 #pragma unroll
     for (int ks = 0; ks < 4 * SPB; ++ks)
@@ -167,7 +154,7 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
     // x ring: local slice L = 4 * (local conv1 block) + s, s = 64-channel slice of x; LDS slot L % 6.  A slice is eight
     // 1 KB DMA groups of 8 pixels: ONE instruction per slice for each of the eight waves (group = wave; an LDS-DMA
     // instruction costs its wave ~200 cycles of issue, so both groups carry half).
-    const int dq = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+    const int dq = PR_DMA_SWIZZLE_SLOT(lane, wave);
     auto issue_slice = [&](int L) {
       const int blk = b0 - 1 + L / SPB, s = L % SPB;
       const int m = blk * 64 + 8 * wave + (lane >> 3);
@@ -231,7 +218,7 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
           if (tap + 1 < 9) fetch(tap + 1, af[(tap + 1) & 1], bf[(tap + 1) & 1]);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int kk = 0; kk < 4; ++kk) acc = MFMA(af[tap & 1][kk], bf[tap & 1][kk], acc, kk);
+          for (int kk = 0; kk < 4; ++kk) acc = MFMA(af[tap & 1][kk], bf[tap & 1][kk], acc);
           __builtin_amdgcn_sched_barrier(0);
         }
         // t2 = bf16(relu(acc + b2)) -> LDS [pixel][channel]; the lane's 16 registers are channels 32 ct + 16 h + r
@@ -270,7 +257,7 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
           if (s + 1 < SPB) fetchx(s + 1, xf[(s + 1) & 1]);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int kk = 0; kk < 4; ++kk) acc = MFMA(w1f[4 * s + kk], xf[s & 1][kk], acc, kk);
+          for (int kk = 0; kk < 4; ++kk) acc = MFMA(w1f[4 * s + kk], xf[s & 1][kk], acc);
           __builtin_amdgcn_sched_barrier(0);
         }
         const int m2 = (b0 - 1 + j) * 64 + prow;
@@ -296,10 +283,10 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
     // previous iteration, stored from the registers -- the VALU / store half, beside group A's MFMAs on the same SIMDs.
     // Wave (ct, pt) owns the output tiles 4 ct .. 4 ct + 3 (channels 128 ct .. 128 ct + 127) of pixel tile pt.
     // =================================================================================================================
-    const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.y_bytes, 0x00020000);
-    const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    const auto ysrc = make_rsrc(a.y, (int)a.y_bytes);
+    const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
     // this group's half of the x ring's LDS-DMA (see group A): group `wave` (4..7) of every slice
-    const int dq = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+    const int dq = PR_DMA_SWIZZLE_SLOT(lane, wave);
     auto issue_slice = [&](int L) {
       const int blk = b0 - 1 + L / SPB, s = L % SPB;
       const int m = blk * 64 + 8 * wave + (lane >> 3);
@@ -336,12 +323,12 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) c3[e] = 0.f;
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) c3 = MFMA(w3f[n][kk], tf[kk], c3, kk);
+      for (int kk = 0; kk < 4; ++kk) c3 = MFMA(w3f[n][kk], tf[kk], c3);
       if (FIRST) {           // the downsample branch: the block's own x rows as the K loop's second half
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           const bf16x8 xb = __builtin_bit_cast(bf16x8, u32x4{res[4 * kk], res[4 * kk + 1], res[4 * kk + 2], res[4 * kk + 3]});
-          c3 = MFMA(w3f[n][K3 - 4 + kk], xb, c3, kk);
+          c3 = MFMA(w3f[n][K3 - 4 + kk], xb, c3);
         }
       }
       const float* bp = reinterpret_cast<const float*>(smem + kOffB3) + 32 * (4 * ct + n) + 16 * h;
@@ -472,15 +459,9 @@ int bottleneck_bf16_launch(const BottleneckProblem& p, hipStream_t stream) {
   void (*kern)(const BnArgs) = p.first ? bottleneck64_bf16<0, true> : bottleneck64_bf16<0, false>;
   a.stamps = nullptr;
 #ifdef PR_TIMING_HOOKS
-  static unsigned long long* stamp_buf = nullptr;
-  static int stamp_calls = 0;
-  const char* stamp_path = getenv("POSERISK_BN_STAMPS");
-  const size_t stamp_n = (size_t)256 * 8 * kStampNJ * kStampK;
-  if (stamp_path) {
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, stamp_n * 8));
-    PR_HIP(hipMemsetAsync(stamp_buf, 0, stamp_n * 8, stream));
-    a.stamps = stamp_buf;
-  }
+  static int stamp_calls = 0;   // the 30th call: a warm launch in the middle of the timing loop
+  StampRecorder stamp_rec("POSERISK_BN_STAMPS", (size_t)256 * 8 * kStampNJ * kStampK, 30, stamp_calls, stream);
+  a.stamps = stamp_rec.stamps();
   if (const char* e = getenv("POSERISK_BN_DBG")) {
     switch (atoi(e)) {
       case 1: kern = p.first ? bottleneck64_bf16<1, true> : bottleneck64_bf16<1, false>; break;
@@ -496,17 +477,6 @@ int bottleneck_bf16_launch(const BottleneckProblem& p, hipStream_t stream) {
   if (p.first) PR_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck64_bf16<0, true>), kLdsBytes, attr_done_first));
   else PR_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bottleneck64_bf16<0, false>), kLdsBytes, attr_done));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), kLdsBytes, stream, a);
-#ifdef PR_TIMING_HOOKS
-  if (stamp_path && ++stamp_calls == 30) {   // a warm launch in the middle of the timing loop
-    std::vector<unsigned long long> host(stamp_n);
-    PR_HIP(hipStreamSynchronize(stream));
-    PR_HIP(hipMemcpy(host.data(), stamp_buf, stamp_n * 8, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(stamp_path, "wb")) {
-      fwrite(host.data(), 8, stamp_n, f);
-      fclose(f);
-    }
-  }
-#endif
   return check_launch("bottleneck64_bf16");
 }
 

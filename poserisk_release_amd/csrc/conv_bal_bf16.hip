@@ -25,22 +25,14 @@
 // Same products, same k order, same epilogue arithmetic as conv_dma_bf16: bit-identical outputs
 // (tests/test_hip_parity.py::test_conv_bal_bf16_equals_tile_kernel).
 #include <algorithm>
-#include <cstdio>
-#include <vector>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 constexpr int kStageBytes = 512 * 64;   // 512 rows (pixels + channels) of 32 k-values
 
 struct BalArgs {
@@ -60,10 +52,6 @@ struct BalArgs {
   int H2, W2, Cin2, stride2, ns1;
   unsigned long long* stamps;   // timing builds only (-DPR_TIMING_HOOKS, POSERISK_BAL_STAMPS): s_memtime at six points of intervals 8 .. 23
 };
-
-__device__ inline unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
 
 __device__ inline void wait_vm(int n) {   // s_waitcnt vmcnt(n), n in {0, 1, 4, 8, 12} (anything else: 0, which is stricter)
   switch (n) {
@@ -122,11 +110,10 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
 #endif
   };
 
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w), 0, (int)a.w_bytes, 0x00020000);
-  [[maybe_unused]] const auto xsrc2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x2 ? a.x2 : a.x), 0,
-                                                                          a.x2 ? (int)a.x2_bytes : 0, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.y_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto wsrc = make_rsrc(a.w, (int)a.w_bytes);
+  [[maybe_unused]] const auto xsrc2 = make_rsrc(a.x2 ? a.x2 : a.x, a.x2 ? (int)a.x2_bytes : 0);
+  const auto ysrc = make_rsrc(a.y, (int)a.y_bytes);
 
   // ---- DMA source addressing.  A piece is 16 LDS rows of 64 bytes; lane l writes row l >> 2, slot l & 3 of its piece,
   // which holds logical slot q.  Wave w issues pixel pieces w + 8 j and channel pieces w + 8 j.
@@ -274,7 +261,6 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
 
   struct Frags {
     bf16x8 w[2], p[PXT];
-    int sel;   // the k-step the fragments belong to (read by experiment builds only)
   };
   f32x16 acc[PXT][2];
   Frags fa, fb;
@@ -291,7 +277,6 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
     constexpr int NP = decltype(np_c)::value;
     auto read_frags = [&](Frags& f, int buf, int kk) {
       const char* st = smem + buf * kStageBytes;
-      f.sel = kk;
       if (DBG & 4) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) f.w[c] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)lane, (unsigned)kk, (unsigned)c, 2u});
@@ -310,7 +295,7 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           if (DBG & 2) asm volatile("" ::"v"(f.w[c]), "v"(f.p[pt]));
-          else acc[pt][c] = mfma_bf16_step(f.w[c], f.p[pt], acc[pt][c], f.sel);
+          else acc[pt][c] = mfma_bf16_step(f.w[c], f.p[pt], acc[pt][c]);
         }
     };
     auto gate = [&]() {                 // the wait for this wave's pieces of stage g_stage, then the barrier
@@ -386,7 +371,7 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
             v0 = fmaxf(v0, 0.f);
             v1 = fmaxf(v1, 0.f);
           }
-          pk[e] = pack2(v0, v1);
+          pk[e] = pack_bf16x2(v0, v1);
         }
         const int soff = (n0 + 64 * cp + 32 * c) * 2;
         if (DBG & 8) {
@@ -418,12 +403,6 @@ __global__ __launch_bounds__(512) void conv_bal_bf16(const BalArgs a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-}
-
-int ilog2_exact_c(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
 }
 
 template <int PQ, int R, int DBG = 0, bool PAIR = false>
@@ -479,7 +458,7 @@ int conv_bal_bf16_launch(const ConvProblem& p, hipStream_t stream, int variant) 
   a.x = reinterpret_cast<const unsigned short*>(p.x); a.w = reinterpret_cast<const unsigned short*>(p.w); a.bias = p.bias;
   a.y = reinterpret_cast<unsigned short*>(p.y);
   a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb; a.y_bytes = (unsigned)yb;
-  a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.log2Cin = std::max(ilog2_exact_c(p.Cin), 0);
+  a.H = p.H; a.W = p.W; a.Cin = p.Cin; a.log2Cin = std::max(ilog2_exact(p.Cin), 0);
   a.Ho = p.Ho; a.Wo = p.Wo; a.HoWo = p.Ho * p.Wo; a.Cout = p.Cout; a.stride = p.stride; a.pad = p.pad;
   a.M = p.M(); a.Kpad = Kpad; a.ns = Kpad / 32;
   a.T = ceil_div(a.M, 32); a.NB = p.Cout / (wide ? 256 : 128); a.relu = p.relu;
@@ -496,26 +475,9 @@ int conv_bal_bf16_launch(const ConvProblem& p, hipStream_t stream, int variant) 
   const int grid = groups * per;
   a.stamps = nullptr;
 #ifdef PR_TIMING_HOOKS
-  static unsigned long long* stamp_buf = nullptr;
-  static int stamp_calls = 0;
-  const char* stamp_path = getenv("POSERISK_BAL_STAMPS");
-  const size_t stamp_n = (size_t)256 * 8 * 16 * 6;
-  if (stamp_path) {
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, stamp_n * 8));
-    PR_HIP(hipMemsetAsync(stamp_buf, 0, stamp_n * 8, stream));
-    a.stamps = stamp_buf;
-    if (++stamp_calls == 20) {   // a warm launch in the middle of the timing loop
-      const int st = wide ? launch_bal<2, 4>(a, p.KH, grid, stream) : launch_bal<4, 4>(a, p.KH, grid, stream);
-      std::vector<unsigned long long> host(stamp_n);
-      PR_HIP(hipStreamSynchronize(stream));
-      PR_HIP(hipMemcpy(host.data(), stamp_buf, stamp_n * 8, hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(stamp_path, "wb")) {
-        fwrite(host.data(), 8, stamp_n, f);
-        fclose(f);
-      }
-      return st;
-    }
-  }
+  static int stamp_calls = 0;   // the 20th call: a warm launch in the middle of the timing loop
+  StampRecorder stamp_rec("POSERISK_BAL_STAMPS", (size_t)256 * 8 * 16 * 6, 20, stamp_calls, stream);
+  a.stamps = stamp_rec.stamps();
   if (const char* e = getenv("POSERISK_BAL_DBG")) {
     switch (atoi(e)) {
       case 1: return wide ? launch_bal<2, 5, 1>(a, p.KH, grid, stream) : launch_bal<4, 5, 1>(a, p.KH, grid, stream);

@@ -11,19 +11,15 @@
 //   advances), one bounds test per row for 3x3 convs (tap decode is scalar), a per-lane tap
 //   decode only for the 7x7 stem (Cin = 4).
 //   One barrier per K-step: wait own DMA (vmcnt(0)) -> barrier -> issue next DMA -> MFMAs.
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int BK = kConvBK;           // 32 floats = 128 B per row per stage
 #if defined(PR_EXPERIMENT) && PR_EXPERIMENT == 10
@@ -31,7 +27,6 @@ constexpr bool kOldKLoop = true;      // A/B builds: round 3's K loop (bursts of
 #else
 constexpr bool kOldKLoop = false;
 #endif
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;  // voffset sentinel: beyond any buffer we accept (< 2 GiB)
 
 struct DArgs {
   const float* x;
@@ -116,14 +111,13 @@ __device__ __forceinline__ void conv_tail_quarter(const DArgs& a, int item, char
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tr.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tr.w), 0, (int)a.w_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(tr.x, (int)a.x_bytes);
+  const auto wsrc = make_rsrc(tr.w, (int)a.w_bytes);
   const int r = 8 * wave + (lane >> 3);   // this lane's row of the 32-row stage (A and B alike)
   int a_base, a_hi0, a_wi0;
   [[maybe_unused]] int a_base2 = (int)kOOB;
-  [[maybe_unused]] const auto xsrc2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? a.x2 : a.x), 0,
-                                                                          DUAL ? (int)a.x2_bytes : 0, 0x00020000);
+  [[maybe_unused]] const auto xsrc2 = make_rsrc(DUAL ? a.x2 : a.x, DUAL ? (int)a.x2_bytes : 0);
   {
     const int m = m0 + r;
     if (m < a.M) {
@@ -277,8 +271,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_f32(const DArg
       return;
     }
   }
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int logical = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int logical = xcd_contiguous_block<int>(bid, nb);
   const int part = SPLIT ? logical % a.splitk : 0;
   const int tile_id = SPLIT ? logical / a.splitk : logical;
   const TileRef tr = tile_ref(a, tile_id);
@@ -294,15 +287,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_f32(const DArg
   // ---- DMA source addressing -------------------------------------------------------------
   // DMA wave w issues groups g = w + DW*i (same parity as w, DW even), lane covers row 8g + (lane>>3)
   // and physical chunk lane&7, i.e. logical chunk q = (lane&7) ^ ((4g + (lane>>4)) & 7).
-  const int q = (lane & 7) ^ ((4 * (dw & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tr.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tr.w), 0, (int)a.w_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, dw);
+  const auto xsrc = make_rsrc(tr.x, (int)a.x_bytes);
+  const auto wsrc = make_rsrc(tr.w, (int)a.w_bytes);
 
   int a_base[IA];  // byte offset of (img, hi0, wi0, ci = 4q); TAP 2: ci = 0
   int a_hi0[IA], a_wi0[IA];
   [[maybe_unused]] int a_base2[IA];   // DUAL: the same rows in the second source
-  [[maybe_unused]] const auto xsrc2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? a.x2 : a.x), 0,
-                                                                          DUAL ? (int)a.x2_bytes : 0, 0x00020000);
+  [[maybe_unused]] const auto xsrc2 = make_rsrc(DUAL ? a.x2 : a.x, DUAL ? (int)a.x2_bytes : 0);
 #pragma unroll
   for (int i = 0; i < IA; ++i) {
     const int r = 8 * (dw + DW * i) + (lane >> 3);
@@ -684,12 +676,6 @@ int launch_dma(const DArgs& da, int ks, int tap, int grid, hipStream_t stream) {
   return PR_ERR_INVALID;
 }
 
-int ilog2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
 }  // namespace
 
 int conv_dma_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, int threads) {
@@ -770,27 +756,11 @@ int conv_dma_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, in
   }
   da.stamps = nullptr;
 #ifdef PR_TIMING_HOOKS
-  // Timing builds: the 20th launch of a process records per-workgroup s_memrealtime stamps (0 entry, 1 first stage landed,
-  // 2 main loop done, 3 stores issued; 4 / 5 s_memtime at entry / exit; 6 HW_ID, 7 XCC_ID) and writes them to the file.
-  static unsigned long long* stamp_buf = nullptr;
+  // Timing builds: the 20th launch of a process (of those with at most 16384 workgroups) records per-workgroup s_memrealtime
+  // stamps (0 entry, 1 first stage landed, 2 main loop done, 3 stores issued; 4 / 5 s_memtime at entry / exit; 6 HW_ID, 7 XCC_ID)
   static int stamp_calls = 0;
-  const char* stamp_path = getenv("POSERISK_CONV_STAMPS");
-  const bool stamp_now = stamp_path && grid <= 16384 && ++stamp_calls == 20;
-  if (stamp_now) {
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, (size_t)16384 * 8 * 8));
-    PR_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)16384 * 8 * 8, stream));
-    da.stamps = stamp_buf;
-  }
-  struct StampDump {
-    bool on; const char* path; int grid; hipStream_t s; unsigned long long* buf;
-    ~StampDump() {
-      if (!on) return;
-      std::vector<unsigned long long> host((size_t)grid * 8);
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(host.data(), buf, host.size() * 8, hipMemcpyDeviceToHost);
-      if (FILE* fo = fopen(path, "wb")) { fwrite(host.data(), 8, host.size(), fo); fclose(fo); }
-    }
-  } stamp_dump{stamp_now, stamp_path, grid, stream, stamp_buf};
+  StampRecorder stamp_rec(grid <= 16384 ? "POSERISK_CONV_STAMPS" : nullptr, (size_t)grid * 8, 20, stamp_calls, stream);
+  da.stamps = stamp_rec.stamps();
 #endif
   const int key = BM * 1000 + BN + (threads == 512 && BM == 128 ? 500000 : 0) + (threads == 128 ? 900000 : 0);
   switch (key) {

@@ -1,5 +1,5 @@
 // bf16 implicit-GEMM convolution (fp32 accumulate) on v_mfma_f32_16x16x32_bf16 (round 6; 32 x 32 output tiles as four
-// 16 x 16 quadrants, common.h Acc32 -- the sums keep the bits of the 32x32x16 form it was written on), LDS-DMA data path.
+// 16 x 16 quadrants, kernel_vocab.h Acc32 -- the sums keep the bits of the 32x32x16 form it was written on), LDS-DMA data path.
 // Twin of conv_dma.hip (see there for the data path, swizzle and zero-fill notes); differences:
 //   * elements are 2 bytes: a 128-byte LDS row holds BK = 64 k-values, one 16-byte chunk = 8 bf16 = the
 //     whole A (or B) fragment of one lane for one MFMA (lane group g takes k = 8g..8g+7 of a 32-k step), so one
@@ -20,18 +20,12 @@
 //   decode only for the 7x7 stem (Cin = 4).
 //   One barrier per K-step: wait own DMA (vmcnt(0)) -> barrier -> issue next DMA -> MFMAs.
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int BK = 64;                // 64 bf16 = 128 B per row per stage
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;  // voffset sentinel: beyond any buffer we accept (< 2 GiB)
 
 struct DArgs {
   const unsigned short* x;   // bf16 bits
@@ -72,8 +66,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_bf16(const DAr
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int logical = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int logical = xcd_contiguous_block<int>(bid, nb);
   const int tile_n = logical % a.tiles_n, tile_m = logical / a.tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -84,15 +77,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_bf16(const DAr
   // ---- DMA source addressing -------------------------------------------------------------
   // Wave w issues groups g = w + NW*i (same parity as w, NW even), lane covers row 8g + (lane>>3)
   // and physical chunk lane&7, i.e. logical chunk q = (lane&7) ^ ((4g + (lane>>4)) & 7).
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w), 0, (int)a.w_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto wsrc = make_rsrc(a.w, (int)a.w_bytes);
 
   int a_base[IA];  // byte offset of (img, hi0, wi0, ci = 4q); TAP 2: ci = 0
   int a_hi0[IA], a_wi0[IA];
   [[maybe_unused]] int a_base2[IA];   // DUAL: the same rows in the second source
-  [[maybe_unused]] const auto xsrc2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(DUAL ? a.x2 : a.x), 0,
-                                                                          DUAL ? (int)a.x2_bytes : 0, 0x00020000);
+  [[maybe_unused]] const auto xsrc2 = make_rsrc(DUAL ? a.x2 : a.x, DUAL ? (int)a.x2_bytes : 0);
 #pragma unroll
   for (int i = 0; i < IA; ++i) {
     const int r = 8 * (wave + NW * i) + (lane >> 3);
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_bf16(const DAr
   };
 
   // ---- fragment read addressing (swizzled) ---------------------------------------------------
-  // v_mfma_f32_16x16x32_bf16 (common.h, Acc32): lane (j = lane & 15, g = lane >> 4) reads row (tile row base + 16 t + j),
+  // v_mfma_f32_16x16x32_bf16 (kernel_vocab.h, Acc32): lane (j = lane & 15, g = lane >> 4) reads row (tile row base + 16 t + j),
   // k 32 s + 8 g .. + 7 of the 64-k stage row: logical 16-byte chunk 4 s + g, physical chunk (4 s + g) ^ ((row >> 1) & 7);
   // row bases are multiples of 32, so the XOR term is (j >> 1) & 7.  A ds_read_b128's 16-lane groups take rows {0-3, 12-15}
   // of one chunk and rows {4-11} of its neighbour: 16 different 16-byte slots of the 256-byte bank row, conflict-free.
@@ -225,56 +217,50 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_bf16(const DAr
   // chunk, adds bias/residual in fp32, applies ReLU, rounds to bf16 and stores 16 bytes, so a row of
   // BN columns leaves as whole 128-byte lines.
   constexpr int CT_STRIDE = BN + 4;
-  // the fp32 tile of a 256 x 256 configuration (266 KB) does not fit LDS: it goes through in EP passes of BM / EP rows
-  constexpr int EP = (size_t)BM * CT_STRIDE * 4 > 160 * 1024 ? 2 : 1, RM = BM / EP;
-  static_assert(WAVES_M % EP == 0 && RM % WM == 0, "an epilogue pass takes whole waves");
   float* Ct = reinterpret_cast<float*>(smem);
   constexpr int CPR = BN / 8;  // 16-byte output chunks per row
+  __syncthreads();  // every wave has finished reading the stage buffers
+  {
+    const int col_l = acc_col(lane), row_h = 4 * acc_half(lane);
 #pragma unroll
-  for (int ep = 0; ep < EP; ++ep) {
-    __syncthreads();  // every wave has finished reading the stage buffers (the previous pass's rows)
-    if (EP == 1 || wm / (WAVES_M / EP) == ep) {
-      const int col_l = acc_col(lane), row_h = 4 * acc_half(lane);
+    for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
+      for (int mi = 0; mi < MI; ++mi) {
+        const f32x16 regs = acc32_regs(acc[mi][ni]);      // the 32x32x16 register layout on lanes (acc_col, acc_half)
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          const f32x16 regs = acc32_regs(acc[mi][ni]);      // the 32x32x16 register layout on lanes (acc_col, acc_half)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int r = wm * WM - ep * RM + mi * 32 + row_h + (e & 3) + 8 * (e >> 2);
-            Ct[r * CT_STRIDE + wn * WN + ni * 32 + col_l] = regs[e];
-          }
-        }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < RM * CPR; idx += NW * 64) {
-      const int r = idx / CPR, cc = idx - r * CPR;
-      const int row = m0 + ep * RM + r, col = n0 + cc * 8;
-      if (row >= a.M) continue;
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(&Ct[r * CT_STRIDE + cc * 8]);
-      const f32x4 v1 = *reinterpret_cast<const f32x4*>(&Ct[r * CT_STRIDE + cc * 8 + 4]);
-      float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      if (a.bias) {
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + col);
-        const f32x4 b1 = *reinterpret_cast<const f32x4*>(a.bias + col + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] += b0[e];
-          v[4 + e] += b1[e];
+        for (int e = 0; e < 16; ++e) {
+          const int r = wm * WM + mi * 32 + row_h + (e & 3) + 8 * (e >> 2);
+          Ct[r * CT_STRIDE + wn * WN + ni * 32 + col_l] = regs[e];
         }
       }
-      const long o = (long)row * a.Cout + col;
-      if (a.res) {
-        const u16x8 rr = *reinterpret_cast<const u16x8*>(a.res + o);
+  }
+  __syncthreads();
+  for (int idx = tid; idx < BM * CPR; idx += NW * 64) {
+    const int r = idx / CPR, cc = idx - r * CPR;
+    const int row = m0 + r, col = n0 + cc * 8;
+    if (row >= a.M) continue;
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(&Ct[r * CT_STRIDE + cc * 8]);
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(&Ct[r * CT_STRIDE + cc * 8 + 4]);
+    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    if (a.bias) {
+      const f32x4 b0 = *reinterpret_cast<const f32x4*>(a.bias + col);
+      const f32x4 b1 = *reinterpret_cast<const f32x4*>(a.bias + col + 4);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32(rr[e]);
+      for (int e = 0; e < 4; ++e) {
+        v[e] += b0[e];
+        v[4 + e] += b1[e];
       }
-      u16x8 out;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) out[e] = f32_to_bf16(a.relu ? fmaxf(v[e], 0.f) : v[e]);
-      *reinterpret_cast<u16x8*>(a.y + o) = out;
     }
+    const long o = (long)row * a.Cout + col;
+    if (a.res) {
+      const u16x8 rr = *reinterpret_cast<const u16x8*>(a.res + o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32(rr[e]);
+    }
+    u16x8 out;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) out[e] = f32_to_bf16(a.relu ? fmaxf(v[e], 0.f) : v[e]);
+    *reinterpret_cast<u16x8*>(a.y + o) = out;
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }
@@ -282,8 +268,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_bf16(const DAr
 template <int BM, int BN, int WAVES_M, int WAVES_N, int KS, int TAP, bool DUAL = false>
 int launch_one_bf16(const DArgs& da, int grid, hipStream_t stream) {
   constexpr int NT = WAVES_M * WAVES_N * 64;
-  constexpr size_t lds_stage = (size_t)2 * (BM + BN) * 128, lds_epi_whole = (size_t)BM * (BN + 4) * 4;
-  constexpr size_t lds_epi = lds_epi_whole > 160 * 1024 ? lds_epi_whole / 2 : lds_epi_whole;   // two passes (the kernel's EP)
+  constexpr size_t lds_stage = (size_t)2 * (BM + BN) * 128, lds_epi = (size_t)BM * (BN + 4) * 4;
   constexpr size_t lds = lds_stage > lds_epi ? lds_stage : lds_epi;
   void (*kern)(const DArgs) = conv_dma_bf16<BM, BN, WAVES_M, WAVES_N, KS, TAP, DUAL>;
   static std::atomic<uint64_t> attr_done{0};  // per instantiation, one bit per device
@@ -305,12 +290,6 @@ int launch_dma_bf16(const DArgs& da, int ks, int tap, int grid, hipStream_t stre
   return PR_ERR_INVALID;
 }
 
-int ilog2_exact_b(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
 }  // namespace
 
 int conv_dma_bf16_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, int threads) {
@@ -322,7 +301,7 @@ int conv_dma_bf16_launch(const ConvProblem& p, int BM, int BN, hipStream_t strea
   const size_t x2b = p.x2 ? (size_t)p.B * p.H2 * p.W2 * p.Cin2 * 2 : 0;
   PR_REQUIRE(xb < (1ull << 31) && wb < (1ull << 31) && (size_t)p.M() * p.Cout < (1ull << 31),
              "conv: tensor too large for one launch (%zu input bytes)", xb);
-  const int l2 = ilog2_exact_b(p.Cin);
+  const int l2 = ilog2_exact(p.Cin);
   int tap;
   if (p.KH == 1 && p.pad == 0) tap = 0;
   else if (p.Cin % BK == 0) tap = 1;     // slice-major K: no power of two needed
@@ -362,7 +341,6 @@ int conv_dma_bf16_launch(const ConvProblem& p, int BM, int BN, hipStream_t strea
     case 64128: return launch_dma_bf16<64, 128, 2, 2>(da, p.KH, tap, grid, stream);
     case 256064: return launch_dma_bf16<256, 64, 4, 2>(da, p.KH, tap, grid, stream);
     case 64256: return launch_dma_bf16<64, 256, 2, 2>(da, p.KH, tap, grid, stream);
-    case 256256: return launch_dma_bf16<256, 256, 4, 2>(da, p.KH, tap, grid, stream);   // bf16 only (round 6: experiment 6)
   }
   set_error("conv_dma: no %dx%d tile", BM, BN);
   return PR_ERR_INVALID;

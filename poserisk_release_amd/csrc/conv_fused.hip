@@ -18,16 +18,12 @@
 #include <cstdlib>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void;
-
 constexpr int BK = kConvBK;
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 
 struct FArgs {
   const float* x;      // t1 [B,H,W,Cin]
@@ -54,8 +50,7 @@ __global__ __launch_bounds__(256, 5) void conv3x3_conv1x1_f32(const FArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int tile_m = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int tile_m = xcd_contiguous_block<int>(bid, nb);
   const int m0 = tile_m * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -63,10 +58,10 @@ __global__ __launch_bounds__(256, 5) void conv3x3_conv1x1_f32(const FArgs a) {
 
   // ---- DMA source addressing (conv_dma.hip): wave w stages row groups w and w + 4, lane = row 8g + (lane>>3),
   // physical chunk lane&7 = logical chunk q
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto w2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w2), 0, (int)a.w2_bytes, 0x00020000);
-  const auto w3src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w3), 0, (int)a.w3_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto w2src = make_rsrc(a.w2, (int)a.w2_bytes);
+  const auto w3src = make_rsrc(a.w3, (int)a.w3_bytes);
   int a_base[2], a_hi0[2], a_wi0[2];
   unsigned b2_off[2], b3_off[2];
   const int K2 = a.nk * BK;
@@ -169,8 +164,8 @@ __global__ __launch_bounds__(256, 5) void conv3x3_conv1x1_f32(const FArgs a) {
   const int col_l = lane & 31, row_h = 4 * (lane >> 5);
   // residual and output through range-checked buffer descriptors, one 32-bit lane offset for both
   const int yz_bytes = a.M * a.N3 * 4;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, yz_bytes, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, yz_bytes, 0x00020000);
+  const auto rsrc = make_rsrc(a.res ? a.res : a.y, yz_bytes);
+  const auto ysrc = make_rsrc(a.y, yz_bytes);
   const int frag_off = ((m0 + wm * 32 + row_h) * a.N3 + wn * 32 + col_l) * 4;
   // Rows >= M of a ragged last tile are dropped by making their VECTOR offset the out-of-range sentinel: fragment row
   // (e & 3) + 8 (e >> 2) is valid while it is < mlim.  (LLVM documents the scalar offset, which carries the row term
@@ -240,18 +235,16 @@ __global__ __launch_bounds__(256, 3) void conv1x1_panel_f32(const PArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int item = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int item = xcd_contiguous_block<int>(bid, nb);
   const int panel = item / a.nsplit, part = item - panel * a.nsplit;
   const int m0 = panel * 64, nbase = part * a.chunks * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  [[maybe_unused]] const auto x2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? a.x2 : a.x), 0,
-                                                                          DUAL ? (int)a.x2_bytes : 0, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, (int)a.w_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  [[maybe_unused]] const auto x2src = make_rsrc(DUAL ? a.x2 : a.x, DUAL ? (int)a.x2_bytes : 0);
+  const auto wsrc = make_rsrc(a.w, (int)a.w_bytes);
   char* ring = smem + a.nk * 8192;
 
   // ---- the row panel: all of K for 64 rows, nk stages in the operand layout ------------------------------------
@@ -295,8 +288,8 @@ __global__ __launch_bounds__(256, 3) void conv1x1_panel_f32(const PArgs a) {
   float rfrag[16];
   const int col_l = lane & 31, row_h = 4 * (lane >> 5);
   const int yz_bytes = a.M * a.N * 4;
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, yz_bytes, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, yz_bytes, 0x00020000);
+  const auto rsrc = make_rsrc(a.res ? a.res : a.y, yz_bytes);
+  const auto ysrc = make_rsrc(a.y, yz_bytes);
   const int frag_off = ((m0 + wm * 32 + row_h) * a.N + nbase + wn * 32 + col_l) * 4;
   const int mlim = a.M - (m0 + wm * 32 + row_h);   // fragment rows < mlim exist (see conv3x3_conv1x1_f32: out-of-range rows get the sentinel as their vector offset)
 
@@ -366,8 +359,6 @@ __global__ __launch_bounds__(256, 3) void conv1x1_panel_f32(const PArgs a) {
 // row; conv_dma_bf16.hip); the staging tile is unpadded (its reads are fully contiguous) and the kernel needs exactly
 // 40 KB of LDS: four workgroups per CU.
 // ---------------------------------------------------------------------------------------------------------------
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
 
 struct FArgsB {
   const unsigned short* x;
@@ -397,16 +388,15 @@ __global__ __launch_bounds__(256, 4) void conv3x3_conv1x1_bf16(const FArgsB a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BKB = 64;
   const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int tile_m = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int tile_m = xcd_contiguous_block<int>(bid, nb);
   const int m0 = tile_m * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  const auto w2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w2), 0, (int)a.w2_bytes, 0x00020000);
-  const auto w3src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w3), 0, (int)a.w3_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  const auto w2src = make_rsrc(a.w2, (int)a.w2_bytes);
+  const auto w3src = make_rsrc(a.w3, (int)a.w3_bytes);
   int a_base[2], a_hi0[2], a_wi0[2];
   unsigned b2_off[2], b3_off[2];
   const int K2 = a.nk * BKB;
@@ -467,7 +457,7 @@ __global__ __launch_bounds__(256, 4) void conv3x3_conv1x1_bf16(const FArgsB a) {
       bf[kk] = *reinterpret_cast<const bf16x8*>(Bb + foff[kk]);
     }
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc = mfma_bf16_step(af[kk], bf[kk], acc, kk);
+    for (int kk = 0; kk < 4; ++kk) acc = mfma_bf16_step(af[kk], bf[kk], acc);
   };
 
   issue(0, 0);
@@ -568,18 +558,16 @@ __global__ __launch_bounds__(256, 2) void conv1x1_panel_bf16(const PArgsB a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BKB = 64;
   const int nb = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nb >> 3, rr = nb & 7;
-  const int item = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int item = xcd_contiguous_block<int>(bid, nb);
   const int panel = item / a.nsplit, part = item - panel * a.nsplit;
   const int m0 = panel * 64, nbase = part * a.chunks * 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
-  [[maybe_unused]] const auto x2src = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(DUAL ? a.x2 : a.x), 0,
-                                                                          DUAL ? (int)a.x2_bytes : 0, 0x00020000);
-  const auto wsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w), 0, (int)a.w_bytes, 0x00020000);
+  const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
+  [[maybe_unused]] const auto x2src = make_rsrc(DUAL ? a.x2 : a.x, DUAL ? (int)a.x2_bytes : 0);
+  const auto wsrc = make_rsrc(a.w, (int)a.w_bytes);
   char* ring = smem + a.nk * 8192;
   float* Ct = reinterpret_cast<float*>(ring + 16384);
 
@@ -656,7 +644,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_panel_bf16(const PArgsB a) {
         bf[kk] = *reinterpret_cast<const bf16x8*>(Bb + foff[kk]);
       }
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) acc = mfma_bf16_step(af[kk], bf[kk], acc, kk);
+      for (int kk = 0; kk < 4; ++kk) acc = mfma_bf16_step(af[kk], bf[kk], acc);
     }
     if (kt == a.nk - 1) {
       {
@@ -702,18 +690,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_panel_bf16(const PArgsB a) {
 #endif
 }
 
-int ilog2_exact_f(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
-
 }  // namespace
 
 int conv_fused3_launch(const ConvProblem& p, hipStream_t stream) {
   PR_REQUIRE(p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cout == 64 && p.Ho == p.H && p.Wo == p.W,
              "conv_fused3: the first convolution must be 3x3 / stride 1 / pad 1 with 64 output channels");
-  const int l2 = ilog2_exact_f(p.Cin);
+  const int l2 = ilog2_exact(p.Cin);
   PR_REQUIRE(l2 >= 0 && p.Cin % (p.precision == 1 ? 64 : BK) == 0, "conv_fused3: Cin must be a power of two >= %d (%d)",
              p.precision == 1 ? 64 : BK, p.Cin);
   PR_REQUIRE(p.w3 && p.bias && p.bias3 && p.y3 && p.N3 > 0 && p.N3 % 64 == 0 && !p.x2 && p.groups == 1,

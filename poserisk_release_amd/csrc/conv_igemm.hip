@@ -2,7 +2,9 @@
 // the LDS-DMA kernels (conv_dma.hip, conv_dma_bf16.hip), the fused kernels (conv_fused.hip) and the row-panel form.
 // The first-generation kernel that lived here (register-staged operands, padded LDS rows; tile configs 0-5) was retired
 // in round 3: production ran on the LDS-DMA kernels since round 1 and the parity tests compare every configuration with
-// torch, not with it.  The indices 0-5 stay reserved (they return PR_ERR_INVALID) so that 6.. keep their numbers.
+// torch, not with it.  The 256x256 bf16 tile (config 18, round 6) was retired too: 25-60 % slower on the shapes it was built
+// for (profiles/r06_tile256_bf16.txt) and never picked.  Retired indices stay reserved (conv_launch refuses them by name) so
+// that the live ones keep their numbers in profiles/ and scripts/tune_conv.py.
 #include "conv_igemm.h"
 
 #include <cstdio>
@@ -19,17 +21,17 @@ struct TileCfg {
   int BM, BN, threads;
   const char* name;
   int blocks_per_cu;   // LDS-limited residency
+  bool live = true;    // false: retired, the index is kept and refused
 };
 
-constexpr int kNumRegCfg = 6;  // 0..5: the first-generation register-staged kernel, retired in round 3 (indices kept); 6..: LDS-DMA kernels (conv_dma.hip)
 constexpr int kNumCfg = 19;
 const TileCfg kCfgs[kNumCfg] = {
-    {128, 128, 256, "reg_128x128x32_w2x2", 2},
-    {128, 64, 256, "reg_128x64x32_w2x2", 2},
-    {64, 64, 256, "reg_64x64x32_w2x2", 4},
-    {256, 128, 512, "reg_256x128x32_w4x2", 1},
-    {64, 128, 256, "reg_64x128x32_w2x2", 2},
-    {256, 64, 512, "reg_256x64x32_w4x2", 1},
+    {128, 128, 256, "reg_128x128x32_w2x2", 2, false},
+    {128, 64, 256, "reg_128x64x32_w2x2", 2, false},
+    {64, 64, 256, "reg_64x64x32_w2x2", 4, false},
+    {256, 128, 512, "reg_256x128x32_w4x2", 1, false},
+    {64, 128, 256, "reg_64x128x32_w2x2", 2, false},
+    {256, 64, 512, "reg_256x64x32_w4x2", 1, false},
     {128, 128, 256, "dma_128x128x32_w2x2", 2},
     {128, 64, 256, "dma_128x64x32_w2x2", 3},
     {64, 64, 256, "dma_64x64x32_w2x2", 5},
@@ -42,14 +44,8 @@ const TileCfg kCfgs[kNumCfg] = {
     {128, 64, 128, "dma_128x64x32_w2x1", 3},     // 2 waves per 128x64 tile (64x64 per wave)
     {64, 128, 128, "dma_64x128x32_w1x2", 3},     // 2 waves per 64x128 tile (64x64 per wave)
     {64, 256, 256, "dma_64x256x32_w2x2", 2},     // whole 256-channel rows per tile (32x128 per wave): short-K conv3
-    {256, 256, 512, "dma_256x256x64_w4x2_bf16", 1},   // bf16 ONLY (fp32's epilogue and registers do not take it): 64x128 per wave
+    {256, 256, 512, "dma_256x256x64_w4x2_bf16", 1, false},   // bf16 only, two-pass epilogue; retired
 };
-
-int ilog2_exact(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return (1 << l) == v ? l : -1;
-}
 
 }  // namespace
 
@@ -82,9 +78,8 @@ int conv_pick_tile_cfg(const ConvProblem& p) {
   const int forced = p.tune.force_cfg;
   // (fp32 dual-source and split-K launches exist on the 64x64 tile only: they keep it)
   const bool fixed_tile = p.precision == 0 && (p.x2 || p.splitk > 1);
-  if (forced >= 0 && forced < kNumCfg && !fixed_tile && p.Cout % kCfgs[forced].BN == 0 && p.M() >= kCfgs[forced].BM &&
-      (p.precision == 1 || forced != 18))
-    return forced;
+  // (a retired index is handed on like a live one: conv_launch refuses it by name, in both precisions)
+  if (forced >= 0 && forced < kNumCfg && !fixed_tile && p.Cout % kCfgs[forced].BN == 0 && p.M() >= kCfgs[forced].BM) return forced;
   if (p.precision == 1) {
     // bf16: the MFMA is 16x faster, so the kernel lives on L2->LDS bandwidth and wants big tiles.  Per-layer times inside
     // the B=256 pipeline, every tile configuration in turn (gpurun_out/r02_layers256_bf16_cfg*.txt; round 1's isolated
@@ -126,19 +121,14 @@ int conv_launch(const ConvProblem& p, int cfg, hipStream_t stream) {
   PR_REQUIRE(cfg >= 0 && cfg < kNumCfg, "conv: bad tile cfg %d", cfg);
   const TileCfg& t = kCfgs[cfg];
   if (p.w3) return conv_fused3_launch(p, stream);
-  if (p.precision == 1) {
-    PR_REQUIRE(cfg >= kNumRegCfg, "conv: bf16 runs on the LDS-DMA tile configs (>= %d) only", kNumRegCfg);
-    return conv_dma_bf16_launch(p, t.BM, t.BN, stream, t.threads);
-  }
+  // a tile that does not fit the layer is refused as such, retired or not; a retired one that fits is refused by name
+  PR_REQUIRE(p.Cout % t.BN == 0, "conv: Cout %d not a multiple of tile N %d", p.Cout, t.BN);
+  PR_REQUIRE(t.live, "conv: tile cfg %d (%s) is retired", cfg, t.name);
+  if (p.precision == 1) return conv_dma_bf16_launch(p, t.BM, t.BN, stream, t.threads);
   PR_REQUIRE(p.KH == p.KW, "conv: square kernels only (got %dx%d)", p.KH, p.KW);
   PR_REQUIRE(p.Cin % 4 == 0, "conv: Cin %% 4 != 0 (%d)", p.Cin);
-  PR_REQUIRE(p.Cout % t.BN == 0, "conv: Cout %d not a multiple of tile N %d", p.Cout, t.BN);
   PR_REQUIRE(p.x && p.w && p.y, "conv: null tensor");
-  PR_REQUIRE(cfg >= kNumRegCfg, "conv: tile cfg %d (%s) was the first-generation register-staged kernel, retired in round 3; "
-             "the LDS-DMA kernels are cfgs %d..%d", cfg, t.name, kNumRegCfg, kNumCfg - 1);
-  PR_REQUIRE(!(t.BM == 256 && t.BN == 256), "conv: tile cfg %d (%s) is a bf16-only tile", cfg, t.name);
   return conv_dma_launch(p, t.BM, t.BN, stream, t.threads);
 }
-
 
 }  // namespace pr

@@ -32,14 +32,12 @@
 // the stage is filled once per NB blocks -- half (a quarter) of the LDS-DMA, the L2 reads and the fragment reads per MFMA.  An
 // output's chain is still bias, then (q, j) ascending: the SAME BITS for every (T, NB).
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
+#include "timing_hooks.h"
 
 namespace pr {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-typedef __attribute__((address_space(3))) void lds_void;
-constexpr unsigned kOOB = 0x80000000u;
 // 16-pixel tiles per unit (T).  Measured in round 4 with 4 at K = 128 (64-pixel units, a unit's fixed costs once per 4 096
 // MFMA cycles as at K = 256): no faster inside the loop and the shares get coarser (6 or 7 units per workgroup instead of 13 or
 // 14): layer2's Winograd GEMM 44.3 -> 45.8 us, its conv3 70.1 -> 72.5 us.
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(256) void conv1x1_regw_f32(const RArgs a) {
   const int u0 = conv_regw_run_begin(blockIdx.x, a.units, G), u1 = conv_regw_run_begin((long)(blockIdx.x + 1), a.units, G);
   if (u0 >= u1) return;
 
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
   // DMA piece i of this wave (i < NDMA): bytes [(wave * NDMA + i) * 1024, + 1024) of the stage; lane covers 16 of them.
   // row0 / lim: the unit's first flat row and its group's end
   auto issue_piece = [&](int row0, int lim, int stage, int i) {
@@ -121,8 +119,8 @@ __global__ __launch_bounds__(256) void conv1x1_regw_f32(const RArgs a) {
   // instructions in a block behind the barrier kept its MFMAs from issuing for 0.9 us of a 4.3 us unit (per-wave stamps,
   // profiles/r04_experiments.txt section 5).  A row outside the unit's group gets the offset 2^31, which the buffer's
   // range check drops (stores) or answers with zero (loads); the "unit before the first" has no rows.
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.y_bytes, 0x00020000);
-  const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, (int)a.y_bytes, 0x00020000);
+  const auto ysrc = make_rsrc(a.y, (int)a.y_bytes);
+  const auto rsrc = make_rsrc(a.res ? a.res : a.y, (int)a.y_bytes);
   const bool has_res = a.res != nullptr;
   const unsigned n4 = (unsigned)a.N * 4u;
   // The weights are the MFMA's A operand and the pixels its B operand, so a lane's four accumulator values are four
@@ -308,25 +306,9 @@ int conv_regw_f32_launch(const ConvProblem& p, hipStream_t stream) {
   if (const char* e = getenv("POSERISK_REGW_EXP")) a.exp = atoi(e);
   // timing builds: the 20th launch records, per wave, s_memrealtime (100 MHz) at entry / exit and the summed time spent on the
   // weight loads, at the unit's wait + barrier, in the epilogue + residual requests, and in the MFMA loop; units; HW_ID
-  static unsigned long long* stamp_buf = nullptr;
   static int stamp_calls = 0;
-  const char* stamp_path = getenv("POSERISK_REGW_STAMPS");
-  const bool stamp_now = stamp_path && ++stamp_calls == 20;
-  if (stamp_now) {
-    if (!stamp_buf) PR_HIP(hipMalloc(&stamp_buf, (size_t)grid * 4 * 8 * 8));
-    PR_HIP(hipMemsetAsync(stamp_buf, 0, (size_t)grid * 4 * 8 * 8, stream));
-    a.stamps = stamp_buf;
-  }
-  struct StampDump {
-    bool on; const char* path; int grid; hipStream_t s; unsigned long long* buf;
-    ~StampDump() {
-      if (!on) return;
-      std::vector<unsigned long long> host((size_t)grid * 4 * 8);
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(host.data(), buf, host.size() * 8, hipMemcpyDeviceToHost);
-      if (FILE* fo = fopen(path, "wb")) { fwrite(host.data(), 8, host.size(), fo); fclose(fo); }
-    }
-  } stamp_dump{stamp_now, stamp_path, grid, stream, stamp_buf};
+  StampRecorder stamp_rec("POSERISK_REGW_STAMPS", (size_t)grid * 4 * 8, 20, stamp_calls, stream);
+  a.stamps = stamp_rec.stamps();
 #endif
   auto go = [&](auto kern, std::atomic<uint64_t>& done) -> int {
     PR_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, done));

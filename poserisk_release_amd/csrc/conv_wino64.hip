@@ -27,16 +27,12 @@
 // file: W3 streams through the same two-stage ring, each stage feeding both 64-pixel halves; y leaves from the
 // accumulators with the residual.
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 #include "wino_transforms.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 constexpr int kTiles = 16;                       // tiles per unit: the B columns of a 16x16x4 MFMA
 constexpr int kSlice = 16;                       // input channels per pass
 constexpr int kPlane = kTiles * kSlice;          // floats of one plane of the V image
@@ -76,7 +72,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino64_f32(const WArgs a) {
   const int tx0 = cc * kTiles;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // output channels 16 wave .. 16 wave + 15
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
 
   // ---- input transform: thread = (tile pj, channel pc of the slice) -------------------------------------------------
   const int pj = tid >> 4, pc = tid & 15;
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino64_f32(const WArgs a) {
   // ---- MFMA: lane = (tile j | row i of the A fragment, k group g) ---------------------------------------------------
   const int j = lane & 15, g = lane >> 4;
   // U through a buffer descriptor: one lane offset, the (plane, slice) term in the scalar offset
-  const auto usrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.u), 0, 36 * 64 * 64 * 4, 0x00020000);
+  const auto usrc = make_rsrc(a.u, 36 * 64 * 64 * 4);
   const int ua = ((16 * wave + j) * kSlice + 4 * g) * 4;      // + (plane * 4 + slice) * 64 * 16 * 4
   const float* const vr = reinterpret_cast<const float*>(smem) + v_pos(j, g);
   f32x4 y[4][4];      // [output row][output column] x four consecutive channels 16 wave + 4 g ..
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino64_f32(const WArgs a) {
   }
 
   const f32x4 b2 = *reinterpret_cast<const f32x4*>(a.bias2 + 16 * wave + 4 * g);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.y_bytes, 0x00020000);
+  const auto ysrc = make_rsrc(a.y, (int)a.y_bytes);
   if constexpr (!FUSE3) {
     // ---- t2 = act(y + b2): 16 bytes per lane and pixel, pixels outside the map dropped by the range check -------------
 #pragma unroll
@@ -191,9 +187,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino64_f32(const WArgs a) {
   } else {
     // ---- conv3 on the unit's t2, eight tiles (two 64-pixel A tiles) at a time: conv_fused.hip's GEMM 2 ---------------
     const int wm = wave >> 1, wn = wave & 1;
-    const int q = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
-    const auto w3src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w3), 0, (int)a.w3_bytes, 0x00020000);
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.y), 0, (int)a.y_bytes, 0x00020000);
+    const int q = PR_DMA_SWIZZLE_SLOT(lane, wave);
+    const auto w3src = make_rsrc(a.w3, (int)a.w3_bytes);
+    const auto rsrc = make_rsrc(a.res ? a.res : a.y, (int)a.y_bytes);
     // a W3 stage is eight 1 KB pieces (8 rows each): pieces wave and wave + 4 are this wave's
     unsigned b3_off[2];
 #pragma unroll

@@ -22,12 +22,11 @@
 #include <algorithm>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 #include "wino_transforms.h"
 
 namespace pr {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 struct WinoArgs {
   const float* x;     // [B,H,W,C]
@@ -125,9 +124,6 @@ __global__ __launch_bounds__(256) void wino_output_transform(const WinoArgs a) {
     }
   }
 }
-
-
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 // ---- F(4x4,3x3): one thread per (tile, 2 channels); 36 values live, both passes in place ---------------------
 // The transform rows bt6<PTS> / at6<PTS> and their two point sets (PTS 0 = conv form 4, PTS 1 = conv form 5): wino_transforms.h

@@ -15,18 +15,10 @@
 #include <algorithm>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 
 struct ExArgs {
   const unsigned short* t;     // [M][K1]
@@ -42,10 +34,6 @@ struct ExArgs {
   unsigned x2_bytes;
   int HoWo, Wo, H2, W2, stride2;
 };
-
-__device__ inline unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
 
 // KS1 / KS2 = k-steps (16 channels) of t / of the second source; TPW = tiles of 32 channels per wave, a workgroup covers
 // 256 TPW output channels; NS = column blocks: N = 256 TPW NS, workgroup w takes column block (w >> 3) % NS of pixel-block
@@ -84,13 +72,11 @@ __global__ __launch_bounds__(512) void expand_res_bf16(const ExArgs a) {
 
   // pixel ring: block b -> slot (b - b0) % kSlots, SL slices of [64 pixels][128 B], 16-byte chunks XOR-swizzled on the source
   // side; a slice is eight 1 KB DMA groups of 8 pixels, wave w issues group w of every slice
-  const auto tsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.t), 0, (int)a.t_bytes, 0x00020000);
-  [[maybe_unused]] const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(KS2 ? a.x2 : a.t), 0,
-                                                                         KS2 ? (int)a.x2_bytes : 0, 0x00020000);
-  [[maybe_unused]] const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(RES ? a.res : a.t), 0,
-                                                                         RES ? (int)a.y_bytes : 0, 0x00020000);
-  const auto ysrc = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (int)a.y_bytes, 0x00020000);
-  const int dq = (lane & 7) ^ ((4 * (wave & 1) + (lane >> 4)) & 7);
+  const auto tsrc = make_rsrc(a.t, (int)a.t_bytes);
+  [[maybe_unused]] const auto xsrc = make_rsrc(KS2 ? a.x2 : a.t, KS2 ? (int)a.x2_bytes : 0);
+  [[maybe_unused]] const auto rsrc = make_rsrc(RES ? a.res : a.t, RES ? (int)a.y_bytes : 0);
+  const auto ysrc = make_rsrc(a.y, (int)a.y_bytes);
+  const int dq = PR_DMA_SWIZZLE_SLOT(lane, wave);
   auto issue_block = [&](int b) {                  // ALWAYS SL pieces
     const int m = b * 64 + 8 * wave + (lane >> 3);
     const bool ok = b < b1 && m < a.M;
@@ -176,7 +162,7 @@ __global__ __launch_bounds__(512) void expand_res_bf16(const ExArgs a) {
 #pragma unroll
         for (int n = 0; n < TPW; ++n)
 #pragma unroll
-          for (int ks = 0; ks < KH; ++ks) acc[n] = mfma_bf16_step(wf[n][k0 + ks], tf[ks], acc[n], ks);
+          for (int ks = 0; ks < KH; ++ks) acc[n] = mfma_bf16_step(wf[n][k0 + ks], tf[ks], acc[n]);
       }
       const int m = b * 64 + 32 * pt + i;
       const unsigned yoff = m < a.M ? (unsigned)(m * (2 * N) + 32 * h) : kOOB;
@@ -196,7 +182,7 @@ __global__ __launch_bounds__(512) void expand_res_bf16(const ExArgs a) {
             v0 = fmaxf(v0, 0.f);
             v1 = fmaxf(v1, 0.f);
           }
-          pk[e] = pack2(v0, v1);
+          pk[e] = pack_bf16x2(v0, v1);
         }
         buffer_store_b128_sreg(u32x4{pk[0], pk[1], pk[2], pk[3]}, ysrc, yoff, csoff + 64 * n);
         buffer_store_b128_sreg(u32x4{pk[4], pk[5], pk[6], pk[7]}, ysrc, yoff + 16, csoff + 64 * n);

@@ -9,11 +9,10 @@
 // (four waves, whatever the batch), so a frame's bits do not depend on its batch or position.
 #include "conv_igemm.h"
 #include "frame_kernels.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // grid (N / (16 NT), ceil(M / (16 MT))), 256 threads.  K % 64 == 0, N % (16 NT) == 0; x rows are K floats apart, y / res rows N floats.
 // MT x NT output tiles of 16x16 per workgroup (round 5, built to test whether the launch is traffic-bound at M = 256, where the

@@ -2,14 +2,13 @@
 //   layout change NCHW->NHWC4, max-pool, global average pool, regressor state init/finalise
 //   (rot6d -> rotmat), rotmat -> axis-angle -> Euler degrees, REBA, RULA.
 #include "frame_kernels.h"
+#include "kernel_vocab.h"
 
 #include <cfloat>
 #include <cmath>
 
 namespace pr {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // ---------------------------------------------------------------------------------------------
 // Encoder plumbing
@@ -113,7 +112,6 @@ __global__ void avgpool_nhwc(const float* __restrict__ x, float* __restrict__ y,
 }
 
 // ---- bf16 encoder plumbing (precision = 1) -----------------------------------------------------------
-using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
 __device__ inline float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 __device__ inline unsigned short f2bf(float f) {
   const __bf16 h = (__bf16)f;
@@ -162,7 +160,6 @@ __global__ void nchw3_to_s2d16_bf16(const float* __restrict__ x, unsigned short*
 // patterns as SIGNED 16-bit integers (-0 = 0x8000 is the smallest, a positive NaN 0x7fc0 the largest, so it propagates
 // like torch's max-pool), so the maximum is four v_pk_max_i16 per tap instead of sixteen conversions and maxima --
 // the float form of this kernel was VALU-bound at 2.3 TB/s (profiles/r02_bench_b256_bf16_lanes1_kernel_stats.csv).
-using i16x8 = __attribute__((ext_vector_type(8))) short;
 __global__ void maxpool3x3s2_nhwc_bf16(const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
                                        int B, int H, int W, int C, int Ho, int Wo) {
   const int c8n = C / 8;

@@ -31,5 +31,10 @@ void set_error(const char* fmt, ...);
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
+inline int ilog2_exact(int v) {   // log2 of a power of two, -1 for anything else
+  int l = 0;
+  while ((1 << l) < v) ++l;
+  return (1 << l) == v ? l : -1;
+}
 
 }  // namespace pr

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
@@ -43,9 +44,6 @@ constexpr int kJ = 24;
 constexpr int kFB = 16;        // frames per wave in the skinning kernel
 constexpr int kRowsPerWave = 63;  // 21 vertices x 3 components
 constexpr int kMaxNB = 16;
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 struct Tree {  // host copy; the kernels read parent/depth from a 48-int device array
   int parent[kJ];
@@ -486,9 +484,8 @@ __global__ __launch_bounds__(kTileThreads, 4) void smpl_skin_tile(const SkinArgs
   // 208 pieces dealt to the two waves that read it), the 16 frames' transforms (18 KB, contiguous in A), shape
   // coefficients and vertex offsets.
   {
-    typedef __attribute__((address_space(3))) void lds_void;
     char* lds = reinterpret_cast<char*>(tile_lds);
-    const auto pmsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.pm_T), 0, (int)((long)a.NPpad * a.Bs * 4), 0x00020000);
+    const auto pmsrc = make_rsrc(a.pm_T, (int)((long)a.NPpad * a.Bs * 4));
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int uu = 2 * hrs + u, i = lane + 64 * uu;
@@ -496,17 +493,17 @@ __global__ __launch_bounds__(kTileThreads, 4) void smpl_skin_tile(const SkinArgs
         __builtin_amdgcn_raw_ptr_buffer_load_lds(pmsrc, (lds_void*)(lds + ((q * pq * kFB) * 4 + uu * 1024)), 16,
                                                  (unsigned)((((q * pq + (i >> 2)) * a.Bs) + fb0 + (i & 3) * 4) * 4), 0, 0, 0);
     }
-    const auto asrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A), 0, (int)((long)a.Bs * kJ * 12 * 4), 0x00020000);
+    const auto asrc = make_rsrc(a.A, (int)((long)a.Bs * kJ * 12 * 4));
     for (int pc = w8; pc < kTileAs / 256; pc += 8)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(asrc, (lds_void*)(lds + (kTilePM + pc * 256) * 4), 16,
                                                (unsigned)((fb0 * kJ * 12 + pc * 256) * 4 + lane * 16), 0, 0, 0);
     if (w8 == 0 && lane < kTileNB * 4) {
-      const auto bsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.betas_T), 0, (int)((long)kMaxNB * a.Bs * 4), 0x00020000);
+      const auto bsrc = make_rsrc(a.betas_T, (int)((long)kMaxNB * a.Bs * 4));
       __builtin_amdgcn_raw_ptr_buffer_load_lds(bsrc, (lds_void*)(lds + (kTilePM + kTileAs + kTileRed + kFB * 3) * 4), 16,
                                                (unsigned)((((lane >> 2) * a.Bs) + fb0 + (lane & 3) * 4) * 4), 0, 0, 0);
     }
     if (w8 == 1 && lane < kFB * 3 / 4) {
-      const auto osrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.voff), 0, (int)((long)a.Bs * 3 * 4), 0x00020000);
+      const auto osrc = make_rsrc(a.voff, (int)((long)a.Bs * 3 * 4));
       __builtin_amdgcn_raw_ptr_buffer_load_lds(osrc, (lds_void*)(lds + (kTilePM + kTileAs + kTileRed) * 4), 16,
                                                (unsigned)(fb0 * 3 * 4 + lane * 16), 0, 0, 0);
     }
@@ -515,8 +512,7 @@ __global__ __launch_bounds__(kTileThreads, 4) void smpl_skin_tile(const SkinArgs
   // out-of-range sentinel as their VECTOR offset (zero, no memory access) instead of relying on the scalar offset,
   // which carries the coefficient, being range-checked (gfx950 does check it: scripts/micro/t_soffset.hip; LLVM's
   // description of the intrinsic says it need not be).
-  const auto pdsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.posedirs_T + (long)q * pq * a.R), 0,
-                                                       (int)((long)pq * a.R * 4), 0x00020000);
+  const auto pdsrc = make_rsrc(a.posedirs_T + (long)q * pq * a.R, (int)((long)pq * a.R * 4));
   const unsigned roff0 = (unsigned)row[0] * 4u, roff1 = (unsigned)row[1] * 4u;
   auto model = [&](int k) {
     const unsigned so = (unsigned)k * (unsigned)a.R * 4u;

@@ -27,19 +27,11 @@
 #include <algorithm>
 
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using i16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-typedef __attribute__((address_space(3))) void lds_void;
-
-[[maybe_unused]] constexpr unsigned kOOB = 0x80000000u;
 constexpr int kInRows = 16;                      // input-row ring
 constexpr int kInRow = 4096;                     // two planes of 128 pixel slots x 16 bytes
 constexpr int kCvRows = 6;                       // conv-row ring
@@ -59,10 +51,6 @@ struct SPArgs {
   unsigned x_bytes;
   int B, H, bands, band_rows;   // workgroups per image, pooled rows per workgroup
 };
-
-__device__ inline unsigned pack2(float lo, float hi) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
 
 __global__ __launch_bounds__(1024) void stem_pool_bf16(const SPArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(1024) void stem_pool_bf16(const SPArgs a) {
   if (tid < 64) *reinterpret_cast<float*>(smem + kOffBias + tid * 4) = a.bias[tid];
 
   // ---- input ring: row r of the image -> slot r & 15; one row = four 1 KB DMA pieces (plane, 64-slot half) ---------------
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
   auto issue_piece = [&](int r, int piece) {        // piece = 2 * plane + half, wave-uniform
     const int plane = piece >> 1, slot = 64 * (piece & 1) + lane, p = slot - 2;
     const bool ok = (unsigned)r < (unsigned)H && (unsigned)p < (unsigned)H;
@@ -115,12 +103,12 @@ __global__ __launch_bounds__(1024) void stem_pool_bf16(const SPArgs a) {
 #pragma unroll
       for (int tw = 0; tw < 4; ++tw) bf[tw] = *reinterpret_cast<const bf16x8*>(row + tw * 16);
 #pragma unroll
-      for (int tw = 0; tw < 4; ++tw) acc = mfma_bf16_step(wf[4 * th + tw], bf[tw], acc, tw);
+      for (int tw = 0; tw < 4; ++tw) acc = mfma_bf16_step(wf[4 * th + tw], bf[tw], acc);
     }
     unsigned pk[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      pk[e] = pack2(fmaxf(acc[2 * e] + bp[2 * e], 0.f), fmaxf(acc[2 * e + 1] + bp[2 * e + 1], 0.f));
+      pk[e] = pack_bf16x2(fmaxf(acc[2 * e] + bp[2 * e], 0.f), fmaxf(acc[2 * e + 1] + bp[2 * e + 1], 0.f));
     if (px < H) {
       // 144-byte pixels: the eight lanes of a ds_write_b128 group (consecutive pixels) write eight different 16-byte bank groups
       // (with 128-byte pixels all eight met on the same banks)

@@ -20,12 +20,10 @@
 // The k order inside a pixel's fmaf chain is (step, j = 0..2, k-group g = 0..3), steps as listed at the weights -- fixed, so a
 // frame's bits do not depend on its batch or position; it is NOT the tile kernel's order (channel-ascending inside a tap).
 #include "conv_igemm.h"
+#include "kernel_vocab.h"
 
 namespace pr {
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int kH = 112, kC = 12, kHP = 56;
 constexpr int kBand = 7;                       // pooled rows per workgroup
@@ -34,7 +32,6 @@ constexpr int kMargin = 2 * kC * 4;            // two zero pixels in front of th
 constexpr int kSlot = 6400;                    // >= kMargin + 6 x 1 KB DMA pieces (the sixth runs past the row: zeros = the right margin)
 constexpr int kRing = 6;
 constexpr int kLds = kRing * kSlot;
-constexpr unsigned kOOB = 0x80000000u;
 
 struct SArgs {
   const float* x;      // [B][112][112][12]
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(256) void stem_pool_f32(const SArgs a) {
   const float bias = a.bias[16 * wave + m];
 
   // ---- input rows by LDS-DMA: streamed row s (s = 0 .. 2 * kBand + 3) is image row y0 - 2 + s, slot s % 6 ------------
-  const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, (int)a.x_bytes, 0x00020000);
+  const auto xsrc = make_rsrc(a.x, (int)a.x_bytes);
   constexpr int kRows = 2 * kBand + 1 + 3;     // 15 conv rows read 18 input rows
   auto issue_row = [&](int s) {                // pieces w and w + 4 of the row's six (wave-uniform)
     const int yy = y0 - 2 + s;

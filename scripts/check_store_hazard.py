@@ -6,7 +6,7 @@ Why (measured on MI355X, scripts/micro/t_store_hazard.hip -> profiles/r03_t_stor
 reach memory instead of the stored value -- 0.4 % of the stores with an SGPR soffset, 22 % with a literal one, under
 back-pressure; ONE wait state still loses 0.5-1.7 % of the literal-soffset / global forms, TWO are always enough.  hipcc pads one
 wait state, and none at all when a buffer store's soffset is a register.  The kernels' own 16-byte buffer stores go through
-`buffer_store_b128_sreg` (csrc/common.h), which carries its wait states; this script checks what the compiler scheduled around
+`buffer_store_b128_sreg` (csrc/kernel_vocab.h), which carries its wait states; this script checks what the compiler scheduled around
 every other wide store.
 
 Second check (scan_counted_waits): no register spill (scratch_*) inside a loop that waits with a counted `s_waitcnt vmcnt(n > 0)`
@@ -173,7 +173,7 @@ def scan_counted_waits(so_path):
 def permlane_swap_groups(ins):
     """v_permlane32_swap_b32 / v_permlane16_swap_b32 of one function as runs of consecutive swaps:
     -> list of (first swap's text, number of swaps in the run, wait states directly in front of the run).
-    csrc/common.h::acc32_regs converts a 32 x 32 tile's accumulators with ONE asm statement of 8 swaps behind `s_nop 15` +
+    csrc/kernel_vocab.h::acc32_regs converts a 32 x 32 tile's accumulators with ONE asm statement of 8 swaps behind `s_nop 15` +
     `s_nop 3` (20 wait states: the matrix pipe's write -> VALU read distance, which hipcc does not pad for asm operands).  A run
     of another length or with a shorter pad did not come from that helper -- e.g. from the builtins, which hipcc 7.2
     miscompiles (second result dropped, calls merged: profiles/r06_experiments.txt 1b)."""

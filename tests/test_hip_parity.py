@@ -59,8 +59,8 @@ def test_conv_matches_torch(gpu_device, case):
             y, _ = ops.conv2d_nhwc(_t(x, gpu_device), w, bias, _t(res, gpu_device), stride=s, pad=p, relu=True,
                                    tile_cfg=cfg)
         except _lib.PoseRiskHipError as e:
-            # this tile does not fit Cout, or it is one of the reserved indices of the retired first-generation kernel
-            assert cfg >= 0 and ("not a multiple of tile N" in str(e) or (cfg < 6 and "retired" in str(e)) or "bf16-only" in str(e)), str(e)
+            # this tile does not fit Cout, or it is one of the reserved indices of a retired kernel (0..5, 18)
+            assert cfg >= 0 and ("not a multiple of tile N" in str(e) or ((cfg < 6 or cfg == 18) and "retired" in str(e))), str(e)
             continue
         err = np.abs(y.cpu().numpy() - ref).max()
         assert err < 2e-5 * max(1.0, np.abs(ref).max()), f"cfg {cfg}: max err {err}"
@@ -882,7 +882,7 @@ def test_conv_bf16_matches_emulation(gpu_device, case):
             y, _ = ops.conv2d_nhwc(x.to(gpu_device), w.numpy(), bias, res.to(gpu_device), stride=s, pad=p, relu=True,
                                    tile_cfg=cfg, precision="bf16")
         except _lib.PoseRiskHipError as e:
-            assert "not a multiple of tile N" in str(e) or "bad channels" in str(e)
+            assert "not a multiple of tile N" in str(e) or "bad channels" in str(e) or (cfg == 18 and "retired" in str(e)), str(e)
             continue
         ran += 1
         got = y.float().cpu()

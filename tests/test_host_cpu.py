@@ -433,7 +433,7 @@ def test_no_wide_store_is_followed_by_a_write_of_its_data_registers():
 def test_accumulator_layout_swaps_carry_their_wait_states():
     """ISA lint (scripts/check_store_hazard.py::scan_permlane_swaps): the bf16 tile kernel converts each 32 x 32 tile's
     16x16x32 accumulators to the 32x32x16 register layout with 8 v_permlane32_swap_b32 in ONE asm statement behind 20 wait
-    states (csrc/common.h::acc32_regs) -- hipcc pads nothing in front of asm operands, and with 2 wait states 96 of 1024 values
+    states (csrc/kernel_vocab.h::acc32_regs) -- hipcc pads nothing in front of asm operands, and with 2 wait states 96 of 1024 values
     came out wrong on the GPU.  Every swap in the shipped library must sit in such a group; and the reason the helper is asm:
     on this toolchain the BUILTIN loses its second result when four calls sit side by side (recorded here so that a fixed
     compiler is noticed)."""
