@@ -20,6 +20,14 @@
  *     blocking copy, so they may be captured into a hipGraph.
  *   - One handle per device; a handle is not thread-safe; distinct handles are independent.
  *   - Layouts are row-major with the last index fastest; float = IEEE binary32.
+ *
+ * Memory contract
+ *   No entry point reads or writes device memory outside the tensors whose extents its
+ *   arguments state (and the handle's own workspaces): not a row past a ragged last tile,
+ *   not the halo in front of the first frame or behind the last one, not the bytes an
+ *   unaligned wide load would drag in behind the last pixel.  This is enforced by the
+ *   guard-band tests (tests/test_guard_band_gpu.py), which run every stand-alone entry with
+ *   its inputs between NaN guards and its outputs between canary guards.
  */
 #ifndef POSERISK_HIP_H
 #define POSERISK_HIP_H

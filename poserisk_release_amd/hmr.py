@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, weights
+from .ops import _out, _outs
 
 
 CONV_FORMS = {"default": -1, "direct": 0, "winograd2": 2, "winograd4": 4, "winograd5": 5, "winograd244": 244,
@@ -128,7 +129,8 @@ class HMR:
         return getattr(self, "_generation", 0)
 
     # ---- forward ------------------------------------------------------------------------
-    def forward(self, x, return_features=False):
+    def forward(self, x, return_features=False, out=None):
+        """out: the tensors to write into, one per returned tensor, in the order they are returned."""
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224):
             raise ValueError(f"expected [B,3,224,224], got {tuple(x.shape)}")
         if x.device.type != "cuda":
@@ -137,11 +139,12 @@ class HMR:
         B = x.shape[0]
         self._ensure(B)
         dev = x.device
-        rotmat = torch.empty((B, 24, 3, 3), dtype=torch.float32, device=dev)
-        betas = torch.empty((B, 10), dtype=torch.float32, device=dev)
-        cam = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        xf = torch.empty((B, 2048), dtype=torch.float32, device=dev) if return_features else None
-        p6 = torch.empty((B, 144), dtype=torch.float32, device=dev) if return_features else None
+        rotmat, betas, cam, xf, p6 = _outs(out, 5) if return_features else _outs(out, 3) + (None, None)
+        rotmat = _out(rotmat, (B, 24, 3, 3), torch.float32, dev)
+        betas = _out(betas, (B, 10), torch.float32, dev)
+        cam = _out(cam, (B, 3), torch.float32, dev)
+        xf = _out(xf, (B, 2048), torch.float32, dev) if return_features else None
+        p6 = _out(p6, (B, 144), torch.float32, dev) if return_features else None
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(_lib.load().pr_hmr_forward(self._handle, x.data_ptr(), B, rotmat.data_ptr(), betas.data_ptr(),
                                               cam.data_ptr(), xf.data_ptr() if xf is not None else None,
@@ -156,10 +159,10 @@ class HMR:
     # (H = W, channels) of the encoder tap's blocks: the stem + max-pool, then layer1..layer4's Bottlenecks
     BLOCK_SHAPES = [(56, 64)] + [(56, 256)] * 3 + [(28, 512)] * 4 + [(14, 1024)] * 6 + [(7, 2048)] * 3
 
-    def encode_until(self, x, block):
+    def encode_until(self, x, block, out=None):
         """Test entry: the encoder of forward() -- same sub-batches, streams and kernel routing -- stopped after `block`
         (0 = stem + max-pool, 1..16 = the Bottlenecks) -> that block's output, NHWC [B,H,W,C] in the handle's dtype
-        (torch.float32, or torch.bfloat16 for the bf16 encoder) (pr_hmr_encode_until)."""
+        (torch.float32, or torch.bfloat16 for the bf16 encoder) (pr_hmr_encode_until).  out: that tensor, to write into."""
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224):
             raise ValueError(f"expected [B,3,224,224], got {tuple(x.shape)}")
         if x.device.type != "cuda":
@@ -168,7 +171,7 @@ class HMR:
         B = x.shape[0]
         self._ensure(B)
         hw, c = self.BLOCK_SHAPES[block] if 0 <= block < len(self.BLOCK_SHAPES) else (1, 1)
-        out = torch.empty((B, hw, hw, c), dtype=torch.bfloat16 if self._precision == 1 else torch.float32, device=x.device)
+        out = _out(out, (B, hw, hw, c), torch.bfloat16 if self._precision == 1 else torch.float32, x.device)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(_lib.load().pr_hmr_encode_until(self._handle, x.data_ptr(), B, int(block), out.data_ptr(), stream),
                    "pr_hmr_encode_until")

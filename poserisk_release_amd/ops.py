@@ -15,71 +15,82 @@ def _need_cuda(t, name):
         raise _lib.PoseRiskHipError(f"{name}: tensor must be on the GPU (no CPU fallback)")
 
 
-def rot6d_to_rotmat(pose6d):
-    """SPIN utils/geometry.py::rot6d_to_rotmat.  f32[N,144] -> f32[N,24,3,3]."""
-    _need_cuda(pose6d, "rot6d_to_rotmat")
-    p = pose6d.contiguous().float()
-    N = p.shape[0]
-    out = torch.empty((N, 24, 3, 3), dtype=torch.float32, device=p.device)
-    _lib.check(_lib.load().pr_rot6d_to_rotmat(p.data_ptr(), N, out.data_ptr(), _stream(p.device)), "pr_rot6d_to_rotmat")
-    return out
-
-
-def pose_to_euler(rotmat):
-    """rot_to_angle + axis_angle_to_euler_angle (lib/utils/coord_utils.py:24-30, 83-95) for a batch.
-    f32[N,24,3,3] -> (axis_angle f32[N,24,3], euler_deg f64[N,24,3], status int32[N])."""
-    _need_cuda(rotmat, "pose_to_euler")
-    r = rotmat.contiguous().float()
-    N = r.shape[0]
-    aa = torch.empty((N, 24, 3), dtype=torch.float32, device=r.device)
-    eul = torch.empty((N, 24, 3), dtype=torch.float64, device=r.device)
-    st = torch.empty((N,), dtype=torch.int32, device=r.device)
-    _lib.check(_lib.load().pr_pose_to_euler(r.data_ptr(), N, aa.data_ptr(), eul.data_ptr(), st.data_ptr(),
-                                            _stream(r.device)), "pr_pose_to_euler")
-    return aa, eul, st
-
-
-def axis_angle_to_euler(axis_angle):
-    """axis_angle_to_euler_angle (lib/utils/coord_utils.py:83-95) for a batch.
-    f32[N,24,3] -> (euler_deg f64[N,24,3], status int32[N])."""
-    _need_cuda(axis_angle, "axis_angle_to_euler")
-    a = axis_angle.contiguous().float()
-    N = a.shape[0]
-    eul = torch.empty((N, 24, 3), dtype=torch.float64, device=a.device)
-    st = torch.empty((N,), dtype=torch.int32, device=a.device)
-    _lib.check(_lib.load().pr_axis_angle_to_euler(a.data_ptr(), N, eul.data_ptr(), st.data_ptr(), _stream(a.device)),
-               "pr_axis_angle_to_euler")
-    return eul, st
-
-
-def reba(euler_deg, info):
-    """REBA.__call__ arithmetic (lib/utils/reba.py:50-81).  f64[N,24,3] -> int32[N,10]."""
-    _need_cuda(euler_deg, "reba")
-    e = euler_deg.contiguous().double()
-    N = e.shape[0]
-    out = torch.empty((N, 10), dtype=torch.int32, device=e.device)
-    s = _lib.reba_info_struct(info)
-    _lib.check(_lib.load().pr_reba(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_reba")
-    return out
-
-
-def rula(euler_deg, info):
-    """RULA.__call__ arithmetic (lib/utils/rula.py:66-98).  f64[N,24,3] -> int32[N,12]."""
-    _need_cuda(euler_deg, "rula")
-    e = euler_deg.contiguous().double()
-    N = e.shape[0]
-    out = torch.empty((N, 12), dtype=torch.int32, device=e.device)
-    s = _lib.rula_info_struct(info)
-    _lib.check(_lib.load().pr_rula(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_rula")
-    return out
-
-
 def _out(out, shape, dt, dev):
     """The output tensor: a fresh one, or the caller's (e.g. a view into a larger buffer with guard rows behind it)."""
     if out is None:
         return torch.empty(shape, dtype=dt, device=dev)
     if tuple(out.shape) != tuple(shape) or out.dtype != dt or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"out must be a contiguous {dt} tensor of shape {tuple(shape)} on {dev}")
+    return out
+
+
+def _outs(out, n):
+    """A wrapper's `out=` for n outputs: None, or one tensor per output in the order they are returned."""
+    if out is None:
+        return (None,) * n
+    if isinstance(out, torch.Tensor) or len(out) != n:
+        raise ValueError(f"out must be a sequence of {n} tensors")
+    return tuple(out)
+
+
+def rot6d_to_rotmat(pose6d, out=None):
+    """SPIN utils/geometry.py::rot6d_to_rotmat.  f32[N,144] -> f32[N,24,3,3]."""
+    _need_cuda(pose6d, "rot6d_to_rotmat")
+    p = pose6d.contiguous().float()
+    N = p.shape[0]
+    out = _out(out, (N, 24, 3, 3), torch.float32, p.device)
+    _lib.check(_lib.load().pr_rot6d_to_rotmat(p.data_ptr(), N, out.data_ptr(), _stream(p.device)), "pr_rot6d_to_rotmat")
+    return out
+
+
+def pose_to_euler(rotmat, out=None):
+    """rot_to_angle + axis_angle_to_euler_angle (lib/utils/coord_utils.py:24-30, 83-95) for a batch.
+    f32[N,24,3,3] -> (axis_angle f32[N,24,3], euler_deg f64[N,24,3], status int32[N]); out: those three, to write into."""
+    _need_cuda(rotmat, "pose_to_euler")
+    r = rotmat.contiguous().float()
+    N = r.shape[0]
+    aa, eul, st = _outs(out, 3)
+    aa = _out(aa, (N, 24, 3), torch.float32, r.device)
+    eul = _out(eul, (N, 24, 3), torch.float64, r.device)
+    st = _out(st, (N,), torch.int32, r.device)
+    _lib.check(_lib.load().pr_pose_to_euler(r.data_ptr(), N, aa.data_ptr(), eul.data_ptr(), st.data_ptr(),
+                                            _stream(r.device)), "pr_pose_to_euler")
+    return aa, eul, st
+
+
+def axis_angle_to_euler(axis_angle, out=None):
+    """axis_angle_to_euler_angle (lib/utils/coord_utils.py:83-95) for a batch.
+    f32[N,24,3] -> (euler_deg f64[N,24,3], status int32[N]); out: those two, to write into."""
+    _need_cuda(axis_angle, "axis_angle_to_euler")
+    a = axis_angle.contiguous().float()
+    N = a.shape[0]
+    eul, st = _outs(out, 2)
+    eul = _out(eul, (N, 24, 3), torch.float64, a.device)
+    st = _out(st, (N,), torch.int32, a.device)
+    _lib.check(_lib.load().pr_axis_angle_to_euler(a.data_ptr(), N, eul.data_ptr(), st.data_ptr(), _stream(a.device)),
+               "pr_axis_angle_to_euler")
+    return eul, st
+
+
+def reba(euler_deg, info, out=None):
+    """REBA.__call__ arithmetic (lib/utils/reba.py:50-81).  f64[N,24,3] -> int32[N,10]."""
+    _need_cuda(euler_deg, "reba")
+    e = euler_deg.contiguous().double()
+    N = e.shape[0]
+    out = _out(out, (N, 10), torch.int32, e.device)
+    s = _lib.reba_info_struct(info)
+    _lib.check(_lib.load().pr_reba(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_reba")
+    return out
+
+
+def rula(euler_deg, info, out=None):
+    """RULA.__call__ arithmetic (lib/utils/rula.py:66-98).  f64[N,24,3] -> int32[N,12]."""
+    _need_cuda(euler_deg, "rula")
+    e = euler_deg.contiguous().double()
+    N = e.shape[0]
+    out = _out(out, (N, 12), torch.int32, e.device)
+    s = _lib.rula_info_struct(info)
+    _lib.check(_lib.load().pr_rula(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_rula")
     return out
 
 
@@ -179,7 +190,7 @@ def conv3x3_wino64_nhwc(x, w2, b2, w3=None, b3=None, residual=None, relu=True, f
     return y
 
 
-def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0):
+def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0, out=None):
     """A whole layer1 Bottleneck (conv1 1x1 -> conv2 3x3 -> conv3 1x1 + identity, ReLU after each; BatchNorm folded by
     the caller) in one persistent bf16 kernel.  Without `wd`: x bf16 [B,H,W,256] CUDA, w1 [64,256], identity = x.  With
     `wd` [256,64] / `bd` [256] (the stage's first block): x bf16 [B,H,W,64], w1 [64,64], identity = the downsample branch.
@@ -195,7 +206,7 @@ def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0):
     b1, b2, b3 = f(b1, (64,)), f(b2, (64,)), f(b3, (256,))
     if first:
         wd, bd = f(wd, (256, 64)), f(bd, (256,))
-    y = torch.empty((B, H, W, 256), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (B, H, W, 256), torch.bfloat16, x.device)
     ms = np.zeros(1, np.float32)
     idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_bottleneck_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
@@ -206,7 +217,7 @@ def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0):
     return y, (float(ms[0]) if repeats > 0 else None)
 
 
-def bottleneck128_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
+def bottleneck128_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0, out=None):
     """A whole layer2 Bottleneck (plain block: conv1 1x1 512 -> 128, conv2 3x3, conv3 1x1 128 -> 512 + identity, ReLU after
     each; BatchNorm folded by the caller) in one persistent bf16 kernel.  x bf16 [B,H,W,512] CUDA (W <= 31), w1 [128,512],
     w2 [128,128,3,3], w3 [512,128] numpy.  Returns (y bf16 [B,H,W,512], ms_per_launch or None)."""
@@ -218,7 +229,7 @@ def bottleneck128_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
     f = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
     w1, w2, w3 = f(w1, (128, 512)), f(w2, (128, 128, 3, 3)), f(w3, (512, 128))
     b1, b2, b3 = f(b1, (128,)), f(b2, (128,)), f(b3, (512,))
-    y = torch.empty((B, H, W, 512), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (B, H, W, 512), torch.bfloat16, x.device)
     ms = np.zeros(1, np.float32)
     idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_bottleneck128_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
@@ -227,7 +238,7 @@ def bottleneck128_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
     return y, (float(ms[0]) if repeats > 0 else None)
 
 
-def bottleneck256_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
+def bottleneck256_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0, out=None):
     """A whole layer3 Bottleneck (plain block: conv1 1x1 1024 -> 256, conv2 3x3, conv3 1x1 256 -> 1024 + identity, ReLU after
     each; BatchNorm folded by the caller) in one bf16 kernel, one frame per workgroup.  x bf16 [B,H,W,1024] CUDA (H W <= 224),
     w1 [256,1024], w2 [256,256,3,3], w3 [1024,256] numpy.  Returns (y bf16 [B,H,W,1024], ms_per_launch or None)."""
@@ -239,7 +250,7 @@ def bottleneck256_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
     f = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
     w1, w2, w3 = f(w1, (256, 1024)), f(w2, (256, 256, 3, 3)), f(w3, (1024, 256))
     b1, b2, b3 = f(b1, (256,)), f(b2, (256,)), f(b3, (1024,))
-    y = torch.empty((B, H, W, 1024), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (B, H, W, 1024), torch.bfloat16, x.device)
     ms = np.zeros(1, np.float32)
     idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_bottleneck256_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
@@ -248,7 +259,7 @@ def bottleneck256_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0):
     return y, (float(ms[0]) if repeats > 0 else None)
 
 
-def stem_pool_nhwc(x, w, bias, repeats=0):
+def stem_pool_nhwc(x, w, bias, repeats=0, out=None):
     """The bf16 encoder's stem in one kernel: 4x4 / stride-1 convolution (window rows y-2 .. y+1, i.e. padding 2 with the
     last row and column of the padded result dropped) over x bf16 [B,H,H,16] CUDA + bias + ReLU + MaxPool2d(3, 2, 1).
     w [64,16,4,4], bias [64] numpy.  Returns (y bf16 [B,H/2,H/2,64], ms_per_launch or None)."""
@@ -259,7 +270,7 @@ def stem_pool_nhwc(x, w, bias, repeats=0):
         raise ValueError("stem_pool_nhwc: x must be [B,H,H,16] with even H")
     w = np.ascontiguousarray(w, dtype=np.float32).reshape(64, 16, 4, 4)
     b = np.ascontiguousarray(bias, dtype=np.float32).reshape(64)
-    y = torch.empty((B, H // 2, H // 2, 64), dtype=torch.bfloat16, device=x.device)
+    y = _out(out, (B, H // 2, H // 2, 64), torch.bfloat16, x.device)
     ms = np.zeros(1, np.float32)
     idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_stem_pool_nhwc(idx, x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, H, repeats,
@@ -267,7 +278,7 @@ def stem_pool_nhwc(x, w, bias, repeats=0):
     return y, (float(ms[0]) if repeats > 0 else None)
 
 
-def stem_pool_f32_nhwc(x, w, bias, repeats=0):
+def stem_pool_f32_nhwc(x, w, bias, repeats=0, out=None):
     """The fp32 encoder's stem in one kernel: 4x4 / stride-1 convolution (window rows y-2 .. y+1) over the space-to-depth
     image x f32 [B,112,112,12] CUDA + bias + ReLU + MaxPool2d(3, 2, 1).  w [64,12,4,4], bias [64] numpy.
     Returns (y f32 [B,56,56,64], ms_per_launch or None)."""
@@ -278,7 +289,7 @@ def stem_pool_f32_nhwc(x, w, bias, repeats=0):
     B = x.shape[0]
     w = np.ascontiguousarray(w, dtype=np.float32).reshape(64, 12, 4, 4)
     b = np.ascontiguousarray(bias, dtype=np.float32).reshape(64)
-    y = torch.empty((B, 56, 56, 64), dtype=torch.float32, device=x.device)
+    y = _out(out, (B, 56, 56, 64), torch.float32, x.device)
     ms = np.zeros(1, np.float32)
     idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_stem_pool_f32_nhwc(idx, x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, repeats,
@@ -286,11 +297,12 @@ def stem_pool_f32_nhwc(x, w, bias, repeats=0):
     return y, (float(ms[0]) if repeats > 0 else None)
 
 
-def crop_frames(frames, bboxes, frame_idx=None, scale=1.2, bgr=False, return_status=False):
+def crop_frames(frames, bboxes, frame_idx=None, scale=1.2, bgr=False, return_status=False, out=None):
     """GPU form of CropDataset.__getitem__ (data/demo_dataset.py:58-74) for a whole batch.
     frames u8[F,H,W,3] CUDA, bboxes f32[N,4] (cx,cy,w,h), frame_idx int32[N] or None -> f32[N,3,224,224].
     A host-side `frame_idx` is range-checked here (ValueError); one that already lives on the GPU is checked by
-    the kernel, which zero-fills such crops and flags them in the int32[N] status (`return_status=True`)."""
+    the kernel, which zero-fills such crops and flags them in the int32[N] status (`return_status=True`).
+    out: the crops tensor to write into, or (crops, status) with `return_status`."""
     _need_cuda(frames, "crop_frames")
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError("frames must be uint8 [F,H,W,3]")
@@ -319,8 +331,9 @@ def crop_frames(frames, bboxes, frame_idx=None, scale=1.2, bgr=False, return_sta
         if idx.dtype.is_floating_point or idx.dtype == torch.bool:
             raise ValueError(f"frame_idx must hold integers, got {idx.dtype}")
         idx = idx.to(torch.int32).contiguous()
-    out = torch.empty((N, 3, 224, 224), dtype=torch.float32, device=frames.device)
-    status = torch.empty((N,), dtype=torch.int32, device=frames.device) if return_status else None
+    out, status = _outs(out, 2) if return_status else (out, None)
+    out = _out(out, (N, 3, 224, 224), torch.float32, frames.device)
+    status = _out(status, (N,), torch.int32, frames.device) if return_status else None
     F, H, W, _ = frames.shape
     _lib.check(_lib.load().pr_crop_frames(frames.data_ptr(), F, H, W, int(bool(bgr)),
                                           idx.data_ptr() if idx is not None else None, bb.data_ptr(), N,

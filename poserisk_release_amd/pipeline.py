@@ -104,6 +104,15 @@ class FramePipeline:
             lane.bufs = {key: o}  # keep one shape resident
         return lane.bufs[key]
 
+    def _callers(self, own, out):
+        if self.graph:
+            raise ValueError("out= is not available in graph mode")
+        for name, t in own.items():
+            u = out.get(name)
+            if u is None or tuple(u.shape) != tuple(t.shape) or u.dtype != t.dtype or u.device != t.device or not u.is_contiguous():
+                raise ValueError(f"out[{name!r}] must be a contiguous {t.dtype} tensor of shape {tuple(t.shape)} on {t.device}")
+        return {name: out[name] for name in own}
+
     def next_stream(self, dev):
         """The stream the NEXT forward() will run its batch on (its lane's own stream, or the current stream for a single
         lane without graph mode): a producer that enqueues the batch's input there needs no extra stream and no event."""
@@ -114,8 +123,10 @@ class FramePipeline:
             return lane.stream
         return torch.cuda.current_stream(torch.device(dev))
 
-    def forward(self, crops):
-        """crops f32[B,3,224,224] on the GPU -> dict of device tensors (reused across calls of equal B)."""
+    def forward(self, crops, out=None):
+        """crops f32[B,3,224,224] on the GPU -> dict of device tensors (reused across calls of equal B).
+        out: a dict with a caller-owned tensor for every name the lane's own buffers have (same shapes and dtypes), written
+        instead of them for this call (not in graph mode, whose capture bakes the lane's pointers in)."""
         if crops.device.type != "cuda":
             raise _lib.PoseRiskHipError("crops must be on the GPU")
         x = crops.contiguous().float()
@@ -131,6 +142,8 @@ class FramePipeline:
         if getattr(lane.hmr, "_concurrency", 1) != len(self._lanes):   # the model may serve another pipeline too (bench.py)
             lane.hmr.set_concurrency(len(self._lanes))
         o = self._out(lane, B, dev)
+        if out is not None:
+            o = self._callers(o, out)
         fo = _lib.FramesOut(o["rotmat"].data_ptr(), o["betas"].data_ptr(), o["cam"].data_ptr(),
                             o["axis_angle"].data_ptr(), o["euler"].data_ptr(), o["joint_cam"].data_ptr(),
                             o["verts"].data_ptr() if self.with_verts else None,

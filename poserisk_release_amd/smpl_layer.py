@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import _out, _outs
 
 
 def _f32(a):
@@ -122,7 +123,8 @@ class SMPLLayer:
             raise ValueError(f"expected {B}x{width} values, got shape {tuple(t.shape)}")
         return t.to(self._device, torch.float32).reshape(B, width).contiguous()
 
-    def forward(self, th_pose_axisang, th_betas=None, th_trans=None, return_verts=True):
+    def forward(self, th_pose_axisang, th_betas=None, th_trans=None, return_verts=True, out=None):
+        """out: (verts, joints) on the layer's GPU to write into (verts None without return_verts)."""
         self._ensure()
         pose_in = torch.as_tensor(th_pose_axisang)
         out_dev = pose_in.device
@@ -130,8 +132,9 @@ class SMPLLayer:
         pose = pose_in.to(self._device, torch.float32).reshape(B, 72).contiguous()
         betas = self._stage(th_betas, B, self.num_betas)
         trans = self._stage(th_trans, B, 3)
-        verts = torch.empty((B, self.num_verts, 3), dtype=torch.float32, device=self._device) if return_verts else None
-        joints = torch.empty((B, self.num_joints, 3), dtype=torch.float32, device=self._device)
+        verts, joints = _outs(out, 2)
+        verts = _out(verts, (B, self.num_verts, 3), torch.float32, self._device) if return_verts else None
+        joints = _out(joints, (B, self.num_joints, 3), torch.float32, self._device)
         stream = torch.cuda.current_stream(self._device).cuda_stream
         _lib.check(_lib.load().pr_smpl_forward(
             self._handle, pose.data_ptr(), betas.data_ptr() if betas is not None else None,
@@ -144,14 +147,16 @@ class SMPLLayer:
 
     __call__ = forward
 
-    def joint_cam(self, axis_angle, return_verts=False):
-        """get_joint_cam (lib/utils/coord_utils.py:7-21) on f32[N,24,3] CUDA tensor; mutates its root rows."""
+    def joint_cam(self, axis_angle, return_verts=False, out=None):
+        """get_joint_cam (lib/utils/coord_utils.py:7-21) on f32[N,24,3] CUDA tensor; mutates its root rows.
+        out: the joint_cam tensor to write into, or (joint_cam, verts) with return_verts."""
         self._ensure()
         if axis_angle.device != self._device or axis_angle.dtype != torch.float32 or not axis_angle.is_contiguous():
             raise ValueError("joint_cam needs a contiguous float32 tensor on the layer's GPU (it is mutated in place)")
         N = axis_angle.shape[0]
-        jc = torch.empty((N, 24, 3), dtype=torch.float32, device=self._device)
-        verts = torch.empty((N, self.num_verts, 3), dtype=torch.float32, device=self._device) if return_verts else None
+        jc, verts = _outs(out, 2) if return_verts else (out, None)
+        jc = _out(jc, (N, 24, 3), torch.float32, self._device)
+        verts = _out(verts, (N, self.num_verts, 3), torch.float32, self._device) if return_verts else None
         stream = torch.cuda.current_stream(self._device).cuda_stream
         _lib.check(_lib.load().pr_smpl_joint_cam(self._handle, axis_angle.data_ptr(), N, jc.data_ptr(),
                                                  verts.data_ptr() if verts is not None else None, stream),

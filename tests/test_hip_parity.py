@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_refs as kr
 from conftest import golden, measured
 from oracle import coord_ref, hmr_ref, pipeline_ref, reba_ref, rula_ref, smpl_ref
 from poserisk_release_amd import _lib, ops, synth
@@ -100,9 +101,7 @@ def test_conv_quarter_tiles_have_the_same_bits(gpu_device, case):
     y64, _ = ops.conv2d_nhwc(x, w, bias, res, stride=s, pad=p, relu=True, tile_cfg=8)
     y128, _ = ops.conv2d_nhwc(x, w, bias, res, stride=s, pad=p, relu=True, tile_cfg=7)
     assert torch.equal(y64, y128)
-    ref = torch.nn.functional.conv2d(x[..., :Cr].cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
-                                     torch.from_numpy(bias).double(), stride=s, padding=p).permute(0, 2, 3, 1)
-    ref = torch.relu(ref + res.cpu().double())
+    ref = kr.conv_ref64(x, w, bias, res, stride=s, pad=p, relu=True)
     err = float((y64.cpu().double() - ref).abs().max())
     assert err < 2e-5 * max(1.0, float(ref.abs().max())), err
     y64, _ = ops.conv2d_nhwc(x, w, None, None, stride=s, pad=p, relu=False, tile_cfg=8)
@@ -127,9 +126,7 @@ def test_conv_split_k(gpu_device, case):
     bias = rng.standard_normal(Cout).astype(np.float32)
     Ho = (H + 2 * pad - k) // st + 1
     res = torch.randn((B, Ho, Ho, Cout), generator=g, device=gpu_device)
-    ref = torch.relu(torch.nn.functional.conv2d(x.cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
-                                                torch.from_numpy(bias).double(), stride=st, padding=pad).permute(0, 2, 3, 1)
-                     + res.cpu().double())
+    ref = kr.conv_ref64(x, w, bias, res, stride=st, pad=pad, relu=True)
     outs = {}
     for S in (2, 3, 4):
         y, _ = ops.conv2d_nhwc(x, w, bias, res, stride=st, pad=pad, relu=True, tile_cfg=200 + S)
@@ -194,8 +191,7 @@ def test_conv_dual_source_matches_torch(gpu_device, case, precision):
     w1 = rnd(torch.from_numpy((rng.standard_normal((Cout, C1)) / np.sqrt(C1)).astype(np.float32)))
     w2 = rnd(torch.from_numpy((rng.standard_normal((Cout, C2)) / np.sqrt(C2)).astype(np.float32)))
     bias = rng.standard_normal(Cout).astype(np.float32)
-    ref = torch.relu(torch.einsum("bhwc,oc->bhwo", t.double(), w1.double()) +
-                     torch.einsum("bhwc,oc->bhwo", x[:, ::s2, ::s2].double(), w2.double()) + torch.from_numpy(bias).double())
+    ref = kr.dual_ref64(t, w1, x, w2, bias, s2)
     assert ref.shape == (B, Ho, Ho, Cout)
     cfgs = [-1, 8] if not bf else [-1, 8, 11]
     for cfg in cfgs:
@@ -279,12 +275,7 @@ def test_conv3x3_conv1x1_fused_matches_torch(gpu_device, case):
     w3 = (rng.standard_normal((N3, 64)) / 8).astype(np.float32)
     b3 = rng.standard_normal(N3).astype(np.float32)
     res = rng.standard_normal((B, H, H, N3)).astype(np.float32) if with_res else None
-    t2 = torch.relu(torch.nn.functional.conv2d(torch.from_numpy(x).permute(0, 3, 1, 2).double(), torch.from_numpy(w2).double(),
-                                               torch.from_numpy(b2).double(), padding=1))
-    ref = torch.einsum("bchw,oc->bhwo", t2, torch.from_numpy(w3).double()) + torch.from_numpy(b3).double()
-    if with_res:
-        ref = ref + torch.from_numpy(res).double()
-    ref = torch.relu(ref).numpy()
+    ref = kr.fused_ref64(x, w2, b2, w3, b3, res).numpy()
     xd = _t(x, gpu_device)
     rd = _t(res, gpu_device) if with_res else None
     y = ops.conv3x3_conv1x1_nhwc(xd, w2, b2, w3, b3, rd, relu=True)
@@ -314,11 +305,7 @@ def test_conv3x3_conv1x1_fused_bf16(gpu_device, case):
     w3 = bf(torch.from_numpy((rng.standard_normal((N3, 64)) / 8).astype(np.float32)))
     b3 = rng.standard_normal(N3).astype(np.float32)
     res = bf(torch.from_numpy(rng.standard_normal((B, H, H, N3)).astype(np.float32))) if with_res else None
-    t2 = bf(torch.relu(torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w2, torch.from_numpy(b2), padding=1)))
-    ref = torch.einsum("bchw,oc->bhwo", t2, w3) + torch.from_numpy(b3)
-    if with_res:
-        ref = ref + res
-    ref = torch.relu(ref)
+    ref = kr.fused_bf16_emulation(x, w2, b2, w3, b3, res)
     xd = x.to(gpu_device)
     rd = res.to(gpu_device) if with_res else None
     y = ops.conv3x3_conv1x1_nhwc(xd, w2.numpy(), b2, w3.numpy(), b3, rd, relu=True, precision="bf16")
@@ -536,13 +523,7 @@ def test_bottleneck_bf16_whole_block_in_one_kernel(gpu_device, case):
     16-wide MFMA groups in the same k order, t1 and t2 rounded to bf16 where those launches store them), and against an
     fp32 emulation with bf16-rounded intermediates.  Ragged maps, a map narrower than a block, single pixels."""
     B, H, W = case
-    rng = np.random.default_rng(B * 1000 + H * 10 + W)
-    bf = lambda t: t.to(torch.bfloat16).float()
-    x = bf(torch.from_numpy(rng.standard_normal((B, H, W, 256)).astype(np.float32)))
-    w1 = bf(torch.from_numpy((rng.standard_normal((64, 256)) / 16).astype(np.float32)))
-    w2 = bf(torch.from_numpy((rng.standard_normal((64, 64, 3, 3)) / 24).astype(np.float32)))
-    w3 = bf(torch.from_numpy((rng.standard_normal((256, 64)) / 8).astype(np.float32)))
-    b1, b2, b3 = (rng.standard_normal(n).astype(np.float32) * 0.5 for n in (64, 64, 256))
+    x, w1, w2, w3, _, (b1, b2, b3) = kr.bottleneck_inputs(64, case)
     xd = x.to(gpu_device)
     y, _ = ops.bottleneck_nhwc(xd, w1.numpy(), b1, w2.numpy(), b2, w3.numpy(), b3)
     assert y.dtype == torch.bfloat16 and y.shape == xd.shape
@@ -552,9 +533,7 @@ def test_bottleneck_bf16_whole_block_in_one_kernel(gpu_device, case):
     nbad = int((y != y2).sum())
     measured("bottleneck64_bf16 vs separate launches: differing elements", nbad, 0)
     # fp32 emulation, intermediates rounded to bf16
-    e1 = bf(torch.relu(torch.einsum("bhwc,oc->bhwo", x, w1) + torch.from_numpy(b1)))
-    e2 = bf(torch.relu(torch.nn.functional.conv2d(e1.permute(0, 3, 1, 2), w2, torch.from_numpy(b2), padding=1)))
-    ref = torch.relu(torch.einsum("bchw,oc->bhwo", e2, w3) + torch.from_numpy(b3) + x)
+    ref = kr.bottleneck_emulation(x, w1, b1, w2, b2, w3, b3)
     got = y.float().cpu()
     tol = ref.abs() * 2.0 ** -7 + 3e-2
     assert bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
@@ -570,13 +549,7 @@ def test_bottleneck128_bf16_whole_block_in_one_kernel(gpu_device, case):
     to bf16 where those launches store them), and against an fp32 emulation with bf16-rounded intermediates.  Ragged maps,
     the widest map the halo allows, single pixels, several chunks per workgroup with images straddling them."""
     B, H, W = case
-    rng = np.random.default_rng(B * 1000 + H * 10 + W)
-    bf = lambda t: t.to(torch.bfloat16).float()
-    x = bf(torch.from_numpy(rng.standard_normal((B, H, W, 512)).astype(np.float32)))
-    w1 = bf(torch.from_numpy((rng.standard_normal((128, 512)) / 22).astype(np.float32)))
-    w2 = bf(torch.from_numpy((rng.standard_normal((128, 128, 3, 3)) / 34).astype(np.float32)))
-    w3 = bf(torch.from_numpy((rng.standard_normal((512, 128)) / 11).astype(np.float32)))
-    b1, b2, b3 = (rng.standard_normal(n).astype(np.float32) * 0.5 for n in (128, 128, 512))
+    x, w1, w2, w3, _, (b1, b2, b3) = kr.bottleneck_inputs(128, case)
     xd = x.to(gpu_device)
     y, _ = ops.bottleneck128_nhwc(xd, w1.numpy(), b1, w2.numpy(), b2, w3.numpy(), b3)
     assert y.dtype == torch.bfloat16 and y.shape == xd.shape
@@ -586,9 +559,7 @@ def test_bottleneck128_bf16_whole_block_in_one_kernel(gpu_device, case):
     nbad = int((y != y2).sum())
     measured("bottleneck128_bf16 vs separate launches: differing elements", nbad, 0)
     if B * H * W <= 4000:
-        e1 = bf(torch.relu(torch.einsum("bhwc,oc->bhwo", x, w1) + torch.from_numpy(b1)))
-        e2 = bf(torch.relu(torch.nn.functional.conv2d(e1.permute(0, 3, 1, 2), w2, torch.from_numpy(b2), padding=1)))
-        ref = torch.relu(torch.einsum("bchw,oc->bhwo", e2, w3) + torch.from_numpy(b3) + x)
+        ref = kr.bottleneck_emulation(x, w1, b1, w2, b2, w3, b3)
         got = y.float().cpu()
         tol = ref.abs() * 2.0 ** -7 + 5e-2
         assert bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
@@ -605,13 +576,7 @@ def test_bottleneck256_bf16_whole_block_in_one_kernel(gpu_device, case):
     intermediates.  Ragged maps, the largest map a frame may have (224 pixels), maps of one to seven pixel tiles (so every
     split of the tiles between the two wave groups), single pixels, more frames than CUs."""
     B, H, W = case
-    rng = np.random.default_rng(B * 1000 + H * 10 + W)
-    bf = lambda t: t.to(torch.bfloat16).float()
-    x = bf(torch.from_numpy(rng.standard_normal((B, H, W, 1024)).astype(np.float32)))
-    w1 = bf(torch.from_numpy((rng.standard_normal((256, 1024)) / 32).astype(np.float32)))
-    w2 = bf(torch.from_numpy((rng.standard_normal((256, 256, 3, 3)) / 48).astype(np.float32)))
-    w3 = bf(torch.from_numpy((rng.standard_normal((1024, 256)) / 16).astype(np.float32)))
-    b1, b2, b3 = (rng.standard_normal(n).astype(np.float32) * 0.5 for n in (256, 256, 1024))
+    x, w1, w2, w3, _, (b1, b2, b3) = kr.bottleneck_inputs(256, case)
     xd = x.to(gpu_device)
     y, _ = ops.bottleneck256_nhwc(xd, w1.numpy(), b1, w2.numpy(), b2, w3.numpy(), b3)
     assert y.dtype == torch.bfloat16 and y.shape == xd.shape
@@ -621,9 +586,7 @@ def test_bottleneck256_bf16_whole_block_in_one_kernel(gpu_device, case):
     nbad = int((y != y2).sum())
     measured("bottleneck256_bf16 vs separate launches: differing elements", nbad, 0)
     if B * H * W <= 2000:
-        e1 = bf(torch.relu(torch.einsum("bhwc,oc->bhwo", x, w1) + torch.from_numpy(b1)))
-        e2 = bf(torch.relu(torch.nn.functional.conv2d(e1.permute(0, 3, 1, 2), w2, torch.from_numpy(b2), padding=1)))
-        ref = torch.relu(torch.einsum("bchw,oc->bhwo", e2, w3) + torch.from_numpy(b3) + x)
+        ref = kr.bottleneck_emulation(x, w1, b1, w2, b2, w3, b3)
         got = y.float().cpu()
         tol = ref.abs() * 2.0 ** -7 + 5e-2
         assert bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
@@ -662,14 +625,7 @@ def test_bottleneck_bf16_first_block_in_one_kernel(gpu_device, case):
     """The stage's first block (64-channel input, downsample branch summed into conv3's K loop, no residual) as one
     launch of the same kernel: bit for bit against the three launches it replaces (conv1, conv2, dual-source conv3)."""
     B, H, W = case
-    rng = np.random.default_rng(B * 999 + H * 10 + W)
-    bf = lambda t: t.to(torch.bfloat16).float()
-    x = bf(torch.from_numpy(rng.standard_normal((B, H, W, 64)).astype(np.float32)))
-    w1 = bf(torch.from_numpy((rng.standard_normal((64, 64)) / 8).astype(np.float32)))
-    w2 = bf(torch.from_numpy((rng.standard_normal((64, 64, 3, 3)) / 24).astype(np.float32)))
-    w3 = bf(torch.from_numpy((rng.standard_normal((256, 64)) / 8).astype(np.float32)))
-    wd = bf(torch.from_numpy((rng.standard_normal((256, 64)) / 8).astype(np.float32)))
-    b1, b2, b3, bd = (rng.standard_normal(n).astype(np.float32) * 0.5 for n in (64, 64, 256, 256))
+    x, w1, w2, w3, wd, (b1, b2, b3, bd) = kr.bottleneck_inputs(64, case, first=True)
     xd = x.to(gpu_device)
     y, _ = ops.bottleneck_nhwc(xd, w1.numpy(), b1, w2.numpy(), b2, w3.numpy(), b3, wd=wd.numpy(), bd=bd)
     assert y.dtype == torch.bfloat16 and y.shape == (B, H, W, 256)
@@ -679,9 +635,7 @@ def test_bottleneck_bf16_first_block_in_one_kernel(gpu_device, case):
     y2 = ops.conv1x1_dual_nhwc(t2, w3.numpy(), xd, wd.numpy(), b3d, relu=True, tile_cfg=8, precision="bf16")
     nbad = int((y != y2).sum())
     measured("bottleneck64_bf16 (first block) vs separate launches: differing elements", nbad, 0)
-    e1 = bf(torch.relu(torch.einsum("bhwc,oc->bhwo", x, w1) + torch.from_numpy(b1)))
-    e2 = bf(torch.relu(torch.nn.functional.conv2d(e1.permute(0, 3, 1, 2), w2, torch.from_numpy(b2), padding=1)))
-    ref = torch.relu(torch.einsum("bchw,oc->bhwo", e2, w3) + torch.einsum("bhwc,oc->bhwo", x, wd) + torch.from_numpy(b3d))
+    ref = kr.bottleneck_emulation(x, w1, b1, w2, b2, w3, b3, wd, bd)
     got = y.float().cpu()
     tol = ref.abs() * 2.0 ** -7 + 3e-2
     assert bool(((got - ref).abs() <= tol).all()), float((got - ref).abs().max())
@@ -695,15 +649,8 @@ def test_stem_pool_bf16_in_one_kernel(gpu_device, case):
     before the pool as the two launches store it.  A conv value at a bf16 rounding boundary may round either way (fp32
     summation order), and the pool passes such a flip on: one bf16 ulp of slack.  Whole and ragged bands, a 1x1 pooled map."""
     B, H = case
-    rng = np.random.default_rng(B * 100 + H)
-    bf = lambda t: t.to(torch.bfloat16).float()
-    x = bf(torch.from_numpy(rng.random((B, H, H, 16)).astype(np.float32)))
-    x[..., 12:] = 0                                  # the space-to-depth image has 12 real channels
-    w = bf(torch.from_numpy((rng.standard_normal((64, 16, 4, 4)) / 12).astype(np.float32)))
-    bias = rng.standard_normal(64).astype(np.float32) * 0.3
+    x, w, bias, ref = kr.stem_pool_bf16_case(case)
     y, _ = ops.stem_pool_nhwc(x.to(gpu_device), w.numpy(), bias)
-    conv = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w, torch.from_numpy(bias), padding=2)[:, :, :H, :H]
-    ref = torch.nn.functional.max_pool2d(bf(torch.relu(conv)), 3, stride=2, padding=1).permute(0, 2, 3, 1)
     assert y.shape == ref.shape and y.dtype == torch.bfloat16
     got = y.float().cpu()
     tol = ref.abs() * 2.0 ** -7 + 1e-6
@@ -962,25 +909,13 @@ def test_pose_to_euler_matches_golden(gpu_device):
     g = golden("euler.npz")
     aa, eul, st = ops.pose_to_euler(_t(g["rotmat"], gpu_device))
     np.testing.assert_allclose(aa.cpu().numpy(), g["axis_angle"], atol=1e-6)
-    # Euler degrees are taken from the float32 axis-angle; where ours differs by one float32 ulp the
-    # angle moves by ~1e-5 deg, so compare through our own axis-angle with the oracle's Euler stage.
     ours_aa = aa.cpu().numpy()
-    ref = np.stack([coord_ref.axis_angle_to_euler_angle(f) for f in ours_aa])
-    d = np.abs(eul.cpu().numpy() - ref)
-    d = np.minimum(d, 360 - d)
+    d, off, ulp, dg = kr.pose_to_euler_errors(ours_aa, eul.cpu().numpy(), g["axis_angle"], g["euler_deg"])
     # device libm vs glibc differ in the last double ulp of sin/cos; where that flips the float32
     # rounding of a matrix entry (coord_utils.py:86 returns float32) the angle moves by ~1e-6 degrees
     assert d.max() < 1e-5 and np.mean(d < 1e-9) > 0.999, (d.max(), np.mean(d < 1e-9))
-    # every frame: our float32 axis-angle is the reference's or its float32 neighbour (device libm vs glibc in the
-    # last double ulp of acos / sqrt), and the Euler angles then move by at most that much
-    # (ulp of the vector's largest component: a component near zero carries the absolute error of the others)
-    big = np.abs(g["axis_angle"]).max(axis=2, keepdims=True).astype(np.float32)
-    ulp = np.broadcast_to(np.spacing(np.maximum(big, np.float32(1e-30))).astype(np.float64), g["axis_angle"].shape)
-    off = np.abs(ours_aa.astype(np.float64) - g["axis_angle"].astype(np.float64))
     assert (off <= ulp).all(), float((off / ulp).max())
     measured("pose_to_euler: axis-angle vs reference golden (float32 ulps)", (off / ulp).max(), 1.0, "ulp")
-    dg = np.abs(eul.cpu().numpy() - g["euler_deg"])
-    dg = np.minimum(dg, 360 - dg)
     measured("pose_to_euler: Euler degrees vs reference golden, all frames", dg.max(), 2e-5, "deg")
     assert dg.max() < 2e-5
     same = (ours_aa == g["axis_angle"]).all(axis=(1, 2))
@@ -1910,9 +1845,7 @@ def test_conv_register_weights_unit_shapes_have_the_same_bits(gpu_device, case, 
     monkeypatch.setenv("POSERISK_REGW_NB", "1")
     want, _ = ops.conv2d_nhwc(x, w, bias, res, relu=True, tile_cfg=400)
     want = want.clone()
-    ref = torch.nn.functional.conv2d(x.cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
-                                     torch.from_numpy(bias).double()).permute(0, 2, 3, 1)
-    ref = torch.relu(ref + res.cpu().double()) if with_res else torch.relu(ref)
+    ref = kr.conv_ref64(x, w, bias, res, relu=True)
     assert float((want.cpu().double() - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
     for T in (1, 2):
         for NB in (1, 2, 4):
@@ -1944,11 +1877,7 @@ def test_conv_register_weights_matches_torch(gpu_device, case):
     w = (rng.standard_normal((Cout, Cin, 1, 1)) / np.sqrt(Cin)).astype(np.float32)
     bias = rng.standard_normal(Cout).astype(np.float32)
     res = torch.randn((B, H, H, Cout), generator=g, device=gpu_device) if with_res else None
-    ref = torch.nn.functional.conv2d(x.cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
-                                     torch.from_numpy(bias).double()).permute(0, 2, 3, 1)
-    if with_res:
-        ref = ref + res.cpu().double()
-    ref = torch.relu(ref)
+    ref = kr.conv_ref64(x, w, bias, res, relu=True)
     y, _ = ops.conv2d_nhwc(x, w, bias, res, relu=True, tile_cfg=400)
     err = float((y.cpu().double() - ref).abs().max())
     assert err < 2e-5 * max(1.0, float(ref.abs().max())), err
@@ -1959,7 +1888,7 @@ def test_conv_register_weights_matches_torch(gpu_device, case):
     yt, _ = ops.conv2d_nhwc(x, w, bias, res, relu=True, tile_cfg=8)
     assert float((y - yt).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
     yn, _ = ops.conv2d_nhwc(x, w, None, None, relu=False, tile_cfg=400)
-    refn = torch.nn.functional.conv2d(x.cpu().double().permute(0, 3, 1, 2), torch.from_numpy(w).double()).permute(0, 2, 3, 1)
+    refn = kr.conv_ref64(x, w)
     assert float((yn.cpu().double() - refn).abs().max()) < 2e-5 * max(1.0, float(refn.abs().max()))
     with pytest.raises(_lib.PoseRiskHipError):
         ops.conv2d_nhwc(x[..., :64].contiguous(), w[:, :64], bias, None, relu=True, tile_cfg=400)
@@ -1969,22 +1898,8 @@ def test_stem_pool_f32_matches_torch(gpu_device):
     """stem_pool_f32 (conv1 as 4x4 taps over the 12-channel space-to-depth image + bias + ReLU + MaxPool2d(3,2,1), weights in
     registers, pooling in registers) against torch fp32 on CPU; every band of every image incl. the image borders; a frame's
     bits do not depend on its batch or position."""
-    rng = np.random.default_rng(33)
     B = 3
-    x = rng.standard_normal((B, 112, 112, 12)).astype(np.float32)
-    # the 7x7 kernel in the 4x4 taps' 8x8 window (a zero row and a zero column in front), as pr_hmr_create lays it out
-    w7 = (rng.standard_normal((64, 3, 7, 7)) / np.sqrt(147)).astype(np.float32)
-    w = np.zeros((64, 12, 4, 4), np.float32)
-    for kh in range(7):
-        for kw in range(7):
-            th, di, tw, dj = (kh + 1) >> 1, (kh + 1) & 1, (kw + 1) >> 1, (kw + 1) & 1
-            w[:, (2 * di + dj) * 3:(2 * di + dj) * 3 + 3, th, tw] = w7[:, :, kh, kw]
-    bias = rng.standard_normal(64).astype(np.float32)
-    xt = torch.from_numpy(x).permute(0, 3, 1, 2)
-    # window rows y-2 .. y+1: pad 2 up/left, 1 down/right
-    conv = torch.nn.functional.conv2d(torch.nn.functional.pad(xt.double(), (2, 1, 2, 1)), torch.from_numpy(w).double(),
-                                      torch.from_numpy(bias).double())
-    ref = torch.nn.functional.max_pool2d(torch.relu(conv), 3, 2, 1).permute(0, 2, 3, 1).numpy()
+    x, w, bias, ref, rng = kr.stem_pool_f32_case(B)
     y, _ = ops.stem_pool_f32_nhwc(_t(x, gpu_device), w, bias)
     got = y.cpu().numpy()
     assert got.shape == (B, 56, 56, 64)

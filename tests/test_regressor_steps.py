@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import encoder_ref as er
+import guard_band as gb
 import regressor_ref as rr
 from conftest import measured
 from poserisk_release_amd import synth
@@ -34,14 +35,16 @@ def _net(dev):
 
 
 def _taps(m, xf):
-    """All eleven taps of one input, each into a buffer with three canary rows behind the batch, each run twice."""
+    """All eleven taps of one input, each into a buffer with three canary rows behind the batch -- itself between the canary
+    guards of an arena (tests/guard_band.py), so that a store in front of the batch shows too --, each run twice."""
     B = xf.shape[0]
     taps = {}
     for step in range(11):
-        buf = torch.full((B + 3, HMR.STEP_COLS[step]), CANARY, device=xf.device)
+        big, buf = gb.arena((B + 3, HMR.STEP_COLS[step]), torch.float32, xf.device, CANARY)
         tap = m.regress_until(xf, step, out=buf)
         assert tap.shape == (B, HMR.STEP_COLS[step]) and tap.dtype == torch.float32
         assert bool((buf[B:] == CANARY).all()), f"step {step}: rows behind the batch were written"
+        gb.assert_guards_intact(big, buf, f"regress_until step {step}")
         assert torch.equal(tap, m.regress_until(xf, step)), f"step {step}: two runs differ"
         taps[step] = tap.clone()
     return taps

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from conftest import measured
-from encoder_ref import _mm
+from kernel_refs import wino64_layer as _layer, wino64_ref64 as _ref64
 from poserisk_release_amd import _lib, ops, synth
 from poserisk_release_amd.hmr import HMR
 
@@ -23,28 +23,6 @@ TOL = 2e-5
 
 def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _layer(shape, n3=256):
-    B, H, W = shape
-    rng = np.random.default_rng(1000 * H + W)
-    x = rng.standard_normal((B, H, W, 64)).astype(np.float32)
-    w2 = (rng.standard_normal((64, 64, 3, 3)) / np.sqrt(64 * 9)).astype(np.float32)
-    b2 = rng.standard_normal(64).astype(np.float32)
-    w3 = (rng.standard_normal((n3, 64)) / np.sqrt(64)).astype(np.float32)
-    b3 = rng.standard_normal(n3).astype(np.float32)
-    res = rng.standard_normal((B, H, W, n3)).astype(np.float32)
-    return x, w2, b2, w3, b3, res
-
-
-def _ref64(x, w2, b2, w3=None, b3=None, res=None):
-    """fp64: relu(conv3x3(x) + b2) [-> relu(. w3^T + b3 + res)], NHWC."""
-    a = torch.from_numpy(x).double().permute(0, 3, 1, 2)
-    t2 = torch.relu(_mm(a, torch.from_numpy(w2).double(), 1, 1) + torch.from_numpy(b2).double().view(1, -1, 1, 1))
-    if w3 is None:
-        return t2.permute(0, 2, 3, 1).numpy()
-    y = _mm(t2, torch.from_numpy(w3).double().view(w3.shape[0], 64, 1, 1), 1, 0) + torch.from_numpy(b3).double().view(1, -1, 1, 1)
-    return torch.relu(y.permute(0, 2, 3, 1) + torch.from_numpy(res).double()).numpy()
 
 
 @pytest.mark.parametrize("form", [5, 4])
