@@ -124,7 +124,6 @@ __global__ __launch_bounds__(512) void bottleneck64_bf16(const BnArgs a) {
   // ---- one-time loads (all eight waves) ------------------------------------------------------------------------------
   {
     // W2 -> LDS: 9 taps x [64 rows][128 B], 16-byte chunks XOR-swizzled on the source side (conv_dma_bf16.hip); the 72
-    // the
     // 1 KB groups of 8 rows are dealt to the eight waves
     const auto w2src = make_rsrc(a.w2, 64 * 576 * 2);
     for (int idx = wave; idx < 72; idx += 8) {

@@ -1,4 +1,6 @@
 // Device-free half of pr_hmr_create (see host_plan.h): blob layout, BatchNorm folding, weight packing, the launch plan.
+// Each whole layout is packed in ONE place -- conv_pack_side_by_side, bottleneck_pack_bf16 -- which the plan (build) and the
+// stand-alone test entries (capi.hip) both call, so the kernels' own tests and the encoder read the same definition.
 // Compiled into libposerisk_hip.so by hipcc as plain C++ and, for tests/native/host_plan_check.cc, by g++ with
 // -fsanitize=address,undefined.  No HIP header may be included here.
 #include "host_plan.h"
@@ -135,6 +137,85 @@ void bottleneck256_pack_w3_frags_bf16(const unsigned short* rows, unsigned short
         }
 }
 
+// ---- whole layouts ----------------------------------------------------------------------------------------------------
+namespace {
+
+void pack_rows(const ConvFilter& f, int Cout, int Cin_real, int cin_pad, int k, float* out) {
+  conv_pack_weights(f.w, f.scale, Cout, Cin_real, cin_pad, k, k, out);
+}
+void pack_rows(const ConvFilter& f, int Cout, int Cin_real, int cin_pad, int k, unsigned short* out) {
+  conv_pack_weights_bf16(f.w, f.scale, Cout, Cin_real, cin_pad, k, k, out);
+}
+
+// [Cout][Kpad(f1) + Kpad(f2)] in T's precision (float, or bf16 bit patterns)
+template <typename T>
+std::vector<T> side_by_side(const ConvFilter& f1, int Cin_real, int cin_pad, int k, const ConvFilter* f2, int Cin2, int Cout) {
+  const int bk = sizeof(T) == 2 ? 64 : kConvBK;
+  const int K1 = ceil_div(k * k * cin_pad, bk) * bk, K2 = f2 ? ceil_div(Cin2, bk) * bk : 0;
+  std::vector<T> a((size_t)Cout * K1);
+  pack_rows(f1, Cout, Cin_real, cin_pad, k, a.data());
+  if (!f2) return a;
+  std::vector<T> b((size_t)Cout * K2), both((size_t)Cout * (K1 + K2));
+  pack_rows(*f2, Cout, Cin2, Cin2, 1, b.data());
+  for (int o = 0; o < Cout; ++o) {
+    std::copy(&a[(size_t)o * K1], &a[(size_t)o * K1] + K1, &both[(size_t)o * (K1 + K2)]);
+    std::copy(&b[(size_t)o * K2], &b[(size_t)o * K2] + K2, &both[(size_t)o * (K1 + K2) + K1]);
+  }
+  return both;
+}
+
+// bf16 bit patterns carried in a float vector, as PlanSink::upload takes every constant
+std::vector<float> as_floats(const std::vector<unsigned short>& v) {
+  std::vector<float> f((v.size() + 1) / 2);
+  memcpy(f.data(), v.data(), v.size() * 2);
+  return f;
+}
+
+std::vector<unsigned short> permuted_rows(const std::vector<unsigned short>& a, int rows) {
+  std::vector<unsigned short> p(a.size());
+  bottleneck_pack_rows_bf16(a.data(), rows, (int)(a.size() / rows), p.data());
+  return p;
+}
+
+std::vector<float> bias_f32(const ConvFilter& f, const ConvFilter* g, int n) {
+  std::vector<float> b(n);
+  for (int o = 0; o < n; ++o) b[o] = (float)(g ? f.bias[o] + g->bias[o] : f.bias[o]);
+  return b;
+}
+
+}  // namespace
+
+std::vector<float> conv_pack_side_by_side(const ConvFilter& f1, int Cin_real, int cin_pad, int k, const ConvFilter* f2, int Cin2,
+                                          int Cout, int precision) {
+  if (precision == 1) return as_floats(side_by_side<unsigned short>(f1, Cin_real, cin_pad, k, f2, Cin2, Cout));
+  return side_by_side<float>(f1, Cin_real, cin_pad, k, f2, Cin2, Cout);
+}
+
+int bottleneck_pack_bf16(int planes, const ConvFilter& c1, const ConvFilter& c2, const ConvFilter& c3, const ConvFilter* down,
+                         BottleneckWeights* out) {
+  PR_REQUIRE(planes == 64 || ((planes == 128 || planes == 256) && !down),
+             "bottleneck_pack_bf16: %d planes%s has no whole-block kernel", planes, down ? " with a downsample branch" : "");
+  PR_REQUIRE(c1.w && c2.w && c3.w && c1.bias && c2.bias && c3.bias && (!down || (down->w && down->bias)), "bottleneck_pack_bf16: null argument");
+  const int P = planes, cin = down ? P : 4 * P;
+  const std::vector<unsigned short> r1 = permuted_rows(side_by_side<unsigned short>(c1, cin, cin, 1, nullptr, 0, P), P);
+  std::vector<unsigned short> r2 = permuted_rows(side_by_side<unsigned short>(c2, P, P, 3, nullptr, 0, P), P);
+  std::vector<unsigned short> r3 = permuted_rows(side_by_side<unsigned short>(c3, P, P, 1, down, cin, 4 * P), 4 * P);
+  if (P == 256) {      // conv2 and conv3 further into the MFMA fragment orders
+    std::vector<unsigned short> g2(r2.size()), g3(r3.size());
+    bottleneck256_pack_w2_frags_bf16(r2.data(), g2.data());
+    bottleneck256_pack_w3_frags_bf16(r3.data(), g3.data());
+    r2.swap(g2);
+    r3.swap(g3);
+  }
+  out->w1 = as_floats(r1);
+  out->w2 = as_floats(r2);
+  out->w3 = as_floats(r3);
+  out->b1 = bias_f32(c1, nullptr, P);
+  out->b2 = bias_f32(c2, nullptr, P);
+  out->b3 = bias_f32(c3, down, 4 * P);
+  return PR_OK;
+}
+
 bool expand_res_bf16_fits(int K, int N) { return (K == 128 && N == 512) || (K == 256 && N == 1024); }
 bool expand_dual_bf16_fits(int K1, int K2, int N) { return K1 == 128 && K2 == 256 && N == 512; }
 bool bottleneck256_bf16_fits(int H, int W) { return H >= 1 && W >= 1 && H * W <= 224; }   // 32 x 7 pixel tiles: kMaxPix of the kernel
@@ -191,6 +272,7 @@ int dev_alloc(Ctx& cx, size_t floats, float** out) { return cx.sink->zeros(std::
 struct FoldedConv {
   const float* w = nullptr;
   std::vector<double> scale, bias;
+  ConvFilter filter() const { return {w, scale.data(), bias.data()}; }
 };
 
 int read_conv_bn(BlobReader& br, int Cout, int Cin_real, int k, FoldedConv* out) {
@@ -210,34 +292,25 @@ int read_conv_bn(BlobReader& br, int Cout, int Cin_real, int k, FoldedConv* out)
   return PR_OK;
 }
 
-// Packed K extent of one convolution's weight rows in the handle's precision.
-int packed_k(const HmrPlan* h, int K) { return h->precision == 1 ? conv_kpad_bf16(K) : ceil_div(K, kConvBK) * kConvBK; }
-
 // Folded weights of one or two convolutions (two: a conv3 and the downsample branch summed into it) -> device
 // rows [Cout][Kpad(f1) + Kpad(f2)] in the handle's precision.
 int upload_packed(Ctx& cx, const ConvSpec& spec, const FoldedConv& f1, const FoldedConv* f2, float** out) {
-  HmrPlan* const h = cx.h;
-  const int K1 = packed_k(h, spec.k * spec.k * spec.Cin), K2 = f2 ? packed_k(h, spec.Cin2) : 0;
-  if (h->precision == 1) {
-    std::vector<unsigned short> a((size_t)spec.Cout * K1), b((size_t)spec.Cout * K2), packed((size_t)spec.Cout * (K1 + K2));
-    conv_pack_weights_bf16(f1.w, f1.scale.data(), spec.Cout, spec.Cin_real, spec.Cin, spec.k, spec.k, a.data());
-    if (f2) conv_pack_weights_bf16(f2->w, f2->scale.data(), spec.Cout, spec.Cin2, spec.Cin2, 1, 1, b.data());
-    for (int o = 0; o < spec.Cout; ++o) {
-      memcpy(&packed[(size_t)o * (K1 + K2)], &a[(size_t)o * K1], (size_t)K1 * 2);
-      if (K2) memcpy(&packed[(size_t)o * (K1 + K2) + K1], &b[(size_t)o * K2], (size_t)K2 * 2);
-    }
-    std::vector<float> as_f((packed.size() + 1) / 2);
-    memcpy(as_f.data(), packed.data(), packed.size() * 2);
-    return upload(cx, as_f, out);
-  }
-  std::vector<float> a((size_t)spec.Cout * K1), b((size_t)spec.Cout * K2), packed((size_t)spec.Cout * (K1 + K2));
-  conv_pack_weights(f1.w, f1.scale.data(), spec.Cout, spec.Cin_real, spec.Cin, spec.k, spec.k, a.data());
-  if (f2) conv_pack_weights(f2->w, f2->scale.data(), spec.Cout, spec.Cin2, spec.Cin2, 1, 1, b.data());
-  for (int o = 0; o < spec.Cout; ++o) {
-    memcpy(&packed[(size_t)o * (K1 + K2)], &a[(size_t)o * K1], (size_t)K1 * 4);
-    if (K2) memcpy(&packed[(size_t)o * (K1 + K2) + K1], &b[(size_t)o * K2], (size_t)K2 * 4);
-  }
-  return upload(cx, packed, out);
+  const ConvFilter g2 = f2 ? f2->filter() : ConvFilter{};
+  return upload(cx, conv_pack_side_by_side(f1.filter(), spec.Cin_real, spec.Cin, spec.k, f2 ? &g2 : nullptr, spec.Cin2, spec.Cout, cx.h->precision), out);
+}
+
+// A Bottleneck's folded weights in its whole-block kernel's layouts (bottleneck_pack_bf16) -> the block's spec
+int upload_block(Ctx& cx, const FoldedConv& f1, const FoldedConv& f2, const FoldedConv& f3, const FoldedConv* fd, ConvSpec* blk) {
+  const ConvFilter gd = fd ? fd->filter() : ConvFilter{};
+  BottleneckWeights bw;
+  PR_TRY(bottleneck_pack_bf16(blk->bneck_planes, f1.filter(), f2.filter(), f3.filter(), fd ? &gd : nullptr, &bw));
+  PR_TRY(upload(cx, bw.w1, &blk->w));
+  PR_TRY(upload(cx, bw.w2, &blk->w2b));
+  PR_TRY(upload(cx, bw.w3, &blk->w3));
+  PR_TRY(upload(cx, bw.b1, &blk->bias));
+  PR_TRY(upload(cx, bw.b2, &blk->bias2b));
+  PR_TRY(upload(cx, bw.b3, &blk->bias3));
+  return PR_OK;
 }
 
 // conv weight + its BatchNorm -> packed folded weights and bias on device.  `second` (a conv3 whose block has a
@@ -389,40 +462,7 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
         blk.stage = L;
         blk.bneck_planes = pl;
         blk.bneck_first = first;
-        auto packed16 = [&](const FoldedConv& f, int Cout, int Cin, int k) {
-          std::vector<unsigned short> a16((size_t)Cout * conv_kpad_bf16(k * k * Cin));
-          conv_pack_weights_bf16(f.w, f.scale.data(), Cout, Cin, Cin, k, k, a16.data());
-          return a16;
-        };
-        auto upload_rows = [&](const std::vector<unsigned short>& a16, int Cout, float** out) -> int {
-          const int K = (int)(a16.size() / Cout);
-          std::vector<unsigned short> p16(a16.size());
-          bottleneck_pack_rows_bf16(a16.data(), Cout, K, p16.data());
-          std::vector<float> as_f((p16.size() + 1) / 2);
-          memcpy(as_f.data(), p16.data(), p16.size() * 2);
-          return upload(cx, as_f, out);
-        };
-        auto bias_of = [&](const FoldedConv& f, const FoldedConv* g, float** out) -> int {
-          std::vector<float> bv(f.bias.size());
-          for (size_t o = 0; o < bv.size(); ++o) bv[o] = (float)(f.bias[o] + (g ? g->bias[o] : 0.0));
-          return upload(cx, bv, out);
-        };
-        PR_TRY(upload_rows(packed16(f1, pl, inpl, 1), pl, &blk.w));
-        PR_TRY(upload_rows(packed16(f2, pl, pl, 3), pl, &blk.w2b));
-        if (first) {
-          const std::vector<unsigned short> a3 = packed16(f3, pl * 4, pl, 1), ad = packed16(fd, pl * 4, inpl, 1);
-          std::vector<unsigned short> both((size_t)pl * 4 * (pl + inpl));
-          for (int o = 0; o < pl * 4; ++o) {
-            memcpy(&both[(size_t)o * (pl + inpl)], &a3[(size_t)o * pl], (size_t)pl * 2);
-            memcpy(&both[(size_t)o * (pl + inpl) + pl], &ad[(size_t)o * inpl], (size_t)inpl * 2);
-          }
-          PR_TRY(upload_rows(both, pl * 4, &blk.w3));
-        } else {
-          PR_TRY(upload_rows(packed16(f3, pl * 4, pl, 1), pl * 4, &blk.w3));
-        }
-        PR_TRY(bias_of(f1, nullptr, &blk.bias));
-        PR_TRY(bias_of(f2, nullptr, &blk.bias2b));
-        PR_TRY(bias_of(f3, first ? &fd : nullptr, &blk.bias3));
+        PR_TRY(upload_block(cx, f1, f2, f3, first ? &fd : nullptr, &blk));
         layer += first ? 3 : 2;  // conv1, conv2 (and the downsample branch) report no launch of their own
         blk.layer = layer++;
         h->convs.push_back(blk);
@@ -446,34 +486,7 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
         fb.blk = ConvSpec{inpl, inpl, pl * 4, 1, 1, 0, H, H, 1, cur, outb, -1};
         fb.blk.stage = L;
         fb.blk.bneck_planes = pl;
-        auto rows16 = [&](const FoldedConv& f, int Cout, int Cin, int k) {
-          std::vector<unsigned short> a16((size_t)Cout * conv_kpad_bf16(k * k * Cin)), p16(a16.size());
-          conv_pack_weights_bf16(f.w, f.scale.data(), Cout, Cin, Cin, k, k, a16.data());
-          bottleneck_pack_rows_bf16(a16.data(), Cout, (int)(a16.size() / Cout), p16.data());
-          return p16;
-        };
-        auto upload16 = [&](const std::vector<unsigned short>& p16, float** out) -> int {
-          std::vector<float> as_f((p16.size() + 1) / 2);
-          memcpy(as_f.data(), p16.data(), p16.size() * 2);
-          return upload(cx, as_f, out);
-        };
-        auto bias_of = [&](const FoldedConv& f, float** out) -> int {
-          std::vector<float> bv(f.bias.size());
-          for (size_t o = 0; o < bv.size(); ++o) bv[o] = (float)f.bias[o];
-          return upload(cx, bv, out);
-        };
-        PR_TRY(upload16(rows16(f1, pl, inpl, 1), &fb.blk.w));
-        {
-          const std::vector<unsigned short> r2 = rows16(f2, pl, pl, 3), r3 = rows16(f3, pl * 4, pl, 1);
-          std::vector<unsigned short> g2(r2.size()), g3(r3.size());
-          bottleneck256_pack_w2_frags_bf16(r2.data(), g2.data());
-          bottleneck256_pack_w3_frags_bf16(r3.data(), g3.data());
-          PR_TRY(upload16(g2, &fb.blk.w2b));
-          PR_TRY(upload16(g3, &fb.blk.w3));
-        }
-        PR_TRY(bias_of(f1, &fb.blk.bias));
-        PR_TRY(bias_of(f2, &fb.blk.bias2b));
-        PR_TRY(bias_of(f3, &fb.blk.bias3));
+        PR_TRY(upload_block(cx, f1, f2, f3, nullptr, &fb.blk));
         h->fused3.push_back(fb);
       }
       a.layer = layer++;

@@ -4,7 +4,9 @@
 //   * the canonical blob's layout and size (include/poserisk_hip.h);
 //   * eval-mode BatchNorm folded into every convolution, in double;
 //   * weight packing for every kernel family: [Cout][K] fp32 and bf16 rows, the space-to-depth stem, the Winograd-domain
-//     weights U = G g G^T, the row permutation of the transposed-MFMA kernels, the fragment orders of bottleneck256_bf16;
+//     weights U = G g G^T, the row permutation of the transposed-MFMA kernels, the fragment orders of bottleneck256_bf16,
+//     and over them the whole layouts (two matrices side by side, a Bottleneck for its whole-block kernel), defined once for
+//     the plan and for the stand-alone test entries of capi.hip;
 //   * the 53-convolution execution plan: which launch carries which layer, buffer rotation, fusions, kernel routing;
 //   * workspace sizes per sub-batch, and what a forward of B frames launches.
 //
@@ -72,6 +74,28 @@ void bottleneck_pack_rows_bf16(const unsigned short* src, int rows, int K, unsig
 // bottleneck256_bf16.hip's fragment orders of conv2's [256][2304] and conv3's [1024][256] permuted rows
 void bottleneck256_pack_w2_frags_bf16(const unsigned short* rows, unsigned short* dst);
 void bottleneck256_pack_w3_frags_bf16(const unsigned short* rows, unsigned short* dst);
+
+// ---- whole layouts: the one definition of each, for the plan (build) and the stand-alone test entries (capi.hip) alike ----
+// One convolution as the packers below take it: the OIHW filter, the per-output-channel scale its BatchNorm folds to
+// (applied in double; null = the filter is already folded) and its bias (null = none).
+struct ConvFilter {
+  const float* w = nullptr;
+  const double* scale = nullptr;
+  const double* bias = nullptr;
+};
+// Rows [Cout][Kpad(k k cin_pad) + Kpad(Cin2)] of `f1` (k x k) and, side by side with it, of the 1x1 `f2` (null = none; a
+// conv3 with the downsample branch summed into it), Kpad by the precision.  precision 1: bf16 bit patterns, two to a float.
+std::vector<float> conv_pack_side_by_side(const ConvFilter& f1, int Cin_real, int cin_pad, int k, const ConvFilter* f2, int Cin2,
+                                          int Cout, int precision);
+// A Bottleneck's weights as the whole-block kernel of its `planes` reads them (64: bottleneck_bf16.hip, 128: bottleneck128_bf16.hip,
+// 256: bottleneck256_bf16.hip): w1 / w2 / w3 bf16 (two to a float) with the rows permuted by bottleneck_pack_rows_bf16, 256
+// planes further into the fragment orders; biases fp32 in channel order.  `down` (64 planes only: the stage's first block,
+// 64-channel input): the downsample branch rides in conv3's K loop, w3 = [conv3 | down] side by side, b3 their sum in double.
+struct BottleneckWeights {
+  std::vector<float> w1, w2, w3, b1, b2, b3;
+};
+int bottleneck_pack_bf16(int planes, const ConvFilter& c1, const ConvFilter& c2, const ConvFilter& c3, const ConvFilter* down,
+                         BottleneckWeights* out);
 
 // shape predicates of the kernels the plan routes to (pure; the kernels' own launchers re-check them)
 bool expand_res_bf16_fits(int K, int N);

@@ -94,49 +94,67 @@ def rula(euler_deg, info, out=None):
     return out
 
 
+def _device_index(t):
+    return t.device.index if t.device.index is not None else torch.cuda.current_device()
+
+
+def _precision(precision):
+    """The library's precision flag and the tensors' dtype."""
+    return (1, torch.bfloat16) if precision == "bf16" else (0, torch.float32)
+
+
+def _f32(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a if shape is None else a.reshape(shape)
+
+
+def _ptr(a):
+    """The data pointer of a numpy array or a tensor; None stays None (an optional argument)."""
+    return None if a is None else a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+
+
+def _timed(call, name, y, repeats):
+    """A stand-alone entry with a `repeats` argument: call(ms) -> status.  Returns (y, ms_per_launch or None)."""
+    ms = np.zeros(1, np.float32)
+    _lib.check(call(ms.ctypes.data), name)
+    return y, (float(ms[0]) if repeats > 0 else None)
+
+
 def conv2d_nhwc(x, w_oihw, bias=None, residual=None, stride=1, pad=0, relu=False, tile_cfg=-1, repeats=0,
                 precision="fp32", out=None):
     """Stand-alone conv on NHWC (test / tuning entry).  x [B,H,W,Cin] CUDA (f32, or bf16 with
     precision="bf16"), w numpy OIHW.  Returns (y [B,Ho,Wo,Cout] in x's dtype, ms_per_launch or None)."""
     _need_cuda(x, "conv2d_nhwc")
-    bf = precision == "bf16"
-    dt = torch.bfloat16 if bf else torch.float32
+    bf, dt = _precision(precision)
     x = x.contiguous().to(dt)
     B, H, W, Cin = x.shape
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    w = _f32(w_oihw)
     Cout, Cin_real, KH, KW = w.shape
     Ho = (H + 2 * pad - KH) // stride + 1
     Wo = (W + 2 * pad - KW) // stride + 1
     y = _out(out, (B, Ho, Wo, Cout), dt, x.device)
-    b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
+    b = _f32(bias) if bias is not None else None
     res = residual.contiguous().to(dt) if residual is not None else None
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_conv2d_nhwc(
-        idx, x.data_ptr(), w.ctypes.data, b.ctypes.data if b is not None else None,
-        res.data_ptr() if res is not None else None, y.data_ptr(), B, H, W, Cin, Cin_real, Cout, KH, KW,
-        stride, pad, int(relu), tile_cfg, 1 if bf else 0, repeats, ms.ctypes.data, _stream(x.device)), "pr_conv2d_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _timed(lambda ms: _lib.load().pr_conv2d_nhwc(
+        _device_index(x), x.data_ptr(), w.ctypes.data, _ptr(b), _ptr(res), y.data_ptr(), B, H, W, Cin, Cin_real, Cout, KH, KW,
+        stride, pad, int(relu), tile_cfg, bf, repeats, ms, _stream(x.device)), "pr_conv2d_nhwc", y, repeats)
 
 
 def conv1x1_dual_nhwc(x1, w1, x2, w2, bias=None, stride2=1, relu=False, tile_cfg=-1, precision="fp32", out=None):
     """relu(x1*W1 + x2[::stride2, ::stride2]*W2 + bias) as one dual-source GEMM (a first Bottleneck's conv3 with its
     downsample branch summed in).  x1 [B,Ho,Wo,C1], x2 [B,H2,W2,C2] CUDA, w1 [Cout,C1], w2 [Cout,C2] numpy."""
     _need_cuda(x1, "conv1x1_dual_nhwc")
-    bf = precision == "bf16"
-    dt = torch.bfloat16 if bf else torch.float32
+    bf, dt = _precision(precision)
     x1, x2 = x1.contiguous().to(dt), x2.contiguous().to(dt)
     B, Ho, Wo, C1 = x1.shape
     _, H2, W2, C2 = x2.shape
-    w1 = np.ascontiguousarray(w1, dtype=np.float32).reshape(-1, C1)
-    w2 = np.ascontiguousarray(w2, dtype=np.float32).reshape(-1, C2)
+    w1, w2 = _f32(w1, (-1, C1)), _f32(w2, (-1, C2))
     Cout = w1.shape[0]
     y = _out(out, (B, Ho, Wo, Cout), dt, x1.device)
-    b = np.ascontiguousarray(bias, dtype=np.float32) if bias is not None else None
-    idx = x1.device.index if x1.device.index is not None else torch.cuda.current_device()
+    b = _f32(bias) if bias is not None else None
     _lib.check(_lib.load().pr_conv1x1_dual_nhwc(
-        idx, x1.data_ptr(), w1.ctypes.data, x2.data_ptr(), w2.ctypes.data, b.ctypes.data if b is not None else None,
-        y.data_ptr(), B, Ho, Wo, C1, H2, W2, C2, stride2, Cout, int(relu), tile_cfg, 1 if bf else 0,
+        _device_index(x1), x1.data_ptr(), w1.ctypes.data, x2.data_ptr(), w2.ctypes.data, _ptr(b),
+        y.data_ptr(), B, Ho, Wo, C1, H2, W2, C2, stride2, Cout, int(relu), tile_cfg, bf,
         _stream(x1.device)), "pr_conv1x1_dual_nhwc")
     return y
 
@@ -145,22 +163,16 @@ def conv3x3_conv1x1_nhwc(x, w2, b2, w3, b3, residual=None, relu=True, precision=
     """relu?(relu(conv3x3(x, w2) + b2) * w3^T + b3 + residual) in one kernel (a layer1 Bottleneck's conv2 + conv3).
     x [B,H,W,Cin] CUDA (f32, or bf16 with precision="bf16"), w2 [64,Cin,3,3], w3 [N3,64] numpy -> [B,H,W,N3]."""
     _need_cuda(x, "conv3x3_conv1x1_nhwc")
-    bf = precision == "bf16"
-    dt = torch.bfloat16 if bf else torch.float32
+    bf, dt = _precision(precision)
     x = x.contiguous().to(dt)
     B, H, W, Cin = x.shape
-    w2 = np.ascontiguousarray(w2, dtype=np.float32)
-    w3 = np.ascontiguousarray(w3, dtype=np.float32).reshape(-1, 64)
-    b2 = np.ascontiguousarray(b2, dtype=np.float32)
-    b3 = np.ascontiguousarray(b3, dtype=np.float32)
+    w2, w3, b2, b3 = _f32(w2), _f32(w3, (-1, 64)), _f32(b2), _f32(b3)
     N3 = w3.shape[0]
     res = residual.contiguous().to(dt) if residual is not None else None
     y = _out(out, (B, H, W, N3), dt, x.device)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_conv3x3_conv1x1_nhwc(
-        idx, x.data_ptr(), w2.ctypes.data, b2.ctypes.data, w3.ctypes.data, b3.ctypes.data,
-        res.data_ptr() if res is not None else None, y.data_ptr(), B, H, W, Cin, N3, int(relu), 1 if bf else 0,
-        _stream(x.device)), "pr_conv3x3_conv1x1_nhwc")
+        _device_index(x), x.data_ptr(), w2.ctypes.data, b2.ctypes.data, w3.ctypes.data, b3.ctypes.data,
+        _ptr(res), y.data_ptr(), B, H, W, Cin, N3, int(relu), bf, _stream(x.device)), "pr_conv3x3_conv1x1_nhwc")
     return y
 
 
@@ -172,22 +184,34 @@ def conv3x3_wino64_nhwc(x, w2, b2, w3=None, b3=None, residual=None, relu=True, f
     _need_cuda(x, "conv3x3_wino64_nhwc")
     x = x.contiguous().float()
     B, H, W, Cin = x.shape
-    w2 = np.ascontiguousarray(w2, dtype=np.float32)
-    b2 = np.ascontiguousarray(b2, dtype=np.float32)
+    w2, b2 = _f32(w2), _f32(b2)
     Cout = w2.shape[0]
     fused = w3 is not None
-    if fused:
-        w3 = np.ascontiguousarray(w3, dtype=np.float32).reshape(-1, 64)
-        b3 = np.ascontiguousarray(b3, dtype=np.float32)
+    w3, b3 = (_f32(w3, (-1, 64)), _f32(b3)) if fused else (None, None)
     N3 = w3.shape[0] if fused else 0
     res = residual.contiguous().float() if residual is not None else None
     y = _out(out, (B, H, W, N3 if fused else Cout), torch.float32, x.device)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
     _lib.check(_lib.load().pr_conv3x3_wino64_nhwc(
-        idx, x.data_ptr(), w2.ctypes.data, b2.ctypes.data, w3.ctypes.data if fused else None,
-        b3.ctypes.data if fused else None, res.data_ptr() if res is not None else None, y.data_ptr(), B, H, W, Cin, Cout,
-        N3, int(relu), int(relu), form, _stream(x.device)), "pr_conv3x3_wino64_nhwc")
+        _device_index(x), x.data_ptr(), w2.ctypes.data, b2.ctypes.data, _ptr(w3), _ptr(b3), _ptr(res), y.data_ptr(), B, H, W,
+        Cin, Cout, N3, int(relu), int(relu), form, _stream(x.device)), "pr_conv3x3_wino64_nhwc")
     return y
+
+
+def _bottleneck(planes, first, name, x, w1, b1, w2, b2, w3, b3, wd, bd, repeats, out):
+    """The three whole-Bottleneck wrappers: `planes` channels inside, 4 * planes out, the same in (a first block: planes)."""
+    _need_cuda(x, name)
+    x = x.contiguous().to(torch.bfloat16)
+    B, H, W, C = x.shape
+    P, cin = planes, planes if first else 4 * planes
+    if C != cin:
+        raise ValueError(f"{name}: {cin} input channels expected, got {C}")
+    w = [_f32(w1, (P, C)), _f32(b1, (P,)), _f32(w2, (P, P, 3, 3)), _f32(b2, (P,)), _f32(w3, (4 * P, P)), _f32(b3, (4 * P,))]
+    if planes == 64:      # the only entry with a downsample branch in its signature
+        w += [_f32(wd, (4 * P, P)), _f32(bd, (4 * P,))] if first else [None, None]
+    y = _out(out, (B, H, W, 4 * P), torch.bfloat16, x.device)
+    entry = getattr(_lib.load(), f"pr_{name}")
+    return _timed(lambda ms: entry(_device_index(x), x.data_ptr(), *map(_ptr, w), y.data_ptr(), B, H, W, repeats, ms,
+                                   _stream(x.device)), f"pr_{name}", y, repeats)
 
 
 def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0, out=None):
@@ -195,68 +219,21 @@ def bottleneck_nhwc(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None, repeats=0, out=
     the caller) in one persistent bf16 kernel.  Without `wd`: x bf16 [B,H,W,256] CUDA, w1 [64,256], identity = x.  With
     `wd` [256,64] / `bd` [256] (the stage's first block): x bf16 [B,H,W,64], w1 [64,64], identity = the downsample branch.
     w2 [64,64,3,3], w3 [256,64] numpy.  Returns (y bf16 [B,H,W,256], ms_per_launch or None)."""
-    _need_cuda(x, "bottleneck_nhwc")
-    x = x.contiguous().to(torch.bfloat16)
-    B, H, W, C = x.shape
-    first = wd is not None
-    if C != (64 if first else 256):
-        raise ValueError(f"bottleneck_nhwc: {64 if first else 256} input channels expected, got {C}")
-    f = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
-    w1, w2, w3 = f(w1, (64, C)), f(w2, (64, 64, 3, 3)), f(w3, (256, 64))
-    b1, b2, b3 = f(b1, (64,)), f(b2, (64,)), f(b3, (256,))
-    if first:
-        wd, bd = f(wd, (256, 64)), f(bd, (256,))
-    y = _out(out, (B, H, W, 256), torch.bfloat16, x.device)
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_bottleneck_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
-                                              b2.ctypes.data, w3.ctypes.data, b3.ctypes.data,
-                                              wd.ctypes.data if first else None, bd.ctypes.data if first else None,
-                                              y.data_ptr(), B, H, W, repeats, ms.ctypes.data, _stream(x.device)),
-               "pr_bottleneck_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _bottleneck(64, wd is not None, "bottleneck_nhwc", x, w1, b1, w2, b2, w3, b3, wd, bd, repeats, out)
 
 
 def bottleneck128_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0, out=None):
     """A whole layer2 Bottleneck (plain block: conv1 1x1 512 -> 128, conv2 3x3, conv3 1x1 128 -> 512 + identity, ReLU after
     each; BatchNorm folded by the caller) in one persistent bf16 kernel.  x bf16 [B,H,W,512] CUDA (W <= 31), w1 [128,512],
     w2 [128,128,3,3], w3 [512,128] numpy.  Returns (y bf16 [B,H,W,512], ms_per_launch or None)."""
-    _need_cuda(x, "bottleneck128_nhwc")
-    x = x.contiguous().to(torch.bfloat16)
-    B, H, W, C = x.shape
-    if C != 512:
-        raise ValueError(f"bottleneck128_nhwc: 512 input channels expected, got {C}")
-    f = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
-    w1, w2, w3 = f(w1, (128, 512)), f(w2, (128, 128, 3, 3)), f(w3, (512, 128))
-    b1, b2, b3 = f(b1, (128,)), f(b2, (128,)), f(b3, (512,))
-    y = _out(out, (B, H, W, 512), torch.bfloat16, x.device)
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_bottleneck128_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
-                                                 b2.ctypes.data, w3.ctypes.data, b3.ctypes.data, y.data_ptr(), B, H, W,
-                                                 repeats, ms.ctypes.data, _stream(x.device)), "pr_bottleneck128_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _bottleneck(128, False, "bottleneck128_nhwc", x, w1, b1, w2, b2, w3, b3, None, None, repeats, out)
 
 
 def bottleneck256_nhwc(x, w1, b1, w2, b2, w3, b3, repeats=0, out=None):
     """A whole layer3 Bottleneck (plain block: conv1 1x1 1024 -> 256, conv2 3x3, conv3 1x1 256 -> 1024 + identity, ReLU after
     each; BatchNorm folded by the caller) in one bf16 kernel, one frame per workgroup.  x bf16 [B,H,W,1024] CUDA (H W <= 224),
     w1 [256,1024], w2 [256,256,3,3], w3 [1024,256] numpy.  Returns (y bf16 [B,H,W,1024], ms_per_launch or None)."""
-    _need_cuda(x, "bottleneck256_nhwc")
-    x = x.contiguous().to(torch.bfloat16)
-    B, H, W, C = x.shape
-    if C != 1024:
-        raise ValueError(f"bottleneck256_nhwc: 1024 input channels expected, got {C}")
-    f = lambda a, shape: np.ascontiguousarray(a, dtype=np.float32).reshape(shape)
-    w1, w2, w3 = f(w1, (256, 1024)), f(w2, (256, 256, 3, 3)), f(w3, (1024, 256))
-    b1, b2, b3 = f(b1, (256,)), f(b2, (256,)), f(b3, (1024,))
-    y = _out(out, (B, H, W, 1024), torch.bfloat16, x.device)
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_bottleneck256_nhwc(idx, x.data_ptr(), w1.ctypes.data, b1.ctypes.data, w2.ctypes.data,
-                                                 b2.ctypes.data, w3.ctypes.data, b3.ctypes.data, y.data_ptr(), B, H, W,
-                                                 repeats, ms.ctypes.data, _stream(x.device)), "pr_bottleneck256_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _bottleneck(256, False, "bottleneck256_nhwc", x, w1, b1, w2, b2, w3, b3, None, None, repeats, out)
 
 
 def stem_pool_nhwc(x, w, bias, repeats=0, out=None):
@@ -268,14 +245,11 @@ def stem_pool_nhwc(x, w, bias, repeats=0, out=None):
     B, H, W, C = x.shape
     if C != 16 or H != W or H % 2:
         raise ValueError("stem_pool_nhwc: x must be [B,H,H,16] with even H")
-    w = np.ascontiguousarray(w, dtype=np.float32).reshape(64, 16, 4, 4)
-    b = np.ascontiguousarray(bias, dtype=np.float32).reshape(64)
+    w, b = _f32(w, (64, 16, 4, 4)), _f32(bias, (64,))
     y = _out(out, (B, H // 2, H // 2, 64), torch.bfloat16, x.device)
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_stem_pool_nhwc(idx, x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, H, repeats,
-                                             ms.ctypes.data, _stream(x.device)), "pr_stem_pool_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _timed(lambda ms: _lib.load().pr_stem_pool_nhwc(
+        _device_index(x), x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, H, repeats, ms, _stream(x.device)),
+        "pr_stem_pool_nhwc", y, repeats)
 
 
 def stem_pool_f32_nhwc(x, w, bias, repeats=0, out=None):
@@ -287,14 +261,11 @@ def stem_pool_f32_nhwc(x, w, bias, repeats=0, out=None):
     if tuple(x.shape[1:]) != (112, 112, 12):
         raise ValueError(f"stem_pool_f32_nhwc: x must be [B,112,112,12], got {tuple(x.shape)}")
     B = x.shape[0]
-    w = np.ascontiguousarray(w, dtype=np.float32).reshape(64, 12, 4, 4)
-    b = np.ascontiguousarray(bias, dtype=np.float32).reshape(64)
+    w, b = _f32(w, (64, 12, 4, 4)), _f32(bias, (64,))
     y = _out(out, (B, 56, 56, 64), torch.float32, x.device)
-    ms = np.zeros(1, np.float32)
-    idx = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load().pr_stem_pool_f32_nhwc(idx, x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, repeats,
-                                                 ms.ctypes.data, _stream(x.device)), "pr_stem_pool_f32_nhwc")
-    return y, (float(ms[0]) if repeats > 0 else None)
+    return _timed(lambda ms: _lib.load().pr_stem_pool_f32_nhwc(
+        _device_index(x), x.data_ptr(), w.ctypes.data, b.ctypes.data, y.data_ptr(), B, repeats, ms, _stream(x.device)),
+        "pr_stem_pool_f32_nhwc", y, repeats)
 
 
 def crop_frames(frames, bboxes, frame_idx=None, scale=1.2, bgr=False, return_status=False, out=None):

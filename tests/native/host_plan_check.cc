@@ -15,7 +15,11 @@
 // For the default fp32 and bf16 plans at B = 64 it writes a manifest of every upload (bytes, FNV-1a) and the raw bytes of
 // the first upload of each size and of the regressor's nine to <dump.bin>: the Python test recomputes BN folding, packing and the Winograd G-transform
 // with numpy from the same state dict (poserisk_release_amd/weights.py order) and compares.
+// The same two plans are held against the packers as the stand-alone test entries (capi.hip) call them -- filters folded to
+// fp32 beforehand, null scales: bottleneck_pack_bf16 for layer1.0 (first), layer1.1, layer2.1 and layer3.1 and
+// conv_pack_side_by_side for layer2.0's conv3 + downsample must give, byte for byte, what the plan uploaded.
 #include <cinttypes>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -287,6 +291,106 @@ static bool build(Built& b, const std::vector<float>& blob, int precision, int f
   return st == PR_OK;
 }
 
+// ---- the packers as the stand-alone test entries call them, against what the plan uploaded ------------------------------
+// One convolution of the blob with its BatchNorm folded HERE, to fp32 -- what a caller of pr_bottleneck*_nhwc passes.
+struct Folded {
+  std::vector<float> w;
+  std::vector<double> bias;
+  ConvFilter filter() const { return {w.data(), nullptr, bias.data()}; }
+};
+static Folded fold(const float*& p, int Cout, int Cin, int k) {
+  const size_t per = (size_t)Cin * k * k;
+  const float *w = p, *g = w + Cout * per, *be = g + Cout, *mu = be + Cout, *var = mu + Cout;
+  p = var + Cout;
+  Folded f;
+  f.w.resize(Cout * per);
+  f.bias.resize(Cout);
+  for (int o = 0; o < Cout; ++o) {
+    const double s = (double)g[o] / std::sqrt((double)var[o] + kBnEps);
+    f.bias[o] = (double)be[o] - (double)mu[o] * s;
+    for (size_t i = 0; i < per; ++i) f.w[o * per + i] = (float)((double)w[o * per + i] * s);
+  }
+  return f;
+}
+struct FoldedBlock {
+  Folded c1, c2, c3, down;
+};
+// Bottleneck b of layer L + 1 (blob order: conv1, conv2, conv3, each with its BatchNorm, then a first block's downsample)
+static FoldedBlock fold_block(const std::vector<float>& blob, int L, int b) {
+  const float* p = blob.data() + 64 * 3 * 49 + 4 * 64;
+  int inpl = 64;
+  for (int l = 0; l < 4; ++l)
+    for (int k = 0; k < kBlocks[l]; ++k) {
+      const int pl = kPlanes[l];
+      if (l == L && k == b) {
+        FoldedBlock f{fold(p, pl, inpl, 1), fold(p, pl, pl, 3), fold(p, 4 * pl, pl, 1), {}};
+        if (b == 0) f.down = fold(p, 4 * pl, inpl, 1);
+        return f;
+      }
+      p += (size_t)pl * inpl + (size_t)pl * pl * 9 + (size_t)4 * pl * pl + 4 * 6 * pl + (k == 0 ? (size_t)4 * pl * inpl + 16 * pl : 0);
+      inpl = 4 * pl;
+    }
+  return {};
+}
+
+static void check_upload(const HostSink& sink, const float* dev, const std::vector<float>& want, const char* tag, const char* what) {
+  for (const Upload& u : sink.ups)
+    if (u.ptr == dev) {
+      CHECK(u.bytes == want.size() * 4 && !memcmp(u.ptr, want.data(), u.bytes), "%s: %s differs from the plan's upload (%zu bytes, %zu uploaded)", tag,
+            what, want.size() * 4, u.bytes);
+      return;
+    }
+  CHECK(false, "%s: %s is no upload of the plan", tag, what);
+}
+
+static void check_block(const Built& b, const ConvSpec* spec, const std::vector<float>& blob, int L, int blk, const char* tag) {
+  CHECK(spec != nullptr, "%s: no whole-block spec in the plan", tag);
+  if (!spec) return;
+  const FoldedBlock f = fold_block(blob, L, blk);
+  const ConvFilter down = f.down.filter();
+  BottleneckWeights bw;
+  const int st = bottleneck_pack_bf16(kPlanes[L], f.c1.filter(), f.c2.filter(), f.c3.filter(), blk == 0 ? &down : nullptr, &bw);
+  CHECK(st == PR_OK, "%s: bottleneck_pack_bf16 failed: %s", tag, g_err.c_str());
+  if (st != PR_OK) return;
+  check_upload(b.sink, spec->w, bw.w1, tag, "w1");
+  check_upload(b.sink, spec->w2b, bw.w2, tag, "w2");
+  check_upload(b.sink, spec->w3, bw.w3, tag, "w3");
+  check_upload(b.sink, spec->bias, bw.b1, tag, "b1");
+  check_upload(b.sink, spec->bias2b, bw.b2, tag, "b2");
+  check_upload(b.sink, spec->bias3, bw.b3, tag, "b3");
+}
+
+// the first whole-block spec of the plan with these planes (layer1.0 when `first`, else the stage's block 1)
+static const ConvSpec* block_spec(const HmrPlan& pl, int planes, bool first) {
+  for (const ConvSpec& c : pl.convs)
+    if (c.bneck_planes == planes && c.bneck_first == first) return &c;
+  return nullptr;
+}
+
+static void check_packers_against_plan(const Built& b, const std::vector<float>& blob) {
+  const HmrPlan& pl = b.plan;
+  if (pl.precision == 1) {
+    check_block(b, block_spec(pl, 64, true), blob, 0, 0, "layer1.0 as the test entry packs it");
+    check_block(b, block_spec(pl, 64, false), blob, 0, 1, "layer1.1 as the test entry packs it");
+    check_block(b, block_spec(pl, 128, false), blob, 1, 1, "layer2.1 as the test entry packs it");
+    check_block(b, pl.fused3.empty() ? nullptr : &pl.fused3[0].blk, blob, 2, 1, "layer3.1 as the test entry packs it");
+    bool refused = bottleneck_pack_bf16(32, {}, {}, {}, nullptr, nullptr) == PR_ERR_INVALID;
+    const ConvFilter none;
+    refused = refused && bottleneck_pack_bf16(128, none, none, none, &none, nullptr) == PR_ERR_INVALID;
+    CHECK(refused, "bottleneck_pack_bf16 takes planes without a whole-block kernel");
+  }
+  // layer2.0's conv3 with its downsample branch side by side (the dual-source GEMM's [512][128 | 256]), in the plan's precision
+  const char* tag = pl.precision ? "layer2.0 conv3 | downsample, bf16" : "layer2.0 conv3 | downsample, fp32";
+  const ConvSpec* dual = nullptr;
+  for (const ConvSpec& c : pl.convs)
+    if (!dual && c.stage == 1 && c.in2_buf >= 0) dual = &c;
+  CHECK(dual && dual->Cin == 128 && dual->Cin2 == 256 && dual->Cout == 512, "%s: not in the plan", tag);
+  if (!dual) return;
+  const FoldedBlock f = fold_block(blob, 1, 0);
+  const ConvFilter down = f.down.filter();
+  check_upload(b.sink, dual->w, conv_pack_side_by_side(f.c3.filter(), 128, 128, 1, &down, 256, 512, pl.precision), tag, "the packed rows");
+}
+
 int main(int argc, char** argv) {
   if (argc < 4) {
     fprintf(stderr, "usage: host_plan_check <blob.f32> <manifest.json> <dump.bin>\n");
@@ -346,7 +450,9 @@ int main(int argc, char** argv) {
       if (precision) CHECK(b.plan.convs.size() == 37 && b.plan.fused3.size() == 5 && b.plan.wino_floats_per_frame == 0, "%s: %zu launches, %zu fused layer3 blocks", tag, b.plan.convs.size(), b.plan.fused3.size());
       if (precision && B == 460) check_counts_follow_the_split(b.plan, tag);
       if ((B == 64) && argc >= 4) {
+        check_packers_against_plan(b, blob);
         // manifest + raw bytes of the first upload of every size (the Python test recomputes them)
+        const ConvSpec* l11 = block_spec(b.plan, 64, false);      // ... and of layer1.1's w1 (the sigma row permutation)
         FILE* mf = fopen(argv[2], precision ? "a" : "w");
         FILE* df = fopen(argv[3], precision ? "ab" : "wb");
         if (!mf || !df) { fprintf(stderr, "cannot write %s / %s\n", argv[2], argv[3]); return 2; }
@@ -358,7 +464,7 @@ int main(int argc, char** argv) {
           long at = -1;
           // the first upload of every size, and the regressor's (the last nine before the zero-filled workspaces)
           const bool regressor = i + 5 + 9 >= b.sink.ups.size();
-          if (!u.zeros && (seen.insert(u.bytes).second || regressor)) {
+          if (!u.zeros && (seen.insert(u.bytes).second || regressor || (l11 && u.ptr == l11->w))) {
             at = pos;
             fwrite(u.ptr, 1, u.bytes, df);
             pos += (long)u.bytes;

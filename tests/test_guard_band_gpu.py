@@ -329,6 +329,38 @@ def test_stem_pool_f32(gpu_device):
     assert np.abs(y.cpu().numpy() - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
+TIMED_BLOCKS = {"bottleneck64": (64, False), "bottleneck64_first": (64, True), "bottleneck128": (128, False), "bottleneck256": (256, False)}
+
+
+def _timed_entry(dev, entry):
+    """-> call(repeats) of a stand-alone entry that takes `repeats`, on the smallest case of its test above."""
+    if entry in TIMED_BLOCKS:
+        mid, first = TIMED_BLOCKS[entry]
+        x, w1, w2, w3, wd, b = kr.bottleneck_inputs(mid, (5, 1, 1) if mid == 256 else (7, 1, 1), first)
+        fn = {64: ops.bottleneck_nhwc, 128: ops.bottleneck128_nhwc, 256: ops.bottleneck256_nhwc}[mid]
+        extra = dict(wd=wd.numpy(), bd=b[3]) if first else {}
+        xd = x.to(dev, BF16)
+        return lambda repeats: fn(xd, w1.numpy(), b[0], w2.numpy(), b[1], w3.numpy(), b[2], repeats=repeats, **extra)
+    if entry == "stem_pool_bf16":
+        x, w, bias, _ = kr.stem_pool_bf16_case((5, 2))
+        xd = x.to(dev, BF16)
+        return lambda repeats: ops.stem_pool_nhwc(xd, w.numpy(), bias, repeats=repeats)
+    x, w, bias, _, _ = kr.stem_pool_f32_case(2)
+    xd = torch.from_numpy(x).to(dev)
+    return lambda repeats: ops.stem_pool_f32_nhwc(xd, w, bias, repeats=repeats)
+
+
+@pytest.mark.parametrize("entry", [*TIMED_BLOCKS, "stem_pool_bf16", "stem_pool_f32"])
+def test_the_timed_loop_times_and_leaves_the_output_as_it_is(gpu_device, entry):
+    """The event-timed `repeats` loop the stand-alone entries share: a time comes back, and the launches it adds write what the
+    first one wrote."""
+    call = _timed_entry(gpu_device, entry)
+    y0, ms0 = call(0)
+    y2, ms2 = call(2)
+    assert ms0 is None and ms2 is not None and np.isfinite(ms2) and ms2 > 0
+    assert torch.equal(y0, y2)
+
+
 # ------------------------------------------------------------------------------------------------
 # behind the encoder: rotations, Euler angles, scores
 # ------------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@ its index arithmetic had never run under a sanitizer (SURVEY.md section 5 asks f
 3's advisor found host UB there by reading).  `tests/native/host_plan_check.cc` builds the full ResNet-50 plan for
 B in {1, 7, 64, 230, 256, 460}, both precisions, every conv form and every plan-shaping switch, against exact-size heap
 blocks, and checks the plans structurally (symbolic dataflow over the buffer rotation, routing, 4 087 136 256 MAC per frame,
-launch counts, workspace sizes).  Here: it is compiled with g++ -fsanitize=address,undefined, run, and the packed weights it
+launch counts, workspace sizes), and holds the two default plans against the packers as the stand-alone test entries call them
+(bottleneck_pack_bf16 / conv_pack_side_by_side on filters folded beforehand: byte-equal to the plan's uploads).  Here: it is compiled with g++ -fsanitize=address,undefined, run, and the packed weights it
 produced are compared with a numpy restatement from the same state dict (weights.py's blob order = lib/core/base.py:83-84's
 checkpoint['model'])."""
 import json
@@ -153,3 +154,11 @@ def test_packed_weights_equal_a_numpy_restatement(native_run):
     want = np.zeros((64, 16, 16), np.float32)                                            # [o][tap][c]
     want[:, :, :12] = v.transpose(0, 2, 3, 1).reshape(64, 16, 12)
     np.testing.assert_array_equal(_dumped(b16, dump, 0, np.uint16).reshape(64, 256), _bf16(want.reshape(64, 256)))
+    # bf16: layer1.1's conv1 (upload 8: behind the stem's two and layer1.0's six) as the whole-block kernel reads it -- the folded
+    # [64][256] matrix with row 32 T + i taken from output channel 32 T + sigma(i), sigma(i) = 16 ((i >> 2) & 1) + 4 (i >> 3) + (i & 3)
+    w, s, _ = _fold(sd, "layer1.1.conv1", "layer1.1.bn1")
+    folded = (w.astype(np.float64) * s[:, None, None, None]).astype(np.float32).reshape(64, 256)
+    i = np.arange(32)
+    sigma = 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3)
+    assert sorted(sigma) == list(range(32)) and b16["uploads"][8]["bytes"] == 64 * 256 * 2
+    np.testing.assert_array_equal(_dumped(b16, dump, 8, np.uint16).reshape(64, 256), _bf16(folded[np.concatenate([sigma, 32 + sigma])]))
