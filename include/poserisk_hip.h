@@ -657,6 +657,114 @@ typedef struct pr_jpeg_args {
 } pr_jpeg_args;
 int pr_jpeg_decode(const pr_jpeg_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j2  u8[F,H,W,3] on the device -> baseline JPEG files, byte-exact with libjpeg          */
+/* replaces: cv2.VideoWriter / one PNG per frame behind the composed canvases             */
+/*           (write_gpu_video, _mesh_writer): only compressed bytes leave the device      */
+/* ------------------------------------------------------------------------------------ */
+/* The inverse of j1.  The host half (pr_jpeg_encode_plan, csrc/jpeg_host.cc, no device) derives the tables and writes the
+ * header bytes; the device half (pr_jpeg_encode, csrc/jpeg_enc.hip) does everything else.  No ABI bump: functions were added.
+ *
+ * Accepted: u8 [F,H,W,3] frames (RGB, or BGR with bgr != 0), 16 <= H, W <= 4096, three components, luma sampling hs x vs =
+ *   1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) with chroma 1x1, quality 1..100, one interleaved scan, a restart interval in MCUs
+ *   (0 = none, -1 = one MCU row; libjpeg keeps at most 65535).  Gray output, progressive mode and optimised Huffman tables are
+ *   out of scope: there is no entry for them.
+ *
+ * Arithmetic contract.  Integer-exact, so that tests/jpeg_enc_ref.py (numpy), the kernels and libjpeg's default compress path
+ *   (jpeg_fdct_islow, no smoothing, the standard Huffman tables, optimize=False: what Pillow's Image.save writes) agree on every
+ *   byte of the file.  All shifts are arithmetic; DESCALE(x, n) = (x + (1 << (n-1))) >> n.
+ * Colour (SCALEBITS 16).  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) +
+ *   32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ * Edges and downsampling, in this order (the order shows in the last chroma block row of a height that is no multiple of 16):
+ *   1. the right column is replicated out to the MCU-padded width 8 hs mx;  2. the bottom row is replicated only up to a
+ *   multiple of vs;  3. chroma is downsampled: h2v2 (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... across OUTPUT columns,
+ *   h2v1 (a + b + bias) >> 1 with bias 0, 1, 0, 1, ...;  4. the last DOWNSAMPLED row is replicated to the MCU rows' height
+ *   8 my.  Luma is replicated in both directions.  (As one rule per sample: clamp the source column to W - 1; for chroma clamp
+ *   the downsampled row to ceil(H / vs) - 1 first, then each of its source rows to H - 1.)
+ * FDCT.  jpeg_fdct_islow of jpeg-6b (jfdctint.c, CONST_BITS 13, PASS1_BITS 2) on sample - 128: pass 1 along the rows, pass 2
+ *   down the columns.  One 1-D pass on d0..d7:
+ *     t0=d0+d7; t7=d0-d7; t1=d1+d6; t6=d1-d6; t2=d2+d5; t5=d2-d5; t3=d3+d4; t4=d3-d4
+ *     t10=t0+t3; t13=t0-t3; t11=t1+t2; t12=t1-t2
+ *     out0 = t10+t11, out4 = t10-t11:  << 2 in pass 1, DESCALE(., 2) in pass 2
+ *     z1=(t12+t13)*4433; out2 = z1+t13*6270; out6 = z1-t12*15137
+ *     z1=t4+t7; z2=t5+t6; z3=t4+t6; z4=t5+t7; z5=(z3+z4)*9633
+ *     t4*=2446; t5*=16819; t6*=25172; t7*=12299; z1*=-7373; z2*=-20995; z3=z3*-16069+z5; z4=z4*-3196+z5
+ *     out7 = t4+z1+z3; out5 = t5+z2+z4; out3 = t6+z2+z3; out1 = t7+z1+z4
+ *   with out1..3 and out5..7 DESCALEd by 11 in pass 1 and by 15 in pass 2.
+ *   32-bit evaluation.  libjpeg computes in `long`; the kernel in 32-bit two's complement.  As in j1 a pass is ring operations,
+ *   so an output before DESCALE is exact whenever its 64-bit value fits int32.  As a matrix a pass has rows whose |c_k| sum to
+ *   65536 (out0, out4), 59386, 60544, 59380, 59386, 60548 (out6: 4 * (10704 + 4433), the largest of the DESCALEd rows) and
+ *   59384; out0 and out4 are plain sums of eight inputs.  With every input of a pass at most PR_JPEG_FDCT_BOUND = 35467 in
+ *   magnitude, |out| + 2^14 <= 60548 * 35467 + 16384 = 2 147 472 300 < 2^31 (35468 would exceed it) and 8 * 35467 << 2 fits
+ *   easily: exact.  Every 8-bit image is inside: pass 1 reads |d| <= 128, so its results are at most 8 * 128 * 4 = 4096
+ *   (out0, out4) and (60548 * 128 + 1024) >> 11 = 3784 (the others); pass 2 reads those, 4096 <= 35467.  Its results, the
+ *   coefficients, are at most (8 * 4096 + 2) >> 2 = 8192 and (60548 * 4096 + 16384) >> 15 = 7569 in magnitude.  The kernel
+ *   therefore checks nothing at run time.
+ * Quantisation.  Tables from `quality` by libjpeg's formula: scale = 5000 / quality below 50, else 200 - 2 quality; entry =
+ *   (base * scale + 50) / 100 clamped to 1..255; base = Annex K (luminance for Y, chrominance for Cb and Cr).  With q8 = 8 *
+ *   entry (the FDCT leaves its results scaled by 8), |c| becomes (|c| + q8 / 2) / q8 and the sign is restored.  The kernel
+ *   multiplies by ceil(2^32 / q8) and keeps the high word: exact for |c| + q8 / 2 < 2^21 (the error of the product is below
+ *   x / 2^32 < 1 / q8), checked exhaustively for every magnitude up to 16384 and every divisor 8..2040 in
+ *   tests/test_jpeg_encode_native.py.
+ * Dummy blocks: those an MCU holds beyond the component's own ceil(size / 8) blocks (luma only, for these samplings).  Their
+ *   AC terms are zero and their DC term equals the DC term of the previous block in MCU order (a run of them copies one value
+ *   along), whether the block lies in the extra column or in the extra block rows.
+ * Entropy coding.  The standard's tables (Annex K.3; luma uses DC 0 / AC 0, chroma DC 1 / AC 1); the DC difference per
+ *   component, reset at every restart; runs of sixteen zeros as ZRL (0xF0) only in front of a non-zero term, EOB (0x00) when
+ *   the block ends in zeros, as jchuff.c's encode_one_block; a negative value v of n bits is sent as v - 1 in n bits.  Every
+ *   segment's last partial byte is filled with 1-bits; every 0xFF of the coded data, that byte included, is followed by 0x00;
+ *   RSTn between segments cycles 0..7.  A block takes at most PR_JPEG_ENC_BLOCK_BITS = 11 + 11 + 63 * (16 + 10) = 1660 bits
+ *   (the longest DC code and value; for each AC term the longest code and value).
+ * File.  SOI; APP0 JFIF 1.01, units 0, density 1 x 1; one DQT marker per table (0, then 1; 8-bit, zig-zag order); SOF0 with
+ *   component ids 1, 2, 3; one DHT marker per table (DC 0, AC 0, DC 1, AC 1); DRI when the interval is non-zero; SOS; the
+ *   data; EOI.
+ * Capacity.  pr_jpeg_encode_bound = the header + PR_JPEG_ENC_BLOCK_BITS / 4 bytes per block (every byte stuffed) + 4 bytes per
+ *   segment (a pad byte, its stuffing, a marker) + EOI: no file exceeds it.  A caller may give each frame a smaller slot:
+ *   a frame that does not fit gets nbytes[f] = 0 and status PR_JPEG_ENC_ST_OVERFLOW and NOTHING is written to its slot; a
+ *   frame writes exactly nbytes[f] bytes from the start of its slot, never another frame's. */
+#define PR_JPEG_FDCT_BOUND 35467
+#define PR_JPEG_ENC_BLOCK_BITS 1660
+#define PR_JPEG_ENC_HEADER_MAX 640
+enum { PR_JPEG_ENC_ST_OVERFLOW = 1 }; /* bits of pr_jpeg_encode's status[f] */
+typedef struct pr_jpeg_enc_plan { /* what one (quality, sampling, restart interval, size) needs; uploaded unchanged */
+  int32_t width, height, hs, vs;
+  int32_t restart_interval;          /* resolved: MCUs per segment, 0 = none */
+  int32_t quality, header_bytes, reserved;
+  uint16_t quant[2][64];             /* natural order: luma, chroma */
+  uint32_t recip[2][64];             /* ceil(2^32 / (8 quant)) */
+  uint16_t dc_code[2][16], ac_code[2][256]; /* per symbol; length 0 = the table has no such symbol */
+  uint8_t dc_len[2][16], ac_len[2][256];
+  uint8_t header[PR_JPEG_ENC_HEADER_MAX];   /* SOI .. SOS, header_bytes of them */
+} pr_jpeg_enc_plan;
+
+/* Fills *plan_host.  PR_ERR_INVALID by name for quality outside 1..100, a sampling other than 1x1, 2x1, 2x2, a size outside
+ * 16..4096, restart_interval < -1 or a null pointer.  No device call. */
+int pr_jpeg_encode_plan(int quality, int hs, int vs, int restart_interval, int H, int W, pr_jpeg_enc_plan* plan_host);
+/* A size no file of these parameters exceeds (0 for invalid ones). */
+size_t pr_jpeg_encode_bound(int H, int W, int hs, int vs, int restart_interval);
+/* Device memory pr_jpeg_encode needs for F frames with `capacity` bytes a slot (0 for invalid parameters). */
+size_t pr_jpeg_encode_workspace_bytes(int F, int H, int W, int hs, int vs, int restart_interval, int64_t capacity);
+
+/* All device pointers: frames u8[F,H,W,3], plan (one pr_jpeg_enc_plan, uploaded), out u8[F,capacity], nbytes int32[F], status
+ * int32[F] (bits PR_JPEG_ENC_ST_*).  H, W, hs, vs, restart_interval as given to pr_jpeg_encode_plan (the host cannot read the
+ * plan; the kernels take the tables and the header from it and the geometry from here).  Each slot receives the whole file,
+ * header and EOI included.  The workspace must be 16-byte aligned.  Argument errors (null pointers, sizes or sampling outside
+ * the accepted ones, capacity < 0 or above 2^31 - 1, a workspace below pr_jpeg_encode_workspace_bytes or misaligned) return
+ * PR_ERR_INVALID by name before any device work; F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no blocking
+ * copy, no synchronisation (capturable). */
+typedef struct pr_jpeg_enc_args {
+  const uint8_t* frames;
+  const pr_jpeg_enc_plan* plan;
+  uint8_t* out;
+  int32_t* nbytes;
+  int32_t* status;
+  int64_t capacity;
+  int F, H, W;
+  int hs, vs, restart_interval;
+  int bgr;
+} pr_jpeg_enc_args;
+int pr_jpeg_encode(const pr_jpeg_enc_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,12 @@ class JpegArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "n_segments", "n_huff", "bgr")]
 
 
+class JpegEncArgs(C.Structure):
+    """pr_jpeg_enc_args (include/poserisk_hip.h, the JPEG encoder)."""
+    _fields_ = [(n, C.c_void_p) for n in ("frames", "plan", "out", "nbytes", "status")] + [("capacity", C.c_int64)] + \
+               [(n, C.c_int) for n in ("F", "H", "W", "hs", "vs", "restart_interval", "bgr")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -106,6 +112,10 @@ SIGNATURES = {
     "pr_jpeg_refusal_name": (C.c_char_p, [_I]),
     "pr_jpeg_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pr_jpeg_decode": (_I, [C.POINTER(JpegArgs), _P, C.c_size_t, _P]),
+    "pr_jpeg_encode_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "pr_jpeg_encode_bound": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "pr_jpeg_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, C.c_int64]),
+    "pr_jpeg_encode": (_I, [C.POINTER(JpegEncArgs), _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -1,11 +1,14 @@
 // Host half of the JPEG decoder (include/poserisk_hip.h, section j1): marker parsing, validation and the per-frame
-// descriptors pr_jpeg_decode's kernels read.  Nothing is decoded here.  Device-free: compiled into libposerisk_hip.so by
+// descriptors pr_jpeg_decode's kernels read.  Nothing is decoded here.  Behind it, the encoder's host half (section j2):
+// pr_jpeg_encode_plan derives the tables and the header bytes pr_jpeg_encode's kernels read, pr_jpeg_encode_bound the size no
+// file exceeds.  Device-free: compiled into libposerisk_hip.so by
 // hipcc as plain C++ and, for tests/native/jpeg_parse_check.cc, by g++ with -fsanitize=address,undefined.  No HIP header may be
 // included here.  Every read goes through Reader, which knows the file's end: a stream cut or corrupted anywhere ends in a
 // refusal or in descriptors whose ranges lie inside the file.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "host_common.h"
@@ -349,5 +352,123 @@ extern "C" int pr_jpeg_parse(const uint8_t* data, const int64_t* offsets, int F,
               segment_capacity, huff_capacity);
     return PR_ERR_CAPACITY;
   }
+  return PR_OK;
+}
+
+// ---- the encoder's host half (include/poserisk_hip.h, section j2) ------------------------------------------------------------
+namespace pr {
+namespace {
+
+// Annex K.1, natural order
+const uint8_t kBaseQuant[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+     100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+// Annex K.3: code counts per length 1..16, then the symbols in code order
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+const uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+
+// MCUs per restart segment as libjpeg keeps it (0 = none), or -2 for parameters the encoder does not accept
+int enc_restart(int H, int W, int hs, int vs, int restart_interval) {
+  const bool sampling = (hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2);
+  if (!sampling || H < 16 || W < 16 || H > 4096 || W > 4096 || restart_interval < -1) return -2;
+  const int ri = restart_interval < 0 ? (W + 8 * hs - 1) / (8 * hs) : restart_interval;
+  return std::min(ri, 65535);
+}
+
+void enc_codes(const uint8_t* bits, const uint8_t* vals, uint16_t* code_of, uint8_t* len_of) {
+  int code = 0, k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    for (int i = 0; i < bits[l - 1]; ++i, ++code, ++k) {
+      code_of[vals[k]] = (uint16_t)code;
+      len_of[vals[k]] = (uint8_t)l;
+    }
+    code <<= 1;
+  }
+}
+
+}  // namespace
+
+// ceil(2^32 / q8) for q8 = 8..2040: the multiplier pr_jpeg_encode's quantiser uses in place of the division
+uint32_t enc_recip(uint32_t q8) { return (uint32_t)(((1ull << 32) + q8 - 1) / q8); }
+
+}  // namespace pr
+
+extern "C" size_t pr_jpeg_encode_bound(int H, int W, int hs, int vs, int restart_interval) {
+  const int ri = pr::enc_restart(H, W, hs, vs, restart_interval);
+  if (ri < 0) return 0;
+  const size_t mcus = (size_t)((W + 8 * hs - 1) / (8 * hs)) * (size_t)((H + 8 * vs - 1) / (8 * vs));
+  const size_t segs = ri ? (mcus + ri - 1) / ri : 1;
+  const size_t head = 623 + (ri ? 6 : 0);
+  return head + mcus * (hs * vs + 2) * PR_JPEG_ENC_BLOCK_BITS / 4 + 4 * segs + 2;
+}
+
+extern "C" int pr_jpeg_encode_plan(int quality, int hs, int vs, int restart_interval, int H, int W, pr_jpeg_enc_plan* plan) {
+  using namespace pr;
+  PR_REQUIRE(plan, "pr_jpeg_encode_plan: null plan_host");
+  PR_REQUIRE(quality >= 1 && quality <= 100, "pr_jpeg_encode_plan: quality = %d outside 1..100", quality);
+  const int ri = enc_restart(H, W, hs, vs, restart_interval);
+  PR_REQUIRE(ri >= 0,
+             "pr_jpeg_encode_plan: %d x %d frames, sampling %d x %d, restart interval %d: sizes are 16..4096, sampling 1x1, 2x1 or "
+             "2x2, the interval -1, 0 or a count of MCUs", W, H, hs, vs, restart_interval);
+  memset(plan, 0, sizeof *plan);
+  plan->width = W;
+  plan->height = H;
+  plan->hs = hs;
+  plan->vs = vs;
+  plan->restart_interval = ri;
+  plan->quality = quality;
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  for (int t = 0; t < 2; ++t) {
+    for (int i = 0; i < 64; ++i) {
+      const int q = std::min(255, std::max(1, (kBaseQuant[t][i] * scale + 50) / 100));
+      plan->quant[t][i] = (uint16_t)q;
+      plan->recip[t][i] = enc_recip(8u * q);
+    }
+    enc_codes(kDcBits[t], kDcVals, plan->dc_code[t], plan->dc_len[t]);
+    enc_codes(kAcBits[t], kAcVals[t], plan->ac_code[t], plan->ac_len[t]);
+  }
+  uint8_t* h = plan->header;
+  int n = 0;
+  auto put = [&](std::initializer_list<int> bytes) {
+    for (int b : bytes) h[n++] = (uint8_t)b;
+  };
+  put({0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+  for (int t = 0; t < 2; ++t) {
+    put({0xFF, 0xDB, 0, 67, t});
+    for (int i = 0; i < 64; ++i) h[n++] = (uint8_t)plan->quant[t][kZigzag[i]];
+  }
+  put({0xFF, 0xC0, 0, 17, 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, hs << 4 | vs, 0, 2, 0x11, 1, 3, 0x11, 1});
+  for (int t = 0; t < 2; ++t) {
+    put({0xFF, 0xC4, 0, 2 + 1 + 16 + 12, t});
+    for (int i = 0; i < 16; ++i) h[n++] = kDcBits[t][i];
+    for (int i = 0; i < 12; ++i) h[n++] = kDcVals[i];
+    put({0xFF, 0xC4, 0, 2 + 1 + 16 + 162, 0x10 | t});
+    for (int i = 0; i < 16; ++i) h[n++] = kAcBits[t][i];
+    for (int i = 0; i < 162; ++i) h[n++] = kAcVals[t][i];
+  }
+  if (ri) put({0xFF, 0xDD, 0, 4, ri >> 8, ri & 255});
+  put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+  plan->header_bytes = n;
   return PR_OK;
 }

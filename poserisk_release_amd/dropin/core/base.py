@@ -140,6 +140,14 @@ class Predictor:
         # the annotated score video composed on the GPU (write_gpu_video): args.gpu_video, else cfg.DATASET.gpu_video (False)
         knob = getattr(args, 'gpu_video', None)
         self.gpu_video = bool(knob if knob is not None else cfg.DATASET.get('gpu_video', False))
+        # how write_gpu_video and the mesh writer store their frames: args.video_codec, else cfg.DATASET.gpu_video_codec.  ''
+        # (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded on the GPU
+        # (jpeg.encode_frames) into <TITLE>_video.avi / <TITLE>_mesh.avi (mjpeg.AviWriter), with or without cv2
+        knob = getattr(args, 'video_codec', None)
+        self.gpu_video_codec = str(knob if knob is not None else cfg.DATASET.get('gpu_video_codec', '') or '')
+        if self.gpu_video_codec not in ('', 'mjpeg'):
+            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames) or 'mjpeg'")
+        self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
             self.debug_joints = None
@@ -379,10 +387,36 @@ class Predictor:
                                  face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
             yield fidx[i:j], img
 
+    def _mjpeg_writer(self, path, width, height, fps, bgr):
+        """-> (write(images u8[b,H,W,3] CUDA), close() -> path): the images encoded to baseline JPEG on the GPU at
+        gpu_video_quality (4:2:0, a restart marker per MCU row) and stored as Motion-JPEG in `path`: only the files' bytes
+        leave the device.  A frame that overflows its default slot is encoded again with the slot no file exceeds.  close()
+        returns `path`, the first file; past 1 GiB the frames continue in <name>.001.avi, ... beside it (mjpeg.AviWriter)."""
+        from poserisk_release_amd import jpeg, mjpeg
+        avi = mjpeg.AviWriter(path, width, height, fps)
+
+        def write(images):
+            images = images.contiguous()
+            buf, nbytes, status = jpeg.encode_frames(images, quality=self.gpu_video_quality, bgr=bgr)
+            files = jpeg.download_files(buf, nbytes)
+            for i in np.nonzero(status.cpu().numpy())[0]:
+                cap = jpeg.encode_bound(height, width)
+                buf1, nbytes1, status1 = jpeg.encode_frames(images[i:i + 1], quality=self.gpu_video_quality, bgr=bgr, capacity=cap)
+                if int(status1[0]):
+                    raise RuntimeError(f"jpeg.encode_frames: status {int(status1[0])} for a frame with the largest slot")
+                files[i] = jpeg.download_files(buf1, nbytes1)[0]
+            for data in files:
+                avi.write(data)
+        return write, lambda: (avi.close(), path)[1]
+
     def _mesh_writer(self, frames, output_path, title, bgr, fps):
         """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): <output>/<TITLE>_mesh.mp4 where cv2 is importable,
-        else <output>/<TITLE>_mesh/%09d.png (frame number)."""
+        else <output>/<TITLE>_mesh/%09d.png (frame number); with gpu_video_codec 'mjpeg' <output>/<TITLE>_mesh.avi either way."""
         import os
+        if self.gpu_video_codec == 'mjpeg':
+            put, close = self._mjpeg_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh.avi"),
+                                            int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
+            return (lambda fr, img: put(img)), close
         try:
             import cv2
         except ImportError:
@@ -409,15 +443,19 @@ class Predictor:
         """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
         frame.  Returns the path written."""
         write, close = self._mesh_writer(frames, output_path, title, bgr, fps)
-        for fr, img in self.render_overlay(out, frames, title, bgr):
-            write(fr, img)
-        return close()
+        try:
+            for fr, img in self.render_overlay(out, frames, title, bgr):
+                write(fr, img)
+        finally:
+            path = close()
+        return path
 
     # ---- base.py:284-327 on the GPU (the gpu_video knob) ---------------------------------------------------------
     def write_gpu_video(self, out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
         """`<TITLE>_video`: every frame of the video at 720 px wide with the target's box, beside the score panel, composed by
         poserisk_release_amd.video (pr_compose_video) from the arrays score_frames returned.  <output>/<TITLE>_video.mp4 where
-        cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame.  With
+        cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame; with
+        gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there.  With
         the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
         parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
         that the mesh output is written from the same rendering.  Returns the path written."""
@@ -446,6 +484,14 @@ class Predictor:
                     mesh_sink(numbers, images)
                 return numbers, images
         batches = video.annotated_frames(frames, draw, self.batch_size, overlay=overlay)
+        if self.gpu_video_codec == 'mjpeg':
+            put, close = self._mjpeg_writer(osp.join(output_path, title + '_video.avi'), resize_w + panel_w, canvas_h, fps, bgr)
+            try:
+                for canvases in batches:
+                    put(canvases)
+            finally:                                # also when encoding raises: the index is written, the headers patched
+                path = close()
+            return path
         try:
             import cv2
         except ImportError:
@@ -642,8 +688,10 @@ class Predictor:
             if getattr(self, 'visualize', True) and self.gpu_video:            # base.py:156,173 on the GPU
                 if self.render_mesh:                # one rendering of the mesh feeds both outputs
                     sink, close = self._mesh_writer(frames, output_path, title, bgr, fps)
-                    self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=sink)
-                    close()
+                    try:
+                        self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=sink)
+                    finally:
+                        close()
                     mesh_written = True
                 else:
                     self.write_gpu_video(out, frames, output_path, title, bgr, fps)

@@ -24,6 +24,10 @@ absent from the reference and all optional:
     cfg.DATASET.gpu_video     False | True: Predictor.__call__ composes <TITLE>_video on the GPU (pr_compose_video) instead of
                               drawing it with OpenCV (<TITLE>_video.mp4, or <TITLE>_video/%09d.png without cv2;
                               args.gpu_video overrides it)
+    cfg.DATASET.gpu_video_codec  '' (default: the two outputs above as they are) | 'mjpeg': <TITLE>_video.avi and <TITLE>_mesh.avi,
+                              baseline JPEG frames encoded on the GPU (pr_jpeg_encode) in a Motion-JPEG AVI written in Python,
+                              with or without cv2 (args.video_codec overrides it); any other name raises
+    cfg.DATASET.gpu_video_quality  the JPEG quality of those frames, 1..100 (90)
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -83,7 +87,7 @@ def _defaults(root):
         'DATASET': {'workers': 16, 'batch_size': 8, 'min_frame_ratio': 0.33, 'bbox_scale': 1.2,
                     'default_information': osp.join(core_dir, 'default_information.json'),
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
-                    'render_mesh': False, 'gpu_video': False},
+                    'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

@@ -4,7 +4,11 @@ lib/core/base.py:47-56, read back by CropDataset with cv2.imread).  The contract
 the marker parser is csrc/jpeg_host.cc (host, no device), everything else csrc/jpeg.hip.
 
 `list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
-go through ONE pinned buffer and ONE upload, then pr_jpeg_decode."""
+go through ONE pinned buffer and ONE upload, then pr_jpeg_decode.
+
+The inverse direction (section j2; csrc/jpeg_enc.hip): `encode_frames` turns u8 frames on the device into complete baseline
+JPEG files in per-frame slots, byte for byte what libjpeg writes with the standard tables; `download_files` brings only the
+used bytes to the host."""
 import ctypes as C
 import os
 
@@ -32,6 +36,13 @@ _ST_NAMES = ((ST_REFUSED, "refused (descriptor or segment range invalid)"), (ST_
 # measured list and nothing overlaps), far above the CPU either way: the restart-free case decides.  Workspace 3.3 MB a frame.
 DEFAULT_CHUNK = 1024
 _EXT = (".jpg", ".jpeg")
+# pr_jpeg_enc_plan as a numpy record
+ENC_PLAN_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("restart_interval", "<i4"),
+                           ("quality", "<i4"), ("header_bytes", "<i4"), ("reserved", "<i4"), ("quant", "<u2", (2, 64)),
+                           ("recip", "<u4", (2, 64)), ("dc_code", "<u2", (2, 16)), ("ac_code", "<u2", (2, 256)),
+                           ("dc_len", "u1", (2, 16)), ("ac_len", "u1", (2, 256)), ("header", "u1", (640,))])
+ENC_ST_OVERFLOW = 1
+SUBSAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
 
 
 def status_text(st):
@@ -209,3 +220,115 @@ def bad_frames(paths_or_bytes, status):
             why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
         out.append((int(i), why))
     return out
+
+
+def encode_plan(quality, subsampling, restart_interval, H, W):
+    """The encoder's host half: the pr_jpeg_enc_plan of these parameters as an ENC_PLAN_DTYPE record (tables, header bytes)."""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling {subsampling!r}: one of {sorted(SUBSAMPLING)}")
+    hs, vs = SUBSAMPLING[subsampling]
+    plan = np.zeros(1, ENC_PLAN_DTYPE)
+    _lib.check(_lib.load().pr_jpeg_encode_plan(int(quality), hs, vs, int(restart_interval), int(H), int(W),
+                                               plan.ctypes.data_as(C.c_void_p)), "pr_jpeg_encode_plan")
+    return plan[0]
+
+
+def encode_bound(H, W, subsampling="4:2:0", restart_interval=-1):
+    """A size in bytes that no file of these parameters exceeds.  It depends on the sampling and the restart interval: pass the
+    ones the encode_frames call uses (restart_rows=1 is interval -1, restart_rows=0 is 0)."""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling {subsampling!r}: one of {sorted(SUBSAMPLING)}")
+    hs, vs = SUBSAMPLING[subsampling]
+    return int(_lib.load().pr_jpeg_encode_bound(int(H), int(W), hs, vs, int(restart_interval)))
+
+
+_plans = {}
+
+
+def _device_plan(key, device):
+    """The uploaded plan of (quality, subsampling, restart interval, H, W) on `device`: made once, kept.  The first call of a
+    parameter set copies the plan from pageable host memory and waits for the copy, so that every stream, then and later, finds
+    the plan complete; every further call only looks it up."""
+    plan = _plans.get((key, device))
+    if plan is None:
+        host = torch.from_numpy(np.frombuffer(encode_plan(*key).tobytes(), np.uint8).copy())
+        plan = host.to(device)
+        torch.cuda.current_stream(device).synchronize()
+        _plans[(key, device)] = plan
+    return plan
+
+
+def encode_frames(frames, quality=90, subsampling="4:2:0", restart_rows=1, bgr=False, capacity=None, out=None, workspace=None):
+    """Encode u8[F,H,W,3] frames on the GPU (RGB, or BGR with bgr=True) to F baseline JPEG files: returns (buffer u8[F,cap],
+    nbytes int32[F], status int32[F]), all on the device; file f is buffer[f, :nbytes[f]], header and EOI included.
+    restart_rows=1 writes a restart marker per MCU row (the streams this package's decoder is fast on), 0 none.  `capacity` is
+    the slot size per frame; None takes min(encode_bound, 4096 + H * W * 3 // 2), which photographs and rendered canvases stay
+    far below at any quality.  A frame that does not fit has nbytes 0 and status ENC_ST_OVERFLOW and its slot is untouched:
+    encode it again with capacity=encode_bound(H, W, subsampling, -1 if restart_rows else 0).  `out` = (buffer, nbytes, status)
+    to write into caller-owned tensors; `workspace` = a u8 device tensor of at least encode_workspace_bytes(...) to reuse across
+    calls on one stream (None allocates one per call).  Asynchronous on the current stream.  The first call of a parameter set
+    on a device uploads its plan and waits for that copy (_device_plan); every later call synchronises nothing, and with `out`
+    and `workspace` given allocates nothing either, so it can be captured into a graph."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise _lib.PoseRiskHipError("encode_frames: the encoder runs on the GPU only (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError(f"encode_frames: frames must be a contiguous uint8 [F, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if restart_rows not in (0, 1):
+        raise ValueError(f"encode_frames: restart_rows = {restart_rows!r}: 1 (a marker per MCU row) or 0 (none)")
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling {subsampling!r}: one of {sorted(SUBSAMPLING)}")
+    device, (F, H, W, _) = frames.device, frames.shape
+    hs, vs = SUBSAMPLING[subsampling]
+    ri = -1 if restart_rows else 0
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        plan = _device_plan((int(quality), subsampling, ri, H, W), device)
+        if capacity is None:
+            capacity = min(encode_bound(H, W, subsampling, ri), 4096 + H * W * 3 // 2)
+        capacity = int(capacity)
+        if out is None:
+            out = (torch.empty((F, capacity), dtype=torch.uint8, device=device), torch.empty(F, dtype=torch.int32, device=device),
+                   torch.empty(F, dtype=torch.int32, device=device))
+        buf, nbytes, status = out
+        for t, shape, dtype in ((buf, (F, capacity), torch.uint8), (nbytes, (F,), torch.int32), (status, (F,), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != device:
+                raise ValueError(f"encode_frames: out must hold contiguous tensors {[F, capacity]} uint8, {[F]} int32, {[F]} int32 on {device}")
+        if F == 0:
+            return buf, nbytes, status
+        need = int(lib.pr_jpeg_encode_workspace_bytes(F, H, W, hs, vs, ri, capacity))
+        if need == 0:
+            raise _lib.PoseRiskHipError(f"encode_frames: {F} frames of {W}x{H} with capacity {capacity} are outside what the encoder "
+                                        "accepts (sizes 16..4096, at most 65535 frames a call, capacity below 2^31)")
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+        elif ws.dtype != torch.uint8 or ws.device != device or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() & 15:
+            raise ValueError(f"encode_frames: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {need} bytes on {device}")
+        stream = torch.cuda.current_stream(device)
+        args = _lib.JpegEncArgs(frames.data_ptr(), plan.data_ptr(), buf.data_ptr(), nbytes.data_ptr(), status.data_ptr(), capacity,
+                                F, H, W, hs, vs, ri, int(bool(bgr)))
+        _lib.check(lib.pr_jpeg_encode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_encode")
+        ws.record_stream(stream)
+    return buf, nbytes, status
+
+
+def encode_workspace_bytes(F, H, W, subsampling="4:2:0", restart_rows=1, capacity=None):
+    """The size of the `workspace` an encode_frames call of these parameters needs (capacity None: the default slot)."""
+    if subsampling not in SUBSAMPLING:
+        raise ValueError(f"subsampling {subsampling!r}: one of {sorted(SUBSAMPLING)}")
+    hs, vs = SUBSAMPLING[subsampling]
+    ri = -1 if restart_rows else 0
+    if capacity is None:
+        capacity = min(encode_bound(H, W, subsampling, ri), 4096 + H * W * 3 // 2)
+    return int(_lib.load().pr_jpeg_encode_workspace_bytes(int(F), int(H), int(W), hs, vs, ri, int(capacity)))
+
+
+def download_files(buffer, nbytes):
+    """[bytes] of an encode_frames result; only the used bytes cross to the host: the sizes first (one small copy), then the
+    slices buffer[f, :nbytes[f]] packed into one device tensor and copied once."""
+    n = nbytes.cpu().numpy().astype(np.int64)
+    if n.size == 0:
+        return []
+    packed = torch.cat([buffer[f, :k] for f, k in enumerate(n.tolist())]).cpu().numpy().tobytes()
+    ends = np.cumsum(n)
+    return [packed[e - k:e] for e, k in zip(ends, n)]
