@@ -765,6 +765,53 @@ typedef struct pr_jpeg_enc_args {
 } pr_jpeg_enc_args;
 int pr_jpeg_encode(const pr_jpeg_enc_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j3  u8[F,H,W,3] -> u8[F,h,w,3] on the device: the front end's bilinear downscale       */
+/* replaces: cv2.resize in get_images lib/utils/funcs_utils.py:18-53 (width > 800 -> 800   */
+/*           wide, elif height > 450 -> 450 high) in front of the tracker and the crops    */
+/* ------------------------------------------------------------------------------------ */
+/* The host half (pr_resize_plan, csrc/resize_host.cc, no device) makes the per-axis tap tables; the device half
+ * (pr_resize_frames, csrc/resize.hip) applies them.  No ABI bump: functions were added.
+ *
+ * Arithmetic contract.  This project's own, integer-defined and modelled on the 8-bit path of OpenCV's INTER_LINEAR
+ *   (fixed-point weights of 2048, a horizontal pass into int32, a vertical pass with two truncating shifts).  OpenCV is not
+ *   available where this project is built and tested, so its bits are NOT promised; what is promised is the following, which
+ *   tests/resize_ref.py restates in numpy and which stays strictly within one level of the float64 bilinear at the same sample
+ *   positions (tests/test_frontend_cpu.py).  The three channels are treated alike: there is no bgr argument.
+ * Taps.  For each axis with source size S and destination size d: scale = 1.0 / ((double)d / S); for i in [0, d):
+ *     f = (float)((i + 0.5) * scale - 0.5)      the product and the difference in double, rounded to float once
+ *     s = floor(f);  f -= s                     in float
+ *     if s < 0:       s = 0,     f = 0
+ *     if s >= S - 1:  s = S - 1, f = 0
+ *     c0 = rne((1.f - f) * 2048.f),  c1 = rne(f * 2048.f)      int16, round to nearest even
+ *   ofs[i] = s, coef[2 i] = c0, coef[2 i + 1] = c1; the second tap is min(s + 1, S - 1).  0 <= c0, c1 <= 2048.
+ * Passes.  With a0, a1 the weights of the destination column and b0, b1 those of the destination row, S0 and S1 the two
+ *   source samples of a row at the column's taps:
+ *     horizontal   T = S0 * a0 + S1 * a1                                              int32, at most 255 * 2049
+ *     vertical     D = (((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2   stored as u8
+ *   T0, T1 are the horizontal results of the destination row's two source rows.  Every term is non-negative and D <= 255
+ *   (2049 * (255 * 2049 >> 4) >> 16 = 1020), so nothing is clamped.
+ * Exactly half in both axes (W == 2 w and H == 2 h; PR_RESIZE_HALF): D = (s00 + s01 + s10 + s11 + 2) >> 2 over the 2 x 2
+ *   source samples of the destination sample.  (W == 2 w alone does not take this rule.)
+ * Same size (PR_RESIZE_COPY): a copy. */
+#define PR_RESIZE_MAX_SIDE 4096
+enum { PR_RESIZE_COPY = 0, PR_RESIZE_HALF = 1, PR_RESIZE_LINEAR = 2 }; /* pr_resize_plan's *mode_host */
+
+/* Fills xofs_host int32[w], xcoef_host int16[2 w], yofs_host int32[h], ycoef_host int16[2 h] (in every mode) and *mode_host.
+ * PR_ERR_INVALID by name for a side outside 1..PR_RESIZE_MAX_SIDE or a null pointer, before anything is written.  No device
+ * call. */
+int pr_resize_plan(int H, int W, int h, int w, int32_t* xofs_host, int16_t* xcoef_host, int32_t* yofs_host, int16_t* ycoef_host,
+                   int32_t* mode_host);
+
+/* All device pointers: src u8[F,H,W,3], dst u8[F,h,w,3] (any alignment: the call's output is written in aligned dwords, with
+ * byte stores only for the up to three bytes at either end), the four tables as pr_resize_plan filled them, uploaded unchanged
+ * (xofs and yofs 4-byte, xcoef and ycoef 2-byte aligned), mode as it gave it.  Reads only src and the tables (table offsets are
+ * clamped to the source on the device), writes every byte of dst and nothing else.  Argument errors (null pointers, a side
+ * outside 1..PR_RESIZE_MAX_SIDE, a mode that is not the one of these sizes, F < 0) return PR_ERR_INVALID by name before any
+ * device work; F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no copy, no synchronisation (capturable). */
+int pr_resize_frames(const uint8_t* src, int F, int H, int W, uint8_t* dst, int h, int w, const int32_t* xofs,
+                     const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

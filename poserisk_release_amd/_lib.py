@@ -116,6 +116,8 @@ SIGNATURES = {
     "pr_jpeg_encode_bound": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_jpeg_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, C.c_int64]),
     "pr_jpeg_encode": (_I, [C.POINTER(JpegEncArgs), _P, C.c_size_t, _P]),
+    "pr_resize_plan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "pr_resize_frames": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

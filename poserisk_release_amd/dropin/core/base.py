@@ -8,9 +8,10 @@
 `get_pose_estimation_results` is the reference's loop (base.py:211-240) with the per-frame Python
 removed: every batch is one `pr_frames_forward` call on the GPU, results stay on the device until the
 end of the loop, and with `torch.distributed` initialised every rank takes a contiguous frame shard and
-the per-frame records are all-gathered once.  Video decoding and tracking (base.py:47-74) are outside the
-accelerated path: `__call__` takes decoded frames + the tracker's dict, finds them in a
-directory, or runs the reference's own front end when cv2 and multi_person_tracker are importable; it writes the
+the per-frame records are all-gathered once.  Tracking and the decoding of videos other than Motion-JPEG AVI
+(base.py:47-74) are outside the accelerated path: `__call__` takes decoded frames + the tracker's
+dict, finds them in a directory, reads a Motion-JPEG AVI on the GPU (poserisk_release_amd/frontend.py), or runs the
+reference's own front end when cv2 and multi_person_tracker are importable; it writes the
 result text files, the score plots, the debug CSVs and the annotated video (drawn by OpenCV where cv2 is importable, or
 composed on the GPU with the gpu_video knob).
 """
@@ -527,7 +528,7 @@ class Predictor:
                                    frame=self.debug_frame)
 
     # ---- main/run.py:31  predictor(args.input, args.info, args.output) -----------------------------------
-    def load_front_end(self, input_path, output_path):
+    def load_front_end(self, input_path, output_path, tracking_results=None):
         """Decoded frames + tracker output for `input_path` -> (frames u8[F,H,W,3], bgr, fps, tracking dict).
 
         Video decoding and multi-person tracking are outside the accelerated path; this only finds them:
@@ -538,7 +539,14 @@ class Predictor:
              optional `fps.txt`: the files are decoded on the GPU, bit-exact with cv2.imread's pixels
              (poserisk_release_amd/jpeg.py), and the frames come back as a device tensor, RGB.  A frame that is not
              baseline JPEG, has another size than the first or is damaged raises, naming the file and the reason;
-          3. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
+          3. a Motion-JPEG AVI file (a camera's, `ffmpeg -c:v mjpeg`'s, this package's own <TITLE>_video.avi): demuxed in
+             Python, decoded and downscaled on the GPU by the reference's rule (poserisk_release_amd/frontend.py;
+             cfg.DATASET.front_max_w / front_max_h), no OpenCV anywhere.  Its tracking is, in this order, the
+             `tracking_results` given to __call__, `<stem>.tracking.pkl` beside the video (boxes in the downscaled frames'
+             coordinates), or multi_person_tracker where importable, run on a folder of JPEGs encoded on the GPU; the frames
+             are then the pixels decoded back from those files, as the reference's CropDataset would read them.  An AVI of
+             another codec, or a damaged one, goes on to 4;
+          4. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
              frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
              written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
              the same JPEG-decoded pixels as the reference's CropDataset."""
@@ -565,6 +573,16 @@ class Predictor:
                 fps_file = osp.join(input_path, 'fps.txt')
                 fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
                 return frames, False, fps, tracking
+        not_mjpeg = None
+        if osp.isfile(input_path):
+            from poserisk_release_amd import mjpeg
+            if mjpeg.is_avi(input_path):
+                try:
+                    reader = mjpeg.AviReader(input_path)
+                except ValueError as e:
+                    not_mjpeg = e                              # an AVI, but not one to read here: cv2 may still open it
+                else:
+                    return self._avi_front_end(reader, input_path, output_path, tracking_results)
         try:
             import cv2
             from multi_person_tracker import MPT
@@ -573,7 +591,8 @@ class Predictor:
                 f"{input_path!r} is neither a directory with frames.npy + tracking.pkl nor one with JPEG frames "
                 f"(*.jpg, decoded on the GPU) + tracking.pkl, and the reference's front end "
                 f"(cv2 video decoding, multi_person_tracker) is not importable here ({e}); decode and track outside, "
-                "then call Predictor.score_frames(frames, tracking_results, info)") from e
+                "then call Predictor.score_frames(frames, tracking_results, info)"
+                + (f" [as a Motion-JPEG AVI it was refused: {not_mjpeg}]" if not_mjpeg is not None else "")) from e
         import os
         import shutil
         image_path = osp.join(output_path, 'tmp')
@@ -601,7 +620,44 @@ class Predictor:
         shutil.rmtree(image_path, ignore_errors=True)
         return frames, True, fps, tracking
 
-    def _front_end_on_rank0(self, input_path, output_path, world, rank):
+    def _avi_front_end(self, reader, input_path, output_path, tracking_results=None):
+        """load_front_end's case 3: `reader` is the mjpeg.AviReader of `input_path`."""
+        import pickle
+        import shutil
+        from poserisk_release_amd import frontend, jpeg
+        frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
+                                          max_h=cfg.DATASET.get('front_max_h', 450))
+        if tracking_results is not None:
+            return frames, False, fps, tracking_results
+        sidecar = osp.splitext(input_path)[0] + '.tracking.pkl'
+        if osp.isfile(sidecar):
+            with open(sidecar, 'rb') as f:
+                return frames, False, fps, pickle.load(f)
+        try:
+            from multi_person_tracker import MPT
+        except ImportError as e:
+            raise RuntimeError(
+                f"{input_path!r}: {frames.shape[0]} frames of {frames.shape[2]} x {frames.shape[1]} were decoded, but there is no "
+                f"tracking for them: {sidecar!r} (multi_person_tracker's dict, boxes in the downscaled frames' coordinates) does not "
+                f"exist, no tracking_results were given and multi_person_tracker is not importable here ({e}).  Write the frames for "
+                f"a tracker with `python -m poserisk_release_amd.frontend prepare {input_path} <dir>`, add its tracking.pkl to <dir> "
+                "and pass <dir>") from e
+        image_path = osp.join(output_path, 'tmp')
+        shutil.rmtree(image_path, ignore_errors=True)
+        try:
+            files = frontend.write_frame_folder(frames, image_path, quality=95)      # cv2.imwrite's default quality
+            tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
+                          output_format='dict', yolo_img_size=416)
+            tracking = tracker(image_path)
+            frames, status = jpeg.decode_files(files, self.device)
+            bad = jpeg.bad_frames(files, status)
+            if bad:
+                raise RuntimeError(f"{image_path!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")
+        finally:
+            shutil.rmtree(image_path, ignore_errors=True)
+        return frames, False, fps, tracking
+
+    def _front_end_on_rank0(self, input_path, output_path, world, rank, **given):
         """Several ranks (one per GPU): the front end writes, runs the tracker in and deletes <output>/tmp, so it runs on
         rank 0 ONLY and its output is broadcast -- every rank then shards the SAME track (a tracker run per rank may select
         different tracks; one rank's rmtree would delete JPEGs another rank is still reading).  The metadata goes as one
@@ -611,7 +667,7 @@ class Predictor:
         frames = None
         if rank == 0:
             try:
-                frames, bgr, fps, tracking = self.load_front_end(input_path, output_path)
+                frames, bgr, fps, tracking = self.load_front_end(input_path, output_path, **given)
                 # a device tensor (the JPEG folder case) stays where it is; arrays become one contiguous host tensor
                 frames = frames.contiguous() if isinstance(frames, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(frames))
                 meta = [dict(shape=tuple(frames.shape), bgr=bool(bgr), fps=float(fps), tracking=tracking)]
@@ -641,10 +697,13 @@ class Predictor:
         os.makedirs(output_path, exist_ok=True)
         world, rank = pl.world_and_rank()
         if frames is None or tracking_results is None:
+            # tracking given without frames: a Motion-JPEG AVI input takes it (load_front_end, case 3); every other input
+            # brings its own, as before
+            given = {'tracking_results': tracking_results} if frames is None and tracking_results is not None else {}
             if world > 1:
-                frames, bgr, fps, tracking_results = self._front_end_on_rank0(input_path, output_path, world, rank)
+                frames, bgr, fps, tracking_results = self._front_end_on_rank0(input_path, output_path, world, rank, **given)
             else:
-                frames, bgr, fps, tracking_results = self.load_front_end(input_path, output_path)
+                frames, bgr, fps, tracking_results = self.load_front_end(input_path, output_path, **given)
         if info_path and osp.isfile(str(info_path)):
             with open(info_path, 'r') as f:
                 add_info = json.load(f)

@@ -28,6 +28,9 @@ absent from the reference and all optional:
                               baseline JPEG frames encoded on the GPU (pr_jpeg_encode) in a Motion-JPEG AVI written in Python,
                               with or without cv2 (args.video_codec overrides it); any other name raises
     cfg.DATASET.gpu_video_quality  the JPEG quality of those frames, 1..100 (90)
+    cfg.DATASET.front_max_w, front_max_h  800, 450: the reference's front-end rule for a Motion-JPEG AVI input (wider than
+                              front_max_w -> that width, else higher than front_max_h -> that height; 0 switches an arm off),
+                              applied on the GPU by poserisk_release_amd.frontend.read_video
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -87,7 +90,8 @@ def _defaults(root):
         'DATASET': {'workers': 16, 'batch_size': 8, 'min_frame_ratio': 0.33, 'bbox_scale': 1.2,
                     'default_information': osp.join(core_dir, 'default_information.json'),
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
-                    'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90},
+                    'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
+                    'front_max_w': 800, 'front_max_h': 450},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

@@ -1,0 +1,194 @@
+"""The reference's front end (lib/utils/funcs_utils.py:18-53: decode the video, downscale it, write `<output>/tmp/%09d.jpg`) for
+a Motion-JPEG AVI, without OpenCV: the container is read in Python (mjpeg.AviReader), every frame is decoded on the GPU
+(jpeg.decode_files), downscaled on the GPU by the integer bilinear contract of include/poserisk_hip.h (section j3;
+csrc/resize_host.cc, csrc/resize.hip) and, where a tracker needs files, encoded on the GPU (jpeg.encode_frames).
+
+    target_size    the reference's rule: wider than 800 -> 800 wide, elif higher than 450 -> 450 high
+    resize_frames  u8[F,H,W,3] -> u8[F,h,w,3] on the device
+    read_video     a Motion-JPEG AVI -> (frames on the device at the target size, fps)
+    prepare        a Motion-JPEG AVI -> a folder of %09d.jpg + fps.txt; with a tracking.pkl added it is an input of
+                   Predictor.load_front_end.   python -m poserisk_release_amd.frontend prepare <video> <dir>"""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, jpeg, mjpeg
+
+MODE_COPY, MODE_HALF, MODE_LINEAR = 0, 1, 2
+MAX_CHUNK = 1024
+
+
+def target_size(W, H, max_w=800, max_h=450):
+    """(w, h) of the reference's front end for a W x H video; max_w = 0 or max_h = 0 switches that arm off.  `elif` as in the
+    reference: a frame that was narrowed is not checked for its height (1080 x 1920 becomes 800 x 1422)."""
+    W, H = int(W), int(H)
+    if max_w and W > max_w:
+        return int(max_w), int(H * max_w / W)
+    if max_h and H > max_h:
+        return int(W * max_h / H), int(max_h)
+    return W, H
+
+
+def resize_plan(H, W, h, w):
+    """pr_resize_plan -> (xofs int32[w], xcoef int16[2w], yofs int32[h], ycoef int16[2h], mode)."""
+    xofs, xcoef = np.zeros(max(int(w), 0), np.int32), np.zeros(2 * max(int(w), 0), np.int16)
+    yofs, ycoef = np.zeros(max(int(h), 0), np.int32), np.zeros(2 * max(int(h), 0), np.int16)
+    mode = np.full(1, -1, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(_lib.load().pr_resize_plan(int(H), int(W), int(h), int(w), ptr(xofs), ptr(xcoef), ptr(yofs), ptr(ycoef), ptr(mode)),
+               "pr_resize_plan")
+    return xofs, xcoef, yofs, ycoef, int(mode[0])
+
+
+_plans = {}
+
+
+def _device_plan(key, device):
+    """The uploaded tables of (H, W, h, w) on `device` -> (u8 tensor [xofs | yofs | xcoef | ycoef], mode): made once, kept.
+    As jpeg._device_plan: the first call of a size pair waits for its copy, every further call only looks it up."""
+    plan = _plans.get((key, device))
+    if plan is None:
+        xofs, xcoef, yofs, ycoef, mode = resize_plan(*key)
+        host = torch.from_numpy(np.frombuffer(xofs.tobytes() + yofs.tobytes() + xcoef.tobytes() + ycoef.tobytes(), np.uint8).copy())
+        tables = host.to(device)
+        torch.cuda.current_stream(device).synchronize()
+        plan = _plans[(key, device)] = (tables, mode)
+    return plan
+
+
+def resize_frames(frames, h, w, out=None):
+    """u8[F,H,W,3] on the device -> u8[F,h,w,3] (`out`, or a new tensor) by the bilinear contract; exactly half in both axes is
+    the 2 x 2 mean, the same size a copy.  Asynchronous on the current stream; with `out` given and the size pair seen before
+    it allocates and synchronises nothing."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise _lib.PoseRiskHipError("resize_frames: the resize runs on the GPU only (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError(f"resize_frames: frames must be a contiguous uint8 [F, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    device, (F, H, W, _) = frames.device, frames.shape
+    h, w = int(h), int(w)
+    with torch.cuda.device(device):
+        tables, mode = _device_plan((H, W, h, w), device)
+        if out is None:
+            out = torch.empty((F, h, w, 3), dtype=torch.uint8, device=device)
+        if tuple(out.shape) != (F, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+            raise ValueError(f"resize_frames: out must be a contiguous uint8 {[F, h, w, 3]} tensor on {device}")
+        base = tables.data_ptr()
+        stream = torch.cuda.current_stream(device)
+        _lib.check(_lib.load().pr_resize_frames(frames.data_ptr(), F, H, W, out.data_ptr(), h, w, base, base + 4 * w + 4 * h,
+                                                base + 4 * w, base + 8 * w + 4 * h, mode, stream.cuda_stream), "pr_resize_frames")
+    return out
+
+
+def chunk_frames(H, W, max_bytes):
+    """Frames decoded per call: the largest count <= 1024 whose source-size pixels plus decoder workspace fit max_bytes; at
+    least 1."""
+    need = lambda n: n * H * W * 3 + jpeg.workspace_bytes(n, H, W)
+    n = max(1, min(MAX_CHUNK, int(max_bytes) // max(need(1), 1)))      # the workspace grows with the frame count, in steps at most
+    while n > 1 and need(n) > max_bytes:
+        n -= 1
+    return n
+
+
+def _raise_refused(path, part, lo, H, W, fallback):
+    _, _, _, pst, *_ = jpeg.parse(part, H, W)
+    bad = np.nonzero(pst)[0]
+    if bad.size:
+        raise RuntimeError(f"{path!r}: frame {lo + int(bad[0])} cannot be decoded: {jpeg.refusal_name(pst[bad[0]])}")
+    raise RuntimeError(f"{path!r}: frames {lo}..{lo + len(part) - 1} cannot be decoded: {fallback}")
+
+
+def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30):
+    """A Motion-JPEG AVI -> (frames u8[F,h,w,3] on `device`, fps): demuxed on the host, decoded on the GPU at the source size,
+    chunk by chunk into one reused buffer, each chunk downscaled into its slice of the result ((w, h) = target_size of the first
+    frame's own size).  RGB, or BGR with bgr=True.  A refused or damaged frame raises RuntimeError naming its index in the file
+    and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PoseRiskHipError("read_video: decoding and resizing run on the GPU only (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    reader = path if isinstance(path, mjpeg.AviReader) else mjpeg.AviReader(path)
+    path = reader.path
+    blobs = reader.frames()
+    F = len(blobs)
+    if F == 0:
+        raise ValueError(f"{path!r}: the video stream holds no frames")
+    _, _, _, pst, H, W, _ = jpeg.parse(blobs[:1])
+    if pst[0]:
+        raise RuntimeError(f"{path!r}: frame 0 cannot be decoded: {jpeg.refusal_name(pst[0])}")
+    w, h = target_size(W, H, max_w, max_h)
+    if h < 1 or w < 1:
+        raise ValueError(f"{path!r}: {W} x {H} frames would become {w} x {h}")
+    same = (h, w) == (H, W)
+    n = min(chunk_frames(H, W, int(max_bytes)), F)
+    with torch.cuda.device(device):
+        result = torch.empty((F, h, w, 3), dtype=torch.uint8, device=device)
+        buffer = None if same else torch.empty((n, H, W, 3), dtype=torch.uint8, device=device)
+        for lo in range(0, F, n):
+            part = blobs[lo:lo + n]
+            m = len(part)
+            into = result[lo:lo + m] if same else buffer[:m]
+            try:
+                _, status = jpeg.decode_files(part, device, bgr=bgr, chunk=m, out=into)
+            except (ValueError, _lib.PoseRiskHipError) as e:     # the chunk's first accepted frame has another size, or none was accepted
+                _raise_refused(path, part, lo, H, W, str(e))
+            bad = jpeg.bad_frames(part, status)
+            if bad:
+                raise RuntimeError(f"{path!r}: frame {lo + bad[0][0]} cannot be decoded: {bad[0][1]}"
+                                   + (f" (and {len(bad) - 1} more frames of its chunk)" if len(bad) > 1 else ""))
+            if not same:
+                resize_frames(into, h, w, out=result[lo:lo + m])
+    return result, float(reader.fps)
+
+
+def write_frame_folder(frames, out_dir, quality=95, fps=None, bgr=False, chunk=64):
+    """u8[F,H,W,3] on the device -> out_dir/%09d.jpg (4:2:0, a restart marker per MCU row, encoded on the GPU) and, with `fps`,
+    fps.txt.  Returns the files' bytes in frame order."""
+    os.makedirs(out_dir, exist_ok=True)
+    F, H, W, _ = frames.shape
+    files = []
+    for lo in range(0, F, chunk):
+        part = frames[lo:lo + chunk]
+        buf, nbytes, status = jpeg.encode_frames(part, quality=quality, subsampling="4:2:0", restart_rows=1, bgr=bgr)
+        if bool(status.any()):                                   # a frame beyond the default slot: the size no file exceeds
+            buf, nbytes, status = jpeg.encode_frames(part, quality=quality, subsampling="4:2:0", restart_rows=1, bgr=bgr,
+                                                     capacity=jpeg.encode_bound(H, W, "4:2:0", -1))
+        for i, data in enumerate(jpeg.download_files(buf, nbytes), lo):
+            with open(os.path.join(out_dir, "{0:09d}.jpg".format(i)), "wb") as f:
+                f.write(data)
+            files.append(data)
+    if fps is not None:
+        with open(os.path.join(out_dir, "fps.txt"), "w") as f:
+            f.write(repr(float(fps)))
+    return files
+
+
+def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_bytes=16 << 30):
+    """A Motion-JPEG AVI -> out_dir/%09d.jpg + fps.txt: the folder the reference's front end leaves for its tracker (quality 95 is
+    cv2.imwrite's default), written without OpenCV.  Returns (number of frames, (w, h), fps)."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    frames, fps = read_video(path, device, max_w=max_w, max_h=max_h, max_bytes=max_bytes)
+    write_frame_folder(frames, out_dir, quality=quality, fps=fps)
+    return int(frames.shape[0]), (int(frames.shape[2]), int(frames.shape[1])), fps
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m poserisk_release_amd.frontend")
+    sub = ap.add_subparsers(dest="command", required=True)
+    p = sub.add_parser("prepare", help="Motion-JPEG AVI -> a folder of %%09d.jpg + fps.txt for a tracker and for Predictor")
+    p.add_argument("video")
+    p.add_argument("out_dir")
+    p.add_argument("--quality", type=int, default=95)
+    p.add_argument("--max-w", type=int, default=800)
+    p.add_argument("--max-h", type=int, default=450)
+    p.add_argument("--gpu", type=int, default=0)
+    a = ap.parse_args(argv)
+    n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h)
+    print(f"{a.out_dir}: {n} frames of {w} x {h} at {fps:g} frames/s; add tracking.pkl (multi_person_tracker's dict) to score it")
+
+
+if __name__ == "__main__":
+    main()
