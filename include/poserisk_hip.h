@@ -63,6 +63,28 @@ const char* pr_build_info(void);
  * No reference counterpart: the reference never captures (lib/core/base.py:81-84 builds its models once, eagerly). */
 int pr_declare_stream(void* stream, int declared);
 
+/* The internal fence (ABI 16; test entries).  With POSERISK_FENCE=1 (head) or 2 (tail) in the environment when a handle is
+ * created (pr_hmr_create, pr_smpl_create, pr_hmr_set_streams; a stand-alone test entry reads it per call) every device
+ * allocation of the library's own -- activations, Winograd work, split-K slab and tickets, packed weights, regressor and SMPL
+ * workspaces, the stand-alone entries' copies -- lies between two guards of at least 64 KiB and one frame, all 0xFF bytes
+ * before use; in tail mode a tensor inside a buffer that is sized as a maximum ends on the buffer's last byte instead of
+ * starting on its first.  Unset or 0: plain hipMalloc, nothing recorded.
+ * pr_fence_check synchronises the device(s), reads every live fenced allocation's guards back and returns how many guard
+ * regions no longer hold 0xFF everywhere, those found when a fenced allocation was freed since the last call included (kept
+ * until reported once); per region one line in `report` (NUL-terminated, cut at a line when `capacity` is too small): the
+ * allocation's name and size, the side, the first and last touched byte relative to the payload, the number of bytes changed.
+ * 0 and an empty report when nothing is fenced.  Refused (PR_ERR_INVALID) under a declared stream capture.
+ * pr_fence_list: one line "name <tab> payload bytes <tab> guard bytes" per live fenced allocation; returns their number.
+ * pr_fence_payload_fill: how many bytes at the start and at the end of the named live allocation's payload (at most 256 MiB)
+ * still hold 0xFF, i.e. were never written: where in a buffer that is sized as a maximum the tensors really lay (head mode:
+ * the end stays untouched, tail mode: the start).  PR_ERR_INVALID for an unknown name.
+ * pr_fence_selftest: a small allocation of its own, fenced whatever the switch says, one byte set directly in front of its
+ * payload and one directly behind it (hipMemset, inside the allocation); 0 when the report names exactly those two bytes. */
+int pr_fence_check(char* report, size_t capacity);
+int pr_fence_list(char* report, size_t capacity);
+int pr_fence_payload_fill(const char* name, size_t* leading, size_t* trailing);
+int pr_fence_selftest(void);
+
 /* The fp32 encoder's stem as ONE kernel (csrc/stem_pool_f32.hip; same arithmetic as above in fp32, weights in registers,
  * pooling in registers): x_dev f32 [B,112,112,12] (the 2x2 space-to-depth image), w_host f32[64,12,4,4] OIHW, bias_host f32[64]
  * -> y_dev f32 [B,56,56,64].  w_host must be a 7x7 kernel laid into the 4x4 taps' 8x8 window with a zero row and a zero

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # pr_build_info() -- printed by bench.py as `library` -- says which build a record came from.
 LIB_PATH = os.environ.get("POSERISK_LIB_PATH") or os.path.join(HERE, "libposerisk_hip.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class PoseRiskHipError(RuntimeError):
@@ -70,6 +70,10 @@ SIGNATURES = {
     "pr_abi_version": (_I, []),
     "pr_build_info": (C.c_char_p, []),
     "pr_declare_stream": (_I, [_P, _I]),
+    "pr_fence_check": (_I, [C.c_char_p, C.c_size_t]),
+    "pr_fence_list": (_I, [C.c_char_p, C.c_size_t]),
+    "pr_fence_payload_fill": (_I, [C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "pr_fence_selftest": (_I, []),
     "pr_hmr_weight_floats": (C.c_size_t, []),
     "pr_hmr_create": (_I, [_I, _P, C.c_size_t, _I, _I, _I, C.POINTER(_P)]),
     "pr_hmr_destroy": (_I, [_P]),

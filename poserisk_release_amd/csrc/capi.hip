@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "conv_igemm.h"
+#include "fence.h"
 #include "frame_kernels.h"
 
 namespace pr {
@@ -34,7 +35,7 @@ void set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* pr_last_error(void) { return pr::g_last_error.c_str(); }
-int pr_abi_version(void) { return 15; }
+int pr_abi_version(void) { return 16; }
 
 int pr_declare_stream(void* stream, int declared) {
   pr::g_stream_declared = declared != 0;
@@ -112,29 +113,31 @@ class StandAlone {
  public:
   hipStream_t s = nullptr;
   ~StandAlone() {
-    for (void* p : bufs_) (void)hipFree(p);
+    for (void* p : bufs_) device_free(p);      // (internal fence: a damaged guard is kept for the next pr_fence_check)
     if (e0_) (void)hipEventDestroy(e0_);
     if (e1_) (void)hipEventDestroy(e1_);
   }
   int open(int device, void* stream) {
     guard_.emplace(device);
     s = (hipStream_t)stream;
+    fence_ = fence_mode_from_env();      // POSERISK_FENCE, per call: the entry's own copies between guards (fence.h)
     return refuse_if_capturing(s, "stand-alone test entry");   // allocates and synchronises: never inside a capture
   }
+  // `name`: what the internal fence records the buffer under ("standalone <name>"); frame_bytes: one frame of it, if it has frames
   template <typename T>
-  T* device_alloc(size_t count) {
+  T* device_alloc(size_t count, const char* name, size_t frame_bytes = 0) {
     void* p = nullptr;
-    if (st_ == PR_OK) st_ = alloc(count * sizeof(T), &p);
+    if (st_ == PR_OK) st_ = alloc(count * sizeof(T), &p, name, frame_bytes);
     return (T*)p;
   }
   template <typename T>
-  T* upload(const T* host, size_t count) {      // nothing to upload (null or empty): null
-    T* p = host && count ? device_alloc<T>(count) : nullptr;
+  T* upload(const T* host, size_t count, const char* name) {      // nothing to upload (null or empty): null
+    T* p = host && count ? device_alloc<T>(count, name) : nullptr;
     if (p) st_ = copy(p, host, count * sizeof(T));
     return st_ == PR_OK ? p : nullptr;
   }
   template <typename T>
-  T* upload(const std::vector<T>& v) { return upload(v.data(), v.size()); }
+  T* upload(const std::vector<T>& v, const char* name) { return upload(v.data(), v.size(), name); }
   // launch once; with repeats > 0 and ms_out, `repeats` more between two events (*ms_out = milliseconds per launch)
   template <typename Launch>
   int run(Launch launch, int repeats = 0, float* ms_out = nullptr) {
@@ -158,8 +161,8 @@ class StandAlone {
   }
 
  private:
-  int alloc(size_t bytes, void** p) {
-    PR_HIP(hipMalloc(p, bytes));
+  int alloc(size_t bytes, void** p, const char* name, size_t frame_bytes) {
+    PR_TRY(pr::device_alloc(p, bytes, fence_, frame_bytes, "standalone %s", name));
     bufs_.push_back(*p);
     return PR_OK;
   }
@@ -171,6 +174,7 @@ class StandAlone {
   std::vector<void*> bufs_;
   hipEvent_t e0_ = nullptr, e1_ = nullptr;
   int st_ = PR_OK;
+  int fence_ = 0;
 };
 
 // The three whole-Bottleneck entries behind their argument checks: w / b = conv1, conv2, conv3, the downsample branch (or null)
@@ -189,8 +193,8 @@ int bottleneck_entry(int planes, int device, const void* x_dev, const float* con
   BottleneckWeights bw;      // the layouts the encoder's plan uploads (host_plan.cc)
   PR_TRY(bottleneck_pack_bf16(planes, f[0], f[1], f[2], w[3] ? &f[3] : nullptr, &bw));
   BottleneckProblem p;
-  p.x = x_dev; p.y = y_dev; p.w1 = sa.upload(bw.w1); p.w2 = sa.upload(bw.w2); p.w3 = sa.upload(bw.w3);
-  p.b1 = sa.upload(bw.b1); p.b2 = sa.upload(bw.b2); p.b3 = sa.upload(bw.b3);
+  p.x = x_dev; p.y = y_dev; p.w1 = sa.upload(bw.w1, "block w1"); p.w2 = sa.upload(bw.w2, "block w2"); p.w3 = sa.upload(bw.w3, "block w3");
+  p.b1 = sa.upload(bw.b1, "block b1"); p.b2 = sa.upload(bw.b2, "block b2"); p.b3 = sa.upload(bw.b3, "block b3");
   p.B = B; p.H = H; p.W = W; p.planes = planes; p.first = w[3] != nullptr;
   return sa.run([&] { return bottleneck_bf16_launch(p, sa.s); }, repeats, ms_out);
 }
@@ -231,26 +235,27 @@ int pr_conv2d_nhwc(int device, const void* x_dev, const float* w_host, const flo
     const int wn = conv_winograd_tile(wino_m) + 2;
     std::vector<float> u((size_t)wn * wn * Cout * Cin);
     conv_winograd_pack_weights(w_host, nullptr, Cout, Cin, wino_m, u.data());
-    wd = sa.upload(u);
-    work = sa.device_alloc<float>(std::max<size_t>(conv_winograd_work_floats(p, wino_m), 4));
+    wd = sa.upload(u, "u");
+    work = sa.device_alloc<float>(std::max<size_t>(conv_winograd_work_floats(p, wino_m), 4), "wino_work",
+                                  B > 0 ? conv_winograd_work_floats(p, wino_m) / B * sizeof(float) : 0);
   } else if (precision == 1) {      // KH x KW may differ here, so the row packers and not conv_pack_side_by_side
     std::vector<unsigned short> packed((size_t)Cout * conv_kpad_bf16(p.K()));
     conv_pack_weights_bf16(w_host, nullptr, Cout, Cin_real, Cin, KH, KW, packed.data());
-    wd = (const float*)sa.upload(packed);
+    wd = (const float*)sa.upload(packed, "weights");
   } else {
     std::vector<float> packed((size_t)Cout * p.Kpad());
     conv_pack_weights(w_host, nullptr, Cout, Cin_real, Cin, KH, KW, packed.data());
-    wd = sa.upload(packed);
+    wd = sa.upload(packed, "weights");
   }
-  p.x = (const float*)x_dev; p.w = wd; p.bias = sa.upload(bias_host, Cout); p.res = (const float*)res_dev; p.y = (float*)y_dev;
+  p.x = (const float*)x_dev; p.w = wd; p.bias = sa.upload(bias_host, Cout, "bias"); p.res = (const float*)res_dev; p.y = (float*)y_dev;
   int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p);
   if (tile_cfg > 200 && tile_cfg <= 208) {      // 64x64 tile with the K-steps of every tile dealt to tile_cfg - 200 workgroups
     PR_REQUIRE(precision == 0, "pr_conv2d_nhwc: split-K is fp32 only");
     cfg = 8;
     p.splitk = tile_cfg - 200;
     const size_t tiles = (size_t)ceil_div(p.M(), 64) * (Cout / 64);
-    p.split_slab = sa.device_alloc<float>(tiles * p.splitk * 4096);
-    p.split_tickets = sa.device_alloc<int>(tiles);
+    p.split_slab = sa.device_alloc<float>(tiles * p.splitk * 4096, "split_slab");
+    p.split_tickets = sa.device_alloc<int>(tiles, "split_tickets");
   }
   return sa.run([&] { return wino ? conv_winograd_launch(p, wd, work, wino_m, sa.s) : conv_launch(p, cfg, sa.s); }, repeats, ms_out);
 }
@@ -272,8 +277,8 @@ int pr_conv1x1_dual_nhwc(int device, const void* x1_dev, const float* w1_host, c
   p.tune = conv_tuning_from_env();
   p.H2 = H2; p.W2 = W2; p.Cin2 = Cin2; p.stride2 = stride2;
   const ConvFilter f1{w1_host}, f2{w2_host};
-  p.w = sa.upload(conv_pack_side_by_side(f1, Cin1, Cin1, 1, &f2, Cin2, Cout, precision));
-  p.x = (const float*)x1_dev; p.x2 = (const float*)x2_dev; p.bias = sa.upload(bias_host, Cout); p.res = nullptr; p.y = (float*)y_dev;
+  p.w = sa.upload(conv_pack_side_by_side(f1, Cin1, Cin1, 1, &f2, Cin2, Cout, precision), "dual weights");
+  p.x = (const float*)x1_dev; p.x2 = (const float*)x2_dev; p.bias = sa.upload(bias_host, Cout, "bias"); p.res = nullptr; p.y = (float*)y_dev;
   const int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p);
   return sa.run([&] { return conv_launch(p, cfg, sa.s); });
 }
@@ -293,10 +298,10 @@ int pr_conv3x3_conv1x1_nhwc(int device, const void* x_dev, const float* w2_host,
   p.precision = precision;
   p.tune = conv_tuning_from_env();
   p.x = (const float*)x_dev;
-  p.w = sa.upload(conv_pack_side_by_side(ConvFilter{w2_host}, Cin, Cin, 3, nullptr, 0, 64, precision));
-  p.bias = sa.upload(b2_host, 64);
-  p.w3 = sa.upload(conv_pack_side_by_side(ConvFilter{w3_host}, 64, 64, 1, nullptr, 0, N3, precision));
-  p.bias3 = sa.upload(b3_host, N3);
+  p.w = sa.upload(conv_pack_side_by_side(ConvFilter{w2_host}, Cin, Cin, 3, nullptr, 0, 64, precision), "conv2 weights");
+  p.bias = sa.upload(b2_host, 64, "conv2 bias");
+  p.w3 = sa.upload(conv_pack_side_by_side(ConvFilter{w3_host}, 64, 64, 1, nullptr, 0, N3, precision), "conv3 weights");
+  p.bias3 = sa.upload(b3_host, N3, "conv3 bias");
   p.res3 = (const float*)res_dev; p.y3 = (float*)y_dev;
   p.N3 = N3; p.relu3 = relu3;
   return sa.run([&] { return conv_launch(p, 8, sa.s); });
@@ -316,13 +321,13 @@ int pr_conv3x3_wino64_nhwc(int device, const void* x_dev, const float* w2_host, 
   std::vector<float> u((size_t)36 * 64 * 64), up(u.size());
   conv_winograd_pack_weights(w2_host, nullptr, 64, 64, form, u.data());
   conv_wino64_pack_u(u.data(), up.data());
-  const float* ud = sa.upload(up);
+  const float* ud = sa.upload(up, "u1");
   ConvProblem p;
   p.B = B; p.H = p.Ho = H; p.W = p.Wo = W; p.Cin = 64; p.Cout = 64; p.KH = p.KW = 3; p.stride = 1; p.pad = 1; p.relu = relu2;
   p.precision = 0;
-  p.x = (const float*)x_dev; p.w = nullptr; p.bias = sa.upload(b2_host, 64); p.res = nullptr; p.y = w3_host ? nullptr : (float*)y_dev;
+  p.x = (const float*)x_dev; p.w = nullptr; p.bias = sa.upload(b2_host, 64, "conv2 bias"); p.res = nullptr; p.y = w3_host ? nullptr : (float*)y_dev;
   if (w3_host) {
-    p.w3 = sa.upload(w3_host, (size_t)N3 * 64); p.bias3 = sa.upload(b3_host, N3);
+    p.w3 = sa.upload(w3_host, (size_t)N3 * 64, "conv3 weights"); p.bias3 = sa.upload(b3_host, N3, "conv3 bias");
     p.res3 = (const float*)res_dev; p.y3 = (float*)y_dev; p.N3 = N3; p.relu3 = relu3;
   }
   return sa.run([&] { return conv_wino64_launch(p, ud, form, sa.s); });
@@ -362,8 +367,8 @@ int pr_stem_pool_nhwc(int device, const void* x_dev, const float* w_host, const 
   PR_REQUIRE(x_dev && w_host && bias_host && y_dev, "pr_stem_pool_nhwc: null argument");
   StandAlone sa;
   PR_TRY(sa.open(device, stream));
-  const float* wd = sa.upload(conv_pack_side_by_side(ConvFilter{w_host}, 16, 16, 4, nullptr, 0, 64, 1));      // k = (th * 4 + tw) * 16 + c
-  const float* bd = sa.upload(bias_host, 64);
+  const float* wd = sa.upload(conv_pack_side_by_side(ConvFilter{w_host}, 16, 16, 4, nullptr, 0, 64, 1), "stem weights");      // k = (th * 4 + tw) * 16 + c
+  const float* bd = sa.upload(bias_host, 64, "stem bias");
   return sa.run([&] { return stem_pool_bf16_launch(x_dev, wd, bd, y_dev, B, H, sa.s); }, repeats, ms_out);
 }
 
@@ -384,8 +389,8 @@ int pr_stem_pool_f32_nhwc(int device, const float* x_dev, const float* w_host, c
                    "pr_stem_pool_f32_nhwc: the weights must be a 7x7 kernel in the 4x4 taps' 8x8 window (zero for tap row 0 / "
                    "sub-row 0 and for tap column 0 / sub-column 0); output channel %d, channel %d is not", o, c12);
       }
-  const float* wd = sa.upload(conv_pack_side_by_side(ConvFilter{w_host}, 12, 12, 4, nullptr, 0, 64, 0));      // k = (th * 4 + tw) * 12 + c
-  const float* bd = sa.upload(bias_host, 64);
+  const float* wd = sa.upload(conv_pack_side_by_side(ConvFilter{w_host}, 12, 12, 4, nullptr, 0, 64, 0), "stem weights");      // k = (th * 4 + tw) * 12 + c
+  const float* bd = sa.upload(bias_host, 64, "stem bias");
   return sa.run([&] { return stem_pool_f32_launch(x_dev, wd, bd, y_dev, B, sa.s); }, repeats, ms_out);
 }
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "conv_igemm.h"
+#include "fence.h"
 #include "frame_kernels.h"
 
 struct pr_hmr : pr::HmrPlan {
@@ -40,6 +41,12 @@ struct pr_hmr : pr::HmrPlan {
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join[kMaxChunks] = {};
   std::vector<float*> act_allocs;
+  // the internal fence (POSERISK_FENCE, read at create and at set_streams; fence.h): 0 = off, 1 = head, 2 = tail.  In tail
+  // mode every tensor in act / wino_work / split_slab ends on its buffer's last byte (`placed` below); `sizes` is what those
+  // buffers hold.  fence_bad: a tensor did not fit its buffer or its size was no multiple of 256 bytes -- the forward fails.
+  int fence = 0;
+  pr::HmrChunkSizes sizes{};
+  bool fence_bad = false;
   // profiling
   bool profile = false;
   std::vector<float> prof_ms;
@@ -57,7 +64,7 @@ struct DeviceSink : PlanSink {
   explicit DeviceSink(pr_hmr* handle) : h(handle) {}
   int upload(const void* host, size_t bytes, float** out) override {
     float* d = nullptr;
-    PR_HIP(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+    PR_TRY(device_alloc((void**)&d, std::max<size_t>(bytes, 16), h->fence, 0, "plan constant %zu", h->dev_allocs.size()));
     h->dev_allocs.push_back(d);
     PR_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
     *out = d;
@@ -65,7 +72,7 @@ struct DeviceSink : PlanSink {
   }
   int zeros(size_t bytes, float** out) override {
     float* d = nullptr;
-    PR_HIP(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+    PR_TRY(device_alloc((void**)&d, std::max<size_t>(bytes, 16), h->fence, 0, "plan workspace %zu", h->dev_allocs.size()));
     h->dev_allocs.push_back(d);
     PR_HIP(hipMemset(d, 0, std::max<size_t>(bytes, 16)));
     *out = d;
@@ -77,32 +84,37 @@ struct DeviceSink : PlanSink {
 int set_chunks(pr_hmr* h, int n) {
   PR_REQUIRE(n >= 1 && n <= pr_hmr::kMaxChunks, "hmr: stream count %d out of range 1..%d", n, pr_hmr::kMaxChunks);
   PR_HIP(hipDeviceSynchronize());
-  for (float* p : h->act_allocs) (void)hipFree(p);
+  PR_REQUIRE(!h->convs.empty() && h->convs[0].in_buf == 0, "hmr: the plan's first entry reads the layout-changed input");
+  for (float* p : h->act_allocs) device_free(p);
   h->act_allocs.clear();
   h->n_chunks = n;
   // a sub-batch is also the unit of one conv launch, whose tensors must stay under 2 GiB (the DMA kernel's
   // out-of-range sentinel): 512 frames x 56x56x256 fp32 = 1.6 GB
   h->chunk_cap = hmr_chunk_cap(h->max_batch, n);
   const HmrChunkSizes z = hmr_chunk_sizes(*h, h->chunk_cap);   // element counts per sub-batch (host_plan.cc)
+  h->sizes = z;
+  // a guard of the internal fence: one frame of the largest tensor the buffer holds
+  const size_t cb = (size_t)h->chunk_cap;
   for (int c = 0; c < n; ++c) {
     for (int i = 0; i <= 5; ++i) {
       float* d = nullptr;
-      PR_HIP(hipMalloc(&d, (i == 0 ? z.act0_floats : z.act_floats) * sizeof(float)));
+      const size_t floats = i == 0 ? z.act0_floats : z.act_floats;
+      PR_TRY(device_alloc((void**)&d, floats * sizeof(float), h->fence, floats * sizeof(float) / cb, "act[%d][%d]", c, i));
       h->act_allocs.push_back(d);
       h->act[c][i] = d;
     }
     if (z.wino_floats) {
       float* d = nullptr;
-      PR_HIP(hipMalloc(&d, z.wino_floats * sizeof(float)));
+      PR_TRY(device_alloc((void**)&d, z.wino_floats * sizeof(float), h->fence, h->wino_floats_per_frame * sizeof(float), "wino_work[%d]", c));
       h->act_allocs.push_back(d);
       h->wino_work[c] = d;
     }
     if (z.slab_floats) {
       float* d = nullptr;
-      PR_HIP(hipMalloc(&d, z.slab_floats * sizeof(float)));
+      PR_TRY(device_alloc((void**)&d, z.slab_floats * sizeof(float), h->fence, z.slab_floats * sizeof(float) / cb, "split_slab[%d]", c));
       h->act_allocs.push_back(d);
       h->split_slab[c] = d;
-      PR_HIP(hipMalloc(&d, z.tickets * sizeof(int)));
+      PR_TRY(device_alloc((void**)&d, z.tickets * sizeof(int), h->fence, 0, "split_tickets[%d]", c));
       h->act_allocs.push_back(d);
       h->split_tickets[c] = reinterpret_cast<int*>(d);
     }
@@ -113,30 +125,65 @@ int set_chunks(pr_hmr* h, int n) {
   return PR_OK;
 }
 
-ConvProblem conv_problem(const pr_hmr* h, const ConvSpec& c, int chunk, int B) {
+// Where a tensor of `bytes` lies in one of the buffers that are sized as a maximum over layers and over the batch: on the
+// buffer's first byte, or -- internal fence in tail mode -- ending on its last, so that the guard behind the buffer is sharp
+// for every layer at every B.  Producer and consumer of a tensor compute the same place from the same dimensions.
+template <typename T>
+T* placed(pr_hmr* h, T* base, size_t capacity_bytes, size_t bytes) {
+  if (h->fence != 2 || !base) return base;
+  bool ok = true;
+  const size_t off = fence_tail_offset(capacity_bytes, bytes, &ok);
+  if (!ok && !h->fence_bad) {
+    h->fence_bad = true;
+    set_error("hmr: internal fence: a tensor of %zu bytes in a buffer of %zu (it must fit and be a multiple of 256 bytes)", bytes,
+              capacity_bytes);
+  }
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + off);
+}
+// A tensor of `bytes` in activation buffer `buf`; act_at: the tensor [B, H, W, C] in the handle's precision
+float* act_placed(pr_hmr* h, int chunk, int buf, size_t bytes) {
+  return placed(h, h->act[chunk][buf], hmr_act_capacity_bytes(h->sizes, buf), bytes);
+}
+float* act_at(pr_hmr* h, int chunk, int buf, int B, int H, int W, int C) {
+  return act_placed(h, chunk, buf, hmr_act_bytes(h->precision, B, H, W, C));
+}
+// The encoder's input after the layout change, as the stem (plan entry 0) reads it
+float* stem_in_at(pr_hmr* h, int chunk, int B) {
+  return act_placed(h, chunk, 0, hmr_conv_tensor_bytes(h->convs[0], h->precision, B).x);
+}
+// V and M of a Winograd layer at this B (hmr_plan_build's wino_floats_per_frame is the maximum of the same product per frame)
+float* wino_work_at(pr_hmr* h, int chunk, const ConvSpec& c, int B) {
+  return placed(h, h->wino_work[chunk], h->sizes.wino_floats * sizeof(float), hmr_wino_work_floats(c, B) * sizeof(float));
+}
+
+ConvProblem conv_problem(pr_hmr* h, const ConvSpec& c, int chunk, int B) {
   ConvProblem p;
-  p.x = h->act[chunk][c.in_buf];
+  const ConvTensorBytes t = hmr_conv_tensor_bytes(c, h->precision, B);
+  p.x = act_placed(h, chunk, c.in_buf, t.x);
   p.w = c.w;
   p.bias = c.bias;
-  p.res = c.res_buf >= 0 ? h->act[chunk][c.res_buf] : nullptr;
-  p.y = h->act[chunk][c.out_buf];
+  p.res = c.res_buf >= 0 ? act_placed(h, chunk, c.res_buf, t.y) : nullptr;
+  p.y = act_placed(h, chunk, c.out_buf, t.y);
   p.B = B; p.H = c.H; p.W = c.W; p.Cin = c.Cin; p.Ho = c.Ho(); p.Wo = c.Wo(); p.Cout = c.Cout;
   p.KH = p.KW = c.k; p.stride = c.stride; p.pad = c.pad; p.relu = c.relu;
   p.precision = h->precision;
   p.tune = h->tune;
   if (c.in2_buf >= 0) {
-    p.x2 = h->act[chunk][c.in2_buf];
+    p.x2 = act_placed(h, chunk, c.in2_buf, t.x2);
     p.H2 = p.W2 = c.H2; p.Cin2 = c.Cin2; p.stride2 = c.stride2;
   }
   if (c.splitk > 1) {
     p.splitk = c.splitk;
-    p.split_slab = h->split_slab[chunk];
+    // one 64x64 fp32 partial tile per K part (hmr_chunk_sizes); the tickets, one int a tile, stay on their buffer's first
+    // byte in both modes: their size is no multiple of 256 bytes
+    const size_t tiles = (size_t)ceil_div(B * c.Ho() * c.Wo(), 64) * (c.Cout / 64);
+    p.split_slab = placed(h, h->split_slab[chunk], h->sizes.slab_floats * sizeof(float), tiles * c.splitk * 4096 * sizeof(float));
     p.split_tickets = h->split_tickets[chunk];
   }
   if (c.w3 && c.out3_buf >= 0) {
     p.w3 = c.w3; p.bias3 = c.bias3; p.N3 = c.N3; p.relu3 = 1;
-    p.res3 = c.res3_buf >= 0 ? h->act[chunk][c.res3_buf] : nullptr;
-    p.y3 = h->act[chunk][c.out3_buf];
+    p.res3 = c.res3_buf >= 0 ? act_placed(h, chunk, c.res3_buf, t.y3) : nullptr;
+    p.y3 = act_placed(h, chunk, c.out3_buf, t.y3);
   }
   return p;
 }
@@ -164,12 +211,6 @@ struct ChunkRun {
   void* tap = nullptr;   // encode_until: where this sub-batch's frames of the tapped block go
 };
 
-// Elements per frame of block k's output (pr_hmr_encode_until): the stem + max-pool, then layer1..layer4's blocks.
-size_t block_frame_elems(int k) {
-  if (k == 0) return (size_t)56 * 56 * 64;
-  const int L = k <= 3 ? 0 : k <= 7 ? 1 : k <= 13 ? 2 : 3, hw = 56 >> L;
-  return (size_t)hw * hw * (256 << L);
-}
 
 // Encoder over n sub-batches: layout change, 53 convs, max-pool, global average pool -> xf[b,2048].
 // Launches are issued layer by layer across the sub-batches so that all streams advance together
@@ -180,11 +221,11 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
   const bool bf = h->precision == 1;
   for (int i = 0; i < n; ++i) {
     if (h->stem_s2d) {
-      if (bf) PR_TRY(launch_nchw3_to_s2d16_bf16(runs[i].x, h->act[runs[i].chunk][0], runs[i].b, kImg, kImg, runs[i].s));
-      else PR_TRY(launch_nchw3_to_s2d12(runs[i].x, h->act[runs[i].chunk][0], runs[i].b, kImg, kImg, runs[i].s));
+      if (bf) PR_TRY(launch_nchw3_to_s2d16_bf16(runs[i].x, stem_in_at(h, runs[i].chunk, runs[i].b), runs[i].b, kImg, kImg, runs[i].s));
+      else PR_TRY(launch_nchw3_to_s2d12(runs[i].x, stem_in_at(h, runs[i].chunk, runs[i].b), runs[i].b, kImg, kImg, runs[i].s));
     } else {
-      if (bf) PR_TRY(launch_nchw3_to_nhwc8_bf16(runs[i].x, h->act[runs[i].chunk][0], runs[i].b, kImg, kImg, runs[i].s));
-      else PR_TRY(launch_nchw3_to_nhwc4(runs[i].x, h->act[runs[i].chunk][0], runs[i].b, kImg, kImg, runs[i].s));
+      if (bf) PR_TRY(launch_nchw3_to_nhwc8_bf16(runs[i].x, stem_in_at(h, runs[i].chunk, runs[i].b), runs[i].b, kImg, kImg, runs[i].s));
+      else PR_TRY(launch_nchw3_to_nhwc4(runs[i].x, stem_in_at(h, runs[i].chunk, runs[i].b), runs[i].b, kImg, kImg, runs[i].s));
     }
   }
   // A frame per workgroup pays when the sub-batch's frames fill whole rounds of CUs: one round lasts as long for 1 frame as
@@ -202,7 +243,8 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
       if (ci < skip_until[i]) continue;      // the block's other two launches: done by the whole-block kernel
       if (alt && fused_pays(r.b)) {
         BottleneckProblem bp;
-        bp.x = h->act[r.chunk][alt->blk.in_buf]; bp.y = h->act[r.chunk][alt->blk.out_buf];
+        const ConvTensorBytes t = hmr_conv_tensor_bytes(alt->blk, h->precision, r.b);
+        bp.x = act_placed(h, r.chunk, alt->blk.in_buf, t.x); bp.y = act_placed(h, r.chunk, alt->blk.out_buf, t.y);
         bp.w1 = alt->blk.w; bp.w2 = alt->blk.w2b; bp.w3 = alt->blk.w3;
         bp.b1 = alt->blk.bias; bp.b2 = alt->blk.bias2b; bp.b3 = alt->blk.bias3;
         bp.B = r.b; bp.H = alt->blk.H; bp.W = alt->blk.W; bp.planes = alt->blk.bneck_planes; bp.first = false;
@@ -230,19 +272,20 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
       const bool stem_pool = ci == 0 && h->stem_s2d && h->fuse_stem;   // the stem and its max-pool as one launch
       auto go = [&]() -> int {
         if (stem_pool && !bf)
-          return stem_pool_f32_launch(h->act[r.chunk][0], c.w, c.bias, h->act[r.chunk][2], r.b, r.s);
+          return stem_pool_f32_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, act_at(h, r.chunk, 2, r.b, 56, 56, 64), r.b, r.s);
         if (stem_pool)
-          return stem_pool_bf16_launch(h->act[r.chunk][0], c.w, c.bias, h->act[r.chunk][2], r.b, kImg / 2, r.s);
+          return stem_pool_bf16_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, act_at(h, r.chunk, 2, r.b, 56, 56, 64), r.b, kImg / 2, r.s);
         if (c.bneck_planes) {
           BottleneckProblem bp;
-          bp.x = h->act[r.chunk][c.in_buf]; bp.y = h->act[r.chunk][c.out_buf];
+          const ConvTensorBytes t = hmr_conv_tensor_bytes(c, h->precision, r.b);
+          bp.x = act_placed(h, r.chunk, c.in_buf, t.x); bp.y = act_placed(h, r.chunk, c.out_buf, t.y);
           bp.w1 = c.w; bp.w2 = c.w2b; bp.w3 = c.w3; bp.b1 = c.bias; bp.b2 = c.bias2b; bp.b3 = c.bias3;
           bp.B = r.b; bp.H = c.H; bp.W = c.W; bp.planes = c.bneck_planes; bp.first = c.bneck_first;
           bp.lead_tiles = h->b128_lead;
           return bottleneck_bf16_launch(bp, r.s);
         }
         if (c.u1) return conv_wino64_launch(p, c.u1, h->stage_form[0], r.s);      // layer1's conv2 (+ conv3) as one-launch F(4x4,3x3)
-        return c.u ? conv_winograd_launch(p, c.u, h->wino_work[r.chunk], c.wino_form, r.s) : conv_launch(p, cfg, r.s);
+        return c.u ? conv_winograd_launch(p, c.u, wino_work_at(h, r.chunk, c, r.b), c.wino_form, r.s) : conv_launch(p, cfg, r.s);
       };
       if (h->profile) {
         hipEvent_t e0, e1;
@@ -257,23 +300,56 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
         PR_TRY(go());
       }
       if (ci == 0 && !stem_pool) {
-        if (bf) PR_TRY(launch_maxpool_bf16(h->act[r.chunk][1], h->act[r.chunk][2], r.b, 112, 112, 64, r.s));
-        else PR_TRY(launch_maxpool(h->act[r.chunk][1], h->act[r.chunk][2], r.b, 112, 112, 64, r.s));
+        float* const pool_in = act_at(h, r.chunk, 1, r.b, 112, 112, 64);
+        float* const pool_out = act_at(h, r.chunk, 2, r.b, 56, 56, 64);
+        if (bf) PR_TRY(launch_maxpool_bf16(pool_in, pool_out, r.b, 112, 112, 64, r.s));
+        else PR_TRY(launch_maxpool(pool_in, pool_out, r.b, 112, 112, 64, r.s));
       }
     }
     if (stop_block >= 0 && ci == (size_t)h->block_last[stop_block]) {
-      const size_t frame_bytes = block_frame_elems(stop_block) * (bf ? 2 : 4);
+      const size_t frame_bytes = hmr_block_frame_elems(stop_block) * (bf ? 2 : 4);
       for (int i = 0; i < n; ++i)
-        PR_HIP(hipMemcpyAsync(runs[i].tap, h->act[runs[i].chunk][h->block_buf[stop_block]], runs[i].b * frame_bytes,
-                              hipMemcpyDeviceToDevice, runs[i].s));
+        PR_HIP(hipMemcpyAsync(runs[i].tap,
+                              act_placed(h, runs[i].chunk, h->block_buf[stop_block], runs[i].b * frame_bytes),
+                              runs[i].b * frame_bytes, hipMemcpyDeviceToDevice, runs[i].s));
       return PR_OK;
     }
   }
   for (int i = 0; i < n; ++i) {
-    if (bf) PR_TRY(launch_avgpool_bf16(h->act[runs[i].chunk][h->final_buf], runs[i].xf_out, runs[i].b, 49, 2048, runs[i].s));
-    else PR_TRY(launch_avgpool(h->act[runs[i].chunk][h->final_buf], runs[i].xf_out, runs[i].b, 49, 2048, runs[i].s));
+    float* const last = act_at(h, runs[i].chunk, h->final_buf, runs[i].b, 7, 7, 2048);
+    if (bf) PR_TRY(launch_avgpool_bf16(last, runs[i].xf_out, runs[i].b, 49, 2048, runs[i].s));
+    else PR_TRY(launch_avgpool(last, runs[i].xf_out, runs[i].b, 49, 2048, runs[i].s));
   }
   return PR_OK;
+}
+
+// The internal fence's names of what hmr_plan_build uploaded: by the network's convolution index (ConvSpec::layer) or the
+// regressor's part.  (The sink sees bytes only; the plan knows whose they are once it is built.)
+void name_plan_constants(pr_hmr* h) {
+  auto conv = [](const ConvSpec& c, const char* kind) {
+    fence_rename(c.w, "%s %d weights", kind, c.layer);
+    fence_rename(c.bias, "%s %d bias", kind, c.layer);
+    fence_rename(c.u, "%s %d u", kind, c.layer);
+    fence_rename(c.u1, "%s %d u1", kind, c.layer);
+    fence_rename(c.w3, "%s %d conv3 weights", kind, c.layer);
+    fence_rename(c.bias3, "%s %d conv3 bias", kind, c.layer);
+    fence_rename(c.w2b, "%s %d conv2 weights", kind, c.layer);
+    fence_rename(c.bias2b, "%s %d conv2 bias", kind, c.layer);
+  };
+  for (const ConvSpec& c : h->convs) conv(c, c.bneck_planes ? "block" : "conv");
+  for (const pr::HmrPlan::FusedBlock& fb : h->fused3) conv(fb.blk, "block256");
+  const FcSpec* fcs[4] = {&h->fc1x, &h->fc1s, &h->fc2, &h->dec};
+  const char* fc_names[4] = {"fc1x", "fc1s", "fc2", "dec"};
+  for (int i = 0; i < 4; ++i) {
+    fence_rename(fcs[i]->w, "%s weights", fc_names[i]);
+    fence_rename(fcs[i]->bias, "%s bias", fc_names[i]);
+  }
+  fence_rename(h->init157, "init157");
+  fence_rename(h->xf, "xf");
+  fence_rename(h->h_static, "h_static");
+  fence_rename(h->h1, "h1");
+  fence_rename(h->h2, "h2");
+  fence_rename(h->state, "state");
 }
 
 }  // namespace
@@ -308,11 +384,13 @@ int pr_hmr_create(int device, const float* weights_host, size_t n_floats, int ma
   // the conv form and every POSERISK_* A/B switch: read here, once per handle (nothing is latched per process)
   hmr_plan_configure(h.get(), precision, conv_form, max_batch);
   h->tune = conv_tuning_from_env();
+  h->fence = fence_mode_from_env();
   (void)hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, h->device);
   DeviceSink sink(h.get());
   int st = hmr_plan_build(h.get(), weights_host, n_floats, sink);
   h->prof_ms.assign(kNumConv, 0.f);
   h->prof_n.assign(kNumConv, 0);
+  if (st == PR_OK && h->fence) name_plan_constants(h.get());
   if (st == PR_OK) {
     int n = 1;  // sub-batch streams: 1 unless POSERISK_HMR_STREAMS / pr_hmr_set_streams ask for more
     if (const char* e = getenv("POSERISK_HMR_STREAMS")) n = atoi(e);
@@ -320,8 +398,8 @@ int pr_hmr_create(int device, const float* weights_host, size_t n_floats, int ma
     st = set_chunks(h.get(), std::min(n, max_batch));
   }
   if (st != PR_OK) {
-    for (float* p : h->dev_allocs) (void)hipFree(p);
-    for (float* p : h->act_allocs) (void)hipFree(p);
+    for (float* p : h->dev_allocs) device_free(p);
+    for (float* p : h->act_allocs) device_free(p);
     return st;
   }
   *out = h.release();
@@ -336,8 +414,8 @@ int pr_hmr_destroy(pr_hmr_t* h) {
     (void)hipEventDestroy(pe.first);
     (void)hipEventDestroy(pe.second);
   }
-  for (float* p : h->dev_allocs) (void)hipFree(p);
-  for (float* p : h->act_allocs) (void)hipFree(p);
+  for (float* p : h->dev_allocs) pr::device_free(p);
+  for (float* p : h->act_allocs) pr::device_free(p);
   for (int c = 0; c < pr_hmr::kMaxChunks; ++c) {
     if (h->streams[c]) (void)hipStreamDestroy(h->streams[c]);
     if (h->ev_join[c]) (void)hipEventDestroy(h->ev_join[c]);
@@ -358,6 +436,7 @@ int pr_hmr_set_streams(pr_hmr_t* h, int n_streams) {
   PR_REQUIRE(h, "pr_hmr_set_streams: null handle");
   pr::DeviceGuard g(h->device);
   PR_TRY(pr::refuse_under_declared_capture("pr_hmr_set_streams"));
+  h->fence = pr::fence_mode_from_env();   // the buffers allocated below are the ones `placed` places tensors in
   return pr::set_chunks(h, std::min(n_streams, h->max_batch));
 }
 
@@ -373,7 +452,7 @@ int encode_batch(pr_hmr_t* h, const float* x_dev, int B, hipStream_t s, int stop
   bool concurrent = false;
   const int nsub = hmr_split_batch(B, h->chunk_cap, h->n_chunks, h->profile != 0, sizes, 4096, &concurrent);
   const size_t frame = (size_t)3 * kImg * kImg;
-  const size_t tap_frame = stop_block >= 0 ? block_frame_elems(stop_block) * (h->precision == 1 ? 2 : 4) : 0;
+  const size_t tap_frame = stop_block >= 0 ? hmr_block_frame_elems(stop_block) * (h->precision == 1 ? 2 : 4) : 0;
   auto tap_at = [&](int b0) { return tap ? (void*)((char*)tap + (size_t)b0 * tap_frame) : nullptr; };
   if (!concurrent) {
     // one sub-batch at a time on the caller's stream (more than one pass if B exceeds a chunk's buffers)
@@ -381,6 +460,7 @@ int encode_batch(pr_hmr_t* h, const float* x_dev, int B, hipStream_t s, int stop
       ChunkRun r{0, x_dev + b0 * frame, sizes[i], h->xf + (size_t)b0 * 2048, s, tap_at(b0)};
       PR_TRY(encode_chunks(h, &r, 1, stop_block));
     }
+    PR_REQUIRE(!h->fence_bad, "%s", pr_last_error());
   } else {
     const int nch = nsub;
     ChunkRun runs[pr_hmr::kMaxChunks];
@@ -390,6 +470,7 @@ int encode_batch(pr_hmr_t* h, const float* x_dev, int B, hipStream_t s, int stop
       PR_HIP(hipStreamWaitEvent(h->streams[c], h->ev_fork, 0));
     }
     PR_TRY(encode_chunks(h, runs, nch, stop_block));
+    PR_REQUIRE(!h->fence_bad, "%s", pr_last_error());
     for (int c = 0; c < nch; ++c) {
       PR_HIP(hipEventRecord(h->ev_join[c], h->streams[c]));
       PR_HIP(hipStreamWaitEvent(s, h->ev_join[c], 0));

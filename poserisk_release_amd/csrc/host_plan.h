@@ -252,6 +252,35 @@ struct HmrChunkSizes {
   size_t act0_floats, act_floats, wino_floats, slab_floats, tickets;
 };
 HmrChunkSizes hmr_chunk_sizes(const HmrPlan& plan, int chunk_cap);
+// Byte sizes of the tensors a plan entry reads and writes at B frames, from the entry's own dimensions: what the internal
+// fence's tail mode places them by (hmr.hip `placed`; DESIGN.md "The internal fence").  A consumer must compute for its input
+// what the producer computed for its output -- tests/native/fence_check.cc walks the plan and holds them to that.
+// res is y's size, res3 is y3's.  A whole-Bottleneck spec is 1x1 / stride 1: x and y are the block's input and output.
+inline size_t hmr_act_bytes(int precision, int B, int H, int W, int C) { return (size_t)B * H * W * C * (precision == 1 ? 2 : 4); }
+struct ConvTensorBytes {
+  size_t x = 0, y = 0, x2 = 0, y3 = 0;
+};
+inline ConvTensorBytes hmr_conv_tensor_bytes(const ConvSpec& c, int precision, int B) {
+  ConvTensorBytes t;
+  t.x = hmr_act_bytes(precision, B, c.H, c.W, c.Cin);
+  t.y = hmr_act_bytes(precision, B, c.Ho(), c.Wo(), c.Cout);
+  if (c.in2_buf >= 0) t.x2 = hmr_act_bytes(precision, B, c.H2, c.H2, c.Cin2);
+  if (c.w3 && c.out3_buf >= 0) t.y3 = hmr_act_bytes(precision, B, c.Ho(), c.Wo(), c.N3);
+  return t;
+}
+// Elements per frame of block k's output (pr_hmr_encode_until): the stem + max-pool, then layer1..layer4's blocks.
+inline size_t hmr_block_frame_elems(int k) {
+  if (k == 0) return (size_t)56 * 56 * 64;
+  const int L = k <= 3 ? 0 : k <= 7 ? 1 : k <= 13 ? 2 : 3, hw = 56 >> L;
+  return (size_t)hw * hw * (256 << L);
+}
+// Capacity in bytes of activation buffer `buf` (0 = the layout-changed input)
+inline size_t hmr_act_capacity_bytes(const HmrChunkSizes& z, int buf) { return (buf == 0 ? z.act0_floats : z.act_floats) * sizeof(float); }
+// V and M of a Winograd layer at B frames, in floats (conv_winograd_work_floats computes the same from its ConvProblem)
+inline size_t hmr_wino_work_floats(const ConvSpec& c, int B) {
+  const int m = c.wino_m;
+  return (size_t)(m + 2) * (m + 2) * B * ((c.H + m - 1) / m) * ((c.W + m - 1) / m) * ((size_t)c.Cin + c.Cout);
+}
 // What one forward of B frames launches (pr_hmr_plan_counts): event brackets (a Winograd layer counts once) and how many
 // of them are Winograd layers.
 // `serial`: the passes run one after the other on the caller's stream (profile mode, or one sub-batch stream).

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "common.h"
+#include "fence.h"
 #include "kernel_vocab.h"
 
 namespace pr {
@@ -670,6 +671,7 @@ struct pr_smpl {
   float *A = nullptr, *pm_T = nullptr, *betas_T = nullptr, *voff = nullptr, *joints_tmp = nullptr;
   int* flags = nullptr;
   int* tree_dev = nullptr;
+  int fence = 0; // POSERISK_FENCE at create (fence.h): the allocations below between guards
   int tile = 1;  // register-tiled skinning kernel (smpl_skin_tile) where it applies; POSERISK_SMPL_TILE=0: A/B timing
 };
 
@@ -677,10 +679,11 @@ namespace pr {
 namespace {
 
 template <typename T>
-int smpl_upload(pr_smpl* h, const std::vector<T>& host, T** out) {
+int smpl_upload(pr_smpl* h, const char* name, size_t frame_bytes, const std::vector<T>& host, T** out) {
   void* d = nullptr;
   const size_t bytes = std::max<size_t>(host.size() * sizeof(T), 16);
-  PR_HIP(hipMalloc(&d, bytes));
+  // (internal fence: a buffer that is padded on purpose -- R rows, Bs frames -- keeps its padding inside the payload)
+  PR_TRY(device_alloc(&d, bytes, h->fence, frame_bytes, "smpl %s", name));
   h->allocs.push_back(d);
   PR_HIP(hipMemset(d, 0, bytes));
   if (!host.empty()) PR_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -700,9 +703,9 @@ int smpl_build(pr_smpl* h, const float* vt, const float* sd, const float* pd, co
     for (int p = 0; p < NP; ++p) pT[(size_t)p * R + r] = pd[(size_t)r * NP + p];
     for (int l = 0; l < NB; ++l) sT[(size_t)l * R + r] = sd[(size_t)r * NB + l];
   }
-  PR_TRY(smpl_upload(h, pT, &h->posedirs_T));
-  PR_TRY(smpl_upload(h, sT, &h->shapedirs_T));
-  PR_TRY(smpl_upload(h, vtp, &h->v_template));
+  PR_TRY(smpl_upload(h, "posedirs_T", (size_t)R * 4, pT, &h->posedirs_T));
+  PR_TRY(smpl_upload(h, "shapedirs_T", (size_t)R * 4, sT, &h->shapedirs_T));
+  PR_TRY(smpl_upload(h, "v_template", 0, vtp, &h->v_template));
   // joint regressor contracted with the template / shape directions in double
   std::vector<float> Jt(kJ * 3), Jd((size_t)kJ * 3 * std::max(NB, 1), 0.f);
   for (int j = 0; j < kJ; ++j)
@@ -716,11 +719,11 @@ int smpl_build(pr_smpl* h, const float* vt, const float* sd, const float* pd, co
         Jd[(size_t)(j * 3 + c) * NB + l] = (float)sl;
       }
     }
-  PR_TRY(smpl_upload(h, Jt, &h->J_template));
-  PR_TRY(smpl_upload(h, Jd, &h->J_dirs));
+  PR_TRY(smpl_upload(h, "J_template", 0, Jt, &h->J_template));
+  PR_TRY(smpl_upload(h, "J_dirs", 0, Jd, &h->J_dirs));
   std::vector<float> mbv(kMaxNB, 0.f);
   if (mb) std::copy(mb, mb + NB, mbv.begin());
-  PR_TRY(smpl_upload(h, mbv, &h->model_betas));
+  PR_TRY(smpl_upload(h, "model_betas", 0, mbv, &h->model_betas));
   // ELL skinning weights
   int nnz = 1;
   for (int v = 0; v < V; ++v) {
@@ -740,8 +743,8 @@ int smpl_build(pr_smpl* h, const float* vt, const float* sd, const float* pd, co
         ++k;
       }
   }
-  PR_TRY(smpl_upload(h, eidx, &h->ell_idx));
-  PR_TRY(smpl_upload(h, ew, &h->ell_w));
+  PR_TRY(smpl_upload(h, "ell_idx", (size_t)V * 4, eidx, &h->ell_idx));
+  PR_TRY(smpl_upload(h, "ell_w", (size_t)V * 4, ew, &h->ell_w));
   // kinematic tree
   for (int j = 0; j < kJ; ++j) h->tree.parent[j] = parents[j];
   h->tree.max_depth = 0;
@@ -757,18 +760,18 @@ int smpl_build(pr_smpl* h, const float* vt, const float* sd, const float* pd, co
   // workspaces
   const int Bs = ceil_div(h->max_batch, kFB) * kFB;
   h->Bs = Bs;
-  PR_TRY(smpl_upload(h, std::vector<float>((size_t)Bs * kJ * 12, 0.f), &h->A));
-  PR_TRY(smpl_upload(h, std::vector<float>((size_t)ceil_div(NP, 8) * 8 * Bs, 0.f), &h->pm_T));
-  PR_TRY(smpl_upload(h, std::vector<float>((size_t)kMaxNB * Bs, 0.f), &h->betas_T));
-  PR_TRY(smpl_upload(h, std::vector<float>((size_t)Bs * 3, 0.f), &h->voff));
-  PR_TRY(smpl_upload(h, std::vector<float>((size_t)Bs * kJ * 3, 0.f), &h->joints_tmp));
-  PR_TRY(smpl_upload(h, std::vector<int>(4, 0), &h->flags));
+  PR_TRY(smpl_upload(h, "A", (size_t)kJ * 12 * 4, std::vector<float>((size_t)Bs * kJ * 12, 0.f), &h->A));
+  PR_TRY(smpl_upload(h, "pm_T", (size_t)Bs * 4, std::vector<float>((size_t)ceil_div(NP, 8) * 8 * Bs, 0.f), &h->pm_T));
+  PR_TRY(smpl_upload(h, "betas_T", (size_t)Bs * 4, std::vector<float>((size_t)kMaxNB * Bs, 0.f), &h->betas_T));
+  PR_TRY(smpl_upload(h, "voff", 0, std::vector<float>((size_t)Bs * 3, 0.f), &h->voff));
+  PR_TRY(smpl_upload(h, "joints_tmp", (size_t)kJ * 3 * 4, std::vector<float>((size_t)Bs * kJ * 3, 0.f), &h->joints_tmp));
+  PR_TRY(smpl_upload(h, "flags", 0, std::vector<int>(4, 0), &h->flags));
   std::vector<int> tr(2 * kJ);
   for (int j = 0; j < kJ; ++j) {
     tr[j] = h->tree.parent[j];
     tr[kJ + j] = h->tree.depth[j];
   }
-  PR_TRY(smpl_upload(h, tr, &h->tree_dev));
+  PR_TRY(smpl_upload(h, "tree", 0, tr, &h->tree_dev));
   return PR_OK;
 }
 
@@ -856,10 +859,11 @@ int pr_smpl_create(int device, const float* v_template_host, const float* shaped
   std::unique_ptr<pr_smpl> h(new pr_smpl);
   h->device = device; h->V = V; h->NB = NB; h->NP = (kJ - 1) * 9; h->max_batch = max_batch;
   if (const char* e = getenv("POSERISK_SMPL_TILE")) h->tile = atoi(e) != 0;
+  h->fence = fence_mode_from_env();
   int st = smpl_build(h.get(), v_template_host, shapedirs_host, posedirs_host, J_regressor_host,
                       weights_host, parents_host, model_betas_host);
   if (st != PR_OK) {
-    for (void* p : h->allocs) (void)hipFree(p);
+    for (void* p : h->allocs) device_free(p);
     return st;
   }
   *out = h.release();
@@ -870,7 +874,7 @@ int pr_smpl_destroy(pr_smpl_t* h) {
   if (!h) return PR_OK;
   pr::DeviceGuard g(h->device);
   PR_TRY(pr::refuse_under_declared_capture("pr_smpl_destroy"));   // the handle stays valid: destroy it after the capture
-  for (void* p : h->allocs) (void)hipFree(p);
+  for (void* p : h->allocs) pr::device_free(p);
   delete h;
   return PR_OK;
 }

@@ -16,7 +16,12 @@ multiple of 256 bytes: a kernel that is one whole frame or one halo row off stil
 256-byte alignment of a torch allocation (pointer alignment is not what this tests; no kernel gets a less-aligned pointer).
 
 What the fence cannot see, by construction:
-  * the library's own workspaces, which the handles hipMalloc themselves: they cannot be fenced from outside;
+  * the library's own workspaces, which the handles hipMalloc themselves: they cannot be fenced from outside.  The
+    INTERNAL fence does that from inside (POSERISK_FENCE=1 | 2, csrc/fence.h, pr_fence_check; DESIGN.md 4.1;
+    tests/test_internal_fence_gpu.py): every allocation of the library's own between 0xFF guards, tensors in the buffers
+    that are sized as a maximum placed head- or tail-aligned.  What remains invisible to both fences:
+  * a buffer the internal fence leaves head-aligned in both modes (the split-K tickets; the max_batch-sized regressor and
+    SMPL workspaces unless max_batch == B): an access behind its tensor lands in the buffer's own slack;
   * an out-of-tensor READ whose value is discarded before it reaches an output (masked, multiplied away by a select, or
     dropped with a row >= M): only a value that takes part in an output shows;
   * an access further away than the guard (a wild pointer rather than an off-by-a-row).

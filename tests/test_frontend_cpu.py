@@ -222,6 +222,6 @@ def test_the_new_symbols_are_declared_and_bound_and_the_abi_stays_15():
     for name in ("pr_resize_plan", "pr_resize_frames"):
         assert re.search(r"\bint " + name + r"\(", header), name
         assert name in _lib.SIGNATURES and getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert lib.pr_abi_version() == 15 == _lib.ABI_VERSION
+    assert lib.pr_abi_version() == 16 == _lib.ABI_VERSION
     assert "PR_RESIZE_COPY = 0, PR_RESIZE_HALF = 1, PR_RESIZE_LINEAR = 2" in header
     assert (frontend.MODE_COPY, frontend.MODE_HALF, frontend.MODE_LINEAR) == (rr.MODE_COPY, rr.MODE_HALF, rr.MODE_LINEAR) == (0, 1, 2)

@@ -12,8 +12,9 @@ Each guarded call is checked three ways: the guards came back intact and the out
 (run_guarded); the outputs equal, bit for bit, the same call on plain tensors (placement must not change arithmetic); and
 they meet the reference and tolerance of the entry's own parity test (tests/kernel_refs.py holds what both share).
 
-Out of the fence's reach: the handles' internal workspaces (hipMalloc'ed inside the library), and reads outside a tensor
-whose value never reaches an output (guard_band.py's docstring)."""
+Out of this fence's reach: the handles' internal workspaces (hipMalloc'ed inside the library; the internal fence of
+tests/test_internal_fence_gpu.py covers them), and reads outside a tensor whose value never reaches an output
+(guard_band.py's docstring)."""
 import numpy as np
 import pytest
 import torch

@@ -57,7 +57,7 @@ def test_new_symbols_are_declared_bound_and_the_abi_stays_15():
     lib = _lib.load()
     for name in ("pr_jpeg_parse", "pr_jpeg_refusal_name", "pr_jpeg_workspace_bytes", "pr_jpeg_decode"):
         assert re.search(r"\b" + name + r"\s*\(", hdr) and name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.pr_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.pr_abi_version() == _lib.ABI_VERSION == 16
     # the binding's records are the header's structs
     assert jpeg.FRAME_DTYPE.itemsize == 15 * 4 + 3 * 64 * 2 and jpeg.SEGMENT_DTYPE.itemsize == 24
     assert jpeg.HUFF_DTYPE.itemsize == 4 * (1024 + 68 + 68 + 256 + 4)

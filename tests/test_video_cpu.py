@@ -192,7 +192,7 @@ def test_compose_abi_and_argument_errors():
     assert re.search(r"\bint\s+pr_compose_video\s*\(\s*const\s+pr_compose_args\s*\*", hdr)
     assert "pr_compose_video" in _lib.SIGNATURES
     lib = _lib.load()
-    assert lib.pr_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.pr_abi_version() == _lib.ABI_VERSION == 16
     msg = lambda: lib.pr_last_error().decode()
     buf = np.zeros(64, np.uint8)
     p = buf.ctypes.data                                            # never dereferenced: every call below is refused first
