@@ -679,6 +679,47 @@ typedef struct pr_jpeg_args {
 } pr_jpeg_args;
 int pr_jpeg_decode(const pr_jpeg_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same decode with the entropy stage run in parallel INSIDE a restart segment (csrc/jpeg_sync.hip):
+ * what a frame without restart markers -- cv2.imwrite's, ffmpeg's, a camera's -- needs, being one serial chain on one lane for
+ * pr_jpeg_decode.  Every segment is cut into sub-sequences of subseq_bytes raw bytes (cuts at begin + i * subseq_bytes; a
+ * segment shorter than that is one), one lane each.  A decoder's state is (position of the next unread bit, never inside a
+ * stuffed 00; block slot within the MCU; next zig-zag index) or DEAD (after a code no table holds or a symbol that reaches
+ * behind the data's end; in the result it propagates to the segment's later sub-sequences, during the rounds a sub-sequence
+ * behind a DEAD one decodes from its own guess, so that those behind it can still synchronise; a run past 63 ends the block
+ * with PR_JPEG_ST_BAD_RUN as for pr_jpeg_decode).  A cold pass decodes every
+ * sub-sequence from (its first bit, 0, 0), skipping a first byte that is the 00 of an FF 00 pair, to the first symbol boundary
+ * at or behind its end and keeps the exit state, the blocks begun and completed and the DC differences' sum per component; up
+ * to max_rounds rounds (one launch each, states ping-ponged) decode it again from the previous sub-sequence's exit of the
+ * round before where that changed.  A frame is converged at the first round in which no exit changed -- by induction from a
+ * segment's first sub-sequence every entry state is then the serial decoder's -- and later rounds skip it; round 1 counts
+ * every sub-sequence from a segment's third on as changed (its entry was a guess's exit), so a frame with more than two
+ * sub-sequences in a segment converges at round 2 at the earliest.  Prefix sums per segment then give every sub-sequence its
+ * first block's ordinal and DC predictions, and a write pass decodes once more and scatters the coefficients to the addresses
+ * pr_jpeg_decode uses, up to the segment's block count (bytes behind the last MCU are not looked at, as there).  A frame not
+ * converged after max_rounds is decoded by pr_jpeg_decode's kernel instead, on the device (fell_back = 1): correctness never
+ * depends on synchronisation having happened.  The IDCT and colour stages are pr_jpeg_decode's.
+ *
+ * Contract.  The memory-safety paragraph above holds unchanged on any bytes (the state arrays live in the workspace and are
+ * written by the kernels only; every block address comes from an ordinal below the segment's block count).  Where
+ * pr_jpeg_decode ends with status 0 this entry gives the same pixels and status 0, for every accepted subseq_bytes and
+ * max_rounds and whether or not the frame fell back.  Where pr_jpeg_decode ends with a non-zero status so does this entry;
+ * which bits are set, and the pixels, are not promised (nothing behind a code no table holds is written here; a segment
+ * that completes fewer blocks than it holds gets PR_JPEG_ST_TRUNCATED).
+ *
+ * opts NULL takes the build's defaults (128 bytes, 16 rounds unless pr_build_info says otherwise).  subseq_bytes: a multiple
+ * of 4 in 16..4096, or 0 for the default; max_rounds: 1..64 (0 is an error: a caller that passes opts names its rounds).  stats: device, [F], may be NULL; n_subseq = the sum over the
+ * frame's segments of ceil(length / subseq_bytes), rounds = the round at which the frame converged, or max_rounds when it fell
+ * back.  pr_jpeg_sync_workspace_bytes is what the call needs for these sizes and options (0 for invalid ones): pr_jpeg_decode's
+ * workspace plus 60 bytes per sub-sequence, of which there are at most data_bytes / subseq_bytes + n_segments + 1.  Otherwise
+ * the rules are pr_jpeg_decode's: all device pointers, a 16-byte aligned workspace, asynchronous on `stream`, no allocation, no
+ * blocking copy, no synchronisation (capturable), argument errors return PR_ERR_INVALID by name before any device work, F = 0
+ * returns PR_OK.  No ABI bump: functions were added. */
+typedef struct pr_jpeg_sync_opts { int32_t subseq_bytes, max_rounds; } pr_jpeg_sync_opts;  /* subseq_bytes 0 = the build's default */
+typedef struct pr_jpeg_sync_stats { int32_t n_subseq, rounds, fell_back, reserved; } pr_jpeg_sync_stats; /* per frame */
+size_t pr_jpeg_sync_workspace_bytes(int F, int H, int W, int64_t data_bytes, int n_segments, const pr_jpeg_sync_opts* opts);
+int pr_jpeg_decode_sync(const pr_jpeg_args* args, const pr_jpeg_sync_opts* opts, pr_jpeg_sync_stats* stats, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* j2  u8[F,H,W,3] on the device -> baseline JPEG files, byte-exact with libjpeg          */
 /* replaces: cv2.VideoWriter / one PNG per frame behind the composed canvases             */

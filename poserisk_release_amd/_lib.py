@@ -51,6 +51,12 @@ class JpegArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "n_segments", "n_huff", "bgr")]
 
 
+class JpegSyncOpts(C.Structure):
+    """pr_jpeg_sync_opts (include/poserisk_hip.h, pr_jpeg_decode_sync): subseq_bytes 0 = the build's default; max_rounds is 1..64
+    (0 is an error: pass no opts at all for both defaults)."""
+    _fields_ = [("subseq_bytes", C.c_int32), ("max_rounds", C.c_int32)]
+
+
 class JpegEncArgs(C.Structure):
     """pr_jpeg_enc_args (include/poserisk_hip.h, the JPEG encoder)."""
     _fields_ = [(n, C.c_void_p) for n in ("frames", "plan", "out", "nbytes", "status")] + [("capacity", C.c_int64)] + \
@@ -116,6 +122,8 @@ SIGNATURES = {
     "pr_jpeg_refusal_name": (C.c_char_p, [_I]),
     "pr_jpeg_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pr_jpeg_decode": (_I, [C.POINTER(JpegArgs), _P, C.c_size_t, _P]),
+    "pr_jpeg_sync_workspace_bytes": (C.c_size_t, [_I, _I, _I, C.c_int64, _I, C.POINTER(JpegSyncOpts)]),
+    "pr_jpeg_decode_sync": (_I, [C.POINTER(JpegArgs), C.POINTER(JpegSyncOpts), _P, _P, C.c_size_t, _P]),
     "pr_jpeg_encode_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pr_jpeg_encode_bound": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_jpeg_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, C.c_int64]),

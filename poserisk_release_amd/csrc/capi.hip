@@ -53,7 +53,17 @@ const char* pr_build_info(void) {
 #ifdef PR_EXPERIMENT
          " +PR_EXPERIMENT=" PR_STR(PR_EXPERIMENT)
 #endif
-#if !defined(PR_TIMING_HOOKS) && !defined(PR_EXPERIMENT)
+#ifdef PR_JPEG_SYNC_SUBSEQ_BYTES
+         " +PR_JPEG_SYNC_SUBSEQ_BYTES=" PR_STR(PR_JPEG_SYNC_SUBSEQ_BYTES)
+#endif
+#ifdef PR_JPEG_SYNC_MAX_ROUNDS
+         " +PR_JPEG_SYNC_MAX_ROUNDS=" PR_STR(PR_JPEG_SYNC_MAX_ROUNDS)
+#endif
+#ifdef PR_JPEG_SYNC_WAVES_PER_CU
+         " +PR_JPEG_SYNC_WAVES_PER_CU=" PR_STR(PR_JPEG_SYNC_WAVES_PER_CU)
+#endif
+#if !defined(PR_TIMING_HOOKS) && !defined(PR_EXPERIMENT) && !defined(PR_JPEG_SYNC_SUBSEQ_BYTES) && \
+    !defined(PR_JPEG_SYNC_MAX_ROUNDS) && !defined(PR_JPEG_SYNC_WAVES_PER_CU)
          " release"
 #endif
       ;

@@ -16,6 +16,7 @@
 //            planes, YCbCr -> RGB, crop to H x W.
 // Kernels index by thread only: no LDS, no barrier, no cross-lane operation, plain C++ and vector stores.
 #include "common.h"
+#include "jpeg_device.h"
 
 namespace pr {
 namespace {
@@ -32,139 +33,6 @@ constexpr int kEntropyThreads = 64;   // one wave a workgroup
 constexpr int kEntropyWavesPerCu = PR_JPEG_ENTROPY_WAVES_PER_CU;
 constexpr int kThreads = 256;
 
-static __device__ const unsigned char kZigzagNatural[64] = {
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct JpegParams {
-  pr_jpeg_args a;
-  short* coef;             // [F][cs] int16, natural order inside a block, blocks row-major per component
-  unsigned char* planes;   // [F][cs] u8, component planes at block-padded size
-  long cs;                 // samples per frame in either: 3 * roundup(W, 16) * roundup(H, 16)
-  int out_aligned;         // out is 4-byte aligned: the colour kernel stores dwords
-  int lanes;               // segments per wave of the entropy kernel, 1..64
-};
-
-// Where a frame's components live inside its cs samples; the same offsets serve coefficients and planes.
-struct Geometry {
-  int mx, my;          // MCUs across and down
-  int bw[3], bh[3];    // blocks across and down per component
-  long off[3];         // first sample per component
-};
-
-// Every descriptor field that later forms an address or a loop bound.  A frame that fails is never decoded: its pixels are zero
-// and its status PR_JPEG_ST_REFUSED.
-__device__ __forceinline__ bool frame_ok(const pr_jpeg_frame& f, const pr_jpeg_args& a) {
-  if (f.width != a.W || f.height != a.H) return false;
-  if (f.ncomp != 1 && f.ncomp != 3) return false;
-  const bool s11 = f.hs == 1 && f.vs == 1, s21 = f.hs == 2 && f.vs == 1, s22 = f.hs == 2 && f.vs == 2;
-  if (!(s11 || (f.ncomp == 3 && (s21 || s22)))) return false;
-  if ((unsigned)f.huff_set >= (unsigned)a.n_huff || f.restart_interval < 0) return false;
-  for (int c = 0; c < 3; ++c)
-    if ((unsigned)f.dc_sel[c] > 1u || (unsigned)f.ac_sel[c] > 1u) return false;
-  return true;
-}
-
-__device__ __forceinline__ Geometry geometry(const pr_jpeg_frame& f) {   // of a frame that passed frame_ok
-  Geometry g;
-  g.mx = (f.width + 8 * f.hs - 1) / (8 * f.hs);
-  g.my = (f.height + 8 * f.vs - 1) / (8 * f.vs);
-  g.bw[0] = g.mx * f.hs;
-  g.bh[0] = g.my * f.vs;
-  g.bw[1] = g.bw[2] = g.mx;
-  g.bh[1] = g.bh[2] = g.my;
-  g.off[0] = 0;
-  g.off[1] = (long)g.bw[0] * g.bh[0] * 64;
-  g.off[2] = g.off[1] + (long)g.mx * g.my * 64;   // <= 3 roundup(W,16) roundup(H,16) - mx my 64 for every accepted sampling
-  return g;
-}
-
-// ---- entropy decoding -----------------------------------------------------------------------------------------------------
-// The bit reader of one segment.  acc holds cnt valid bits in its low end; `pad` of them (the lowest) are zeros made up
-// because the data ended: consuming one of those sets PR_JPEG_ST_TRUNCATED.  pos never leaves [begin, end].  A refill takes four
-// bytes with one load where none of them is 0xFF (the common case: an encoder's output is close to uniform bytes) and goes
-// byte by byte, unstuffing, otherwise and at the segment's end.
-struct Bits {
-  const unsigned char* data;
-  long pos, end;
-  unsigned long long acc;
-  int cnt, pad;
-  bool ended;
-  int st;
-};
-
-__device__ __forceinline__ void fill(Bits& b) {
-  if (b.cnt > 24) return;
-  if (!b.ended && b.pos + 4 <= b.end) {
-    unsigned w;
-    __builtin_memcpy(&w, b.data + b.pos, 4);                 // any alignment
-    if (((~w - 0x01010101u) & w & 0x80808080u) == 0u) {      // no byte of w is 0xFF
-      b.acc = (b.acc << 32) | __builtin_bswap32(w);
-      b.cnt += 32;
-      b.pos += 4;
-      return;
-    }
-  }
-  while (b.cnt <= 24) {
-    unsigned byte = 0u;
-    if (!b.ended && b.pos < b.end) {
-      byte = b.data[b.pos];
-      if (byte == 0xFFu) {
-        if (b.pos + 1 < b.end && b.data[b.pos + 1] == 0u) {
-          b.pos += 2;                 // a stuffed 0xFF
-        } else {
-          b.ended = true;             // a marker, fill bytes or a lone 0xFF at the end: no data behind it
-          byte = 0u;
-        }
-      } else {
-        ++b.pos;
-      }
-    } else {
-      b.ended = true;
-    }
-    if (b.ended) b.pad += 8;
-    b.acc = (b.acc << 8) | byte;
-    b.cnt += 8;
-  }
-}
-
-__device__ __forceinline__ unsigned peek(const Bits& b, int n) {   // 1 <= n <= 16 <= cnt
-  return (unsigned)(b.acc >> (b.cnt - n)) & ((1u << n) - 1u);
-}
-
-__device__ __forceinline__ void consume(Bits& b, int n) {
-  b.cnt -= n;
-  if (b.cnt < b.pad) {
-    b.st |= PR_JPEG_ST_TRUNCATED;
-    b.pad = b.cnt;
-  }
-}
-
-// The next Huffman symbol, or -1 when no code of the table matches.
-__device__ __forceinline__ int next_symbol(Bits& b, const pr_jpeg_hufftab& t) {
-  fill(b);
-  const unsigned e = t.look[peek(b, PR_JPEG_LOOK_BITS)];
-  if (e) {
-    consume(b, (int)(e >> 8) & 15);
-    return (int)(e & 255u);
-  }
-  for (int l = PR_JPEG_LOOK_BITS + 1; l <= 16; ++l) {
-    const int code = (int)peek(b, l);
-    if (code <= t.maxcode[l]) {
-      consume(b, l);
-      return t.vals[(t.valoff[l] + code) & 255];
-    }
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int receive_extend(Bits& b, int s) {   // 1 <= s <= 15
-  fill(b);
-  const int r = (int)peek(b, s);
-  consume(b, s);
-  return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r;
-}
-
 __global__ void __launch_bounds__(kEntropyThreads) jpeg_entropy_kernel(JpegParams p) {
   const pr_jpeg_args& a = p.a;
   const int t = (int)blockIdx.x * p.lanes + (int)threadIdx.x;
@@ -173,6 +41,7 @@ __global__ void __launch_bounds__(kEntropyThreads) jpeg_entropy_kernel(JpegParam
   if ((unsigned)sg.frame >= (unsigned)a.F) return;               // belongs to no frame of this call
   const pr_jpeg_frame& fr = a.frames[sg.frame];
   if (!frame_ok(fr, a)) return;                                   // the colour kernel reports it
+  if (p.gate && !p.gate[sg.frame].fell_back) return;             // pr_jpeg_decode_sync: the sub-sequence kernels decoded it
   const Geometry g = geometry(fr);
   const int total = g.mx * g.my;
   if (sg.begin < 0 || sg.end > a.data_bytes || sg.begin > sg.end || sg.first_mcu < 0 || sg.first_mcu >= total) {
@@ -198,6 +67,7 @@ __global__ void __launch_bounds__(kEntropyThreads) jpeg_entropy_kernel(JpegParam
   b.pad = 0;
   b.ended = false;
   b.st = 0;
+  b.marks = 0u;
   int pred[3] = {0, 0, 0};
   int mxi = sg.first_mcu % g.mx, myi = sg.first_mcu / g.mx;
   bool dead = false;
@@ -438,9 +308,25 @@ __global__ void __launch_bounds__(kThreads) jpeg_colour_kernel(JpegParams p) {
   }
 }
 
-inline long padded_samples(int H, int W) { return 3l * ((W + 15) & ~15) * ((H + 15) & ~15); }
-
 }  // namespace
+
+int jpeg_launch_serial_entropy(const JpegParams& params, hipStream_t s) {
+  if (params.a.n_segments <= 0) return PR_OK;
+  JpegParams p = params;
+  int cus = 0;
+  PR_TRY(current_device_cus(&cus));
+  p.lanes = std::min(kEntropyThreads, std::max(1, ceil_div(p.a.n_segments, cus * kEntropyWavesPerCu)));
+  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)ceil_div(p.a.n_segments, p.lanes)), dim3(kEntropyThreads), 0, s, p);
+  return check_launch("jpeg_entropy_kernel");
+}
+
+int jpeg_launch_back_end(const JpegParams& p, hipStream_t s) {
+  const long quads = ceil_div((long)p.a.F * p.a.H * p.a.W, 4l);
+  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)ceil_div(p.cs / 64, (long)kThreads), (unsigned)p.a.F), dim3(kThreads), 0, s, p);
+  PR_TRY(check_launch("jpeg_idct_kernel"));
+  hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)ceil_div(quads, (long)kThreads)), dim3(kThreads), 0, s, p);
+  return check_launch("jpeg_colour_kernel");
+}
 }  // namespace pr
 
 extern "C" size_t pr_jpeg_workspace_bytes(int F, int H, int W) {
@@ -477,20 +363,12 @@ extern "C" int pr_jpeg_decode(const pr_jpeg_args* a, void* workspace, size_t wor
   p.cs = padded_samples(a->H, a->W);
   p.out_aligned = ((uintptr_t)a->out & 3) == 0;
   p.lanes = 1;
+  p.gate = nullptr;
   p.coef = (short*)workspace;
   p.planes = (unsigned char*)workspace + (size_t)a->F * p.cs * 2;
   hipStream_t s = (hipStream_t)stream;
   PR_HIP(hipMemsetAsync(p.coef, 0, (size_t)a->F * p.cs * 2, s));
   PR_HIP(hipMemsetAsync(a->status, 0, (size_t)a->F * sizeof(int32_t), s));
-  if (a->n_segments > 0) {
-    int cus = 0;
-    PR_TRY(current_device_cus(&cus));
-    p.lanes = std::min(kEntropyThreads, std::max(1, ceil_div(a->n_segments, cus * kEntropyWavesPerCu)));
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)ceil_div(a->n_segments, p.lanes)), dim3(kEntropyThreads), 0, s, p);
-    PR_TRY(check_launch("jpeg_entropy_kernel"));
-  }
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)ceil_div(p.cs / 64, (long)kThreads), (unsigned)a->F), dim3(kThreads), 0, s, p);
-  PR_TRY(check_launch("jpeg_idct_kernel"));
-  hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)ceil_div(quads, (long)kThreads)), dim3(kThreads), 0, s, p);
-  return check_launch("jpeg_colour_kernel");
+  PR_TRY(jpeg_launch_serial_entropy(p, s));
+  return jpeg_launch_back_end(p, s);
 }

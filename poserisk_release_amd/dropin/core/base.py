@@ -563,7 +563,7 @@ class Predictor:
             names = jpeg.list_frames(input_path)
             if names:
                 paths = [osp.join(input_path, n) for n in names]
-                frames, status = jpeg.decode_files(paths, self.device)
+                frames, status = jpeg.decode_files(paths, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
                 bad = jpeg.bad_frames(paths, status)
                 if bad:
                     raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
@@ -626,7 +626,8 @@ class Predictor:
         import shutil
         from poserisk_release_amd import frontend, jpeg
         frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
-                                          max_h=cfg.DATASET.get('front_max_h', 450))
+                                          max_h=cfg.DATASET.get('front_max_h', 450),
+                                          entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
         if tracking_results is not None:
             return frames, False, fps, tracking_results
         sidecar = osp.splitext(input_path)[0] + '.tracking.pkl'
@@ -649,7 +650,7 @@ class Predictor:
             tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
                           output_format='dict', yolo_img_size=416)
             tracking = tracker(image_path)
-            frames, status = jpeg.decode_files(files, self.device)
+            frames, status = jpeg.decode_files(files, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
             bad = jpeg.bad_frames(files, status)
             if bad:
                 raise RuntimeError(f"{image_path!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")

@@ -81,10 +81,15 @@ def resize_frames(frames, h, w, out=None):
     return out
 
 
-def chunk_frames(H, W, max_bytes):
+def chunk_frames(H, W, max_bytes, frame_bytes=0):
     """Frames decoded per call: the largest count <= 1024 whose source-size pixels plus decoder workspace fit max_bytes; at
-    least 1."""
-    need = lambda n: n * H * W * 3 + jpeg.workspace_bytes(n, H, W)
+    least 1.  frame_bytes > 0 (the largest file of the video) sizes the workspace as pr_jpeg_decode_sync needs it, which keeps
+    60 bytes per 128 compressed bytes and per restart segment (at most one per row of blocks assumed) on top."""
+    if frame_bytes:
+        space = lambda n: jpeg.sync_workspace_bytes(n, H, W, n * frame_bytes, n * ((H + 7) // 8 + 1))
+    else:
+        space = lambda n: jpeg.workspace_bytes(n, H, W)
+    need = lambda n: n * H * W * 3 + space(n)
     n = max(1, min(MAX_CHUNK, int(max_bytes) // max(need(1), 1)))      # the workspace grows with the frame count, in steps at most
     while n > 1 and need(n) > max_bytes:
         n -= 1
@@ -99,11 +104,12 @@ def _raise_refused(path, part, lo, H, W, fallback):
     raise RuntimeError(f"{path!r}: frames {lo}..{lo + len(part) - 1} cannot be decoded: {fallback}")
 
 
-def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30):
+def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, entropy="auto"):
     """A Motion-JPEG AVI -> (frames u8[F,h,w,3] on `device`, fps): demuxed on the host, decoded on the GPU at the source size,
     chunk by chunk into one reused buffer, each chunk downscaled into its slice of the result ((w, h) = target_size of the first
     frame's own size).  RGB, or BGR with bgr=True.  A refused or damaged frame raises RuntimeError naming its index in the file
-    and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made."""
+    and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made.
+    `entropy` is jpeg.decode_files' ("auto" | "serial" | "sync")."""
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.PoseRiskHipError("read_video: decoding and resizing run on the GPU only (no CPU fallback)")
@@ -122,7 +128,7 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
     if h < 1 or w < 1:
         raise ValueError(f"{path!r}: {W} x {H} frames would become {w} x {h}")
     same = (h, w) == (H, W)
-    n = min(chunk_frames(H, W, int(max_bytes)), F)
+    n = min(chunk_frames(H, W, int(max_bytes), 0 if entropy == "serial" else max(map(len, blobs))), F)
     with torch.cuda.device(device):
         result = torch.empty((F, h, w, 3), dtype=torch.uint8, device=device)
         buffer = None if same else torch.empty((n, H, W, 3), dtype=torch.uint8, device=device)
@@ -131,7 +137,7 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
             m = len(part)
             into = result[lo:lo + m] if same else buffer[:m]
             try:
-                _, status = jpeg.decode_files(part, device, bgr=bgr, chunk=m, out=into)
+                _, status = jpeg.decode_files(part, device, bgr=bgr, chunk=m, out=into, entropy=entropy)
             except (ValueError, _lib.PoseRiskHipError) as e:     # the chunk's first accepted frame has another size, or none was accepted
                 _raise_refused(path, part, lo, H, W, str(e))
             bad = jpeg.bad_frames(part, status)

@@ -29,11 +29,12 @@ ST_REFUSED, ST_TRUNCATED, ST_BAD_RUN, ST_BAD_CODE, ST_IDCT_RANGE, ST_COEF_RANGE 
 _ST_NAMES = ((ST_REFUSED, "refused (descriptor or segment range invalid)"), (ST_TRUNCATED, "entropy-coded data ends early"),
              (ST_BAD_RUN, "a zero run leaves the block"), (ST_BAD_CODE, "a Huffman code no table holds"),
              (ST_IDCT_RANGE, "coefficients outside the 32-bit IDCT bound"), (ST_COEF_RANGE, "a DC value outside int16"))
-# Frames per pr_jpeg_decode call, from profiles/jpeg_decode.json (MI355X, 800x450 4:2:0 quality 95, scripts/bench_jpeg.py).  A frame
-# without restart markers -- what cv2.imwrite writes -- is one serial chain on one lane and takes 112 ms whether 64 or 256 of
-# them are in flight, so the rate is the chunk: decode_files gives 571 / 2220 / 5142 frames/s at 64 / 256 / 1024 (Pillow on 16
-# threads: 2033).  Frames with a restart marker per MCU row peak at 256 (18.9 k, 13.3 k at 1024, where one chunk is the whole
-# measured list and nothing overlaps), far above the CPU either way: the restart-free case decides.  Workspace 3.3 MB a frame.
+# Frames per decode call.  1024 was chosen for pr_jpeg_decode, for which a frame without restart markers -- what cv2.imwrite
+# writes -- is one serial chain on one lane, 112 ms whether 64 or 256 of them are in flight, so that the rate was the chunk
+# (571 / 2220 / 5142 frames/s at 64 / 256 / 1024; Pillow on 16 threads: 2033).  entropy="auto" now decodes such frames with
+# pr_jpeg_decode_sync: decode_files gives 13.2 k / 25.2 k / 19.1 k frames/s at 64 / 256 / 1024 (profiles/jpeg_decode.json,
+# DESIGN.md section 3.9), so the large chunk is no longer needed and 256 would be faster; the default is left where it was in
+# this change.  Workspace 3.3 MB a frame.
 DEFAULT_CHUNK = 1024
 _EXT = (".jpg", ".jpeg")
 # pr_jpeg_enc_plan as a numpy record
@@ -102,17 +103,42 @@ def workspace_bytes(F, H, W):
     return int(_lib.load().pr_jpeg_workspace_bytes(int(F), int(H), int(W)))
 
 
+ENTROPY = ("auto", "serial", "sync")
+SYNC_STATS_DTYPE = np.dtype([("n_subseq", "<i4"), ("rounds", "<i4"), ("fell_back", "<i4"), ("reserved", "<i4")])   # pr_jpeg_sync_stats
+
+
+def _sync_opts(sync_opts):
+    """None (the build's defaults) or (subseq_bytes, max_rounds) -> what pr_jpeg_decode_sync takes."""
+    if sync_opts is None:
+        return None
+    S, R = sync_opts
+    return _lib.JpegSyncOpts(int(S), int(R))
+
+
+def sync_workspace_bytes(F, H, W, data_bytes, n_segments, sync_opts=None):
+    """Device memory a pr_jpeg_decode_sync call needs (0 for sizes or options it refuses): workspace_bytes(F, H, W) plus the
+    sub-sequences' states.  sync_opts: None, or (subseq_bytes, max_rounds)."""
+    return int(_lib.load().pr_jpeg_sync_workspace_bytes(int(F), int(H), int(W), int(data_bytes), int(n_segments), _sync_opts(sync_opts)))
+
+
 def _align(n, a=256):
     return (n + a - 1) // a * a
 
 
-def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None):
+def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, entropy="auto", stats=False, sync_opts=None):
     """Decode F baseline JPEG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread
     gives with bgr=True).  Returns (frames, status int32[F] on the device): status[f] != 0 marks a frame that was refused
     (bit 0; its pixels are zero) or whose stream was damaged; `bad_frames` puts the reasons into words.  Per chunk of `chunk`
     files the bytes are read into ONE pinned host buffer, the parser writes its descriptors behind them in the same buffer, and
     ONE asynchronous copy uploads it; the decode neither allocates nor synchronises (include/poserisk_hip.h, pr_jpeg_decode).
-    The host waits for chunk k's upload (not its decode) before it reads chunk k + 1 into the buffer."""
+    The host waits for chunk k's upload (not its decode) before it reads chunk k + 1 into the buffer.
+    `entropy`: "serial" decodes with one lane per restart segment (pr_jpeg_decode), "sync" with one lane per sub-sequence of a
+    segment (pr_jpeg_decode_sync: what frames without restart markers need), "auto" picks per chunk: sync where any accepted
+    frame of the chunk has no restart interval, serial otherwise.  `sync_opts` = (subseq_bytes, max_rounds) instead of the
+    build's defaults.  stats=True returns (frames, status, stats): a SYNC_STATS_DTYPE int32[F, 4] tensor on the device, per
+    frame (n_subseq, rounds, fell_back, 0); all zero for frames of a chunk that went the serial way."""
+    if entropy not in ENTROPY:
+        raise ValueError(f"decode_files: entropy = {entropy!r}: one of {ENTROPY}")
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.PoseRiskHipError("decode_files: the decoder runs on the GPU only (no CPU fallback)")
@@ -122,7 +148,8 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     F, chunk = len(items), max(int(chunk), 1)
     lib = _lib.load()
     H, W, seg_per_frame = 0, 0, 2
-    frames_out = status = pinned = ws = uploaded = first_refusal = None
+    frames_out = status = pinned = ws = uploaded = first_refusal = sync_stats = None
+    opts = _sync_opts(sync_opts)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device)
         for lo in range(0, F, chunk):
@@ -180,6 +207,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
                         or frames_out.device != device:
                     raise ValueError(f"out must be a contiguous uint8 {[F, H, W, 3]} tensor on {device}")
                 status = torch.full((F,), ST_REFUSED, dtype=torch.int32, device=device)   # chunks before the first size
+                sync_stats = torch.zeros((F, 4), dtype=torch.int32, device=device) if stats else None
                 frames_out[:lo].zero_()
             if H == 0:
                 continue                                         # nothing accepted so far: no size to decode at
@@ -188,13 +216,22 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             dev.copy_(pinned[:used], non_blocking=True)          # the chunk's one upload
             uploaded = torch.cuda.Event()
             uploaded.record(stream)
-            need = workspace_bytes(n, H, W)
+            ok = fr[pst == 0]
+            sync = entropy == "sync" or (entropy == "auto" and bool((ok["restart_interval"] == 0).any()))
+            need = sync_workspace_bytes(n, H, W, total, n_segs, sync_opts) if sync else workspace_bytes(n, H, W)
+            if sync and need == 0:
+                raise _lib.PoseRiskHipError(f"decode_files: sync_opts = {sync_opts!r}: subseq_bytes is a multiple of 4 in 16..4096 "
+                                            "(or 0 for the default), max_rounds 1..64")
             if ws is None or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.uint8, device=device)
             base = dev.data_ptr()
             args = _lib.JpegArgs(base, base + o_fr, base + o_seg, base + o_huff, frames_out[lo:lo + n].data_ptr(),
                                  status[lo:lo + n].data_ptr(), total, n, H, W, n_segs, n_huff, int(bool(bgr)))
-            _lib.check(lib.pr_jpeg_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode")
+            if sync:
+                st_ptr = sync_stats[lo:lo + n].data_ptr() if stats else None
+                _lib.check(lib.pr_jpeg_decode_sync(args, opts, st_ptr, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode_sync")
+            else:
+                _lib.check(lib.pr_jpeg_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode")
             dev.record_stream(stream)
             ws.record_stream(stream)
         if uploaded is not None:
@@ -204,7 +241,8 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             raise _lib.PoseRiskHipError(f"decode_files: no frame was accepted; frame {first_refusal[0]}: {first_refusal[1]}")
         frames_out = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
         status = torch.zeros(0, dtype=torch.int32, device=device)
-    return frames_out, status
+        sync_stats = torch.zeros((0, 4), dtype=torch.int32, device=device)
+    return (frames_out, status, sync_stats) if stats else (frames_out, status)
 
 
 def bad_frames(paths_or_bytes, status):

@@ -136,17 +136,21 @@ def main():
                 demux.append(time.perf_counter() - t0)
             assert got == blobs
             chunk = min(frontend.chunk_frames(H, W, 16 << 30), N_FRAMES)
-            buf = torch.empty((N_FRAMES, H, W, 3), dtype=torch.uint8, device=dev)
-            jpeg.decode_files(got, dev, chunk=chunk, out=buf)
-            decode = best_of(lambda: jpeg.decode_files(got, dev, chunk=chunk, out=buf))
-            del buf
-            torch.cuda.empty_cache()
-            frontend.read_video(path, dev)
-            e2e = best_of(lambda: frontend.read_video(path, dev))
             r = dict(file_bytes=os.path.getsize(path), compressed_bytes_per_frame=sum(map(len, distinct)) // DISTINCT, chunk=chunk,
-                     demux_ms=[round(t * 1e3, 2) for t in demux], decode_ms=[round(t * 1e3, 2) for t in decode],
-                     decode_frames_per_s=round(N_FRAMES / min(decode), 1), end_to_end_ms=[round(t * 1e3, 2) for t in e2e],
-                     end_to_end_frames_per_s=round(N_FRAMES / min(e2e), 1))
+                     demux_ms=[round(t * 1e3, 2) for t in demux])
+            for entropy in ("serial", "sync"):                   # the two entropy stages side by side, the same frames
+                buf = torch.empty((N_FRAMES, H, W, 3), dtype=torch.uint8, device=dev)
+                _, _, stats = jpeg.decode_files(got, dev, chunk=chunk, out=buf, entropy=entropy, stats=True)
+                decode = best_of(lambda: jpeg.decode_files(got, dev, chunk=chunk, out=buf, entropy=entropy))
+                del buf
+                torch.cuda.empty_cache()
+                frontend.read_video(path, dev, entropy=entropy)
+                e2e = best_of(lambda: frontend.read_video(path, dev, entropy=entropy))
+                r[entropy] = dict(decode_ms=[round(t * 1e3, 2) for t in decode], decode_frames_per_s=round(N_FRAMES / min(decode), 1),
+                                  end_to_end_ms=[round(t * 1e3, 2) for t in e2e], end_to_end_frames_per_s=round(N_FRAMES / min(e2e), 1))
+                if entropy == "sync":
+                    st = stats[:DISTINCT].cpu().numpy()
+                    r[entropy].update(rounds=sorted(int(v) for v in st[:, 1]), fell_back=int(st[:, 2].sum()))
             if variant == "no_restart":
                 r["pillow_16_threads"] = measure_pillow(blobs, h, w)
             record["variants"][variant] = r

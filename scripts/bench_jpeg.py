@@ -1,5 +1,8 @@
-"""Measure the JPEG decoder (pr_jpeg_decode, csrc/jpeg.hip) on 800x450 4:2:0 quality-95 frames -- what cv2.imwrite writes, the
-streams of tests/golden/jpeg_frames.npz -- with and without restart markers:
+"""Measure the JPEG decoder on 800x450 4:2:0 quality-95 frames -- what cv2.imwrite writes, the streams of
+tests/golden/jpeg_frames.npz -- with and without restart markers, with the entropy stage both ways side by side in one run:
+"serial" (pr_jpeg_decode, csrc/jpeg.hip: one lane per restart segment) and "sync" (pr_jpeg_decode_sync, csrc/jpeg_sync.hip: one
+lane per sub-sequence; the rows carry the frames' rounds and how many fell back; `--sync-sweep 64,128,256` adds rows at other
+sub-sequence sizes with 64 rounds allowed, from which the defaults were chosen):
 
   decode      frames/s of pr_jpeg_decode alone from device events (descriptors and bytes already on the device), at chunk sizes
               64, 256 and 1024, warmed up, windows of at least a second, the whole list run twice in the same process;
@@ -14,7 +17,8 @@ python scripts/bench_jpeg.py --trace-run --variant V` for per-kernel times, then
 adds them, each against its byte floor, to the JSON.  The timed frames are DISTINCT different frames in rotation (see streams).
 
 usage: python scripts/bench_jpeg.py [--out profiles/jpeg_decode.json] [--chunks 64,256,1024] [--skip-e2e] [--decode-only]
-       python scripts/bench_jpeg.py --trace-run
+                                    [--sync-sweep 64,128,256]
+       python scripts/bench_jpeg.py --trace-run [--entropy sync]
        python scripts/bench_jpeg.py --kernel-stats <csv> --out profiles/jpeg_decode.json      (no GPU needed)"""
 import argparse
 import csv
@@ -36,7 +40,7 @@ from poserisk_release_amd import _lib, jpeg  # noqa: E402
 HBM_BYTES_PER_S = 5.3e12   # achievable streaming rate used for the floors (as scripts/bench_render.py)
 H, W = 450, 800
 
-
+TRACE_CALLS = 12   # decode calls of a --trace-run
 DISTINCT = 16   # different frames per variant, so that the lanes of a wave do not all take the same branches
 
 _STREAMS = {}
@@ -71,8 +75,9 @@ def repeated(blobs, n):
     return [blobs[i % len(blobs)] for i in range(n)]
 
 
-def decode_call(blobs, chunk, dev):
-    """-> (callable enqueuing one pr_jpeg_decode of `chunk` frames, the streams in rotation; out tensor; status tensor)"""
+def decode_call(blobs, chunk, dev, entropy="serial", sync_opts=None):
+    """-> (callable enqueuing one pr_jpeg_decode / pr_jpeg_decode_sync of `chunk` frames, the streams in rotation; out tensor;
+    status tensor); call.stats is the sync entry's per-frame statistics tensor (None for serial)."""
     items = repeated(blobs, chunk)
     blob = b"".join(items)
     frames, segs, huff, pst, h, w, offsets = jpeg.parse(items)
@@ -80,11 +85,20 @@ def decode_call(blobs, chunk, dev):
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
     t = dict(data=up(np.frombuffer(blob, np.uint8)), frames=up(frames), segs=up(segs), huff=up(huff),
              out=torch.empty((chunk, H, W, 3), dtype=torch.uint8, device=dev), status=torch.empty(chunk, dtype=torch.int32, device=dev),
-             ws=torch.empty(jpeg.workspace_bytes(chunk, H, W), dtype=torch.uint8, device=dev))
+             ws=torch.empty(jpeg.workspace_bytes(chunk, H, W) if entropy == "serial" else
+                            jpeg.sync_workspace_bytes(chunk, H, W, len(blob), len(segs), sync_opts), dtype=torch.uint8, device=dev))
     args = _lib.JpegArgs(t["data"].data_ptr(), t["frames"].data_ptr(), t["segs"].data_ptr(), t["huff"].data_ptr(), t["out"].data_ptr(),
                          t["status"].data_ptr(), len(blob), chunk, H, W, len(segs), len(huff), 0)
     lib, stream = _lib.load(), torch.cuda.current_stream(dev).cuda_stream
-    call = lambda: _lib.check(lib.pr_jpeg_decode(args, t["ws"].data_ptr(), t["ws"].numel(), stream), "pr_jpeg_decode")
+    if entropy == "serial":
+        call = lambda: _lib.check(lib.pr_jpeg_decode(args, t["ws"].data_ptr(), t["ws"].numel(), stream), "pr_jpeg_decode")
+        call.stats = None
+    else:
+        t["stats"] = torch.zeros((chunk, 4), dtype=torch.int32, device=dev)
+        opts = None if sync_opts is None else _lib.JpegSyncOpts(*sync_opts)
+        call = lambda: _lib.check(lib.pr_jpeg_decode_sync(args, opts, t["stats"].data_ptr(), t["ws"].data_ptr(), t["ws"].numel(), stream),
+                                  "pr_jpeg_decode_sync")
+        call.stats = t["stats"]
     call.keep = (t, args)
     return call, t["out"], t["status"]
 
@@ -105,23 +119,34 @@ def timed_window(call, min_s=1.0):
     return a.elapsed_time(b) / n, n
 
 
-def measure_decode(dev, chunks):
+def measure_decode(dev, chunks, sweep=()):
     rows = []
+    ways = [("serial", None), ("sync", None)] + [("sync", (S, 64)) for S in sweep]
     for run in (1, 2):
         for variant, blobs in streams().items():
             for chunk in chunks:
-                call, out, status = decode_call(blobs, chunk, dev)
-                call()
-                call()
-                torch.cuda.synchronize()
-                assert not status.any()
-                ms, n = timed_window(call)
-                rows.append(dict(run=run, stream=variant, chunk=chunk, ms_per_call=round(ms, 3), calls_in_window=n,
-                                 frames_per_s=round(chunk / ms * 1e3, 1), distinct_streams=len(blobs),
-                                 compressed_bytes_per_frame=sum(map(len, blobs)) // len(blobs)))
-                print(rows[-1], flush=True)
-                del call, out, status
-                torch.cuda.empty_cache()
+                reference = None
+                for entropy, opts in ways:
+                    call, out, status = decode_call(blobs, chunk, dev, entropy, opts)
+                    call()
+                    call()
+                    torch.cuda.synchronize()
+                    assert not status.any()
+                    if reference is None:
+                        reference = out[:DISTINCT].clone()
+                    assert torch.equal(out[:DISTINCT], reference), (variant, chunk, entropy, opts)   # the same pixels either way
+                    ms, n = timed_window(call)
+                    row = dict(run=run, stream=variant, chunk=chunk, entropy=entropy, ms_per_call=round(ms, 3), calls_in_window=n,
+                               frames_per_s=round(chunk / ms * 1e3, 1), distinct_streams=len(blobs),
+                               compressed_bytes_per_frame=sum(map(len, blobs)) // len(blobs))
+                    if call.stats is not None:
+                        st = call.stats[:len(blobs)].cpu().numpy()             # the distinct frames, once each
+                        row.update(sync_opts="default" if opts is None else list(opts), subseq_per_frame=int(st[:, 0].mean()),
+                                   rounds=sorted(int(r) for r in st[:, 1]), fell_back=int(st[:, 2].sum()))
+                    rows.append(row)
+                    print(row, flush=True)
+                    del call, out, status
+                    torch.cuda.empty_cache()
     return rows
 
 
@@ -130,17 +155,18 @@ def measure_files(dev, chunks, n_frames=1024):
     for variant, blobs in streams().items():
         items = repeated(blobs, n_frames)
         for chunk in chunks:
-            jpeg.decode_files(items, dev, chunk=chunk)
-            torch.cuda.synchronize()
-            best = []
-            for _ in range(3):
-                t0 = time.perf_counter()
-                jpeg.decode_files(items, dev, chunk=chunk)
+            for entropy in ("serial", "sync"):
+                jpeg.decode_files(items, dev, chunk=chunk, entropy=entropy)
                 torch.cuda.synchronize()
-                best.append(time.perf_counter() - t0)
-            out[f"{variant}_chunk{chunk}"] = dict(frames=n_frames, seconds=[round(b, 4) for b in best],
-                                                   frames_per_s=round(n_frames / min(best), 1))
-            print("files", variant, chunk, out[f"{variant}_chunk{chunk}"], flush=True)
+                best = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    jpeg.decode_files(items, dev, chunk=chunk, entropy=entropy)
+                    torch.cuda.synchronize()
+                    best.append(time.perf_counter() - t0)
+                key = f"{variant}_chunk{chunk}_{entropy}"
+                out[key] = dict(frames=n_frames, seconds=[round(b, 4) for b in best], frames_per_s=round(n_frames / min(best), 1))
+                print("files", key, out[key], flush=True)
     return out
 
 
@@ -233,7 +259,11 @@ def kernel_stats(path, record, variant):
               "fillBuffer": ("the clear of the int16 coefficient workspace, sized for 4:4:4 (3 padded planes): 2 B a sample written",
                              2 * 3 * pw * ph),
               "jpeg_idct_kernel": ("int16 coefficients in, u8 samples out", 3 * samples),
-              "jpeg_colour_kernel": ("u8 planes in, 3 B a pixel out", samples + 3 * H * W)}
+              "jpeg_colour_kernel": ("u8 planes in, 3 B a pixel out", samples + 3 * H * W),
+              "jpeg_sync_decode_kernel": ("all launches of a call together (cold pass, rounds, write pass): compressed bytes in once a "
+                                          "pass + coefficients out once; bound by the dependent chain of one sub-sequence", comp + 2 * samples),
+              "jpeg_sync_map_kernel": ("one lane per segment: 4 B a sub-sequence written", 0),
+              "jpeg_sync_scan_kernel": ("one lane per segment: a serial walk over its sub-sequences' counts", 0)}
     out = {}
     with open(path) as f:
         for row in csv.DictReader(f):
@@ -241,10 +271,16 @@ def kernel_stats(path, record, variant):
             for k, (what, nbytes) in floors.items():
                 if k in name:
                     mean_ms = float(row["AverageNs"]) / 1e6
+                    if k.startswith("jpeg_sync"):            # several launches a decode call: their sum, per call of the trace run
+                        mean_ms = float(row["TotalDurationNs"]) / 1e6 / TRACE_CALLS
                     if k == "fillBuffer":                    # two fills a decode call: the slowest one is the workspace's
                         mean_ms = float(row["MaxNs"]) / 1e6
                     floor_ms = chunk * nbytes / HBM_BYTES_PER_S * 1e3
-                    out[k] = dict(calls=int(row["Calls"]), mean_ms=round(mean_ms, 4), bytes_per_call=chunk * nbytes, bound=what,
+                    if not nbytes:
+                        out[k] = dict(calls=int(row["Calls"]), mean_ms=round(mean_ms, 4), bound=what)
+                        continue
+                    out[k] = dict(calls=int(row["Calls"]), mean_ms=round(mean_ms, 4), total_ms=round(float(row["TotalDurationNs"]) / 1e6, 3)
+                                  if "TotalDurationNs" in row else None, bytes_per_call=chunk * nbytes, bound=what,
                                   floor_ms=round(floor_ms, 4), share_of_floor=round(floor_ms / mean_ms, 4))
     return out
 
@@ -258,25 +294,28 @@ def main():
     ap.add_argument("--trace-run", action="store_true")
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--variant", default="no_restart", choices=("no_restart", "restart_per_mcu_row"))
+    ap.add_argument("--entropy", default="serial", choices=("serial", "sync"), help="which entry --trace-run decodes with")
+    ap.add_argument("--sync-sweep", default="", help="further sub-sequence sizes for the device-event rates, 64 rounds allowed")
     a = ap.parse_args()
     if a.kernel_stats:
         record = json.load(open(a.out)) if a.out and os.path.exists(a.out) else {}
-        record.setdefault("kernels_chunk256", {})[a.variant] = kernel_stats(a.kernel_stats, record, a.variant)
-        print(json.dumps(record["kernels_chunk256"][a.variant], indent=1))
+        key = a.variant if a.entropy == "serial" else a.variant + "_sync"
+        record.setdefault("kernels_chunk256", {})[key] = kernel_stats(a.kernel_stats, record, a.variant)
+        print(json.dumps(record["kernels_chunk256"][key], indent=1))
         if a.out:
             json.dump(record, open(a.out, "w"), indent=1)
         return
     dev = torch.device("cuda", 0)
     if a.trace_run:
-        call, out, status = decode_call(streams()[a.variant], 256, dev)
-        for _ in range(12):
+        call, out, status = decode_call(streams()[a.variant], 256, dev, a.entropy)
+        for _ in range(TRACE_CALLS):
             call()
         torch.cuda.synchronize()
         assert not status.any()
         return
     chunks = [int(c) for c in a.chunks.split(",")]
     record = dict(device=torch.cuda.get_device_name(0), library=_lib.load().pr_build_info().decode(), frame="800x450 4:2:0 quality 95",
-                  decode=measure_decode(dev, chunks))
+                  decode=measure_decode(dev, chunks, [int(v) for v in a.sync_sweep.split(",") if v]))
     if not a.decode_only:
         record.update(files=measure_files(dev, chunks),
                   pillow_16_threads=measure_pillow(dev), raw_h2d=measure_raw_h2d(dev))
