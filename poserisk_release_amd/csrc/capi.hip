@@ -258,7 +258,7 @@ int pr_conv2d_nhwc(int device, const void* x_dev, const float* w_host, const flo
     wd = sa.upload(packed, "weights");
   }
   p.x = (const float*)x_dev; p.w = wd; p.bias = sa.upload(bias_host, Cout, "bias"); p.res = (const float*)res_dev; p.y = (float*)y_dev;
-  int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p);
+  int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p.shape(), p.tune);
   if (tile_cfg > 200 && tile_cfg <= 208) {      // 64x64 tile with the K-steps of every tile dealt to tile_cfg - 200 workgroups
     PR_REQUIRE(precision == 0, "pr_conv2d_nhwc: split-K is fp32 only");
     cfg = 8;
@@ -289,7 +289,7 @@ int pr_conv1x1_dual_nhwc(int device, const void* x1_dev, const float* w1_host, c
   const ConvFilter f1{w1_host}, f2{w2_host};
   p.w = sa.upload(conv_pack_side_by_side(f1, Cin1, Cin1, 1, &f2, Cin2, Cout, precision), "dual weights");
   p.x = (const float*)x1_dev; p.x2 = (const float*)x2_dev; p.bias = sa.upload(bias_host, Cout, "bias"); p.res = nullptr; p.y = (float*)y_dev;
-  const int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p);
+  const int cfg = tile_cfg >= 0 ? tile_cfg : conv_pick_tile_cfg(p.shape(), p.tune);
   return sa.run([&] { return conv_launch(p, cfg, sa.s); });
 }
 

@@ -417,30 +417,8 @@ int launch_bal(const BalArgs& a, int ks, int grid, hipStream_t stream) {
 
 }  // namespace
 
-bool conv_bal_bf16_fits(const ConvProblem& p) {
-  if (p.precision != 1 || p.groups != 1 || p.w3 || p.res || p.KH != p.KW) return false;
-  if (p.Cout % 128 || p.Cin % 64) return false;
-  if (p.x2 && (p.KH != 1 || p.Cin2 % 64 || p.stride2 <= 0)) return false;   // a second source: 1x1 only
-  if (p.KH == 1) return p.pad == 0;
-  return p.KH == 3;
-}
-
-// Where it pays.  MEASURED inside the encoder at B = 256, same box, per layer (profiles/r03_conv_bal.txt): the layers with
-// 256-channel blocks and runs of >= 6 pixel tiles gain 7-13 % (layer3's conv1 / conv2, the first conv1 of layer3 and
-// layer4); with 3 tiles per run the weights a workgroup streams per chunk outweigh its pixels (layer4: 0.8x the tile
-// kernel stand-alone).  Of the layers with 128 output channels only layer2's first conv1 gains (4 %); the others read
-// a tensor the expansion kernel has just written and lose 2-12 % against the tile kernel's order of tiles.
-// The outputs are the tile kernel's bit for bit, so the choice may depend on the batch.
-bool conv_bal_bf16_pays(const ConvProblem& p, int cus) {
-  if (!conv_bal_bf16_fits(p)) return false;
-  const int nb = p.Cout / (p.Cout % 256 == 0 ? 256 : 128);
-  const int runs = std::max(cus / (8 * nb), 1) * 8;
-  if (ceil_div(p.M(), 32) < 6 * runs) return false;
-  return p.Cout % 256 == 0 || (p.KH == 1 && p.Cin <= 256);
-}
-
 int conv_bal_bf16_launch(const ConvProblem& p, hipStream_t stream, int variant) {
-  PR_REQUIRE(conv_bal_bf16_fits(p), "conv_bal_bf16: bf16, no residual, 1x1 (pad 0) or 3x3, Cin %% 64 == 0, "
+  PR_REQUIRE(conv_bal_bf16_fits(p.shape()), "conv_bal_bf16: bf16, no residual, 1x1 (pad 0) or 3x3, Cin %% 64 == 0, "
              "Cout %% 128 == 0; got %dx%d Cin=%d Cout=%d", p.KH, p.KW, p.Cin, p.Cout);
   const int K2 = p.x2 ? p.Cin2 : 0;
   const int K = p.K(), Kpad1 = ceil_div(K, 64) * 64, Kpad = Kpad1 + K2;

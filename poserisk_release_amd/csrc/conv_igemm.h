@@ -52,15 +52,18 @@ struct ConvProblem {
   ConvTuning tune;
   int M() const { return B * Ho * Wo; }
   int K() const { return KH * KW * Cin; }
+  ConvShape shape() const {      // what the kernel choice may read of it (host_plan.h: conv_pick_tile_cfg, conv_*_fits)
+    ConvShape s;
+    s.precision = precision; s.groups = groups; s.M = M(); s.Cin = Cin; s.Cout = Cout; s.KH = KH; s.KW = KW; s.stride = stride; s.pad = pad;
+    s.Cin2 = Cin2; s.stride2 = stride2; s.splitk = splitk;
+    s.second = x2 != nullptr; s.residual = res != nullptr; s.conv3 = w3 != nullptr; s.bias = bias != nullptr; s.relu = relu != 0;
+    return s;
+  }
   int Kpad() const { return ceil_div(K(), kConvBK) * kConvBK; }
   double flops() const { return 2.0 * (double)M() * (Cout * (K() + (x2 ? Cin2 : 0)) + (w3 ? (double)N3 * Cout : 0.0)); }
 };
 
-int conv_num_tile_cfgs();
-const char* conv_tile_cfg_name(int cfg);
-// Picks a tile configuration for the problem (chip-filling heuristic).
-int conv_pick_tile_cfg(const ConvProblem& p);
-// Asynchronous launch on `stream`.  cfg from conv_pick_tile_cfg or an explicit index.
+// Asynchronous launch on `stream`.  cfg from conv_pick_tile_cfg (host_plan.h) or an explicit index.
 int conv_launch(const ConvProblem& p, int cfg, hipStream_t stream);
 
 // 3x3 conv + the 1x1 conv behind it in one kernel (conv_fused.hip); reached through conv_launch when p.w3 is set.
@@ -76,7 +79,6 @@ int conv_dma_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, in
 // bf16 twin (conv_dma_bf16.hip): x, w, res, y of the ConvProblem point at bf16 data (cast to float* only
 // to share the struct); weights packed by conv_pack_weights_bf16 (K padded to a multiple of 64).
 int conv_dma_bf16_launch(const ConvProblem& p, int BM, int BN, hipStream_t stream, int threads = 0);
-int conv_tile_dims(int cfg, int* BM, int* BN);
 
 // Winograd F(m x m, 3x3), m = 2 or 4, for 3x3 / stride 1 / pad 1 fp32 convolutions (conv_winograd.hip), n = m + 2:
 //   V[n*n][P][Cin] = B^T d B per n x n input patch,  M_k = V_k U_k^T (n*n grouped GEMMs on the MFMA kernel),
@@ -145,14 +147,11 @@ int expand_res_bf16_launch(const void* t, const void* w, const float* bias, cons
 // bf16 convolution with the pixels dealt evenly to one persistent workgroup per CU (conv_bal_bf16.hip): 1x1 or 3x3,
 // Cin % 64 == 0, Cout % 128 == 0, optional bias / ReLU, no residual; weights in conv_pack_weights_bf16 layout.
 // variant 0: channel blocks of 256 where Cout allows, else 128; variant 1: blocks of 128.
-bool conv_bal_bf16_fits(const ConvProblem& p);
-bool conv_bal_bf16_pays(const ConvProblem& p, int cus);   // the measured rule for choosing it over the tile kernel
 int conv_bal_bf16_launch(const ConvProblem& p, hipStream_t stream, int variant = 0);
 // kConvCfgBalanced (301, host_plan.h): conv_launch: 301 = variant 0, 302 = variant 1
 
 // fp32 1x1 / stride-1 convolution with Cin = 128 or 256 and the weights resident in registers (conv_regw_f32.hip): optional
 // bias / residual / ReLU, weights in conv_pack_weights layout ([Cout][Cin]); its own fixed k order (not the tile kernel's bits).
-bool conv_regw_f32_fits(const ConvProblem& p);
 int conv_regw_f32_launch(const ConvProblem& p, hipStream_t stream);
 // kConvCfgRegW (400, host_plan.h): conv_launch routes a matching problem to that kernel
 

@@ -266,14 +266,8 @@ __global__ __launch_bounds__(256) void conv1x1_regw_f32(const RArgs a) {
 
 }  // namespace
 
-bool conv_regw_f32_fits(const ConvProblem& p) {
-  return p.precision == 0 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && !p.x2 && !p.w3 && p.groups >= 1 &&
-         (p.groups == 1 || (!p.bias && !p.res && !p.relu)) && p.splitk == 1 && (p.Cin == 128 || p.Cin == 256) &&
-         p.Cout % 64 == 0 && p.M() > 0;
-}
-
 int conv_regw_f32_launch(const ConvProblem& p, hipStream_t stream) {
-  PR_REQUIRE(conv_regw_f32_fits(p), "conv_regw: fp32 1x1 / stride 1, one source, Cin 128 or 256, Cout %% 64 == 0, plain stores when grouped (got Cin %d, Cout %d)",
+  PR_REQUIRE(conv_regw_f32_fits(p.shape()), "conv_regw: fp32 1x1 / stride 1, one source, Cin 128 or 256, Cout %% 64 == 0, plain stores when grouped (got Cin %d, Cout %d)",
              p.Cin, p.Cout);
   PR_REQUIRE(p.x && p.w && p.y, "conv_regw: null tensor");
   const size_t xb = (size_t)p.groups * p.M() * p.Cin * 4, yb = (size_t)p.groups * p.M() * p.Cout * 4;

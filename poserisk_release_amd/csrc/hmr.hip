@@ -4,8 +4,9 @@
 // The host side that needs no device -- parsing the canonical weight blob (include/poserisk_hip.h), folding eval-mode
 // BatchNorm into the convolutions in double, packing weights for every kernel family, the 53-conv execution plan over NHWC
 // activation buffers, the regressor's fc1 split into its constant part (pooled features, computed once) and its state part
-// (157 inputs, recomputed per iteration) -- is host_plan.cc (plain C++, also built under ASan + UBSan by tests/native).
-// Here: device memory, workspaces, streams, the launch sequence.
+// (157 inputs, recomputed per iteration), and which kernel carries which plan entry at which batch (hmr_route) -- is
+// host_plan.cc (plain C++, also built under ASan + UBSan by tests/native).
+// Here: device memory, workspaces, streams, and the launch sequence, which executes hmr_route's answer entry by entry.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -197,7 +198,7 @@ int fc_launch(const pr_hmr* h, const FcSpec& fc, const float* x, const float* re
   p.B = B; p.H = p.W = p.Ho = p.Wo = 1; p.Cin = fc.K; p.Cout = fc.N;
   p.KH = p.KW = 1; p.stride = 1; p.pad = 0; p.relu = 0;
   p.tune = h->tune;
-  return conv_launch(p, conv_pick_tile_cfg(p), s);
+  return conv_launch(p, conv_pick_tile_cfg(p.shape(), p.tune), s);
 }
 
 
@@ -212,9 +213,37 @@ struct ChunkRun {
 };
 
 
+// A whole Bottleneck (a bneck_planes entry, or layer3's alternate) is launched from its spec's own fields: no ConvProblem.
+// lead_tiles is bottleneck128_bf16's alone; the other two kernels ignore it.
+BottleneckProblem bottleneck_problem(pr_hmr* h, const ConvSpec& c, int chunk, int B) {
+  BottleneckProblem bp;
+  const ConvTensorBytes t = hmr_conv_tensor_bytes(c, h->precision, B);
+  bp.x = act_placed(h, chunk, c.in_buf, t.x); bp.y = act_placed(h, chunk, c.out_buf, t.y);
+  bp.w1 = c.w; bp.w2 = c.w2b; bp.w3 = c.w3; bp.b1 = c.bias; bp.b2 = c.bias2b; bp.b3 = c.bias3;
+  bp.B = B; bp.H = c.H; bp.W = c.W; bp.planes = c.bneck_planes; bp.first = c.bneck_first;
+  bp.lead_tiles = h->b128_lead;
+  return bp;
+}
+
+// One launch of the plan; in profile mode bracketed by events that pr_hmr_profile_read adds up under `layer`
+template <typename Launch>
+int timed(pr_hmr* h, int layer, hipStream_t s, Launch launch) {
+  if (!h->profile) return launch();
+  hipEvent_t e0, e1;
+  PR_HIP(hipEventCreate(&e0));
+  PR_HIP(hipEventCreate(&e1));
+  PR_HIP(hipEventRecord(e0, s));
+  PR_TRY(launch());
+  PR_HIP(hipEventRecord(e1, s));
+  h->pending.emplace_back(e0, e1);
+  h->pending_layer.push_back(layer);
+  return PR_OK;
+}
+
 // Encoder over n sub-batches: layout change, 53 convs, max-pool, global average pool -> xf[b,2048].
 // Launches are issued layer by layer across the sub-batches so that all streams advance together
 // (issuing one whole sub-batch after another would stagger them by the host's enqueue time).
+// Which kernel carries an entry for a sub-batch, and how many entries it covers: hmr_route (host_plan.cc); this executes it.
 // stop_block >= 0 (pr_hmr_encode_until): after the plan entry that completes that block, each sub-batch's copy of it goes to
 // its run's `tap` and nothing further is launched.
 int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
@@ -228,78 +257,31 @@ int encode_chunks(pr_hmr* h, const ChunkRun* runs, int n, int stop_block = -1) {
       else PR_TRY(launch_nchw3_to_nhwc4(runs[i].x, stem_in_at(h, runs[i].chunk, runs[i].b), runs[i].b, kImg, kImg, runs[i].s));
     }
   }
-  // A frame per workgroup pays when the sub-batch's frames fill whole rounds of CUs: one round lasts as long for 1 frame as
-  // for `cus` (stand-alone at B=256: 137 us against 165 us for the three launches).
-  auto fused_pays = [&](int b) { return hmr_fused3_pays(b, h->cus); };
-  size_t skip_until[pr_hmr::kMaxChunks] = {};
+  size_t next[pr_hmr::kMaxChunks] = {};      // per sub-batch: the first entry no launch has covered yet
   for (size_t ci = 0; ci < h->convs.size(); ++ci) {
-    ConvSpec& c = h->convs[ci];
-    const int li = c.layer;
-    const pr::HmrPlan::FusedBlock* alt = nullptr;
-    for (const pr::HmrPlan::FusedBlock& fb : h->fused3)
-      if (fb.first == ci) alt = &fb;
     for (int i = 0; i < n; ++i) {
       const ChunkRun& r = runs[i];
-      if (ci < skip_until[i]) continue;      // the block's other two launches: done by the whole-block kernel
-      if (alt && fused_pays(r.b)) {
-        BottleneckProblem bp;
-        const ConvTensorBytes t = hmr_conv_tensor_bytes(alt->blk, h->precision, r.b);
-        bp.x = act_placed(h, r.chunk, alt->blk.in_buf, t.x); bp.y = act_placed(h, r.chunk, alt->blk.out_buf, t.y);
-        bp.w1 = alt->blk.w; bp.w2 = alt->blk.w2b; bp.w3 = alt->blk.w3;
-        bp.b1 = alt->blk.bias; bp.b2 = alt->blk.bias2b; bp.b3 = alt->blk.bias3;
-        bp.B = r.b; bp.H = alt->blk.H; bp.W = alt->blk.W; bp.planes = alt->blk.bneck_planes; bp.first = false;
-        if (h->profile) {
-          hipEvent_t e0, e1;
-          PR_HIP(hipEventCreate(&e0));
-          PR_HIP(hipEventCreate(&e1));
-          PR_HIP(hipEventRecord(e0, r.s));
-          PR_TRY(bottleneck_bf16_launch(bp, r.s));
-          PR_HIP(hipEventRecord(e1, r.s));
-          h->pending.emplace_back(e0, e1);
-          h->pending_layer.push_back(alt->blk.layer);
-        } else {
-          PR_TRY(bottleneck_bf16_launch(bp, r.s));
+      if (ci < next[i]) continue;
+      const HmrRoute rt = hmr_route(*h, h->tune, ci, r.b);
+      const ConvSpec& c = *rt.spec;
+      next[i] = ci + rt.span;
+      PR_TRY(timed(h, rt.layer, r.s, [&]() -> int {
+        switch (rt.kernel) {
+          case HmrKernel::StemPool: {
+            float* const y = act_at(h, r.chunk, 2, r.b, 56, 56, 64);
+            if (bf) return stem_pool_bf16_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, y, r.b, kImg / 2, r.s);
+            return stem_pool_f32_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, y, r.b, r.s);
+          }
+          case HmrKernel::Bottleneck: return bottleneck_bf16_launch(bottleneck_problem(h, c, r.chunk, r.b), r.s);
+          case HmrKernel::Wino64: return conv_wino64_launch(conv_problem(h, c, r.chunk, r.b), c.u1, h->stage_form[0], r.s);
+          case HmrKernel::Winograd:
+            return conv_winograd_launch(conv_problem(h, c, r.chunk, r.b), c.u, wino_work_at(h, r.chunk, c, r.b), c.wino_form, r.s);
+          case HmrKernel::Fused3: case HmrKernel::Tile: case HmrKernel::Panel: case HmrKernel::RegW: case HmrKernel::Expand:
+          case HmrKernel::Balanced: return conv_launch(conv_problem(h, c, r.chunk, r.b), rt.cfg, r.s);
         }
-        skip_until[i] = ci + 3;
-        continue;
-      }
-      // a whole-Bottleneck spec (bneck_planes) is launched from its own fields: it has no conv3 output buffer of its own
-      // (out3_buf = -1), so no ConvProblem is built for it
-      ConvProblem p = c.bneck_planes ? ConvProblem{} : conv_problem(h, c, r.chunk, r.b);
-      int cfg = c.cfg >= 0 || c.bneck_planes ? c.cfg : conv_pick_tile_cfg(p);
-      if (bf && h->balanced && c.cfg < 0 && !c.bneck_planes && !c.u && conv_bal_bf16_pays(p, h->cus)) cfg = kConvCfgBalanced;
-      // a Winograd layer is three launches (transform, 16 grouped GEMMs, transform); it is timed as one conv
-      const bool stem_pool = ci == 0 && h->stem_s2d && h->fuse_stem;   // the stem and its max-pool as one launch
-      auto go = [&]() -> int {
-        if (stem_pool && !bf)
-          return stem_pool_f32_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, act_at(h, r.chunk, 2, r.b, 56, 56, 64), r.b, r.s);
-        if (stem_pool)
-          return stem_pool_bf16_launch(stem_in_at(h, r.chunk, r.b), c.w, c.bias, act_at(h, r.chunk, 2, r.b, 56, 56, 64), r.b, kImg / 2, r.s);
-        if (c.bneck_planes) {
-          BottleneckProblem bp;
-          const ConvTensorBytes t = hmr_conv_tensor_bytes(c, h->precision, r.b);
-          bp.x = act_placed(h, r.chunk, c.in_buf, t.x); bp.y = act_placed(h, r.chunk, c.out_buf, t.y);
-          bp.w1 = c.w; bp.w2 = c.w2b; bp.w3 = c.w3; bp.b1 = c.bias; bp.b2 = c.bias2b; bp.b3 = c.bias3;
-          bp.B = r.b; bp.H = c.H; bp.W = c.W; bp.planes = c.bneck_planes; bp.first = c.bneck_first;
-          bp.lead_tiles = h->b128_lead;
-          return bottleneck_bf16_launch(bp, r.s);
-        }
-        if (c.u1) return conv_wino64_launch(p, c.u1, h->stage_form[0], r.s);      // layer1's conv2 (+ conv3) as one-launch F(4x4,3x3)
-        return c.u ? conv_winograd_launch(p, c.u, wino_work_at(h, r.chunk, c, r.b), c.wino_form, r.s) : conv_launch(p, cfg, r.s);
-      };
-      if (h->profile) {
-        hipEvent_t e0, e1;
-        PR_HIP(hipEventCreate(&e0));
-        PR_HIP(hipEventCreate(&e1));
-        PR_HIP(hipEventRecord(e0, r.s));
-        PR_TRY(go());
-        PR_HIP(hipEventRecord(e1, r.s));
-        h->pending.emplace_back(e0, e1);
-        h->pending_layer.push_back(li);
-      } else {
-        PR_TRY(go());
-      }
-      if (ci == 0 && !stem_pool) {
+        return PR_ERR_INVALID;
+      }));
+      if (ci == 0 && rt.kernel != HmrKernel::StemPool) {
         float* const pool_in = act_at(h, r.chunk, 1, r.b, 112, 112, 64);
         float* const pool_out = act_at(h, r.chunk, 2, r.b, 56, 56, 64);
         if (bf) PR_TRY(launch_maxpool_bf16(pool_in, pool_out, r.b, 112, 112, 64, r.s));
@@ -512,7 +494,6 @@ int pr_hmr_forward(pr_hmr_t* h, const float* x_dev, int B, float* rotmat_dev, fl
     set_error("pr_hmr_forward: batch %d exceeds max_batch %d", B, h->max_batch);
     return PR_ERR_CAPACITY;
   }
-  if (B == 0) return PR_OK;
   hipStream_t s = (hipStream_t)stream;
   PR_TRY(encode_batch(h, x_dev, B, s, -1, nullptr));
   if (xf_dev) PR_HIP(hipMemcpyAsync(xf_dev, h->xf, (size_t)B * 2048 * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -487,6 +487,7 @@ int build(Ctx& cx, const float* blob, size_t n_floats) {
         fb.blk.stage = L;
         fb.blk.bneck_planes = pl;
         PR_TRY(upload_block(cx, f1, f2, f3, nullptr, &fb.blk));
+        a.alt3 = (int)h->fused3.size();
         h->fused3.push_back(fb);
       }
       a.layer = layer++;
@@ -684,27 +685,128 @@ int hmr_split_batch(int B, int chunk_cap, int n_chunks, bool serial, int* sizes,
   return n;
 }
 
+// ---- which kernel -------------------------------------------------------------------------------------------------------
+namespace {
+
+// The first-generation kernel (register-staged operands, padded LDS rows; configs 0-5) was retired in round 3: production ran
+// on the LDS-DMA kernels since round 1 and the parity tests compare every configuration with torch, not with it.  The 256x256
+// bf16 tile (config 18, round 6) was retired too: 25-60 % slower on the shapes it was built for (profiles/r06_tile256_bf16.txt)
+// and never picked.
+constexpr int kNumCfg = 19;
+const ConvTileCfg kCfgs[kNumCfg] = {
+    {128, 128, 256, "reg_128x128x32_w2x2", 2, false},
+    {128, 64, 256, "reg_128x64x32_w2x2", 2, false},
+    {64, 64, 256, "reg_64x64x32_w2x2", 4, false},
+    {256, 128, 512, "reg_256x128x32_w4x2", 1, false},
+    {64, 128, 256, "reg_64x128x32_w2x2", 2, false},
+    {256, 64, 512, "reg_256x64x32_w4x2", 1, false},
+    {128, 128, 256, "dma_128x128x32_w2x2", 2},
+    {128, 64, 256, "dma_128x64x32_w2x2", 3},
+    {64, 64, 256, "dma_64x64x32_w2x2", 5},
+    {256, 128, 512, "dma_256x128x32_w4x2", 1},
+    {64, 128, 256, "dma_64x128x32_w2x2", 3},
+    {256, 64, 512, "dma_256x64x32_w4x2", 2},
+    {128, 128, 512, "dma_128x128x32_w4x2", 2},   // 8 waves per 128x128 tile (32x64 per wave)
+    {128, 64, 512, "dma_128x64x32_w4x2", 3},     // 8 waves per 128x64 tile (32x32 per wave)
+    {64, 64, 128, "dma_64x64x32_w2x1", 5},       // 2 waves per 64x64 tile (32x64 per wave)
+    {128, 64, 128, "dma_128x64x32_w2x1", 3},     // 2 waves per 128x64 tile (64x64 per wave)
+    {64, 128, 128, "dma_64x128x32_w1x2", 3},     // 2 waves per 64x128 tile (64x64 per wave)
+    {64, 256, 256, "dma_64x256x32_w2x2", 2},     // whole 256-channel rows per tile (32x128 per wave): short-K conv3
+    {256, 256, 512, "dma_256x256x64_w4x2_bf16", 1, false},   // bf16 only, two-pass epilogue; retired
+};
+
+}  // namespace
+
+int conv_num_tile_cfgs() { return kNumCfg; }
+const ConvTileCfg* conv_tile_cfg(int cfg) { return cfg >= 0 && cfg < kNumCfg ? &kCfgs[cfg] : nullptr; }
+
+int conv_pick_tile_cfg(const ConvShape& p, const ConvTuning& tune) {
+  // Experiment hook (ConvTuning::force_cfg): one tile configuration wherever it fits.
+  const int forced = tune.force_cfg;
+  // (fp32 dual-source and split-K launches exist on the 64x64 tile only: they keep it)
+  const bool fixed_tile = p.precision == 0 && (p.second || p.splitk > 1);
+  // (a retired index is handed on like a live one: conv_launch refuses it by name, in both precisions)
+  if (forced >= 0 && forced < kNumCfg && !fixed_tile && p.Cout % kCfgs[forced].BN == 0 && p.M >= kCfgs[forced].BM) return forced;
+  if (p.precision == 1) {
+    // bf16: the MFMA is 16x faster, so the kernel lives on L2->LDS bandwidth and wants big tiles.  Per-layer times inside
+    // the B=256 pipeline, every tile configuration in turn (gpurun_out/r02_layers256_bf16_cfg*.txt; round 1's isolated
+    // sweep without residuals had put the 256x64 tile first): the 8-wave 128x128 tile (32x64 per wave) is the fastest on
+    // every layer with >= 128 output channels (4.18 ms of conv per step against 4.49 with 256x64) except layer2's short-K
+    // expansions with residual, where 128x64 wins (125 vs 140 us); 64-channel 1x1 layers take 128x64, the stem and
+    // layer1's 3x3 keep 256x64 (all tiles within 1 %).  The tile index goes by the rows of the launch:
+    if (p.Cout % 128 == 0 && p.M >= 128) return (p.KH == 1 && !p.second && p.residual && p.Cin <= 128) ? 13 : 12;
+    if (p.M >= 256) return p.KH == 1 ? 13 : 11;
+    return 8;
+  }
+  // fp32: the 4-wave 64x64 LDS-DMA tile (5 workgroups per CU, quarter tiles for the remainder).  Sweeps of all 23
+  // ResNet-50 shapes at B=64 and B=256 (profiles/r01_conv_tile_sweep_b64.txt, ..._b256_fp32.txt): it is the fastest or
+  // within a few percent of the fastest configuration on every shape; an earlier cost model that weighed tile
+  // efficiency against quantisation picked larger tiles at B=256 and lost 10 % of the conv time there.
+  return 8;
+}
+
+bool conv_bal_bf16_fits(const ConvShape& p) {
+  if (p.precision != 1 || p.groups != 1 || p.conv3 || p.residual || p.KH != p.KW) return false;
+  if (p.Cout % 128 || p.Cin % 64) return false;
+  if (p.second && (p.KH != 1 || p.Cin2 % 64 || p.stride2 <= 0)) return false;   // a second source: 1x1 only
+  if (p.KH == 1) return p.pad == 0;
+  return p.KH == 3;
+}
+
+// Where it pays.  MEASURED inside the encoder at B = 256, same box, per layer (profiles/r03_conv_bal.txt): the layers with
+// 256-channel blocks and runs of >= 6 pixel tiles gain 7-13 % (layer3's conv1 / conv2, the first conv1 of layer3 and
+// layer4); with 3 tiles per run the weights a workgroup streams per chunk outweigh its pixels (layer4: 0.8x the tile
+// kernel stand-alone).  Of the layers with 128 output channels only layer2's first conv1 gains (4 %); the others read
+// a tensor the expansion kernel has just written and lose 2-12 % against the tile kernel's order of tiles.
+// The outputs are the tile kernel's bit for bit, so the choice may depend on the batch.
+bool conv_bal_bf16_pays(const ConvShape& p, int cus) {
+  if (!conv_bal_bf16_fits(p)) return false;
+  const int nb = p.Cout / (p.Cout % 256 == 0 ? 256 : 128);
+  const int runs = std::max(cus / (8 * nb), 1) * 8;
+  if (ceil_div(p.M, 32) < 6 * runs) return false;
+  return p.Cout % 256 == 0 || (p.KH == 1 && p.Cin <= 256);
+}
+
+bool conv_regw_f32_fits(const ConvShape& p) {
+  return p.precision == 0 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && !p.second && !p.conv3 && p.groups >= 1 &&
+         (p.groups == 1 || (!p.bias && !p.residual && !p.relu)) && p.splitk == 1 && (p.Cin == 128 || p.Cin == 256) &&
+         p.Cout % 64 == 0 && p.M > 0;
+}
+
+HmrRoute hmr_route(const HmrPlan& plan, const ConvTuning& tune, size_t ci, int b) {
+  const ConvSpec& c = plan.convs[ci];
+  HmrRoute r{HmrKernel::Tile, -1, &c, 1, c.layer};
+  if (c.alt3 >= 0 && hmr_fused3_pays(b, plan.cus)) {      // the block's other two entries: done by the whole-block kernel
+    const ConvSpec* blk = &plan.fused3[c.alt3].blk;
+    r = HmrRoute{HmrKernel::Bottleneck, -1, blk, 3, blk->layer};
+  } else if (ci == 0 && plan.stem_s2d && plan.fuse_stem) r.kernel = HmrKernel::StemPool;      // the stem and its max-pool as one launch
+  else if (c.bneck_planes) r.kernel = HmrKernel::Bottleneck;
+  else if (c.u1) r.kernel = HmrKernel::Wino64;        // layer1's conv2 (+ conv3) as one-launch F(4x4,3x3)
+  else if (c.u) r.kernel = HmrKernel::Winograd;       // three launches (transform, grouped GEMMs, transform), timed as one conv
+  else {
+    const ConvShape s = c.shape(plan.precision, b);
+    r.cfg = c.cfg >= 0 ? c.cfg : conv_pick_tile_cfg(s, tune);
+    if (plan.precision == 1 && plan.balanced && c.cfg < 0 && conv_bal_bf16_pays(s, plan.cus)) r.cfg = kConvCfgBalanced;
+    r.kernel = s.conv3 ? HmrKernel::Fused3 : r.cfg == kConvCfgPanel ? HmrKernel::Panel : r.cfg == kConvCfgRegW ? HmrKernel::RegW
+               : r.cfg == kConvCfgExpand ? HmrKernel::Expand : r.cfg == kConvCfgBalanced ? HmrKernel::Balanced : HmrKernel::Tile;
+  }
+  return r;
+}
+
 void hmr_plan_counts(const HmrPlan& plan, int B, int chunk_cap, int n_chunks, bool serial, int* conv_launches, int* winograd_layers) {
   // as encode_chunks walks the plan, once per sub-batch pr_hmr_forward really runs: the last serial pass is shorter and
-  // concurrent shares are B / n frames each, and whether a whole-block kernel pays is decided per sub-batch
+  // concurrent shares are B / n frames each, and whether a whole-block kernel pays is decided per sub-batch (no count
+  // depends on the tile choice: the default tuning serves)
   std::vector<int> sizes((size_t)std::max(n_chunks, ceil_div(std::max(B, 1), std::max(chunk_cap, 1))) + 1);
   const int n = hmr_split_batch(B, chunk_cap, n_chunks, serial, sizes.data(), (int)sizes.size(), nullptr);
   int launches = 0, wino = 0;
-  for (int i = 0; i < n; ++i) {
-    const bool fused3 = hmr_fused3_pays(sizes[i], plan.cus);
-    size_t skip_until = 0;
-    for (size_t ci = 0; ci < plan.convs.size(); ++ci) {
-      if (ci < skip_until) continue;
-      bool alt = false;
-      for (const HmrPlan::FusedBlock& fb : plan.fused3) alt = alt || fb.first == ci;
+  for (int i = 0; i < n; ++i)
+    for (size_t ci = 0; ci < plan.convs.size();) {
+      const HmrRoute r = hmr_route(plan, ConvTuning{}, ci, sizes[i]);
       ++launches;
-      if (alt && fused3) {
-        skip_until = ci + 3;
-        continue;
-      }
-      if (plan.convs[ci].u) ++wino;
+      wino += r.kernel == HmrKernel::Winograd;
+      ci += r.span;
     }
-  }
   if (conv_launches) *conv_launches = launches;
   if (winograd_layers) *winograd_layers = wino;
 }

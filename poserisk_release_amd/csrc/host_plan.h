@@ -7,7 +7,9 @@
 //     weights U = G g G^T, the row permutation of the transposed-MFMA kernels, the fragment orders of bottleneck256_bf16,
 //     and over them the whole layouts (two matrices side by side, a Bottleneck for its whole-block kernel), defined once for
 //     the plan and for the stand-alone test entries of capi.hip;
-//   * the 53-convolution execution plan: which launch carries which layer, buffer rotation, fusions, kernel routing;
+//   * the 53-convolution execution plan: which launch carries which layer, buffer rotation, fusions;
+//   * kernel routing: the kernels' shape predicates (over ConvShape) and hmr_route, the ONE place that decides which kernel
+//     carries a plan entry at b frames -- hmr.hip's encode_chunks, hmr_plan_counts and the walkers under tests/native follow it;
 //   * workspace sizes per sub-batch, and what a forward of B frames launches.
 //
 // Nothing here includes a HIP header: device memory is reached through PlanSink.  The library's sink allocates and copies
@@ -102,6 +104,13 @@ bool expand_res_bf16_fits(int K, int N);
 bool expand_dual_bf16_fits(int K1, int K2, int N);
 bool bottleneck256_bf16_fits(int H, int W);
 
+// What a kernel choice may read of a convolution launch: integers and whether a tensor is there.  Two producers:
+// ConvProblem::shape() (conv_igemm.h) and ConvSpec::shape(precision, b), a plan entry at b frames as hmr.hip's conv_problem fills it in.
+struct ConvShape {
+  int precision = 0, groups = 1, M = 0, Cin = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad = 0, Cin2 = 0, stride2 = 1, splitk = 1;
+  bool second = false, residual = false, conv3 = false, bias = false, relu = false;   // x2 / res / w3 / bias given; ReLU
+};
+
 // ---- the plan -------------------------------------------------------------------------------------------------
 struct ConvSpec {
   int Cin_real, Cin, Cout, k, stride, pad, H, W;  // input H,W
@@ -140,6 +149,14 @@ struct ConvSpec {
   bool bneck_first = false;      // the stage's first block: 64-channel input, downsample branch in conv3's K loop
   float* w2b = nullptr;
   float* bias2b = nullptr;
+  int alt3 = -1;                 // the first of a plain layer3 block's three entries: index of its alternate in HmrPlan::fused3
+  ConvShape shape(int precision, int b) const {
+    ConvShape s;
+    s.precision = precision; s.M = b * Ho() * Wo(); s.Cin = Cin; s.Cout = Cout; s.KH = s.KW = k; s.stride = stride; s.pad = pad; s.splitk = splitk;
+    s.second = in2_buf >= 0; s.residual = res_buf >= 0; s.conv3 = w3 && out3_buf >= 0; s.bias = bias != nullptr; s.relu = relu != 0;
+    if (s.second) { s.Cin2 = Cin2; s.stride2 = stride2; }
+    return s;
+  }
   int Ho() const { return out_hw ? out_hw : (H + 2 * pad - k) / stride + 1; }
   int Wo() const { return out_hw ? out_hw : (W + 2 * pad - k) / stride + 1; }
   double macs_per_frame() const {
@@ -209,7 +226,8 @@ struct HmrPlan {
   size_t wino_floats_per_frame = 0;
   int final_buf = 0;
   // A plain layer3 block as ONE launch (a frame per workgroup) beside its three ordinary launches `first .. first + 2` of the
-  // plan: taken per sub-batch when its frames fill whole rounds of CUs (fused_pays), bit-identical either way.
+  // plan: taken per sub-batch when its frames fill whole rounds of CUs (hmr_route), bit-identical either way.
+  // convs[first].alt3 is its index here.
   struct FusedBlock {
     size_t first;
     ConvSpec blk;
@@ -238,7 +256,8 @@ void hmr_plan_configure(HmrPlan* plan, int precision, int conv_form, int max_bat
 // blob -> BN-folded packed weights (through `sink`) + the launch plan.  PR_OK or PR_ERR_INVALID (message set).
 int hmr_plan_build(HmrPlan* plan, const float* blob, size_t n_floats, PlanSink& sink);
 
-// A frame per workgroup pays when the sub-batch's frames fill whole rounds of CUs (bottleneck256_bf16.hip)
+// A frame per workgroup (bottleneck256_bf16.hip) pays when the sub-batch's frames fill whole rounds of CUs: one round lasts as
+// long for 1 frame as for `cus` (stand-alone at B=256: 137 us against 165 us for the three launches).
 inline bool hmr_fused3_pays(int b, int cus) {
   const int rounds = (b + cus - 1) / cus;
   return b > 0 && (long)b * 100 >= (long)rounds * cus * 85;
@@ -282,7 +301,7 @@ inline size_t hmr_wino_work_floats(const ConvSpec& c, int B) {
   return (size_t)(m + 2) * (m + 2) * B * ((c.H + m - 1) / m) * ((c.W + m - 1) / m) * ((size_t)c.Cin + c.Cout);
 }
 // What one forward of B frames launches (pr_hmr_plan_counts): event brackets (a Winograd layer counts once) and how many
-// of them are Winograd layers.
+// of them are Winograd layers -- hmr_route walked over hmr_split_batch's sub-batches.
 // `serial`: the passes run one after the other on the caller's stream (profile mode, or one sub-batch stream).
 void hmr_plan_counts(const HmrPlan& plan, int B, int chunk_cap, int n_chunks, bool serial, int* conv_launches, int* winograd_layers);
 // How pr_hmr_forward cuts B frames into sub-batches (the one place that decides it): serial passes of at most chunk_cap
@@ -377,11 +396,34 @@ inline int conv_panel_nsplit(int panels, int nchunks) {
   return nsplit;
 }
 
-// conv_pick_tile_cfg's bf16 half (conv_igemm.hip has the measurements): the tile index by the rows of the launch
-inline int conv_tile_cfg_bf16(int M, int Cin, int Cout, int KH, bool second_source, bool residual) {
-  if (Cout % 128 == 0 && M >= 128) return (KH == 1 && !second_source && residual && Cin <= 128) ? 13 : 12;
-  if (M >= 256) return KH == 1 ? 13 : 11;
-  return 8;
-}
+// ---- which kernel --------------------------------------------------------------------------------------------------
+// The tile configurations conv_launch takes an index into.  Retired indices stay reserved (conv_launch refuses them by name)
+// so that the live ones keep their numbers in profiles/ and scripts/tune_conv.py.
+struct ConvTileCfg {
+  int BM, BN, threads;
+  const char* name;
+  int blocks_per_cu;   // LDS-limited residency
+  bool live = true;    // false: retired, the index is kept and refused
+};
+int conv_num_tile_cfgs();
+const ConvTileCfg* conv_tile_cfg(int cfg);      // null outside 0 .. conv_num_tile_cfgs() - 1
+int conv_pick_tile_cfg(const ConvShape& s, const ConvTuning& tune);      // chip-filling heuristic
+// What conv_bal_bf16_launch / conv_regw_f32_launch take, and the measured rule for the balanced kernel over the tile kernel
+bool conv_bal_bf16_fits(const ConvShape& s);
+bool conv_bal_bf16_pays(const ConvShape& s, int cus);
+bool conv_regw_f32_fits(const ConvShape& s);
+
+// Which kernel carries plan entry `ci` when the sub-batch has `b` frames, in this order of precedence: layer3's whole-block
+// alternate where hmr_fused3_pays; the stem with its max-pool; a whole-Bottleneck spec; layer1's one-launch Winograd; a
+// three-launch Winograd layer; else conv_launch with the entry's own cfg or the picked tile, balanced where conv_bal_bf16_pays.
+enum class HmrKernel { StemPool, Bottleneck, Wino64, Winograd, Fused3, Tile, Panel, RegW, Expand, Balanced };
+struct HmrRoute {
+  HmrKernel kernel;
+  int cfg;                // what conv_launch gets (Fused3 .. Balanced), else -1
+  const ConvSpec* spec;   // what is launched: the entry, or FusedBlock::blk for layer3's alternate
+  int span;               // plan entries the launch covers: 3 for that alternate, else 1
+  int layer;              // the profile reports it under this convolution index
+};
+HmrRoute hmr_route(const HmrPlan& plan, const ConvTuning& tune, size_t ci, int b);
 
 }  // namespace pr

@@ -10,8 +10,9 @@ from conftest import REPO
 
 ANCHORED = (1, 64)      # checked against fp64 block by block (tests/test_encoder_blocks.py)
 # A greedy cover of the classes of the three configurations below over B = 1 .. 256, plus 37 (a "whole rounds + quarter tail +
-# ragged last tile" size that tests/test_encoder_blocks.py also checks against fp64).
-COVER_BATCHES = (2, 4, 16, 17, 32, 37, 94, 115, 146, 192, 208, 218, 256)
+# ragged last tile" size that tests/test_encoder_blocks.py also checks against fp64), plus 251 (the first size at which layer3.0's
+# 3x3 / stride-2 conv runs on the bf16 balanced kernel, with a ragged last 32-row tile).
+COVER_BATCHES = (2, 4, 16, 17, 32, 37, 94, 115, 146, 192, 208, 218, 251, 256)
 
 # name -> (precision, conv_form of pr_hmr_create, HMR's conv_form name)
 CONFIGS = {"fp32_default": (0, -1, "default"), "fp32_direct": (0, 0, "direct"), "bf16": (1, -1, "default")}

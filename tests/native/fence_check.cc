@@ -6,7 +6,7 @@
 //
 //   * guard sizes over a range of frame sizes: a multiple of 4096 bytes, never below 64 KiB, never below the frame;
 //   * tail placement: for the three configurations of tests/geometry_classes.py (fp32 default form, fp32 direct, bf16), a handle
-//     of capacity 256 and B in {1, 37, 256}, the plan is walked launch by launch as hmr.hip's encode_chunks issues it.  Every
+//     of capacity 256 and B in {1, 37, 217, 256}, the plan is walked launch by launch as hmr_route (host_plan.h) routes it at that B.  Every
 //     tensor a launch reads or writes: fits its buffer, has a non-negative offset that is a multiple of 256 bytes, ends on
 //     the buffer's last byte; and what a consumer computes for its input is what the producer computed when it wrote that
 //     buffer (the stem's input, residuals, the second source of a dual-source conv3, the whole-block alternates of layer3,
@@ -95,18 +95,23 @@ static void walk(const HmrPlan& pl, const HmrChunkSizes& z, int B, const char* t
   size_t tapped[HmrPlan::kBlocks] = {};
   holds[0] = hmr_conv_tensor_bytes(pl.convs[0], prec, B).x;      // the layout change (stem_in_at)
   const size_t pooled = hmr_act_bytes(prec, B, 56, 56, 64);
-  for (size_t ci = 0; ci < pl.convs.size(); ++ci) {
+  const ConvTuning tune;
+  for (size_t ci = 0, span = 1; ci < pl.convs.size(); ci += span) {
     const ConvSpec& c = pl.convs[ci];
     const ConvTensorBytes t = hmr_conv_tensor_bytes(c, prec, B);
-    for (const HmrPlan::FusedBlock& fb : pl.fused3)
-      if (fb.first == ci) {      // the whole-block alternate of entries ci .. ci + 2: same input, and the output the third one writes
-        const ConvTensorBytes a = hmr_conv_tensor_bytes(fb.blk, prec, B);
-        reads(ci, "block256 x", fb.blk.in_buf, a.x);
-        const ConvSpec& last = pl.convs[ci + 2];
-        CHECK(fb.blk.out_buf == last.out_buf && a.y == hmr_conv_tensor_bytes(last, prec, B).y, "%s entry %zu: block256 writes another tensor than conv3", tag, ci);
-        check_place(tag, "block256 y", ci, hmr_act_capacity_bytes(z, fb.blk.out_buf), a.y);
-      }
-    if (ci == 0 && pl.stem_s2d && pl.fuse_stem) {      // stem + max-pool in one launch: act[0] -> act[2]
+    const HmrRoute rt = hmr_route(pl, tune, ci, B);
+    span = (size_t)rt.span;
+    if (c.alt3 >= 0) {      // the whole-block alternate of entries ci .. ci + 2: same input, and the output the third one writes
+      const ConvSpec& blk = pl.fused3[c.alt3].blk;
+      const ConvTensorBytes a = hmr_conv_tensor_bytes(blk, prec, B);
+      reads(ci, "block256 x", blk.in_buf, a.x);
+      const ConvSpec& last = pl.convs[ci + 2];
+      CHECK(blk.out_buf == last.out_buf && a.y == hmr_conv_tensor_bytes(last, prec, B).y, "%s entry %zu: block256 writes another tensor than conv3", tag, ci);
+      check_place(tag, "block256 y", ci, hmr_act_capacity_bytes(z, blk.out_buf), a.y);
+      if (rt.span == 3) writes(ci, "block256 y", blk.out_buf, a.y);      // at this B it is the launch that runs, entries ci .. ci + 2 do not
+    }
+    if (rt.span == 3) CHECK(rt.spec == &pl.fused3[c.alt3].blk, "%s entry %zu: three entries taken by another spec than their alternate", tag, ci);
+    else if (rt.kernel == HmrKernel::StemPool) {      // stem + max-pool in one launch: act[0] -> act[2]
       reads(ci, "stem x", 0, t.x);
       writes(ci, "stem-pool y", 2, pooled);
     } else {
@@ -134,7 +139,7 @@ static void walk(const HmrPlan& pl, const HmrChunkSizes& z, int B, const char* t
       check_place(tag, "split-K slab", ci, z.slab_floats * sizeof(float), tiles * c.splitk * 4096 * sizeof(float));
     }
     for (int k = 0; k < HmrPlan::kBlocks; ++k)
-      if ((size_t)pl.block_last[k] == ci) tapped[k] = holds[pl.block_buf[k]];
+      if ((size_t)pl.block_last[k] >= ci && (size_t)pl.block_last[k] < ci + span) tapped[k] = holds[pl.block_buf[k]];
   }
   reads(pl.convs.size(), "average pool x", pl.final_buf, hmr_act_bytes(prec, B, 7, 7, 2048));
   for (int k = 0; k < HmrPlan::kBlocks; ++k)
@@ -155,7 +160,7 @@ static void check_tail_offsets(const std::vector<float>& blob) {
   // tests/geometry_classes.py CONFIGS: (precision, conv_form); + split-K on, which alone allocates the slab
   const struct { const char* name; int precision, form, splitk; } configs[] = {
       {"fp32_default", 0, -1, 1}, {"fp32_direct", 0, 0, 1}, {"bf16", 1, -1, 1}, {"fp32_direct_splitk", 0, 0, 3}};
-  const int cap = 256, batches[] = {1, 37, 256};
+  const int cap = 256, batches[] = {1, 37, 217, 256};      // 217: the last B at which layer3's plain bf16 blocks are three launches, 256: one
   for (const auto& cf : configs) {
     HmrPlan plan;
     HostSink sink;

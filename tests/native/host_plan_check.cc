@@ -108,6 +108,7 @@ static void check_dataflow(const HmrPlan& pl, const char* tag) {
   };
   auto buf_ok = [&](int b, bool input) { return b >= (input ? 0 : 1) && b <= 5; };
   int inpl = 64, H = 56, blk_no = 1;
+  size_t n_alt3 = 0;
   // the encoder tap (pr_hmr_encode_until): block 0 is the max-pooled stem, written by launch 0 into buffer 2
   CHECK(pl.block_last[0] == 0 && pl.block_buf[0] == 2, "%s: block 0 tapped after launch %d from buffer %d", tag, pl.block_last[0], pl.block_buf[0]);
   for (int L = 0; L < 4; ++L)
@@ -120,13 +121,14 @@ static void check_dataflow(const HmrPlan& pl, const char* tag) {
       CHECK(ci < cv.size(), "%s: plan ends inside block %d.%d", tag, L, b);
       if (ci >= cv.size()) return;
       const ConvSpec& c0 = cv[ci];
-      for (const HmrPlan::FusedBlock& fb : pl.fused3)
-        if (fb.first == ci) {
-          CHECK(ci + 2 < cv.size() && fb.blk.in_buf == c0.in_buf && fb.blk.out_buf == cv[ci + 2].out_buf && fb.blk.layer == cv[ci + 2].layer,
-                "%s: fused layer3 block at launch %zu does not span its three launches", tag, ci);
-          CHECK(fb.blk.bneck_planes == pln && fb.blk.H == H && fb.blk.w && fb.blk.w2b && fb.blk.w3 && fb.blk.bias && fb.blk.bias2b && fb.blk.bias3,
-                "%s: fused layer3 block incomplete", tag);
-        }
+      if (c0.alt3 >= 0) {      // hmr_route finds the alternate through this index
+        CHECK((size_t)c0.alt3 < pl.fused3.size() && (size_t)c0.alt3 == n_alt3++, "%s: launch %zu names alternate %d of %zu", tag, ci, c0.alt3, pl.fused3.size());
+        const HmrPlan::FusedBlock& fb = pl.fused3[c0.alt3];
+        CHECK(ci == fb.first && ci + 2 < cv.size() && fb.blk.in_buf == c0.in_buf && fb.blk.out_buf == cv[ci + 2].out_buf && fb.blk.layer == cv[ci + 2].layer,
+              "%s: fused layer3 block at launch %zu does not span its three launches", tag, ci);
+        CHECK(fb.blk.bneck_planes == pln && fb.blk.H == H && fb.blk.w && fb.blk.w2b && fb.blk.w3 && fb.blk.bias && fb.blk.bias2b && fb.blk.bias3,
+              "%s: fused layer3 block incomplete", tag);
+      }
       if (c0.bneck_planes) {
         CHECK(c0.bneck_planes == pln && c0.bneck_first == (b == 0) && c0.H == H && c0.Cin == inpl && c0.Cout == 4 * pln, "%s: whole-block spec %d.%d has the wrong shape", tag, L, b);
         CHECK(buf_ok(c0.in_buf, true) && buf_ok(c0.out_buf, false) && c0.in_buf != c0.out_buf, "%s: whole-block buffers", tag);
@@ -196,6 +198,7 @@ static void check_dataflow(const HmrPlan& pl, const char* tag) {
       H = Ho;
     }
   CHECK(ci == cv.size(), "%s: %zu launches left over", tag, cv.size() - ci);
+  CHECK(n_alt3 == pl.fused3.size(), "%s: %zu of %zu fused layer3 blocks are reachable from the plan", tag, n_alt3, pl.fused3.size());
   CHECK(holds[pl.final_buf] == "in(4,0)", "%s: the average pool reads buffer %d holding '%s'", tag, pl.final_buf, holds[pl.final_buf].c_str());
   // indices carried by nobody must be exactly those folded into whole-block launches (conv1, conv2, downsample of such blocks)
   int folded = 0;

@@ -1,7 +1,7 @@
 // CPU-only: what every launch of the encoder plan looks like at a given batch size -- which kernel family carries it and
-// which branch of that family's launch geometry the size selects -- from the launchers' own rules (host_plan.h: hmr_split_batch,
-// conv_tail_split, conv_regw_geometry, conv_panel_nsplit, conv_tile_cfg_bf16, hmr_fused3_pays) applied to the real plan
-// (tests/test_launch_geometry.py).
+// which branch of that family's launch geometry the size selects.  The kernel is hmr_route's answer (host_plan.h), the one
+// the forward executes; the geometry is the launchers' own rules (hmr_split_batch, conv_tail_split, conv_regw_geometry,
+// conv_panel_nsplit, the tile table), applied to the real plan (tests/test_launch_geometry.py).
 //
 //   launch_geometry <blob.f32> <precision 0|1> <conv_form> <max_batch> <streams> <concurrency> <B first> <B last>
 //
@@ -21,8 +21,9 @@
 //     crosses a channel block (reloads its weights) or a group (the next GEMM of a Winograd layer), whether the last unit of a
 //     GEMM is partly filled
 //   Winograd layers: the transform passes' last 256-thread block partly filled or not, P % 64, then the grouped GEMM's class
-//   bf16: the tile index (conv_tile_cfg_bf16) and its ragged last block, whether layer3's plain blocks take the
-//     frame-per-workgroup kernel (hmr_fused3_pays); conv_bal_bf16_pays and the persistent kernels' own grids are not modelled
+//   bf16: the tile index and its ragged last block; whether layer3's plain blocks take the frame-per-workgroup kernel; balanced
+//     (conv_bal_bf16.hip): channel blocks of 256 or 128, pixel runs capped by the CUs or by the pixel tiles, last 32-row tile
+//     ragged or not.  The whole-Bottleneck and expansion kernels size their grids in their own launchers: not modelled
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -123,45 +124,48 @@ int main(int argc, char** argv) {
     const int n = hmr_split_batch(B, chunk_cap, n_chunks, false, sizes.data(), (int)sizes.size(), &concurrent);
     const std::set<int> distinct(sizes.begin(), sizes.begin() + n);
     printf("B %d | split %s %d %s\n", B, concurrent ? "concurrent" : "serial", n, distinct.size() == 1 ? "equal" : "unequal");
-    for (int b : distinct) {
-      size_t skip_until = 0;
-      for (size_t ci = 0; ci < plan.convs.size(); ++ci) {
-        const ConvSpec& c = plan.convs[ci];
+    for (int b : distinct)
+      for (size_t ci = 0; ci < plan.convs.size();) {
+        const HmrRoute rt = hmr_route(plan, tune, ci, b);
+        const ConvSpec& c = *rt.spec;
+        ci += rt.span;
+        if (rt.span == 3) {                 // a block the frame-per-workgroup kernel has taken
+          printf("B %d | block %d @%d | bottleneck256 frame-per-workgroup %s\n", B, c.Cin, c.H, b <= plan.cus ? "one-round" : "rounds");
+          continue;
+        }
         const int M = b * c.Ho() * c.Wo();
         const std::string fam = fmt("k%d s%d %d%s->%d @%d%s%s", c.k, c.stride, c.Cin, c.in2_buf >= 0 ? fmt("+%d", c.Cin2).c_str() : "",
                                     c.N3 ? c.N3 : c.Cout, c.H, c.res_buf >= 0 || c.res3_buf >= 0 ? " +res" : "", c.N3 ? " +conv3" : "");
         std::string cls;
-        bool alt = false;
-        for (const HmrPlan::FusedBlock& fb : plan.fused3) alt = alt || fb.first == ci;
-        if (ci < skip_until) continue;                      // inside a block the frame-per-workgroup kernel has taken
-        if (alt && hmr_fused3_pays(b, plan.cus)) {
-          skip_until = ci + 3;
-          printf("B %d | block %d @%d | bottleneck256 frame-per-workgroup %s\n", B, c.Cin, c.H, b <= plan.cus ? "one-round" : "rounds");
-          continue;
+        switch (rt.kernel) {
+          case HmrKernel::StemPool: cls = "stem_pool"; break;
+          case HmrKernel::Bottleneck: cls = fmt("bottleneck%d%s", c.bneck_planes, c.bneck_first ? " first" : ""); break;
+          case HmrKernel::Wino64: cls = "wino64"; break;
+          case HmrKernel::Winograd: {
+            const int m = c.wino_m, P = b * ((c.H + m - 1) / m) * ((c.W + m - 1) / m), per = m == 4 ? tune.wino_vec : 4;
+            ConvShape g;                    // the grouped GEMM, as conv_winograd_launch hands it on
+            g.groups = (m + 2) * (m + 2); g.M = P; g.Cin = c.Cin; g.Cout = c.Cout;
+            cls = fmt("winograd%d xform-ragged=%d,%d P%%64=%d | ", c.wino_form, (long)P * (c.Cin / per) % 256 != 0,
+                      (long)P * (c.Cout / per) % 256 != 0, P % 64 != 0) +
+                  (tune.wino_regw && conv_regw_f32_fits(g) ? "regw " + regw_class(P, c.Cin, c.Cout, g.groups, tune, plan.cus)
+                                                           : "tile " + dma_class(P, c.Cout, g.groups, tune));
+            break;
+          }
+          case HmrKernel::Fused3: cls = fmt("fused3 ragged=%d", M % 64 != 0); break;
+          case HmrKernel::RegW: cls = "regw " + regw_class(M, c.Cin, c.Cout, 1, tune, plan.cus); break;
+          case HmrKernel::Panel: cls = fmt("panel nsplit=%d ragged=%d", conv_panel_nsplit(ceil_div(M, 64), c.Cout / 64), M % 64 != 0); break;
+          case HmrKernel::Expand: cls = "expand"; break;
+          case HmrKernel::Balanced: {
+            const int wide = c.Cout % 256 == 0 ? 256 : 128, by_cus = std::max(plan.cus / (8 * (c.Cout / wide)), 1);
+            cls = fmt("balanced nb%d runs=%s ragged=%d", wide, std::max(ceil_div(M, 32) / 8, 1) < by_cus ? "tiles" : "cus", M % 32 != 0);
+            break;
+          }
+          case HmrKernel::Tile:
+            cls = bf ? fmt("tile cfg%d ragged=%d", rt.cfg, M % conv_tile_cfg(rt.cfg)->BM != 0) : c.splitk > 1 ? "tile split-k" : "tile " + dma_class(M, c.Cout, 1, tune);
+            break;
         }
-        if (ci == 0 && plan.stem_s2d && plan.fuse_stem) cls = "stem_pool";
-        else if (c.bneck_planes) cls = fmt("bottleneck%d%s", c.bneck_planes, c.bneck_first ? " first" : "");
-        else if (c.u1) cls = "wino64";
-        else if (c.u) {
-          const int m = c.wino_m, P = b * ((c.H + m - 1) / m) * ((c.W + m - 1) / m), per = m == 4 ? tune.wino_vec : 4;
-          const bool regw = tune.wino_regw && (c.Cin == 128 || c.Cin == 256) && c.Cout % 64 == 0;      // conv_regw_f32_fits of the grouped GEMM
-          cls = fmt("winograd%d xform-ragged=%d,%d P%%64=%d | ", c.wino_form, (long)P * (c.Cin / per) % 256 != 0,
-                    (long)P * (c.Cout / per) % 256 != 0, P % 64 != 0) +
-                (regw ? "regw " + regw_class(P, c.Cin, c.Cout, (m + 2) * (m + 2), tune, plan.cus)
-                      : "tile " + dma_class(P, c.Cout, (m + 2) * (m + 2), tune));
-        } else if (c.w3 && c.out3_buf >= 0) cls = fmt("fused3 ragged=%d", M % 64 != 0);
-        else if (c.cfg == kConvCfgRegW) cls = "regw " + regw_class(M, c.Cin, c.Cout, 1, tune, plan.cus);
-        else if (c.cfg == kConvCfgPanel) cls = fmt("panel nsplit=%d ragged=%d", conv_panel_nsplit(ceil_div(M, 64), c.Cout / 64), M % 64 != 0);
-        else if (c.cfg == kConvCfgExpand) cls = "expand";
-        else if (bf) {
-          const int cfg = conv_tile_cfg_bf16(M, c.Cin, c.Cout, c.k, c.in2_buf >= 0, c.res_buf >= 0);
-          const int bm = cfg == 8 ? 64 : cfg == 11 ? 256 : 128;      // kCfgs of conv_igemm.hip
-          cls = fmt("tile cfg%d ragged=%d", cfg, M % bm != 0);
-        } else if (c.splitk > 1) cls = "tile split-k";
-        else cls = "tile " + dma_class(M, c.Cout, 1, tune);
         printf("B %d | %s | %s\n", B, fam.c_str(), cls.c_str());
       }
-    }
   }
   return 0;
 }

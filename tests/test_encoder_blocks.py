@@ -87,3 +87,25 @@ def test_encoder_blocks_match_fp64_reference(gpu_device, name):
         rf = float(er.ratios(xf.double(), ref_f, E_f).max())
         measured(f"{name} pooled features: max |gpu - ref| / E", rf, 1.0)
         assert rf <= 1.0, rf
+
+
+# 218: the smallest batch at which layer3's plain blocks take the whole-block alternate on 256 CUs (CONFIGS above)
+@pytest.mark.parametrize("precision,B", [("fp32", 1), ("bf16", 3), ("bf16", 218)])
+def test_profile_brackets_every_launch_once(gpu_device, precision, B):
+    """Profile mode: one event bracket per launch of the plan -- the ordinary entries and layer3's alternate alike -- summed
+    per layer by profile_read, which also clears them; the forward computes the same bits with the brackets around it."""
+    assert torch.cuda.get_device_properties(gpu_device).multi_processor_count == 256
+    m = HMR(max_batch=B, precision=precision).to(gpu_device)
+    m.load_state_dict(synth.hmr_state_dict(seed=1))
+    x = torch.rand((B, 3, 224, 224), device=gpu_device, generator=torch.Generator(device=gpu_device).manual_seed(7))
+    with torch.no_grad():
+        plain = m(x, return_features=True)
+        m.profile_enable(True)
+        profiled = m(x, return_features=True)
+    ms, launches, _ = m.profile_read()
+    assert int(launches.sum()) == m.plan_counts(B)[0]
+    assert (ms[launches > 0] > 0).all() and not ms[launches == 0].any()
+    again_ms, again_launches, _ = m.profile_read()
+    assert not again_ms.any() and not again_launches.any()
+    m.profile_enable(False)
+    assert len(plain) == len(profiled) == 5 and all(torch.equal(a, b) for a, b in zip(plain, profiled))

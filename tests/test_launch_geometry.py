@@ -3,26 +3,26 @@
 The fp32 kernels choose their launch geometry from the batch: conv_dma_launch cuts the tiles beyond the last whole round of
 256 CUs into quarter blocks (conv_tail_split), conv1x1_regw_f32 deals its units to persistent workgroups as contiguous runs
 that may cross a channel block (conv_regw_geometry), the row-panel form splits its columns by the panel count
-(conv_panel_nsplit), the bf16 tile index goes by the rows of the launch (conv_tile_cfg_bf16) and layer3's plain bf16 blocks
-take a frame-per-workgroup kernel when the frames fill whole rounds of CUs (hmr_fused3_pays).  All of these are inline
-functions of csrc/host_plan.h that the launchers call; tests/native/launch_geometry.cc applies them to the real plan and
-prints one class per plan entry and batch size (its header describes the classes).
+(conv_panel_nsplit).  The bf16 encoder chooses the KERNEL from the batch: the tile index goes by the rows of the launch
+(conv_pick_tile_cfg), the evenly dealt kernel takes a layer whose pixel runs are long enough (conv_bal_bf16_pays) and layer3's
+plain blocks take a frame-per-workgroup kernel when the frames fill whole rounds of CUs (hmr_fused3_pays).  All of these are
+pure functions of csrc/host_plan.h, the kernel choice behind hmr_route, which the forward executes;
+tests/native/launch_geometry.cc walks the real plan with hmr_route and prints one class per launch and batch size (its
+header describes the classes).
 
 Held here: geometry_classes.COVER_BATCHES together with the fp64-verified sizes 1 and 64 runs EVERY class that occurs for
 B = 1 .. 256, per configuration, and the number of classes is pinned -- a new routing rule, or a changed threshold, fails
 this test until the list (which tests/test_encoder_batch_sweep.py taps block by block on the GPU) covers it again.
 
-Not modelled: conv_bal_bf16_pays (the bf16 encoder's evenly dealt kernel) is a predicate over a whole ConvProblem inside
-conv_bal_bf16.hip, beside the shape test it shares with that file's launcher, and the persistent bf16 kernels (the
-whole-Bottleneck kernels, expand_res_bf16) size their grids inside their own launchers; moving them would be surgery on
-kernels this change does not otherwise touch.  The dense sweep of tests/test_encoder_batch_sweep.py, which leaves no batch
+Not modelled: the persistent bf16 kernels that have no rule in host_plan.h (the whole-Bottleneck kernels, expand_res_bf16)
+size their grids inside their own launchers.  The dense sweep of tests/test_encoder_batch_sweep.py, which leaves no batch
 size out, is what covers them."""
 import pytest
 
 import geometry_classes as gc
 
 # distinct "<layer family> | <geometry class>" strings over B = 1 .. 256 (the sub-batch split's class included)
-CLASS_COUNTS = {"fp32_default": 136, "fp32_direct": 145, "bf16": 39}
+CLASS_COUNTS = {"fp32_default": 136, "fp32_direct": 145, "bf16": 49}
 
 
 @pytest.fixture(scope="module")
