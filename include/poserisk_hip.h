@@ -721,6 +721,112 @@ int pr_jpeg_decode_sync(const pr_jpeg_args* args, const pr_jpeg_sync_opts* opts,
                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* j1b progressive and multi-scan JPEG frames -> the same pixels, through the same back   */
+/*     end (what cjpeg -progressive, mozjpeg, Pillow's progressive=True write)            */
+/* ------------------------------------------------------------------------------------ */
+/* pr_jpeg_parse_scans (csrc/jpeg_scans_host.cc, no device) is pr_jpeg_parse with scans; pr_jpeg_decode_scans
+ * (csrc/jpeg_scans.hip) fills the int16 coefficient workspace from all scans of a frame and then runs j1's IDCT and colour
+ * kernels unchanged.  A COMPLETE progressive file decodes to the pixels of the baseline file with the same coefficients
+ * (libjpeg's inter-block smoothing runs on incomplete files only), so the arithmetic contract of j1 is the contract here.
+ * pr_jpeg_parse and pr_jpeg_decode are unchanged and keep refusing these files.  No ABI bump: functions and structs were added.
+ *
+ * Accepted: everything pr_jpeg_parse accepts -- for such a frame the pr_jpeg_frame and pr_jpeg_segment records are the ones
+ *   pr_jpeg_parse writes, so a call without multi-scan frames (counts[6] == 0) can go to pr_jpeg_decode / pr_jpeg_decode_sync --
+ *   and additionally SOF2 (8-bit, Huffman, progressive) and SOF0 whose components come in more than one scan (every scan one
+ *   component or an interleaved subset in frame order, Ss = 0, Se = 63, Ah = Al = 0, every component exactly once).  Sizes,
+ *   component counts, sampling, quantiser precision and table ids are limited as in j1.  Tables may be redefined between
+ *   scans: every scan names the table set in force at its SOS (the tables that scan uses; identical sets are stored once);
+ *   a component's quantiser is the one in force at its FIRST scan (as libjpeg latches it); a DRI between scans holds for the
+ *   later scans.  A multi-scan frame's pr_jpeg_frame has restart_interval, huff_set of its first scan and dc_sel / ac_sel as
+ *   of each component's first scan (the device reads the scan records instead); first_segment / n_segments cover all scans.
+ * Refused by name (pr_jpeg_scan_refusal_name; codes below 16 are pr_jpeg_parse's), never guessed at:
+ *   PR_JPEG_E_SCAN_BAND           Ss > Se, Se > 63, Ah or Al > 13, or an SOF2 scan with Ss = 0 and Se != 0
+ *   PR_JPEG_E_SCAN_AC_COMPONENTS  an AC scan (Ss > 0) with more than one component
+ *   PR_JPEG_E_SCAN_FIRST_AH       the first scan of its coefficients has Ah != 0
+ *   PR_JPEG_E_SCAN_REFINE         a refinement whose Ah is not the previous Al of every coefficient it covers, or Al != Ah - 1
+ *   PR_JPEG_E_SCAN_AC_BEFORE_DC   an AC scan of a component before that component's first DC scan
+ *   PR_JPEG_E_SCAN_REFINE_UNSENT  a refinement that covers sent coefficients and ones never sent
+ *   PR_JPEG_E_SCAN_TWICE          a component or coefficient coded twice at one precision (Ah = 0 again, or Al = its present Al)
+ *   PR_JPEG_E_SCAN_INCOMPLETE     at EOI a coefficient 0..63 of a component was never sent or has not reached Al = 0: libjpeg
+ *                                 would smooth such a file and its pixels are not this contract's
+ *   SOF0 scans with spectral selection or approximation get PR_JPEG_E_PROGRESSIVE, SOF1 / arithmetic / 12-bit their j1 codes.
+ * Scans.  pr_jpeg_scan: the frame, the components of the scan (indices into the frame's, ascending), Ss, Se, Ah, Al, the
+ *   selectors, the table set, the restart interval, its run of the segment array, its MCU count and its level.  Every
+ *   segment has a byte range, its frame (pr_jpeg_segment), its scan (segment_scan[i]) and its first MCU OF THAT SCAN.  A scan
+ *   of several components walks the frame's MCU grid (ceil(W / 8 hs) x ceil(H / 8 vs) MCUs of h x v blocks per component); a
+ *   scan of ONE component has one block per MCU and covers only ceil(dw / 8) x ceil(dh / 8) blocks of the component's own
+ *   size dw x dh, row by row -- not the MCU-padded grid (W = 17 at 4:2:0: 3 luma blocks a row, 4 in an interleaved scan).
+ * Levels.  level = 0 where no earlier scan of the frame touches one of the scan's (component, coefficient) pairs, else 1 + the
+ *   largest level among the earlier scans that do.  Scans of one level write disjoint coefficients and are decoded
+ *   concurrently, one launch per level: libjpeg's default scripts (10 scans colour, 6 gray) have 3 levels, a sequential
+ *   multi-scan file 1.  Scans of one level may share 8x8 BLOCKS (other coefficients of them): a kernel writes single
+ *   coefficients, never a whole block.
+ * Device.  A lane is one (scan, restart segment), lanes dealt thinly over waves as in pr_jpeg_decode.  Five procedures:
+ *   sequential (Ss = 0, Se = 63): j1's block decode over the scan's own MCU geometry;
+ *   DC first (Ss = Se = 0, Ah = 0): prediction per component, reset at each restart; stored pred * 2^Al;
+ *   DC refine (Ss = Se = 0, Ah > 0): one raw bit per block, OR-ed in as 1 << Al;
+ *   AC first (Ss > 0, Ah = 0): run/size symbols, ZRL, EOBn with the EOBRUN counter (reset at each restart); stored v * 2^Al;
+ *   AC refine (Ss > 0, Ah > 0): T.81 G.1.2.3 -- a new coefficient has size 1 and the value +-(1 << Al); correction bits for the
+ *     non-zero coefficients passed over in a run and in EOB runs, applied where (coef & (1 << Al)) == 0, adding 1 << Al to a
+ *     positive and subtracting it from a negative coefficient.
+ * Status and memory safety (on ANY bytes; j1's paragraph holds for this entry): every read of `data` lies inside the
+ *   segment's byte range; every block address comes from an ordinal below the scan's block count; an EOB run longer than the
+ *   blocks left in its segment or a run past Se ends the segment with PR_JPEG_ST_BAD_RUN, a refinement symbol of size > 1 or a
+ *   code no table holds with PR_JPEG_ST_BAD_CODE (in a sequential scan a run past 63 ends the block, as in j1); a value that
+ *   leaves int16 after the shift or a correction is clamped with PR_JPEG_ST_COEF_RANGE; every descriptor field that forms an
+ *   address or a shift (segment_scan, the scan's frame, level, component indices and order, Ss / Se / Ah / Al, table set,
+ *   selectors, restart interval, first MCU) is checked on the device and a failure gives the frame PR_JPEG_ST_REFUSED; a bad
+ *   frame never touches another frame's workspace, pixels or status.  Parity with libjpeg on corrupt streams is NOT promised.
+ * Mixed calls.  A frame pr_jpeg_parse accepts is one interleaved sequential scan at level 0 and gets pr_jpeg_decode's pixels
+ *   and status; in such a call it is decoded one lane per restart segment (pr_jpeg_decode_sync's sub-sequence kernels do not
+ *   run for a call that holds a multi-scan frame). */
+enum { /* pr_jpeg_parse_scans' parse_status[f] beyond pr_jpeg_parse's; pr_jpeg_scan_refusal_name gives the words of all */
+  PR_JPEG_E_SCAN_BAND = 16, PR_JPEG_E_SCAN_AC_COMPONENTS = 17, PR_JPEG_E_SCAN_FIRST_AH = 18, PR_JPEG_E_SCAN_REFINE = 19,
+  PR_JPEG_E_SCAN_AC_BEFORE_DC = 20, PR_JPEG_E_SCAN_REFINE_UNSENT = 21, PR_JPEG_E_SCAN_TWICE = 22,
+  PR_JPEG_E_SCAN_INCOMPLETE = 23, PR_JPEG_E_SCAN_COUNT = 24
+};
+#define PR_JPEG_MAX_LEVELS 16 /* Al <= 13: a first scan and at most 14 refinements of a coefficient */
+typedef struct pr_jpeg_scan {
+  int32_t frame;
+  int32_t ncomp;                     /* components in the scan, 1..3 */
+  int32_t comp[3];                   /* indices into the frame's components, ascending */
+  int32_t dc_sel[3], ac_sel[3];      /* per component of the scan: 0 or 1 */
+  int32_t ss, se, ah, al;
+  int32_t huff_set;
+  int32_t restart_interval;          /* MCUs of THIS scan per restart segment, 0 = none */
+  int32_t first_segment, n_segments; /* this scan's run of the segment array */
+  int32_t n_mcus;                    /* MCUs of this scan (blocks, for a scan of one component) */
+  int32_t level;
+} pr_jpeg_scan;
+
+/* pr_jpeg_parse with scans: the same arguments, rules, capacity protocol and error returns, plus scans_host[scan_capacity]
+ * and segment_scan_host[segment_capacity] (segment i belongs to scan segment_scan_host[i]; scans and segments are in file
+ * order, frame by frame).  counts_host[8] = segments, table sets, H, W, scans, levels (1 + the largest level of an accepted
+ * frame, 0 without one), frames with more than one scan, 0.  PR_ERR_CAPACITY when any of the three capacities was too small.
+ * Never reads outside [offsets_host[0], offsets_host[F]). */
+int pr_jpeg_parse_scans(const uint8_t* data_host, const int64_t* offsets_host, int F, int H, int W, pr_jpeg_frame* frames_host,
+                        pr_jpeg_segment* segments_host, int32_t* segment_scan_host, int segment_capacity, pr_jpeg_huff* huff_host,
+                        int huff_capacity, pr_jpeg_scan* scans_host, int scan_capacity, int32_t* parse_status_host,
+                        int32_t* counts_host);
+const char* pr_jpeg_scan_refusal_name(int code);
+
+/* Device memory pr_jpeg_decode_scans needs: pr_jpeg_workspace_bytes(F, H, W). */
+size_t pr_jpeg_scans_workspace_bytes(int F, int H, int W);
+
+/* base: as for pr_jpeg_decode, from pr_jpeg_parse_scans' records; scans, segment_scan: its other two arrays, uploaded
+ * unchanged; n_levels = counts[5].  One asynchronous clear of the coefficients and the status words, one entropy launch per
+ * level, then pr_jpeg_decode's IDCT and colour kernels.  Argument rules, asynchrony and capturability are pr_jpeg_decode's
+ * (no allocation, no blocking copy, no synchronisation); n_levels outside 0..PR_JPEG_MAX_LEVELS or scans missing where there
+ * are segments return PR_ERR_INVALID. */
+typedef struct pr_jpeg_scans_args {
+  pr_jpeg_args base;
+  const pr_jpeg_scan* scans;
+  const int32_t* segment_scan;
+  int32_t n_scans, n_levels;
+} pr_jpeg_scans_args;
+int pr_jpeg_decode_scans(const pr_jpeg_scans_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* j2  u8[F,H,W,3] on the device -> baseline JPEG files, byte-exact with libjpeg          */
 /* replaces: cv2.VideoWriter / one PNG per frame behind the composed canvases             */
 /*           (write_gpu_video, _mesh_writer): only compressed bytes leave the device      */

@@ -51,6 +51,11 @@ class JpegArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "n_segments", "n_huff", "bgr")]
 
 
+class JpegScansArgs(C.Structure):
+    """pr_jpeg_scans_args (include/poserisk_hip.h, pr_jpeg_decode_scans)."""
+    _fields_ = [("base", JpegArgs), ("scans", C.c_void_p), ("segment_scan", C.c_void_p), ("n_scans", C.c_int32), ("n_levels", C.c_int32)]
+
+
 class JpegSyncOpts(C.Structure):
     """pr_jpeg_sync_opts (include/poserisk_hip.h, pr_jpeg_decode_sync): subseq_bytes 0 = the build's default; max_rounds is 1..64
     (0 is an error: pass no opts at all for both defaults)."""
@@ -124,6 +129,10 @@ SIGNATURES = {
     "pr_jpeg_decode": (_I, [C.POINTER(JpegArgs), _P, C.c_size_t, _P]),
     "pr_jpeg_sync_workspace_bytes": (C.c_size_t, [_I, _I, _I, C.c_int64, _I, C.POINTER(JpegSyncOpts)]),
     "pr_jpeg_decode_sync": (_I, [C.POINTER(JpegArgs), C.POINTER(JpegSyncOpts), _P, _P, C.c_size_t, _P]),
+    "pr_jpeg_parse_scans": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _P]),
+    "pr_jpeg_scan_refusal_name": (C.c_char_p, [_I]),
+    "pr_jpeg_scans_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "pr_jpeg_decode_scans": (_I, [C.POINTER(JpegScansArgs), _P, C.c_size_t, _P]),
     "pr_jpeg_encode_plan": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "pr_jpeg_encode_bound": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_jpeg_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, C.c_int64]),

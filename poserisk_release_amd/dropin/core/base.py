@@ -563,8 +563,10 @@ class Predictor:
             names = jpeg.list_frames(input_path)
             if names:
                 paths = [osp.join(input_path, n) for n in names]
-                frames, status = jpeg.decode_files(paths, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
-                bad = jpeg.bad_frames(paths, status)
+                progressive = bool(cfg.DATASET.get('jpeg_progressive', True))
+                frames, status = jpeg.decode_files(paths, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
+                                                   progressive=progressive)
+                bad = jpeg.bad_frames(paths, status, progressive=progressive)
                 if bad:
                     raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
                                        + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
@@ -627,7 +629,8 @@ class Predictor:
         from poserisk_release_amd import frontend, jpeg
         frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
                                           max_h=cfg.DATASET.get('front_max_h', 450),
-                                          entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
+                                          entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
+                                          progressive=bool(cfg.DATASET.get('jpeg_progressive', True)))
         if tracking_results is not None:
             return frames, False, fps, tracking_results
         sidecar = osp.splitext(input_path)[0] + '.tracking.pkl'
@@ -650,8 +653,10 @@ class Predictor:
             tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
                           output_format='dict', yolo_img_size=416)
             tracking = tracker(image_path)
-            frames, status = jpeg.decode_files(files, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'))
-            bad = jpeg.bad_frames(files, status)
+            progressive = bool(cfg.DATASET.get('jpeg_progressive', True))
+            frames, status = jpeg.decode_files(files, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
+                                               progressive=progressive)
+            bad = jpeg.bad_frames(files, status, progressive=progressive)
             if bad:
                 raise RuntimeError(f"{image_path!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")
         finally:

@@ -34,6 +34,9 @@ absent from the reference and all optional:
     cfg.DATASET.jpeg_entropy  'auto' | 'serial' | 'sync': how JPEG frames (a folder's, a Motion-JPEG AVI's) are entropy-decoded
                               (poserisk_release_amd.jpeg.decode_files): one lane per restart segment, self-synchronising
                               sub-sequences inside a segment, or (auto) the latter where a chunk holds restart-free frames
+    cfg.DATASET.jpeg_progressive  True: progressive JPEG frames, and sequential ones whose components come in several scans, are
+                              decoded too (jpeg.decode_files(progressive=True), pr_jpeg_decode_scans); False refuses them by
+                              name, as the single-scan parser does
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -94,7 +97,7 @@ def _defaults(root):
                     'default_information': osp.join(core_dir, 'default_information.json'),
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
                     'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
-                    'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto'},
+                    'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

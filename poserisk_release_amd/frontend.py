@@ -96,20 +96,21 @@ def chunk_frames(H, W, max_bytes, frame_bytes=0):
     return n
 
 
-def _raise_refused(path, part, lo, H, W, fallback):
-    _, _, _, pst, *_ = jpeg.parse(part, H, W)
+def _raise_refused(path, part, lo, H, W, fallback, progressive=False):
+    _, _, _, pst, *_ = jpeg.parse_scans(part, H, W) if progressive else jpeg.parse(part, H, W)
     bad = np.nonzero(pst)[0]
     if bad.size:
-        raise RuntimeError(f"{path!r}: frame {lo + int(bad[0])} cannot be decoded: {jpeg.refusal_name(pst[bad[0]])}")
+        raise RuntimeError(f"{path!r}: frame {lo + int(bad[0])} cannot be decoded: {jpeg.scan_refusal_name(pst[bad[0]])}")
     raise RuntimeError(f"{path!r}: frames {lo}..{lo + len(part) - 1} cannot be decoded: {fallback}")
 
 
-def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, entropy="auto"):
+def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, entropy="auto", progressive=False):
     """A Motion-JPEG AVI -> (frames u8[F,h,w,3] on `device`, fps): demuxed on the host, decoded on the GPU at the source size,
     chunk by chunk into one reused buffer, each chunk downscaled into its slice of the result ((w, h) = target_size of the first
     frame's own size).  RGB, or BGR with bgr=True.  A refused or damaged frame raises RuntimeError naming its index in the file
     and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made.
-    `entropy` is jpeg.decode_files' ("auto" | "serial" | "sync")."""
+    `entropy` is jpeg.decode_files' ("auto" | "serial" | "sync"), and so is `progressive`: False refuses a progressive frame by
+    name, True decodes it (pr_jpeg_decode_scans)."""
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.PoseRiskHipError("read_video: decoding and resizing run on the GPU only (no CPU fallback)")
@@ -121,9 +122,9 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
     F = len(blobs)
     if F == 0:
         raise ValueError(f"{path!r}: the video stream holds no frames")
-    _, _, _, pst, H, W, _ = jpeg.parse(blobs[:1])
+    _, _, _, pst, H, W, *_ = jpeg.parse_scans(blobs[:1]) if progressive else jpeg.parse(blobs[:1])
     if pst[0]:
-        raise RuntimeError(f"{path!r}: frame 0 cannot be decoded: {jpeg.refusal_name(pst[0])}")
+        raise RuntimeError(f"{path!r}: frame 0 cannot be decoded: {jpeg.scan_refusal_name(pst[0])}")
     w, h = target_size(W, H, max_w, max_h)
     if h < 1 or w < 1:
         raise ValueError(f"{path!r}: {W} x {H} frames would become {w} x {h}")
@@ -137,10 +138,10 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
             m = len(part)
             into = result[lo:lo + m] if same else buffer[:m]
             try:
-                _, status = jpeg.decode_files(part, device, bgr=bgr, chunk=m, out=into, entropy=entropy)
+                _, status = jpeg.decode_files(part, device, bgr=bgr, chunk=m, out=into, entropy=entropy, progressive=progressive)
             except (ValueError, _lib.PoseRiskHipError) as e:     # the chunk's first accepted frame has another size, or none was accepted
-                _raise_refused(path, part, lo, H, W, str(e))
-            bad = jpeg.bad_frames(part, status)
+                _raise_refused(path, part, lo, H, W, str(e), progressive)
+            bad = jpeg.bad_frames(part, status, progressive=progressive)
             if bad:
                 raise RuntimeError(f"{path!r}: frame {lo + bad[0][0]} cannot be decoded: {bad[0][1]}"
                                    + (f" (and {len(bad) - 1} more frames of its chunk)" if len(bad) > 1 else ""))
@@ -171,11 +172,11 @@ def write_frame_folder(frames, out_dir, quality=95, fps=None, bgr=False, chunk=6
     return files
 
 
-def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_bytes=16 << 30):
+def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_bytes=16 << 30, progressive=False):
     """A Motion-JPEG AVI -> out_dir/%09d.jpg + fps.txt: the folder the reference's front end leaves for its tracker (quality 95 is
     cv2.imwrite's default), written without OpenCV.  Returns (number of frames, (w, h), fps)."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    frames, fps = read_video(path, device, max_w=max_w, max_h=max_h, max_bytes=max_bytes)
+    frames, fps = read_video(path, device, max_w=max_w, max_h=max_h, max_bytes=max_bytes, progressive=progressive)
     write_frame_folder(frames, out_dir, quality=quality, fps=fps)
     return int(frames.shape[0]), (int(frames.shape[2]), int(frames.shape[1])), fps
 
@@ -192,7 +193,8 @@ def main(argv=None):
     p.add_argument("--max-h", type=int, default=450)
     p.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
-    n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h)
+    n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h,
+                             progressive=True)
     print(f"{a.out_dir}: {n} frames of {w} x {h} at {fps:g} frames/s; add tracking.pkl (multi_person_tracker's dict) to score it")
 
 

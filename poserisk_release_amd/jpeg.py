@@ -4,7 +4,9 @@ lib/core/base.py:47-56, read back by CropDataset with cv2.imread).  The contract
 the marker parser is csrc/jpeg_host.cc (host, no device), everything else csrc/jpeg.hip.
 
 `list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
-go through ONE pinned buffer and ONE upload, then pr_jpeg_decode.
+go through ONE pinned buffer and ONE upload, then pr_jpeg_decode.  Progressive files and files whose components come in
+several scans (section j1b; csrc/jpeg_scans_host.cc, csrc/jpeg_scans.hip) are opt-in: `parse_scans` is their host half,
+`decode_files(progressive=True)` sends a chunk that holds one to pr_jpeg_decode_scans.
 
 The inverse direction (section j2; csrc/jpeg_enc.hip): `encode_frames` turns u8 frames on the device into complete baseline
 JPEG files in per-frame slots, byte for byte what libjpeg writes with the standard tables; `download_files` brings only the
@@ -25,6 +27,10 @@ SEGMENT_DTYPE = np.dtype([("begin", "<i8"), ("end", "<i8"), ("frame", "<i4"), ("
 HUFFTAB_DTYPE = np.dtype([("look", "<u2", (512,)), ("maxcode", "<i4", (17,)), ("valoff", "<i4", (17,)), ("vals", "u1", (256,)),
                           ("defined", "<i4")])
 HUFF_DTYPE = np.dtype([("tab", HUFFTAB_DTYPE, (4,))])
+# pr_jpeg_scan (section j1b: progressive and multi-scan files)
+SCAN_DTYPE = np.dtype([("frame", "<i4"), ("ncomp", "<i4"), ("comp", "<i4", (3,)), ("dc_sel", "<i4", (3,)), ("ac_sel", "<i4", (3,)),
+                       ("ss", "<i4"), ("se", "<i4"), ("ah", "<i4"), ("al", "<i4"), ("huff_set", "<i4"), ("restart_interval", "<i4"),
+                       ("first_segment", "<i4"), ("n_segments", "<i4"), ("n_mcus", "<i4"), ("level", "<i4")])
 ST_REFUSED, ST_TRUNCATED, ST_BAD_RUN, ST_BAD_CODE, ST_IDCT_RANGE, ST_COEF_RANGE = 1, 2, 4, 8, 16, 32
 _ST_NAMES = ((ST_REFUSED, "refused (descriptor or segment range invalid)"), (ST_TRUNCATED, "entropy-coded data ends early"),
              (ST_BAD_RUN, "a zero run leaves the block"), (ST_BAD_CODE, "a Huffman code no table holds"),
@@ -53,6 +59,11 @@ def status_text(st):
 
 def refusal_name(code):
     return _lib.load().pr_jpeg_refusal_name(int(code)).decode()
+
+
+def scan_refusal_name(code):
+    """The words for a pr_jpeg_parse_scans refusal (pr_jpeg_parse's codes and the progression rules')."""
+    return _lib.load().pr_jpeg_scan_refusal_name(int(code)).decode()
 
 
 def list_frames(directory):
@@ -99,6 +110,38 @@ def parse(blobs, H=0, W=0):
         seg_cap, huff_cap = max(seg_cap, int(counts[0])), max(huff_cap, int(counts[1]))
 
 
+def _parse_scans_into(data, offsets, H, W, frames, segs, seg_scan, huff, scans, pstatus):
+    """pr_jpeg_parse_scans into caller-owned numpy arrays -> (status code, counts int32[8] = segments, table sets, H, W, scans,
+    levels, frames with more than one scan, 0)."""
+    counts = np.zeros(8, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = _lib.load().pr_jpeg_parse_scans(ptr(data), ptr(offsets), len(offsets) - 1, int(H), int(W), ptr(frames), ptr(segs),
+                                         ptr(seg_scan), len(segs), ptr(huff), len(huff), ptr(scans), len(scans), ptr(pstatus),
+                                         ptr(counts))
+    return rc, counts
+
+
+def parse_scans(blobs, H=0, W=0):
+    """The scan-aware host half (pr_jpeg_parse_scans: progressive files and sequential files in several scans beside
+    everything `parse` accepts) on a list of bytes objects: `parse`'s tuple (frames, segments, huff, parse_status, H, W,
+    offsets) followed by scans SCAN_DTYPE[N], segment_scan int32[S] (segment i belongs to scans[segment_scan[i]]), the number
+    of levels and the number of frames with more than one scan.  scan_refusal_name gives a refusal's words."""
+    offsets = _packed(blobs)
+    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    F = len(blobs)
+    frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
+    seg_cap, huff_cap, scan_cap = 64 + 16 * F, 4 + F, 16 * F
+    while True:
+        segs, seg_scan = np.zeros(seg_cap, SEGMENT_DTYPE), np.zeros(seg_cap, np.int32)
+        huff, scans = np.zeros(huff_cap, HUFF_DTYPE), np.zeros(scan_cap, SCAN_DTYPE)
+        rc, counts = _parse_scans_into(data, offsets, H, W, frames, segs, seg_scan, huff, scans, pstatus)
+        if rc != -4:                                             # PR_ERR_CAPACITY: counts says what is needed
+            _lib.check(rc, "pr_jpeg_parse_scans")
+            return (frames, segs[:counts[0]], huff[:counts[1]], pstatus, int(counts[2]), int(counts[3]), offsets, scans[:counts[4]],
+                    seg_scan[:counts[0]], int(counts[5]), int(counts[6]))
+        seg_cap, huff_cap, scan_cap = max(seg_cap, int(counts[0])), max(huff_cap, int(counts[1])), max(scan_cap, int(counts[4]))
+
+
 def workspace_bytes(F, H, W):
     return int(_lib.load().pr_jpeg_workspace_bytes(int(F), int(H), int(W)))
 
@@ -125,7 +168,8 @@ def _align(n, a=256):
     return (n + a - 1) // a * a
 
 
-def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, entropy="auto", stats=False, sync_opts=None):
+def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, entropy="auto", stats=False, sync_opts=None,
+                 progressive=False):
     """Decode F baseline JPEG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread
     gives with bgr=True).  Returns (frames, status int32[F] on the device): status[f] != 0 marks a frame that was refused
     (bit 0; its pixels are zero) or whose stream was damaged; `bad_frames` puts the reasons into words.  Per chunk of `chunk`
@@ -136,7 +180,12 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     segment (pr_jpeg_decode_sync: what frames without restart markers need), "auto" picks per chunk: sync where any accepted
     frame of the chunk has no restart interval, serial otherwise.  `sync_opts` = (subseq_bytes, max_rounds) instead of the
     build's defaults.  stats=True returns (frames, status, stats): a SYNC_STATS_DTYPE int32[F, 4] tensor on the device, per
-    frame (n_subseq, rounds, fell_back, 0); all zero for frames of a chunk that went the serial way."""
+    frame (n_subseq, rounds, fell_back, 0); all zero for frames of a chunk that went the serial way.
+    `progressive`: False refuses progressive files and files whose components come in several scans, as ever.  True parses
+    every chunk with pr_jpeg_parse_scans (section j1b): a chunk WITHOUT such a frame takes exactly the path above (the same
+    records, entries and `entropy` rule); a chunk with at least one is decoded by pr_jpeg_decode_scans, one launch per level of
+    the scan scripts, its baseline frames one lane per restart segment whatever `entropy` says, its `stats` rows zero.  For
+    such a call `bad_frames(..., progressive=True)` names the refusals."""
     if entropy not in ENTROPY:
         raise ValueError(f"decode_files: entropy = {entropy!r}: one of {ENTROPY}")
     device = torch.device(device)
@@ -147,7 +196,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     items = list(paths_or_bytes)
     F, chunk = len(items), max(int(chunk), 1)
     lib = _lib.load()
-    H, W, seg_per_frame = 0, 0, 2
+    H, W, seg_per_frame, scan_per_frame, huff_room = 0, 0, 2, (10 if progressive else 0), 0
     frames_out = status = pinned = ws = uploaded = first_refusal = sync_stats = None
     opts = _sync_opts(sync_opts)
     with torch.cuda.device(device):
@@ -158,12 +207,18 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             sizes = [os.path.getsize(p) if isinstance(p, (str, os.PathLike)) else len(p) for p in part]
             offsets = np.zeros(n + 1, np.int64)
             np.cumsum(sizes, out=offsets[1:])
-            total, seg_room = int(offsets[-1]), 64 + seg_per_frame * n
-            # [file bytes | frames | segments | table sets]: the parser reads the bytes where they lie and writes beside them
+            total, seg_room, scan_room, huff_room = int(offsets[-1]), 64 + seg_per_frame * n, scan_per_frame * n, max(huff_room, n)
+            # [file bytes | frames | segments | (segments' scans | scans |) table sets]: the parser reads the bytes where they lie
+            # and writes beside them; the two arrays in brackets are empty without `progressive`
             o_fr = _align(max(total, 1))
             o_seg = _align(o_fr + n * FRAME_DTYPE.itemsize)
-            o_huff = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
-            room = o_huff + n * HUFF_DTYPE.itemsize
+
+            def layout():
+                o_ss = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
+                o_sc = _align(o_ss + (seg_room * 4 if progressive else 0))
+                o_huff = _align(o_sc + scan_room * SCAN_DTYPE.itemsize)
+                return o_ss, o_sc, o_huff, o_huff + huff_room * HUFF_DTYPE.itemsize
+            o_ss, o_sc, o_huff, room = layout()
             if uploaded is not None:
                 uploaded.synchronize()                           # the previous chunk has left the buffer
                 uploaded = None
@@ -182,24 +237,31 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             while True:
                 fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
                 segs = host[o_seg:o_seg + seg_room * SEGMENT_DTYPE.itemsize].view(SEGMENT_DTYPE)
-                huff = host[o_huff:o_huff + n * HUFF_DTYPE.itemsize].view(HUFF_DTYPE)
-                rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, segs, huff, pst)
+                huff = host[o_huff:o_huff + huff_room * HUFF_DTYPE.itemsize].view(HUFF_DTYPE)
+                if progressive:
+                    seg_scan = host[o_ss:o_ss + seg_room * 4].view(np.int32)
+                    scans = host[o_sc:o_sc + scan_room * SCAN_DTYPE.itemsize].view(SCAN_DTYPE)
+                    rc, counts = _parse_scans_into(host[:max(total, 1)], offsets, H, W, fr, segs, seg_scan, huff, scans, pst)
+                else:
+                    rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, segs, huff, pst)
                 if rc != -4:                                     # PR_ERR_CAPACITY: more restart segments than guessed
-                    _lib.check(rc, "pr_jpeg_parse")
+                    _lib.check(rc, "pr_jpeg_parse_scans" if progressive else "pr_jpeg_parse")
                     break
                 # parse again where the bytes lie, with the room the parser asked for; later chunks start from what this one
                 # needed a frame (a folder one encoder wrote has one restart interval)
                 seg_room = int(counts[0])
                 seg_per_frame = max(seg_per_frame, -(-seg_room // n))
-                o_huff = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
-                room = o_huff + n * HUFF_DTYPE.itemsize
+                if progressive:
+                    scan_room, huff_room = max(scan_room, int(counts[4])), max(huff_room, int(counts[1]))
+                    scan_per_frame = max(scan_per_frame, -(-scan_room // n))
+                o_ss, o_sc, o_huff, room = layout()
                 if pinned.numel() < room:
                     bigger = torch.empty(room, dtype=torch.uint8).pin_memory()
                     bigger[:total] = pinned[:total]
                     pinned, host = bigger, bigger.numpy()
             n_segs, n_huff = int(counts[0]), int(counts[1])
             if H == 0 and pst.any() and first_refusal is None:
-                first_refusal = (lo + int(np.nonzero(pst)[0][0]), refusal_name(pst[np.nonzero(pst)[0][0]]))
+                first_refusal = (lo + int(np.nonzero(pst)[0][0]), scan_refusal_name(pst[np.nonzero(pst)[0][0]]))
             if H == 0 and counts[2]:
                 H, W = int(counts[2]), int(counts[3])
                 frames_out = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
@@ -217,7 +279,8 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             uploaded = torch.cuda.Event()
             uploaded.record(stream)
             ok = fr[pst == 0]
-            sync = entropy == "sync" or (entropy == "auto" and bool((ok["restart_interval"] == 0).any()))
+            multi = progressive and int(counts[6]) > 0
+            sync = not multi and (entropy == "sync" or (entropy == "auto" and bool((ok["restart_interval"] == 0).any())))
             need = sync_workspace_bytes(n, H, W, total, n_segs, sync_opts) if sync else workspace_bytes(n, H, W)
             if sync and need == 0:
                 raise _lib.PoseRiskHipError(f"decode_files: sync_opts = {sync_opts!r}: subseq_bytes is a multiple of 4 in 16..4096 "
@@ -227,7 +290,10 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             base = dev.data_ptr()
             args = _lib.JpegArgs(base, base + o_fr, base + o_seg, base + o_huff, frames_out[lo:lo + n].data_ptr(),
                                  status[lo:lo + n].data_ptr(), total, n, H, W, n_segs, n_huff, int(bool(bgr)))
-            if sync:
+            if multi:
+                sargs = _lib.JpegScansArgs(args, base + o_sc, base + o_ss, int(counts[4]), int(counts[5]))
+                _lib.check(lib.pr_jpeg_decode_scans(sargs, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode_scans")
+            elif sync:
                 st_ptr = sync_stats[lo:lo + n].data_ptr() if stats else None
                 _lib.check(lib.pr_jpeg_decode_sync(args, opts, st_ptr, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode_sync")
             else:
@@ -245,17 +311,18 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     return (frames_out, status, sync_stats) if stats else (frames_out, status)
 
 
-def bad_frames(paths_or_bytes, status):
+def bad_frames(paths_or_bytes, status, progressive=False):
     """[(frame index, reason)] for every frame of a decode_files call whose status is non-zero (one device -> host copy; a
-    refused frame's file is parsed again on its own to name the parser's reason)."""
+    refused frame's file is parsed again on its own to name the parser's reason: with progressive=True, as the call was made,
+    by the scan-aware parser)."""
     items, st, out = list(paths_or_bytes), status.cpu().numpy(), []
     for i in np.nonzero(st)[0]:
         why = status_text(int(st[i]))
         if st[i] & ST_REFUSED:
             p = items[i]
             blob = open(p, "rb").read() if isinstance(p, (str, os.PathLike)) else bytes(p)
-            _, _, _, pst, h, w, _ = parse([blob])
-            why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
+            _, _, _, pst, h, w, *_ = parse_scans([blob]) if progressive else parse([blob])
+            why = scan_refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
         out.append((int(i), why))
     return out
 
