@@ -981,6 +981,117 @@ int pr_resize_plan(int H, int W, int h, int w, int32_t* xofs_host, int16_t* xcoe
 int pr_resize_frames(const uint8_t* src, int F, int H, int W, uint8_t* dst, int h, int w, const int32_t* xofs,
                      const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, int mode, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j4  PNG frames decoded on the GPU, exact with zlib and libpng                           */
+/* no reference counterpart: the reference's front end writes JPEG; PNG is what ffmpeg,    */
+/*           screen recorders, annotation tools and this project's own report path write   */
+/* ------------------------------------------------------------------------------------ */
+/* The host half (pr_png_parse, csrc/png_host.cc, no device) walks the chunks and emits descriptors only; the device half
+ * (pr_png_decode, csrc/png.hip over csrc/png_device.h) gathers each frame's IDAT payloads, inflates them, undoes the filters,
+ * verifies the Adler-32 and writes the pixels.  tests/png_ref.py restates this section in Python.  No ABI bump: functions and
+ * structs were added.
+ *
+ * Accepted.  PNG of bit depth 8, colour type 0 (gray), 2 (RGB), 3 (palette), 4 (gray + alpha) or 6 (RGBA), non-interlaced,
+ *   1..PR_PNG_MAX_SIDE pixels a side, any number of IDAT chunks of any length (empty ones included).  All frames of a call
+ *   have one size.
+ * Output.  u8[F,H,W,3], RGB, or BGR when bgr != 0.  Gray is replicated.  Alpha is DROPPED, not composited (what cv2.imread's
+ *   default and Pillow's .convert("RGB") do).  tRNS, gAMA, iCCP and every other ancillary chunk are ignored (their CRC is
+ *   still verified).  The parser uploads a palette padded to 256 entries with zeros, so an index past PLTE reads black;
+ *   Pillow 12 does the same (tests/test_png_cpu.py checks it).
+ * Refused by name (parse_status, pr_png_refusal_name): not a PNG signature; a file that ends inside a chunk; a chunk CRC-32
+ *   mismatch; a missing or misplaced IHDR, PLTE, IDAT or IEND (IHDR not first or not 13 bytes, a second IHDR, PLTE behind
+ *   IDAT or twice or missing for colour type 3 or not 3..768 bytes in threes, IDAT chunks not consecutive, no IDAT, no IEND);
+ *   16-bit depth; bit depth 1, 2 or 4; Adam7 interlace; Apple's CgBI; an IHDR no PNG has (another depth or colour type, a
+ *   depth the colour type does not allow, compression or filter method not 0, a side of 0 or above PR_PNG_MAX_SIDE); a size
+ *   other than the call's; a zlib header with CM != 8, a window above 32 KiB, FDICT set, a bad FCHECK, or shorter than 2 bytes.
+ * Inflate rule.  RFC 1951 with zlib 1.2.11's acceptance rules: a frame gets a non-zero device status exactly where
+ *   zlib.decompress would raise.  Errors (PR_PNG_ST_BAD_CODE): block type 3; a stored block with LEN != ~NLEN; HLIT above 286
+ *   or HDIST above 30 symbols; an over-subscribed code-length set; an incomplete set, unless it is a literal/length or distance
+ *   set that is a single code of length 1 (the code-length code itself may not be incomplete; a distance set with no code at
+ *   all is legal until a distance is decoded); a set with no end-of-block code; a repeat code 16 / 17 / 18 that runs past
+ *   HLIT + HDIST; a repeat code 16 with nothing before it; a bit pattern no code of the set matches; a length symbol above 285
+ *   or a distance symbol above 29; a distance that reaches before the start of the output.  Input that ends before the final
+ *   block's end-of-block code or inside the four Adler-32 bytes behind it is PR_PNG_ST_TRUNCATED.  Bytes behind the Adler-32
+ *   are ignored, as zlib.decompress ignores them.
+ *   Beyond zlib: output shorter or longer than H (1 + W bpp) bytes is PR_PNG_ST_SIZE (decoding stops at the first byte that
+ *   would not fit), a filter byte above 4 PR_PNG_ST_FILTER (the row is taken as filter 0), an Adler-32 of the inflated bytes
+ *   that differs from the trailer PR_PNG_ST_CHECKSUM.
+ * Unfilter.  The spec's unsigned-byte arithmetic per byte, with a = the byte bpp to the left, b = the byte above, c = the byte
+ *   above a (0 outside the image): None x, Sub x + a, Up x + b, Average x + ((a + b) >> 1), Paeth x + the one of a, b, c that
+ *   is nearest p = a + b - c, ties in the order a, b, c.
+ * Status and pixels.  status[f] = 0: the frame's pixels are exact.  A frame the parser refused, or whose descriptor or IDAT
+ *   ranges fail the device's checks, has PR_PNG_ST_REFUSED and zero pixels; a frame whose inflate failed (TRUNCATED, BAD_CODE,
+ *   SIZE) has zero pixels; a frame with PR_PNG_ST_FILTER or PR_PNG_ST_CHECKSUM alone has the pixels its bytes give.
+ * Isolation and memory safety (on ANY bytes).  A frame's stream lies in its own part of the workspace, bounded by the stream
+ *   length its descriptor states, which the gather checks against the IDAT ranges, themselves checked against data_bytes and
+ *   against each other (ascending, not overlapping); every read of the stream is bounded by its end (bits behind it do not
+ *   exist: a symbol that needs one is PR_PNG_ST_TRUNCATED); every write of the inflated bytes is bounded by H (1 + W bpp) and
+ *   every match reads only bytes this frame has already written; pixels go to the frame's own slot of `out`.  A bad frame
+ *   leaves every other frame's pixels and status untouched. */
+#define PR_PNG_MAX_SIDE 4096
+enum { /* bits of pr_png_decode's status[f] */
+  PR_PNG_ST_REFUSED = 1, PR_PNG_ST_TRUNCATED = 2, PR_PNG_ST_BAD_CODE = 4, PR_PNG_ST_SIZE = 8, PR_PNG_ST_FILTER = 16,
+  PR_PNG_ST_CHECKSUM = 32
+};
+enum { /* pr_png_parse's parse_status[f]; pr_png_refusal_name gives the words */
+  PR_PNG_OK = 0, PR_PNG_E_SIGNATURE = 1, PR_PNG_E_TRUNCATED = 2, PR_PNG_E_CRC = 3, PR_PNG_E_CHUNK_ORDER = 4, PR_PNG_E_DEPTH16 = 5,
+  PR_PNG_E_DEPTH_SUB8 = 6, PR_PNG_E_INTERLACE = 7, PR_PNG_E_CGBI = 8, PR_PNG_E_IHDR = 9, PR_PNG_E_SIZE_DIFFERS = 10,
+  PR_PNG_E_ZLIB_HEADER = 11, PR_PNG_E_COUNT = 12
+};
+typedef struct pr_png_frame {
+  int32_t width, height;
+  int32_t color_type;          /* 0, 2, 3, 4 or 6 */
+  int32_t bpp;                 /* bytes per pixel: 1, 3, 1, 2, 4; 0 = refused by the parser (the device zero-fills the frame) */
+  int32_t first_idat, n_idat;  /* this frame's run of the IDAT range array */
+  int32_t palette;             /* slot in the palette array for colour type 3, else -1 */
+  int32_t reserved;
+  int64_t zlib_bytes;          /* the zlib stream's length: the sum of the IDAT ranges' lengths */
+} pr_png_frame;
+typedef struct pr_png_idat { /* one IDAT chunk's payload: a byte range in `data` */
+  int64_t begin, end;
+} pr_png_idat;
+
+/* data_host, offsets_host, F, H, W as for pr_jpeg_parse (H, W: the size every frame must have, or 0, 0 to adopt the first
+ * accepted frame's).  Checks the signature, walks the chunks, verifies every chunk's CRC-32, validates IHDR and the zlib
+ * header (found across IDAT boundaries) and fills frames_host[F], parse_status_host[F] (PR_PNG_OK or a refusal; a refused
+ * frame has bpp = 0 and no ranges), up to idat_capacity ranges in idat_host, up to palette_capacity palettes of 256 x 3 bytes
+ * (RGB, zero behind PLTE's entries) in palettes_host, and counts_host[4] = ranges used, palettes used, H, W.  No payload is
+ * copied.  Returns PR_OK also when frames were refused (the last refusal is named in pr_last_error with its frame index),
+ * PR_ERR_CAPACITY when a capacity was too small (counts_host then holds what is needed; nothing else is valid),
+ * PR_ERR_INVALID for a null pointer, F < 0, a size outside 1..PR_PNG_MAX_SIDE or offsets out of order, before anything is
+ * dereferenced.  F = 0 is legal.  Ranges are absolute offsets in data_host and lie inside their file.  Never reads outside
+ * [offsets_host[0], offsets_host[F]). */
+int pr_png_parse(const uint8_t* data_host, const int64_t* offsets_host, int F, int H, int W, pr_png_frame* frames_host,
+                 pr_png_idat* idat_host, int idat_capacity, uint8_t* palettes_host, int palette_capacity,
+                 int32_t* parse_status_host, int32_t* counts_host);
+const char* pr_png_refusal_name(int code);
+
+/* Device memory pr_png_decode needs for F frames of H x W whose files hold data_bytes bytes in all: the gathered streams
+ * (data_bytes, padded), one record per frame, and the inflated scanlines at 4 bytes a pixel.  0 for sizes it refuses. */
+size_t pr_png_workspace_bytes(int F, int H, int W, int64_t data_bytes);
+
+/* All device pointers: data u8[data_bytes] (what pr_png_parse read, uploaded), frames / idat / palettes its descriptors
+ * uploaded unchanged (frames and idat 8-byte aligned), out u8[F,H,W,3] (any alignment; written in dwords where the frame's
+ * first byte is 4-byte aligned), status int32[F] (required; bits PR_PNG_ST_*).  The workspace must be 16-byte aligned.  Three
+ * kernels behind one asynchronous clear of the status words: gather (a workgroup per frame copies the IDAT payloads into one
+ * contiguous stream), inflate (one wavefront per frame, four frames a workgroup), unfilter + Adler-32 + colour (a workgroup
+ * per frame).  Argument errors (null pointers, sizes outside 1..PR_PNG_MAX_SIDE, a workspace below pr_png_workspace_bytes --
+ * PR_ERR_CAPACITY -- or misaligned, negative counts, ranges without data) are returned by name before any device work;
+ * F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no blocking copy, no synchronisation (capturable). */
+typedef struct pr_png_args {
+  const uint8_t* data;
+  const pr_png_frame* frames;
+  const pr_png_idat* idat;
+  const uint8_t* palettes;
+  uint8_t* out;
+  int32_t* status;
+  int64_t data_bytes;
+  int F, H, W;
+  int n_idat, n_palettes;
+  int bgr;
+} pr_png_args;
+int pr_png_decode(const pr_png_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

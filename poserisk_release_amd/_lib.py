@@ -68,6 +68,12 @@ class JpegEncArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "hs", "vs", "restart_interval", "bgr")]
 
 
+class PngArgs(C.Structure):
+    """pr_png_args (include/poserisk_hip.h, the PNG decoder)."""
+    _fields_ = [(n, C.c_void_p) for n in ("data", "frames", "idat", "palettes", "out", "status")] + [("data_bytes", C.c_int64)] + \
+               [(n, C.c_int) for n in ("F", "H", "W", "n_idat", "n_palettes", "bgr")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -137,6 +143,10 @@ SIGNATURES = {
     "pr_jpeg_encode_bound": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_jpeg_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, C.c_int64]),
     "pr_jpeg_encode": (_I, [C.POINTER(JpegEncArgs), _P, C.c_size_t, _P]),
+    "pr_png_parse": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "pr_png_refusal_name": (C.c_char_p, [_I]),
+    "pr_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, C.c_int64]),
+    "pr_png_decode": (_I, [C.POINTER(PngArgs), _P, C.c_size_t, _P]),
     "pr_resize_plan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pr_resize_frames": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
 }

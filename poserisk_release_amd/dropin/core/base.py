@@ -16,6 +16,7 @@ result text files, the score plots, the debug CSVs and the annotated video (draw
 composed on the GPU with the gpu_video knob).
 """
 import json
+import os
 import os.path as osp
 
 import numpy as np
@@ -528,6 +529,17 @@ class Predictor:
                                    frame=self.debug_frame)
 
     # ---- main/run.py:31  predictor(args.input, args.info, args.output) -----------------------------------
+    @staticmethod
+    def _folder_sidecars(folder):
+        """What every frame folder carries beside its frames -> (fps, tracking): `fps.txt` (optional, 30.0 without it) and
+        `tracking.pkl`."""
+        import pickle
+        with open(osp.join(folder, 'tracking.pkl'), 'rb') as f:
+            tracking = pickle.load(f)
+        fps_file = osp.join(folder, 'fps.txt')
+        fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
+        return fps, tracking
+
     def load_front_end(self, input_path, output_path, tracking_results=None):
         """Decoded frames + tracker output for `input_path` -> (frames u8[F,H,W,3], bgr, fps, tracking dict).
 
@@ -539,6 +551,12 @@ class Predictor:
              optional `fps.txt`: the files are decoded on the GPU, bit-exact with cv2.imread's pixels
              (poserisk_release_amd/jpeg.py), and the frames come back as a device tensor, RGB.  A frame that is not
              baseline JPEG, has another size than the first or is damaged raises, naming the file and the reason;
+          2b. a directory without `frames.npy`, with `tracking.pkl`, at least one `*.png` name and no `*.jpg` / `*.jpeg` name
+             (what `ffmpeg -i video %09d.png`, screen recorders and this package's own report path write): the files are
+             decoded on the GPU, exact with zlib and libpng (poserisk_release_amd/png.py), RGB on the device, gray replicated
+             and alpha dropped; optional `fps.txt`.  A file that is not an 8-bit non-interlaced PNG, has another size than
+             the first or is damaged raises, naming the file and the reason.  A folder that mixes the two kinds of names
+             goes to 2 and is refused there;
           3. a Motion-JPEG AVI file (a camera's, `ffmpeg -c:v mjpeg`'s, this package's own <TITLE>_video.avi): demuxed in
              Python, decoded and downscaled on the GPU by the reference's rule (poserisk_release_amd/frontend.py;
              cfg.DATASET.front_max_w / front_max_h), no OpenCV anywhere.  Its tracking is, in this order, the
@@ -550,16 +568,20 @@ class Predictor:
              frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
              written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
              the same JPEG-decoded pixels as the reference's CropDataset."""
-        import pickle
         if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'frames.npy')):
             frames = np.load(osp.join(input_path, 'frames.npy'))
-            with open(osp.join(input_path, 'tracking.pkl'), 'rb') as f:
-                tracking = pickle.load(f)
-            fps_file = osp.join(input_path, 'fps.txt')
-            fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
-            return frames, False, fps, tracking
+            return (frames, False) + self._folder_sidecars(input_path)
         if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'tracking.pkl')):
-            from poserisk_release_amd import jpeg
+            from poserisk_release_amd import jpeg, png
+            names = png.list_frames(input_path)
+            if names and not any(n.lower().endswith(('.jpg', '.jpeg')) for n in os.listdir(input_path)):
+                paths = [osp.join(input_path, n) for n in names]
+                frames, status = png.decode_files(paths, self.device)
+                bad = png.bad_frames(paths, status)
+                if bad:
+                    raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
+                                       + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+                return (frames, False) + self._folder_sidecars(input_path)
             names = jpeg.list_frames(input_path)
             if names:
                 paths = [osp.join(input_path, n) for n in names]
@@ -570,11 +592,7 @@ class Predictor:
                 if bad:
                     raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
                                        + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
-                with open(osp.join(input_path, 'tracking.pkl'), 'rb') as f:
-                    tracking = pickle.load(f)
-                fps_file = osp.join(input_path, 'fps.txt')
-                fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
-                return frames, False, fps, tracking
+                return (frames, False) + self._folder_sidecars(input_path)
         not_mjpeg = None
         if osp.isfile(input_path):
             from poserisk_release_amd import mjpeg
@@ -591,11 +609,10 @@ class Predictor:
         except ImportError as e:
             raise RuntimeError(
                 f"{input_path!r} is neither a directory with frames.npy + tracking.pkl nor one with JPEG frames "
-                f"(*.jpg, decoded on the GPU) + tracking.pkl, and the reference's front end "
+                f"(*.jpg, decoded on the GPU) or PNG frames (*.png, decoded on the GPU) + tracking.pkl, and the reference's front end "
                 f"(cv2 video decoding, multi_person_tracker) is not importable here ({e}); decode and track outside, "
                 "then call Predictor.score_frames(frames, tracking_results, info)"
                 + (f" [as a Motion-JPEG AVI it was refused: {not_mjpeg}]" if not_mjpeg is not None else "")) from e
-        import os
         import shutil
         image_path = osp.join(output_path, 'tmp')
         shutil.rmtree(image_path, ignore_errors=True)

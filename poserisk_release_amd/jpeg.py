@@ -69,7 +69,8 @@ def scan_refusal_name(code):
 def list_frames(directory):
     """The frame files of `directory`: names ending in .jpg / .jpeg (any case), sorted -- position in that order is the frame
     index, as in the reference's sorted(os.listdir) (multi_person_tracker's ImageFolder, CropDataset).  A .png among them is
-    refused by name: there is no PNG decoder here.  Other files (tracking.pkl, fps.txt) are ignored."""
+    refused by name: this module decodes no PNG (a folder of PNG frames alone is png.py's).  Other files (tracking.pkl,
+    fps.txt) are ignored."""
     names = sorted(os.listdir(directory))
     png = [n for n in names if n.lower().endswith(".png")]
     if png:

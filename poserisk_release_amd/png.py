@@ -1,0 +1,227 @@
+"""PNG frames decoded on the GPU, exact with zlib and libpng (what cv2.imread and Pillow's .convert("RGB") give): the front of
+the accelerated path for a folder of lossless frames as `ffmpeg -i clip.mp4 %09d.png`, screen recorders, annotation tools and
+this package's own report path write them.  The contract is in include/poserisk_hip.h (section j4); the chunk walk is
+csrc/png_host.cc (host, no device), everything else csrc/png.hip over csrc/png_device.h.
+
+`list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
+go through ONE pinned buffer and ONE upload, then pr_png_decode (gather, inflate, unfilter + Adler-32 + colour)."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# pr_png_frame, pr_png_idat as numpy records (tests compare them with the C structs); a palette is 256 x 3 bytes
+FRAME_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("color_type", "<i4"), ("bpp", "<i4"), ("first_idat", "<i4"),
+                        ("n_idat", "<i4"), ("palette", "<i4"), ("reserved", "<i4"), ("zlib_bytes", "<i8")])
+IDAT_DTYPE = np.dtype([("begin", "<i8"), ("end", "<i8")])
+PALETTE_BYTES = 768
+ST_REFUSED, ST_TRUNCATED, ST_BAD_CODE, ST_SIZE, ST_FILTER, ST_CHECKSUM = 1, 2, 4, 8, 16, 32
+_ST_NAMES = ((ST_REFUSED, "refused (the file, its descriptor or its IDAT ranges are invalid)"),
+             (ST_TRUNCATED, "the deflate stream ends early"), (ST_BAD_CODE, "the deflate stream breaks a rule of RFC 1951"),
+             (ST_SIZE, "the stream does not inflate to the image's size"), (ST_FILTER, "a scanline's filter byte is above 4"),
+             (ST_CHECKSUM, "the Adler-32 of the inflated bytes does not match"))
+# Frames per decode call.  A frame is one serial chain of symbols on one wavefront, so the rate comes from the frames in flight
+# (800 x 450, Pillow's default level: 170 / 515 / 1 058 frames/s at 64 / 256 / 1024 a call, profiles/png_decode.json); 256 keeps
+# the workspace, 2.1 MB a frame at that size, at half a gigabyte.  Pass chunk=1024 where the memory is there.
+DEFAULT_CHUNK = 256
+DEFAULT_MAX_BYTES = 4 << 30
+_EXT = (".png",)
+
+
+def status_text(st):
+    """The words for a pr_png_decode status."""
+    return "; ".join(t for bit, t in _ST_NAMES if st & bit) or "ok"
+
+
+def refusal_name(code):
+    """The words for a pr_png_parse refusal."""
+    return _lib.load().pr_png_refusal_name(int(code)).decode()
+
+
+def list_frames(directory):
+    """The frame files of `directory`: names ending in .png (any case), sorted -- position in that order is the frame index, as
+    in sorted(os.listdir).  Other files (tracking.pkl, fps.txt) are ignored; a folder that also holds .jpg / .jpeg frames is
+    for the caller to refuse (dropin/core/base.py does)."""
+    return [n for n in sorted(os.listdir(directory)) if n.lower().endswith(_EXT)]
+
+
+def _parse_into(data, offsets, H, W, frames, idat, palettes, pstatus):
+    """pr_png_parse into caller-owned numpy arrays -> (status code, counts int32[4] = ranges, palettes, H, W)."""
+    counts = np.zeros(4, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = _lib.load().pr_png_parse(ptr(data), ptr(offsets), len(offsets) - 1, int(H), int(W), ptr(frames), ptr(idat), len(idat),
+                                  ptr(palettes), len(palettes) // PALETTE_BYTES, ptr(pstatus), ptr(counts))
+    return rc, counts
+
+
+def parse(blobs, H=0, W=0):
+    """Host half on a list of bytes objects: (frames FRAME_DTYPE[F], idat IDAT_DTYPE[N], palettes u8[P, 256, 3], parse_status
+    int32[F], H, W, offsets int64[F+1]).  Refused frames have parse_status != 0 (refusal_name gives the words)."""
+    offsets = np.zeros(len(blobs) + 1, np.int64)
+    np.cumsum([len(b) for b in blobs], out=offsets[1:])
+    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    F = len(blobs)
+    frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
+    idat_cap, pal_cap = 16 + 2 * F, 1
+    while True:
+        idat, palettes = np.zeros(idat_cap, IDAT_DTYPE), np.zeros(pal_cap * PALETTE_BYTES, np.uint8)
+        rc, counts = _parse_into(data, offsets, H, W, frames, idat, palettes, pstatus)
+        if rc != -4:                                             # PR_ERR_CAPACITY: counts says what is needed
+            _lib.check(rc, "pr_png_parse")
+            return (frames, idat[:counts[0]], palettes[:counts[1] * PALETTE_BYTES].reshape(-1, 256, 3), pstatus, int(counts[2]),
+                    int(counts[3]), offsets)
+        idat_cap, pal_cap = max(idat_cap, int(counts[0])), max(pal_cap, int(counts[1]))
+
+
+def workspace_bytes(F, H, W, data_bytes):
+    """Device memory a pr_png_decode call needs (0 for sizes it refuses)."""
+    return int(_lib.load().pr_png_workspace_bytes(int(F), int(H), int(W), int(data_bytes)))
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def _size(p):
+    return os.path.getsize(p) if isinstance(p, (str, os.PathLike)) else len(p)
+
+
+def _peek_size(items):
+    """(H, W) of the first item that starts like a PNG (its IHDR's numbers, unchecked: only chunks are sized by them)."""
+    for p in items:
+        if isinstance(p, (str, os.PathLike)):
+            with open(p, "rb") as f:
+                head = f.read(24)
+        else:
+            head = bytes(p[:24])
+        if len(head) == 24 and head[:8] == b"\x89PNG\r\n\x1a\n" and head[12:16] == b"IHDR":
+            w, h = int.from_bytes(head[16:20], "big"), int.from_bytes(head[20:24], "big")
+            if 1 <= w <= 4096 and 1 <= h <= 4096:
+                return h, w
+    return 0, 0
+
+
+def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, max_bytes=DEFAULT_MAX_BYTES):
+    """Decode F PNG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread gives with
+    bgr=True; gray replicated, alpha dropped).  Returns (frames, status int32[F] on the device): status[f] != 0 marks a frame
+    that was refused (bit 0; its pixels are zero) or whose stream was damaged; `bad_frames` puts the reasons into words.  The
+    files are taken in chunks of at most `chunk`, cut shorter so that a chunk's workspace and its slice of the output stay
+    within `max_bytes` of device memory (at least one frame a chunk).  Per chunk the bytes are read into ONE pinned host
+    buffer, the parser writes its descriptors behind them in the same buffer, and ONE asynchronous copy uploads it; the decode
+    neither allocates nor synchronises (include/poserisk_hip.h, pr_png_decode).  The host waits for chunk k's upload (not its
+    decode) before it reads chunk k + 1 into the buffer."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PoseRiskHipError("decode_files: the decoder runs on the GPU only (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    items = list(paths_or_bytes)
+    F, chunk = len(items), max(int(chunk), 1)
+    lib = _lib.load()
+    sizes = [_size(p) for p in items]
+    H, W = 0, 0
+    h0, w0 = _peek_size(items)
+    per_frame = (h0 * (1 + 4 * w0) + 16 + 16) + h0 * w0 * 3      # workspace without the files' bytes, and the output
+    frames_out = status = pinned = ws = uploaded = first_refusal = None
+    idat_per_frame = 2
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device)
+        lo = 0
+        while lo < F:
+            n, total = 0, 0
+            while lo + n < F and n < chunk and (n == 0 or (n + 1) * per_frame + total + sizes[lo + n] + 32 <= max_bytes):
+                total += sizes[lo + n]
+                n += 1
+            part = items[lo:lo + n]
+            offsets = np.zeros(n + 1, np.int64)
+            np.cumsum(sizes[lo:lo + n], out=offsets[1:])
+            idat_room, pal_room = 16 + idat_per_frame * n, n
+            # [file bytes | frames | palettes | IDAT ranges]: the parser reads the bytes where they lie and writes beside them
+            o_fr = _align(max(total, 1))
+            o_pal = _align(o_fr + n * FRAME_DTYPE.itemsize)
+            o_idat = _align(o_pal + pal_room * PALETTE_BYTES)
+            room = o_idat + idat_room * IDAT_DTYPE.itemsize
+            if uploaded is not None:
+                uploaded.synchronize()                           # the previous chunk has left the buffer
+                uploaded = None
+            if pinned is None or pinned.numel() < room:
+                pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
+            host = pinned.numpy()
+            for p, a, b in zip(part, offsets[:-1], offsets[1:]):
+                if isinstance(p, (str, os.PathLike)):
+                    with open(p, "rb") as f:
+                        got = f.readinto(memoryview(host[a:b]))
+                    if got != b - a:
+                        raise OSError(f"{p!r} changed size while it was read")
+                else:
+                    host[a:b] = np.frombuffer(bytes(p), np.uint8)
+            pst = np.zeros(n, np.int32)
+            while True:
+                fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
+                pal = host[o_pal:o_pal + pal_room * PALETTE_BYTES]
+                idat = host[o_idat:o_idat + idat_room * IDAT_DTYPE.itemsize].view(IDAT_DTYPE)
+                rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, idat, pal, pst)
+                if rc != -4:                                     # PR_ERR_CAPACITY: more IDAT chunks than guessed
+                    _lib.check(rc, "pr_png_parse")
+                    break
+                idat_room = int(counts[0])
+                idat_per_frame = max(idat_per_frame, -(-idat_room // n))
+                room = o_idat + idat_room * IDAT_DTYPE.itemsize
+                if pinned.numel() < room:
+                    bigger = torch.empty(room, dtype=torch.uint8).pin_memory()
+                    bigger[:total] = pinned[:total]
+                    pinned, host = bigger, bigger.numpy()
+            n_idat, n_pal = int(counts[0]), int(counts[1])
+            if H == 0 and pst.any() and first_refusal is None:
+                first_refusal = (lo + int(np.nonzero(pst)[0][0]), refusal_name(pst[np.nonzero(pst)[0][0]]))
+            if H == 0 and counts[2]:
+                H, W = int(counts[2]), int(counts[3])
+                frames_out = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
+                if tuple(frames_out.shape) != (F, H, W, 3) or frames_out.dtype != torch.uint8 or not frames_out.is_contiguous() \
+                        or frames_out.device != device:
+                    raise ValueError(f"out must be a contiguous uint8 {[F, H, W, 3]} tensor on {device}")
+                status = torch.full((F,), ST_REFUSED, dtype=torch.int32, device=device)   # chunks before the first size
+                frames_out[:lo].zero_()
+                per_frame = (H * (1 + 4 * W) + 32) + H * W * 3
+            if H != 0:
+                used = o_idat + n_idat * IDAT_DTYPE.itemsize
+                dev = torch.empty(used, dtype=torch.uint8, device=device)
+                dev.copy_(pinned[:used], non_blocking=True)      # the chunk's one upload
+                uploaded = torch.cuda.Event()
+                uploaded.record(stream)
+                need = workspace_bytes(n, H, W, total)
+                if ws is None or ws.numel() < need:
+                    ws = torch.empty(need, dtype=torch.uint8, device=device)
+                base = dev.data_ptr()
+                args = _lib.PngArgs(base, base + o_fr, base + o_idat, base + o_pal, frames_out[lo:lo + n].data_ptr(),
+                                    status[lo:lo + n].data_ptr(), total, n, H, W, n_idat, n_pal, int(bool(bgr)))
+                _lib.check(lib.pr_png_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_png_decode")
+                dev.record_stream(stream)
+                ws.record_stream(stream)
+            lo += n
+        if uploaded is not None:
+            uploaded.synchronize()
+    if frames_out is None:
+        if first_refusal:
+            raise _lib.PoseRiskHipError(f"decode_files: no frame was accepted; frame {first_refusal[0]}: {first_refusal[1]}")
+        frames_out = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
+        status = torch.zeros(0, dtype=torch.int32, device=device)
+    return frames_out, status
+
+
+def bad_frames(paths_or_bytes, status):
+    """[(frame index, reason)] for every frame of a decode_files call whose status is non-zero (one device -> host copy; a
+    refused frame's file is parsed again on its own to name the parser's reason)."""
+    items, st, out = list(paths_or_bytes), status.cpu().numpy(), []
+    for i in np.nonzero(st)[0]:
+        why = status_text(int(st[i]))
+        if st[i] & ST_REFUSED:
+            p = items[i]
+            blob = open(p, "rb").read() if isinstance(p, (str, os.PathLike)) else bytes(p)
+            _, _, _, pst, h, w, _ = parse([blob])
+            why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
+        out.append((int(i), why))
+    return out
