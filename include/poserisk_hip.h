@@ -1092,6 +1092,118 @@ typedef struct pr_png_args {
 } pr_png_args;
 int pr_png_decode(const pr_png_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j5  u8[F,H,W,3] on the device -> PNG files: filters, run-length deflate, dynamic codes  */
+/* replaces: the raw download + Pillow save of one PNG per frame behind the composed       */
+/*           canvases (write_gpu_video, _mesh_writer): only compressed bytes leave         */
+/* ------------------------------------------------------------------------------------ */
+/* The lossless counterpart of j2 and the inverse of j4.  The host half (pr_png_encode_plan, csrc/png_enc_host.cc, no device)
+ * writes the fixed bytes and the CRC power table; the device half (pr_png_encode, csrc/png_enc.hip over
+ * csrc/png_enc_device.h) does everything else.  tests/png_enc_ref.py restates this section in numpy and Python.  No ABI bump:
+ * functions and structs were added.
+ *
+ * What is promised.  The bytes are NOT any library's bytes (zlib's match choices and tree heuristics are no contract).  Instead:
+ *   (a) every file is a valid PNG that zlib, libpng, Pillow and pr_png_decode decode to exactly the input pixels;
+ *   (b) the bytes are a deterministic function of pixels and parameters, fixed by the rules below; kernel and reference agree
+ *   on every byte.
+ * Accepted.  u8 [F,H,W,3] frames (RGB, or BGR with bgr != 0), 1 <= H, W <= PR_PNG_MAX_SIDE.  Output: colour type 2, depth 8,
+ *   non-interlaced.  filter 0..4 = that filter on every row, 5 = adaptive.  mode PR_PNG_ENC_STORED or PR_PNG_ENC_RLE.  Other
+ *   colour types, alpha and interlace have no entry.
+ * Filtering.  j4's unfilter rules inverted, on unsigned bytes with bpp = 3 (None x, Sub x - a, Up x - b, Average
+ *   x - ((a + b) >> 1), Paeth x - the nearest of a, b, c to a + b - c, ties a, b, c; all mod 256).  a, b, c are taken from the
+ *   RAW pixels of this row and the row above (0 outside the image), so rows are independent.  Adaptive: per row the filter
+ *   whose 3 W output bytes (the type byte is not counted) have the smallest sum of |signed byte| (v < 128 ? v : 256 - v); ties
+ *   go to the lowest filter number.  PR_PNG_ENC_STORED uses filter 0 whatever is asked.
+ * Segments.  The filtered stream of H (1 + 3 W) bytes is cut into segments of PR_PNG_ENC_SEGMENT = 16384 bytes, the last one
+ *   shorter.  Each is coded with no reference to bytes before it and begins and ends on a byte boundary.  A coded segment is
+ *   one dynamic block; every segment but the last is followed by an empty stored block (the 3 header bits 000, zero bits up to
+ *   the byte boundary, 00 00 FF FF); in the last segment the data block carries BFINAL, is padded with zero bits, and there is
+ *   no empty block.
+ * Tokens (PR_PNG_ENC_RLE): zlib's deflate_rle rule.  At position i behind the segment's start, if the next three bytes equal
+ *   byte i - 1, a match of distance 1 whose length is the run's, capped at 258 and at the segment's end; otherwise a literal.
+ *   A maximal run of L equal bytes is therefore one literal, then with R = L - 1: R / 258 matches of 258 and, for the rest r =
+ *   R % 258, one match of r when r >= 3, else r literals.
+ * Codes.  Literal/length code lengths from the segment's own histogram of literals and length symbols plus one end-of-block
+ *   symbol, limit 15 bits; HLIT covers the highest used symbol (at least 257).  The distance set is always the single code 0
+ *   of length 1, in a segment without a match too (HDIST = 1; zlib and j4 accept the incomplete set, and a segment without a
+ *   match never reads it).  The HLIT + 1 lengths are ONE sequence (a run may pass from the literal/length lengths into the
+ *   distance length).  Runs in it: a run of zeros sends, while at least 3 remain, symbol 18 for min(run, 138) when at least 11
+ *   remain and else symbol 17 for all of them, and fewer than 3 as they are; a run of a non-zero length sends the length once,
+ *   then symbol 16 for min(rest, 6) while at least 3 remain, then the rest as they are.  The code-length code is built from
+ *   that sequence's histogram by the same construction with limit 7; HCLEN covers the last used symbol in RFC 1951's order, at
+ *   least 4.  Both alphabets always have at least two used symbols (a segment holds a byte and the end-of-block symbol; the
+ *   sequence holds the distance length 1 and a literal length above 1), so both codes are complete.
+ *   Construction (any alphabet, limit M).  1. The used symbols in (count, symbol) order.  2. Huffman's merge with two queues,
+ *   leaves in that order and internal nodes in the order they were made; each step takes the two smallest weights, and of two
+ *   equal weights the internal node before the leaf.  Only the NUMBER of codes per depth is kept.  3. Codes deeper than M are
+ *   counted at M; while the Kraft sum exceeds 1: one code of length M is dropped, one code of the greatest length d < M that
+ *   has any becomes two codes of length d + 1 (one unit of 2^-M a step).  4. The lengths are handed out longest first in the
+ *   order of 1.  5. Canonical codes as in RFC 1951 3.2.2.  Nothing depends on lane order: the histogram is integer sums, the
+ *   order of 1 is a total order, 2 - 5 are serial.
+ * Fallback.  A segment of n bytes is written as ONE stored block (a byte with BFINAL, LEN, NLEN, the n bytes; no empty block
+ *   behind it, it ends aligned) when its coded form, the empty block included, would take 5 + n bytes or more, and always in
+ *   PR_PNG_ENC_STORED.  So no segment takes more than 5 + n bytes.
+ * File.  Signature; IHDR; ONE IDAT chunk holding the zlib header 78 01, the segments, and the Adler-32 of all filtered bytes
+ *   big-endian; IEND.  Chunk CRC-32s are computed on the device (IHDR's and IEND's are constants of the plan).  Both checksums
+ *   are computed per segment and combined: Adler by the sum rule (A = 1 + sum a_s, B = N + sum (b_s + a_s * bytes behind s),
+ *   mod 65521), CRC by multiplying each segment's register by x^(8 * bytes behind it) mod the polynomial, with x^(2^k) from
+ *   the plan; inside a segment the 64 lanes do the same with their 1/64ths.
+ * Capacity.  pr_png_encode_bound(H, W) = 63 + N + 5 * ceil(N / 16384), N = H (1 + 3 W): 8 signature + 25 IHDR + 12 IDAT
+ *   framing + 2 zlib header + 4 Adler-32 + 12 IEND, and 5 + n per segment by the fallback rule.  No file exceeds it; a
+ *   PR_PNG_ENC_STORED file has exactly that size.  A caller may give each frame a smaller slot: a frame that does not fit gets
+ *   nbytes[f] = 0 and status PR_PNG_ENC_ST_OVERFLOW and NOTHING is written to its slot; a frame writes exactly nbytes[f] bytes
+ *   from the start of its slot, never another frame's. */
+#define PR_PNG_ENC_SEGMENT 16384
+#define PR_PNG_ENC_HEAD_BYTES 43 /* signature .. the zlib header */
+#define PR_PNG_ENC_TAIL_BYTES 12 /* IEND */
+enum { PR_PNG_ENC_STORED = 0, PR_PNG_ENC_RLE = 1 };
+enum { PR_PNG_ENC_FILTER_ADAPTIVE = 5 };
+enum { PR_PNG_ENC_ST_OVERFLOW = 1 }; /* bits of pr_png_encode's status[f] */
+typedef struct pr_png_enc_plan { /* what one (filter, mode, size) needs; uploaded unchanged */
+  /* The first six are informational: they say what the plan was made for (a caller's cache key, a test's check).  The device
+   * reads none of them -- the host cannot read an uploaded plan, so pr_png_encode takes the geometry from its arguments, and
+   * of the plan only crc_pow, idat_crc_head, head (whose IHDR states the size) and tail. */
+  int32_t width, height, filter, mode;
+  int32_t n_segments, reserved;
+  int64_t raw_bytes;                     /* N = H (1 + 3 W) */
+  uint32_t crc_pow[32];                  /* x^(2^k) mod the CRC-32 polynomial, bit-reflected as the CRC register is */
+  uint32_t idat_crc_head;                /* the CRC register (not inverted) behind "IDAT" 78 01 */
+  uint32_t reserved2;
+  uint8_t head[48];                      /* signature, IHDR with its CRC, four zero bytes for IDAT's length, "IDAT", 78 01 */
+  uint8_t tail[16];                      /* IEND with its CRC */
+} pr_png_enc_plan;
+
+/* Fills *plan_host.  PR_ERR_INVALID by name for a filter outside 0..5, a mode other than the two, a size outside
+ * 1..PR_PNG_MAX_SIDE or a null pointer, before anything is dereferenced.  No device call. */
+int pr_png_encode_plan(int filter, int mode, int H, int W, pr_png_enc_plan* plan_host);
+/* A size no file of an H x W frame exceeds (0 for an invalid size). */
+size_t pr_png_encode_bound(int H, int W);
+/* Device memory pr_png_encode needs for F frames (0 for invalid parameters): a staging area of 16400 bytes and 20 bytes of
+ * records per segment, one filter byte per row, one word per frame. */
+size_t pr_png_encode_workspace_bytes(int F, int H, int W);
+
+/* All device pointers: frames u8[F,H,W,3], plan (one pr_png_enc_plan, uploaded), out u8[F,capacity] (any alignment), nbytes
+ * int32[F], status int32[F] (bits PR_PNG_ENC_ST_*).  H, W, filter, mode as given to pr_png_encode_plan.  Each slot receives
+ * the whole file.  Kernels: choose (adaptive only; a wavefront per row picks its filter), segment (a wavefront per segment:
+ * filters its bytes into LDS, tokens, histogram, codes, bits, checksums, into the segment's own staging area), assemble (a
+ * workgroup per frame: prefix sum of the segment sizes, the combined checksums, the capacity check, head and tail, nbytes and
+ * status), place (a workgroup per segment copies it into the slot, in aligned dwords).  The workspace must be 16-byte aligned.
+ * Argument errors (null pointers, a size, filter or mode outside the accepted ones, F < 0 or above 65535, capacity < 0 or above
+ * 2^31 - 1, a workspace below pr_png_encode_workspace_bytes or misaligned) return PR_ERR_INVALID by name before any device
+ * work; F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no blocking copy, no synchronisation (capturable). */
+typedef struct pr_png_enc_args {
+  const uint8_t* frames;
+  const pr_png_enc_plan* plan;
+  uint8_t* out;
+  int32_t* nbytes;
+  int32_t* status;
+  int64_t capacity;
+  int F, H, W;
+  int filter, mode;
+  int bgr;
+} pr_png_enc_args;
+int pr_png_encode(const pr_png_enc_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,12 @@ class PngArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "n_idat", "n_palettes", "bgr")]
 
 
+class PngEncArgs(C.Structure):
+    """pr_png_enc_args (include/poserisk_hip.h, the PNG encoder)."""
+    _fields_ = [(n, C.c_void_p) for n in ("frames", "plan", "out", "nbytes", "status")] + [("capacity", C.c_int64)] + \
+               [(n, C.c_int) for n in ("F", "H", "W", "filter", "mode", "bgr")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -147,6 +153,10 @@ SIGNATURES = {
     "pr_png_refusal_name": (C.c_char_p, [_I]),
     "pr_png_workspace_bytes": (C.c_size_t, [_I, _I, _I, C.c_int64]),
     "pr_png_decode": (_I, [C.POINTER(PngArgs), _P, C.c_size_t, _P]),
+    "pr_png_encode_plan": (_I, [_I, _I, _I, _I, _P]),
+    "pr_png_encode_bound": (C.c_size_t, [_I, _I]),
+    "pr_png_encode_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "pr_png_encode": (_I, [C.POINTER(PngEncArgs), _P, C.c_size_t, _P]),
     "pr_resize_plan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pr_resize_frames": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
 }

@@ -144,11 +144,13 @@ class Predictor:
         self.gpu_video = bool(knob if knob is not None else cfg.DATASET.get('gpu_video', False))
         # how write_gpu_video and the mesh writer store their frames: args.video_codec, else cfg.DATASET.gpu_video_codec.  ''
         # (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded on the GPU
-        # (jpeg.encode_frames) into <TITLE>_video.avi / <TITLE>_mesh.avi (mjpeg.AviWriter), with or without cv2
+        # (jpeg.encode_frames) into <TITLE>_video.avi / <TITLE>_mesh.avi (mjpeg.AviWriter), with or without cv2; 'png' = lossless,
+        # encoded on the GPU (png.encode_frames) into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2
         knob = getattr(args, 'video_codec', None)
         self.gpu_video_codec = str(knob if knob is not None else cfg.DATASET.get('gpu_video_codec', '') or '')
-        if self.gpu_video_codec not in ('', 'mjpeg'):
-            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames) or 'mjpeg'")
+        if self.gpu_video_codec not in ('', 'mjpeg', 'png'):
+            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg' "
+                             "or 'png'")
         self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
@@ -411,10 +413,37 @@ class Predictor:
                 avi.write(data)
         return write, lambda: (avi.close(), path)[1]
 
+    def _png_writer(self, path, bgr):
+        """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): the images encoded to PNG on the GPU (adaptive
+        filters, run-length deflate; png.encode_frames) and written as `path`/%09d.png by frame number: only the files' bytes
+        leave the device.  A slot holds half the raw size, which rendered canvases stay far below; a frame that overflows it
+        (noise does) is encoded again alone with the slot no file exceeds."""
+        import os
+        from poserisk_release_amd import png
+        os.makedirs(path, exist_ok=True)
+
+        def write(numbers, images):
+            images = images.contiguous()
+            H, W = int(images.shape[1]), int(images.shape[2])
+            buf, nbytes, status = png.encode_frames(images, bgr=bgr, capacity=min(png.encode_bound(H, W), 4096 + H * W * 3 // 2))
+            files = png.download_files(buf, nbytes)
+            for i in np.nonzero(status.cpu().numpy())[0]:
+                buf1, nbytes1, status1 = png.encode_frames(images[i:i + 1], bgr=bgr, capacity=png.encode_bound(H, W))
+                if int(status1[0]):
+                    raise RuntimeError(f"png.encode_frames: status {int(status1[0])} for a frame with the largest slot")
+                files[i] = png.download_files(buf1, nbytes1)[0]
+            for f, data in zip(numbers, files):
+                with open(osp.join(path, '{0:09d}.png'.format(int(f))), 'wb') as fh:
+                    fh.write(data)
+        return write, lambda: path
+
     def _mesh_writer(self, frames, output_path, title, bgr, fps):
         """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): <output>/<TITLE>_mesh.mp4 where cv2 is importable,
-        else <output>/<TITLE>_mesh/%09d.png (frame number); with gpu_video_codec 'mjpeg' <output>/<TITLE>_mesh.avi either way."""
+        else <output>/<TITLE>_mesh/%09d.png (frame number); with gpu_video_codec 'mjpeg' <output>/<TITLE>_mesh.avi either way,
+        with 'png' <output>/<TITLE>_mesh/%09d.png encoded on the GPU either way."""
         import os
+        if self.gpu_video_codec == 'png':
+            return self._png_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh"), bgr)
         if self.gpu_video_codec == 'mjpeg':
             put, close = self._mjpeg_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh.avi"),
                                             int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
@@ -457,7 +486,8 @@ class Predictor:
         """`<TITLE>_video`: every frame of the video at 720 px wide with the target's box, beside the score panel, composed by
         poserisk_release_amd.video (pr_compose_video) from the arrays score_frames returned.  <output>/<TITLE>_video.mp4 where
         cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame; with
-        gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there.  With
+        gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there; with
+        'png' <output>/<TITLE>_video/%09d.png, encoded on the GPU (lossless), whether or not cv2 is there.  With
         the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
         parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
         that the mesh output is written from the same rendering.  Returns the path written."""
@@ -494,6 +524,13 @@ class Predictor:
             finally:                                # also when encoding raises: the index is written, the headers patched
                 path = close()
             return path
+        if self.gpu_video_codec == 'png':
+            put, close = self._png_writer(osp.join(output_path, title + '_video'), bgr)
+            i = 0
+            for canvases in batches:
+                put(range(i, i + int(canvases.shape[0])), canvases)
+                i += int(canvases.shape[0])
+            return close()
         try:
             import cv2
         except ImportError:

@@ -26,7 +26,9 @@ absent from the reference and all optional:
                               args.gpu_video overrides it)
     cfg.DATASET.gpu_video_codec  '' (default: the two outputs above as they are) | 'mjpeg': <TITLE>_video.avi and <TITLE>_mesh.avi,
                               baseline JPEG frames encoded on the GPU (pr_jpeg_encode) in a Motion-JPEG AVI written in Python,
-                              with or without cv2 (args.video_codec overrides it); any other name raises
+                              with or without cv2 | 'png': <TITLE>_video/%09d.png and <TITLE>_mesh/%09d.png, lossless frames
+                              encoded on the GPU (pr_png_encode), with or without cv2 (args.video_codec overrides it); any other
+                              name raises
     cfg.DATASET.gpu_video_quality  the JPEG quality of those frames, 1..100 (90)
     cfg.DATASET.front_max_w, front_max_h  800, 450: the reference's front-end rule for a Motion-JPEG AVI input (wider than
                               front_max_w -> that width, else higher than front_max_h -> that height; 0 switches an arm off),

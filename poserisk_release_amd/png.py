@@ -3,6 +3,8 @@ the accelerated path for a folder of lossless frames as `ffmpeg -i clip.mp4 %09d
 this package's own report path write them.  The contract is in include/poserisk_hip.h (section j4); the chunk walk is
 csrc/png_host.cc (host, no device), everything else csrc/png.hip over csrc/png_device.h.
 
+The other direction -- `encode_frames`, u8 frames on the device to PNG files, section j5 -- is at the end of this file.
+
 `list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
 go through ONE pinned buffer and ONE upload, then pr_png_decode (gather, inflate, unfilter + Adler-32 + colour)."""
 import ctypes as C
@@ -12,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .jpeg import download_files   # noqa: F401  (buffer, nbytes) -> [bytes]: one shape of result for both encoders
 
 # pr_png_frame, pr_png_idat as numpy records (tests compare them with the C structs); a palette is 256 x 3 bytes
 FRAME_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("color_type", "<i4"), ("bpp", "<i4"), ("first_idat", "<i4"),
@@ -225,3 +228,103 @@ def bad_frames(paths_or_bytes, status):
             why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
         out.append((int(i), why))
     return out
+
+
+# ---- the encoder (include/poserisk_hip.h, section j5): host half csrc/png_enc_host.cc, device half csrc/png_enc.hip ------------
+ENC_PLAN_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("filter", "<i4"), ("mode", "<i4"), ("n_segments", "<i4"),
+                           ("reserved", "<i4"), ("raw_bytes", "<i8"), ("crc_pow", "<u4", (32,)), ("idat_crc_head", "<u4"),
+                           ("reserved2", "<u4"), ("head", "u1", (48,)), ("tail", "u1", (16,))])   # pr_png_enc_plan
+ENC_ST_OVERFLOW = 1
+ENC_SEGMENT = 16384
+FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+MODES = {"stored": 0, "rle": 1}
+
+
+def _filter_mode(filter, mode):
+    f = FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    m = MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if not isinstance(f, int) or isinstance(f, bool) or f not in FILTERS.values():
+        raise ValueError(f"filter {filter!r}: one of {sorted(FILTERS)} or 0..5")
+    if not isinstance(m, int) or isinstance(m, bool) or m not in MODES.values():
+        raise ValueError(f"mode {mode!r}: one of {sorted(MODES)} or 0, 1")
+    return int(f), int(m)
+
+
+def encode_plan(filter, mode, H, W):
+    """The encoder's host half: the pr_png_enc_plan of these parameters as an ENC_PLAN_DTYPE record (the file's fixed bytes,
+    the CRC power table)."""
+    f, m = _filter_mode(filter, mode)
+    plan = np.zeros(1, ENC_PLAN_DTYPE)
+    _lib.check(_lib.load().pr_png_encode_plan(f, m, int(H), int(W), plan.ctypes.data_as(C.c_void_p)), "pr_png_encode_plan")
+    return plan[0]
+
+
+def encode_bound(H, W):
+    """A size in bytes that no PNG file of an H x W frame exceeds (a stored-mode file has exactly this size)."""
+    return int(_lib.load().pr_png_encode_bound(int(H), int(W)))
+
+
+def encode_workspace_bytes(F, H, W):
+    """The size of the `workspace` an encode_frames call of F frames of H x W needs."""
+    return int(_lib.load().pr_png_encode_workspace_bytes(int(F), int(H), int(W)))
+
+
+_plans = {}
+
+
+def _device_plan(key, device):
+    """The uploaded plan of (filter, mode, H, W) on `device`: made once, kept.  The first call of a parameter set copies the plan
+    from pageable host memory and waits for the copy; every further call only looks it up."""
+    plan = _plans.get((key, device))
+    if plan is None:
+        host = torch.from_numpy(np.frombuffer(encode_plan(*key).tobytes(), np.uint8).copy())
+        plan = host.to(device)
+        torch.cuda.current_stream(device).synchronize()
+        _plans[(key, device)] = plan
+    return plan
+
+
+def encode_frames(frames, filter="adaptive", mode="rle", bgr=False, capacity=None, out=None, workspace=None):
+    """Encode u8[F,H,W,3] frames on the GPU (RGB, or BGR with bgr=True) to F PNG files (colour type 2, depth 8): returns (buffer
+    u8[F,cap], nbytes int32[F], status int32[F]), all on the device; file f is buffer[f, :nbytes[f]].  `filter` is a name of
+    FILTERS or 0..5, `mode` "rle" (distance-1 matches and dynamic codes per 16 KiB segment) or "stored".  `capacity` is the slot
+    size per frame; None takes encode_bound(H, W), which no file exceeds.  A frame that does not fit a smaller slot has nbytes 0
+    and status ENC_ST_OVERFLOW and its slot is untouched: encode it again with capacity=encode_bound(H, W).  `out` = (buffer,
+    nbytes, status) to write into caller-owned tensors; `workspace` = a u8 device tensor of at least encode_workspace_bytes(F,
+    H, W) to reuse across calls on one stream (None allocates one per call).  Asynchronous on the current stream.  The first
+    call of a parameter set on a device uploads its plan and waits for that copy; every later call synchronises nothing, and
+    with `out` and `workspace` given allocates nothing either, so it can be captured into a graph."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise _lib.PoseRiskHipError("encode_frames: the encoder runs on the GPU only (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError(f"encode_frames: frames must be a contiguous uint8 [F, H, W, 3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    f, m = _filter_mode(filter, mode)
+    device, (F, H, W, _) = frames.device, frames.shape
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        plan = _device_plan((f, m, H, W), device)
+        capacity = encode_bound(H, W) if capacity is None else int(capacity)
+        if out is None:
+            out = (torch.empty((F, capacity), dtype=torch.uint8, device=device), torch.empty(F, dtype=torch.int32, device=device),
+                   torch.empty(F, dtype=torch.int32, device=device))
+        buf, nbytes, status = out
+        for t, shape, dtype in ((buf, (F, capacity), torch.uint8), (nbytes, (F,), torch.int32), (status, (F,), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != device:
+                raise ValueError(f"encode_frames: out must hold contiguous tensors {[F, capacity]} uint8, {[F]} int32, {[F]} int32 on {device}")
+        if F == 0:
+            return buf, nbytes, status
+        need = encode_workspace_bytes(F, H, W)
+        if need == 0:
+            raise _lib.PoseRiskHipError(f"encode_frames: {F} frames of {W}x{H} are outside what the encoder accepts (sizes 1..4096, "
+                                        "at most 65535 frames a call)")
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+        elif ws.dtype != torch.uint8 or ws.device != device or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() & 15:
+            raise ValueError(f"encode_frames: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {need} bytes on {device}")
+        stream = torch.cuda.current_stream(device)
+        args = _lib.PngEncArgs(frames.data_ptr(), plan.data_ptr(), buf.data_ptr(), nbytes.data_ptr(), status.data_ptr(), capacity,
+                               F, H, W, f, m, int(bool(bgr)))
+        _lib.check(lib.pr_png_encode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_png_encode")
+        ws.record_stream(stream)
+    return buf, nbytes, status
