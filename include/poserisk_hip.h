@@ -1204,6 +1204,111 @@ typedef struct pr_png_enc_args {
 } pr_png_enc_args;
 int pr_png_encode(const pr_png_enc_args* args, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j6  YUV4MPEG2 streams -> u8[F,h,w,3] on the device: chroma upsampling, the colour       */
+/*     matrix and the front end's downscale in one kernel                                  */
+/* replaces: cv2.VideoCapture in get_images lib/utils/funcs_utils.py:18-53 for any video   */
+/*           a decoder can pipe out (`ffmpeg -i clip.mp4 -f yuv4mpegpipe -`)               */
+/* ------------------------------------------------------------------------------------ */
+/* The host half (pr_y4m_parse_header, pr_y4m_index, pr_yuv_plan; csrc/y4m_host.cc, no device) reads the stream syntax and
+ * makes the matrix integers; the device half (pr_yuv_frames, csrc/yuv.hip) turns the raw planes of a chunk of the stream,
+ * uploaded as they came, into RGB frames, at the source size or downscaled by j3's contract.  tests/yuv_ref.py restates this
+ * section in numpy.  No ABI bump: functions and structs were added.
+ *
+ * Stream syntax.  "YUV4MPEG2", then tagged fields separated by spaces, up to '\n' (within PR_Y4M_MAX_HEADER bytes).  W and H
+ *   are required, 1..PR_RESIZE_MAX_SIDE.  F num:den is the frame rate (fps_num = fps_den = 0 when absent; a caller takes
+ *   0:0 as 30.0).  I: 'p' and '?' are accepted, 't', 'b', 'm' (interlaced) refused by name.  A and tags this section does
+ *   not name are ignored.  C: 420jpeg, 420mpeg2, 420 (= 420jpeg), 422, 444, mono; absent = 420jpeg; 420paldv, every
+ *   high-bit-depth variant (420p10, 422p12, 444p16, mono10, ...), 411 and 444alpha are refused by name, any other value as an
+ *   unknown layout.  X fields are ignored, except XCOLORRANGE=FULL | LIMITED (full_range 1 | 0; -1 when absent).
+ *   Each frame is "FRAME", optional fields, '\n' (within PR_Y4M_MAX_FRAME_HEADER bytes), then frame_bytes = W H + 2 cw ch
+ *   bytes: the Y plane, the U plane, the V plane, each row after row without padding; cw = (W + 1) / 2 for 420 and 422, else
+ *   W; ch = (H + 1) / 2 for 420, else H; mono has no chroma planes.
+ * Chroma to full resolution.  Per axis every output sample has two taps whose weights sum to 4 (indices clamped to the plane):
+ *     centred (both axes of 420jpeg, the vertical axis of 420mpeg2)    2 i: 3 c[i] + c[i - 1]     2 i + 1: 3 c[i] + c[i + 1]
+ *     co-sited (the horizontal axis of 420mpeg2 and of 422)            2 i: 4 c[i]                2 i + 1: 2 c[i] + 2 c[i + 1]
+ *     not subsampled                                                   i:   4 c[i]
+ *   C16 = the product of the two axes: up to four taps with weights summing to 16, kept at that scale, nothing rounded.
+ * Matrix.  Kr, Kb = 0.299, 0.114 (PR_YUV_601) or 0.2126, 0.0722 (PR_YUV_709); Kg = 1 - Kr - Kb.  Limited range: sy = 255 / 219,
+ *   sc = 255 / 224, yo = 16; full range: sy = sc = 1, yo = 0.  pr_yuv_plan computes in double and rounds to nearest even:
+ *     cy = sy 65536   crv = 2 (1 - Kr) sc 65536   cbu = 2 (1 - Kb) sc 65536   cgu = 2 Kb (1 - Kb) / Kg sc 65536
+ *     cgv = 2 Kr (1 - Kr) / Kg sc 65536            (601 limited: 76309, 104597, 132201, 25675, 53279)
+ *   With y = 16 (Y - yo), u = U16 - 2048, v = V16 - 2048 in int32 (mono: u = v = 0), the shift arithmetic (floor):
+ *     R = clamp8((cy y + crv v + 2^19) >> 20)   G = clamp8((cy y - cgu u - cgv v + 2^19) >> 20)   B = clamp8((cy y + cbu u + 2^19) >> 20)
+ *   No sum exceeds 6.0e8 in magnitude.  The result stays within one level of the float64 evaluation of the same taps and the
+ *   exact matrix (tests/test_y4m_cpu.py).  These are this project's own bits; swscale's are not promised, as j3 says of OpenCV's.
+ * Downscale.  j3's contract applied to that RGB: with the four tables given, pr_yuv_frames writes bit for bit what
+ *   pr_resize_frames makes of the source-size output, in all three modes, and the source-size RGB is never written. */
+#define PR_Y4M_MAX_HEADER 1024
+#define PR_Y4M_MAX_FRAME_HEADER 256
+enum { PR_Y4M_C420JPEG = 0, PR_Y4M_C420MPEG2 = 1, PR_Y4M_C422 = 2, PR_Y4M_C444 = 3, PR_Y4M_CMONO = 4 }; /* pr_y4m_info.chroma */
+enum { PR_YUV_601 = 0, PR_YUV_709 = 1 };
+enum { /* what pr_y4m_parse_header and pr_y4m_index return besides PR_OK and PR_ERR_INVALID; pr_y4m_refusal_name gives the words */
+  PR_Y4M_OK = 0, PR_Y4M_E_MAGIC = 1, PR_Y4M_E_HEADER = 2, PR_Y4M_E_FIELD = 3, PR_Y4M_E_NO_SIZE = 4, PR_Y4M_E_SIZE = 5,
+  PR_Y4M_E_INTERLACED = 6, PR_Y4M_E_PALDV = 7, PR_Y4M_E_HIGH_DEPTH = 8, PR_Y4M_E_411 = 9, PR_Y4M_E_ALPHA = 10,
+  PR_Y4M_E_CHROMA = 11, PR_Y4M_E_FRAME = 12, PR_Y4M_E_COUNT = 13
+};
+typedef struct pr_y4m_info {
+  int32_t width, height;
+  int32_t fps_num, fps_den;    /* 0, 0 when the header has no F field */
+  int32_t chroma;              /* PR_Y4M_C* */
+  int32_t full_range;          /* 1 XCOLORRANGE=FULL, 0 XCOLORRANGE=LIMITED, -1 absent */
+  int32_t header_bytes;        /* the stream header, its '\n' included: the first FRAME starts here */
+  int32_t reserved;
+  int64_t frame_bytes;         /* one frame's payload: W H + 2 cw ch */
+} pr_y4m_info;
+typedef struct pr_yuv_coeffs { /* pr_yuv_plan's six integers */
+  int32_t cy, crv, cbu, cgu, cgv, yo;
+} pr_yuv_coeffs;
+
+/* The stream header in data_host[0, n).  PR_OK and *info_host filled, or a refusal (PR_Y4M_E_*, named in pr_last_error too;
+ * PR_Y4M_E_HEADER also when n bytes do not reach the '\n'), or PR_ERR_INVALID for a null pointer or n < 0.  *info_host is
+ * written only on PR_OK.  No device call. */
+int pr_y4m_parse_header(const uint8_t* data_host, int64_t n, pr_y4m_info* info_host);
+const char* pr_y4m_refusal_name(int code);
+
+/* data_host[0, n) begins at a frame boundary (a FRAME header).  Walks the FRAME headers and fills offsets_host with the payload
+ * offset of every COMPLETE frame, up to max_frames of them; *n_frames_host = their count, *consumed_host = the bytes up to the
+ * end of the last complete frame, so that a streaming caller carries data_host[consumed, n) into its next chunk.  A frame
+ * whose header or payload the n bytes do not reach is not an error here (only the caller knows whether more bytes follow; at
+ * the end of the stream a remainder is an incomplete frame).  Bytes that cannot begin a FRAME header are PR_Y4M_E_FRAME, named
+ * with the frame's index in this buffer; PR_ERR_INVALID for a null pointer, n < 0, max_frames < 0 or an info no header gives.
+ * The three outputs are written only on PR_OK.  No device call. */
+int pr_y4m_index(const uint8_t* data_host, int64_t n, const pr_y4m_info* info_host, int64_t* offsets_host, int max_frames,
+                 int32_t* n_frames_host, int64_t* consumed_host);
+
+/* Fills *plan_host for matrix PR_YUV_601 | PR_YUV_709 and full_range 0 | 1; PR_ERR_INVALID by name for anything else or a null
+ * pointer, before anything is written.  No device call. */
+int pr_yuv_plan(int matrix, int full_range, pr_yuv_coeffs* plan_host);
+
+/* Device pointers: data u8[data_bytes] (a chunk of the stream as it was read, any alignment), offsets int64[F] (payload
+ * offsets in data, as pr_y4m_index gave them, 8-byte aligned; a payload may start at any byte), dst u8[F,h,w,3] (any alignment:
+ * the call's output is written in aligned dwords, three a lane, with byte stores only for the few bytes at either end).
+ * H, W, chroma: the stream's; plan: pr_yuv_plan's integers, by value; bgr != 0 swaps R and B.  Without a downscale h = w = 0,
+ * mode = 0 and the four tables are NULL: dst is u8[F,H,W,3].  With one, h, w, the tables and mode are pr_resize_plan's for
+ * (H, W, h, w), uploaded as for pr_resize_frames.  Reads only data, offsets and the tables (table offsets are clamped to the
+ * source on the device; a frame whose payload does not lie inside [0, data_bytes) is written as zeros and nothing of it is
+ * read), writes every byte of dst and nothing else.  Argument errors (null pointers, a side outside 1..PR_RESIZE_MAX_SIDE, an
+ * unknown chroma, only some of the downscale's arguments, a mode that is not the one of these sizes, F < 0, data_bytes < 0)
+ * return PR_ERR_INVALID by name before any device work; F = 0 returns PR_OK.  Asynchronous on `stream`, no allocation, no
+ * copy, no synchronisation (capturable). */
+typedef struct pr_yuv_args {
+  const uint8_t* data;
+  const int64_t* offsets;
+  uint8_t* dst;
+  const int32_t* xofs;
+  const int16_t* xcoef;
+  const int32_t* yofs;
+  const int16_t* ycoef;
+  int64_t data_bytes;
+  pr_yuv_coeffs plan;
+  int F, H, W;
+  int chroma;
+  int bgr;
+  int h, w, mode;
+} pr_yuv_args;
+int pr_yuv_frames(const pr_yuv_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

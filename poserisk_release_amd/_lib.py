@@ -80,6 +80,23 @@ class PngEncArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "filter", "mode", "bgr")]
 
 
+class Y4mInfo(C.Structure):
+    """pr_y4m_info (include/poserisk_hip.h, the YUV4MPEG2 reader)."""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "fps_num", "fps_den", "chroma", "full_range", "header_bytes", "reserved")] + \
+               [("frame_bytes", C.c_int64)]
+
+
+class YuvCoeffs(C.Structure):
+    """pr_yuv_coeffs (include/poserisk_hip.h, pr_yuv_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("cy", "crv", "cbu", "cgu", "cgv", "yo")]
+
+
+class YuvArgs(C.Structure):
+    """pr_yuv_args (include/poserisk_hip.h, pr_yuv_frames)."""
+    _fields_ = [(n, C.c_void_p) for n in ("data", "offsets", "dst", "xofs", "xcoef", "yofs", "ycoef")] + [("data_bytes", C.c_int64)] + \
+               [("plan", YuvCoeffs)] + [(n, C.c_int) for n in ("F", "H", "W", "chroma", "bgr", "h", "w", "mode")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -159,6 +176,11 @@ SIGNATURES = {
     "pr_png_encode": (_I, [C.POINTER(PngEncArgs), _P, C.c_size_t, _P]),
     "pr_resize_plan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "pr_resize_frames": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "pr_y4m_parse_header": (_I, [_P, C.c_int64, C.POINTER(Y4mInfo)]),
+    "pr_y4m_refusal_name": (C.c_char_p, [_I]),
+    "pr_y4m_index": (_I, [_P, C.c_int64, C.POINTER(Y4mInfo), _P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "pr_yuv_plan": (_I, [_I, _I, C.POINTER(YuvCoeffs)]),
+    "pr_yuv_frames": (_I, [C.POINTER(YuvArgs), _P]),
 }
 
 _lib = None

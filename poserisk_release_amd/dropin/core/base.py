@@ -152,6 +152,10 @@ class Predictor:
             raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg' "
                              "or 'png'")
         self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
+        # load_front_end's case 3c: args.video_decoder, else cfg.DATASET.video_decoder ('' = off): a command line with {input}
+        # whose standard output is read as YUV4MPEG2
+        knob = getattr(args, 'video_decoder', None)
+        self.video_decoder = str(knob if knob is not None else cfg.DATASET.get('video_decoder', '') or '')
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
             self.debug_joints = None
@@ -600,7 +604,16 @@ class Predictor:
              `tracking_results` given to __call__, `<stem>.tracking.pkl` beside the video (boxes in the downscaled frames'
              coordinates), or multi_person_tracker where importable, run on a folder of JPEGs encoded on the GPU; the frames
              are then the pixels decoded back from those files, as the reference's CropDataset would read them.  An AVI of
-             another codec, or a damaged one, goes on to 4;
+             another codec, or a damaged one, goes on to 3c and 4;
+          3b. a YUV4MPEG2 file (one that starts with `YUV4MPEG2 `: what `ffmpeg -f yuv4mpegpipe`, mpv, x264 and the AV1 tools
+             write): read in chunks into pinned memory, converted to RGB (cfg.DATASET.yuv_matrix, '601') and downscaled by the
+             same rule in one kernel on the GPU (poserisk_release_amd/y4m.py).  Its tracking comes from the same sources as 3's,
+             in the same order;
+          3c. with cfg.DATASET.video_decoder / args.video_decoder set (off, '', by default), any other regular file: the knob
+             is a command line containing `{input}`, e.g. `ffmpeg -v error -i {input} -f yuv4mpegpipe -pix_fmt yuv420p -`; it
+             is started as a fresh child process (shlex.split, no shell), its standard output is read as YUV4MPEG2 exactly as
+             3b reads a file, and it is always reaped.  A child that exits non-zero or writes no stream header raises
+             RuntimeError naming the command, the exit status and the tail of its standard error;
           4. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
              frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
              written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
@@ -640,6 +653,11 @@ class Predictor:
                     not_mjpeg = e                              # an AVI, but not one to read here: cv2 may still open it
                 else:
                     return self._avi_front_end(reader, input_path, output_path, tracking_results)
+            from poserisk_release_amd import y4m
+            if y4m.is_y4m(input_path):
+                return self._y4m_front_end(y4m.Reader(input_path), input_path, output_path, tracking_results)
+            if self.video_decoder:
+                return self._decoder_front_end(input_path, output_path, tracking_results)
         try:
             import cv2
             from multi_person_tracker import MPT
@@ -678,13 +696,72 @@ class Predictor:
 
     def _avi_front_end(self, reader, input_path, output_path, tracking_results=None):
         """load_front_end's case 3: `reader` is the mjpeg.AviReader of `input_path`."""
-        import pickle
-        import shutil
-        from poserisk_release_amd import frontend, jpeg
+        from poserisk_release_amd import frontend
         frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
                                           max_h=cfg.DATASET.get('front_max_h', 450),
                                           entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
                                           progressive=bool(cfg.DATASET.get('jpeg_progressive', True)))
+        return self._tracking_for(frames, fps, input_path, output_path, tracking_results)
+
+    def _y4m_front_end(self, reader, input_path, output_path, tracking_results=None):
+        """load_front_end's cases 3b and 3c: `reader` is the y4m.Reader of `input_path` or of a decoder's standard output."""
+        from poserisk_release_amd import frontend
+        with reader:
+            frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
+                                              max_h=cfg.DATASET.get('front_max_h', 450),
+                                              matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+        return self._tracking_for(frames, fps, input_path, output_path, tracking_results)
+
+    def _decoder_front_end(self, input_path, output_path, tracking_results=None):
+        """load_front_end's case 3c: self.video_decoder, with {input} replaced, runs as a child process whose standard output
+        is read as YUV4MPEG2.  Never a shell and never this process's own program; the child is reaped whatever happens."""
+        import shlex
+        import subprocess
+        import tempfile
+        from poserisk_release_amd import y4m
+        if '{input}' not in self.video_decoder:
+            raise ValueError(f"video_decoder {self.video_decoder!r} must be a command line containing {{input}}")
+        argv = [a.replace('{input}', input_path) for a in shlex.split(self.video_decoder)]
+        shown = ' '.join(shlex.quote(a) for a in argv)
+        failure, read_to_the_end = None, False
+        with tempfile.TemporaryFile() as err:
+            try:
+                child = subprocess.Popen(argv, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=err)
+            except OSError as e:
+                raise RuntimeError(f"{input_path!r}: the video decoder `{shown}` could not be started: {e}") from e
+            try:
+                try:
+                    reader = y4m.Reader(child.stdout)
+                except ValueError as e:
+                    failure = f"wrote no YUV4MPEG2 stream header ({e})"
+                else:
+                    try:
+                        return_value = self._y4m_front_end(reader, input_path, output_path, tracking_results)
+                        read_to_the_end = True
+                    except ValueError as e:                     # the stream broke off: the child's status says why
+                        failure = str(e)
+            finally:
+                child.stdout.close()                            # a child still writing gets EPIPE and ends by itself
+                try:
+                    status = child.wait(timeout=60 if read_to_the_end else 5)
+                except subprocess.TimeoutExpired:
+                    child.kill()
+                    status = child.wait()
+            err.seek(0)
+            tail = err.read()[-2000:].decode('utf-8', 'replace').strip()
+        if failure is not None or status != 0:
+            raise RuntimeError(f"{input_path!r}: the video decoder `{shown}` failed with exit status {status}"
+                               + (f": it {failure}" if failure is not None and failure.startswith('wrote no') else
+                                  f": {failure}" if failure is not None else '')
+                               + (f"; its standard error ends: {tail}" if tail else ''))
+        return return_value
+
+    def _tracking_for(self, frames, fps, input_path, output_path, tracking_results=None):
+        """The second half of cases 3, 3b and 3c: the tracking of a video file's decoded, downscaled `frames`, in this order: the
+        `tracking_results` given, `<stem>.tracking.pkl`, multi_person_tracker where importable, else the named error."""
+        import pickle
+        import shutil
+        from poserisk_release_amd import frontend, jpeg
         if tracking_results is not None:
             return frames, False, fps, tracking_results
         sidecar = osp.splitext(input_path)[0] + '.tracking.pkl'

@@ -39,6 +39,12 @@ absent from the reference and all optional:
     cfg.DATASET.jpeg_progressive  True: progressive JPEG frames, and sequential ones whose components come in several scans, are
                               decoded too (jpeg.decode_files(progressive=True), pr_jpeg_decode_scans); False refuses them by
                               name, as the single-scan parser does
+    cfg.DATASET.yuv_matrix    '601' | '709' | 'auto' (709 above 576 rows): the colour matrix of a YUV4MPEG2 input
+                              (poserisk_release_amd.y4m.decode); '601' is what swscale's unconfigured conversion uses at every size
+    cfg.DATASET.video_decoder  '' (off) | a command line containing {input}, e.g. `ffmpeg -v error -i {input} -f yuv4mpegpipe
+                              -pix_fmt yuv420p -`: a regular file that is neither a Motion-JPEG AVI nor a YUV4MPEG2 file is decoded
+                              by running it as a child process (no shell) and reading its standard output as YUV4MPEG2
+                              (args.video_decoder overrides it)
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -99,7 +105,8 @@ def _defaults(root):
                     'default_information': osp.join(core_dir, 'default_information.json'),
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
                     'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
-                    'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True},
+                    'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True,
+                    'yuv_matrix': '601', 'video_decoder': ''},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

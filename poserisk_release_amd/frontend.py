@@ -2,11 +2,13 @@
 a Motion-JPEG AVI, without OpenCV: the container is read in Python (mjpeg.AviReader), every frame is decoded on the GPU
 (jpeg.decode_files), downscaled on the GPU by the integer bilinear contract of include/poserisk_hip.h (section j3;
 csrc/resize_host.cc, csrc/resize.hip) and, where a tracker needs files, encoded on the GPU (jpeg.encode_frames).
+A YUV4MPEG2 stream (a `.y4m` file, a y4m.Reader, or "-" for standard input: what a decoder of any codec pipes out) takes the
+same way through y4m.decode: chroma upsampling, colour matrix and the same downscale in one kernel (section j6; csrc/yuv.hip).
 
     target_size    the reference's rule: wider than 800 -> 800 wide, elif higher than 450 -> 450 high
     resize_frames  u8[F,H,W,3] -> u8[F,h,w,3] on the device
-    read_video     a Motion-JPEG AVI -> (frames on the device at the target size, fps)
-    prepare        a Motion-JPEG AVI -> a folder of %09d.jpg + fps.txt; with a tracking.pkl added it is an input of
+    read_video     a Motion-JPEG AVI or a YUV4MPEG2 stream -> (frames on the device at the target size, fps)
+    prepare        the same inputs -> a folder of %09d.jpg + fps.txt; with a tracking.pkl added it is an input of
                    Predictor.load_front_end.   python -m poserisk_release_amd.frontend prepare <video> <dir>"""
 import ctypes as C
 import os
@@ -104,8 +106,33 @@ def _raise_refused(path, part, lo, H, W, fallback, progressive=False):
     raise RuntimeError(f"{path!r}: frames {lo}..{lo + len(part) - 1} cannot be decoded: {fallback}")
 
 
-def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, entropy="auto", progressive=False):
-    """A Motion-JPEG AVI -> (frames u8[F,h,w,3] on `device`, fps): demuxed on the host, decoded on the GPU at the source size,
+def _y4m_source(path):
+    """The y4m.Reader of `path` where it is a YUV4MPEG2 source (a Reader, "-", or a file that starts with the signature), else None."""
+    from . import y4m
+    if isinstance(path, y4m.Reader):
+        return path
+    if isinstance(path, (str, os.PathLike)) and (os.fspath(path) == "-" or y4m.is_y4m(path)):
+        return y4m.Reader(path)
+    return None
+
+
+def read_y4m(reader, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, matrix="601", full_range=None, fused=None):
+    """read_video's YUV4MPEG2 arm: `reader` is a y4m.Reader -> (frames u8[F,h,w,3] on `device`, fps), (w, h) = target_size of the
+    stream's own size, downscaled by the same contract as an AVI's frames (in the conversion kernel itself unless fused=False).
+    A stream that ends inside a frame raises ValueError naming the frame's index."""
+    from . import y4m
+    w, h = target_size(reader.width, reader.height, max_w, max_h)
+    if h < 1 or w < 1:
+        raise ValueError(f"{reader.path!r}: {reader.width} x {reader.height} frames would become {w} x {h}")
+    frames = y4m.decode(reader, device, matrix=matrix, full_range=full_range, bgr=bgr, size=(h, w), fused=fused, max_bytes=max_bytes)
+    if frames.shape[0] == 0:
+        raise ValueError(f"{reader.path!r}: the video stream holds no frames")
+    return frames, float(reader.fps)
+
+
+def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30, entropy="auto", progressive=False, matrix="601"):
+    """A YUV4MPEG2 stream (a path, a y4m.Reader, or "-" for standard input) goes to read_y4m with `matrix` ("601" | "709" | "auto").
+    A Motion-JPEG AVI -> (frames u8[F,h,w,3] on `device`, fps): demuxed on the host, decoded on the GPU at the source size,
     chunk by chunk into one reused buffer, each chunk downscaled into its slice of the result ((w, h) = target_size of the first
     frame's own size).  RGB, or BGR with bgr=True.  A refused or damaged frame raises RuntimeError naming its index in the file
     and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made.
@@ -116,6 +143,9 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
         raise _lib.PoseRiskHipError("read_video: decoding and resizing run on the GPU only (no CPU fallback)")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
+    y4m_reader = None if isinstance(path, mjpeg.AviReader) else _y4m_source(path)
+    if y4m_reader is not None:
+        return read_y4m(y4m_reader, device, max_w=max_w, max_h=max_h, bgr=bgr, max_bytes=max_bytes, matrix=matrix)
     reader = path if isinstance(path, mjpeg.AviReader) else mjpeg.AviReader(path)
     path = reader.path
     blobs = reader.frames()
@@ -172,11 +202,11 @@ def write_frame_folder(frames, out_dir, quality=95, fps=None, bgr=False, chunk=6
     return files
 
 
-def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_bytes=16 << 30, progressive=False):
-    """A Motion-JPEG AVI -> out_dir/%09d.jpg + fps.txt: the folder the reference's front end leaves for its tracker (quality 95 is
+def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_bytes=16 << 30, progressive=False, matrix="601"):
+    """A Motion-JPEG AVI or a YUV4MPEG2 stream (read_video's inputs) -> out_dir/%09d.jpg + fps.txt: the folder the reference's front end leaves for its tracker (quality 95 is
     cv2.imwrite's default), written without OpenCV.  Returns (number of frames, (w, h), fps)."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    frames, fps = read_video(path, device, max_w=max_w, max_h=max_h, max_bytes=max_bytes, progressive=progressive)
+    frames, fps = read_video(path, device, max_w=max_w, max_h=max_h, max_bytes=max_bytes, progressive=progressive, matrix=matrix)
     write_frame_folder(frames, out_dir, quality=quality, fps=fps)
     return int(frames.shape[0]), (int(frames.shape[2]), int(frames.shape[1])), fps
 
@@ -185,16 +215,18 @@ def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m poserisk_release_amd.frontend")
     sub = ap.add_subparsers(dest="command", required=True)
-    p = sub.add_parser("prepare", help="Motion-JPEG AVI -> a folder of %%09d.jpg + fps.txt for a tracker and for Predictor")
+    p = sub.add_parser("prepare", help="Motion-JPEG AVI, .y4m file or - (a YUV4MPEG2 stream on standard input) -> a folder of %%09d.jpg + fps.txt for a tracker and for Predictor")
     p.add_argument("video")
     p.add_argument("out_dir")
     p.add_argument("--quality", type=int, default=95)
     p.add_argument("--max-w", type=int, default=800)
     p.add_argument("--max-h", type=int, default=450)
     p.add_argument("--gpu", type=int, default=0)
+    p.add_argument("--matrix", choices=("601", "709", "auto"), default="601",
+                   help="the colour matrix of a YUV4MPEG2 input (auto: 709 above 576 rows); a Motion-JPEG AVI ignores it")
     a = ap.parse_args(argv)
     n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h,
-                             progressive=True)
+                             progressive=True, matrix=a.matrix)
     print(f"{a.out_dir}: {n} frames of {w} x {h} at {fps:g} frames/s; add tracking.pkl (multi_person_tracker's dict) to score it")
 
 
