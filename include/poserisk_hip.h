@@ -1309,6 +1309,74 @@ typedef struct pr_yuv_args {
 } pr_yuv_args;
 int pr_yuv_frames(const pr_yuv_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j7  u8[F,H,W,3] on the device -> the bytes of a YUV4MPEG2 stream: the colour matrix,   */
+/*     chroma subsampling and the FRAME headers in one kernel                              */
+/* replaces: cv2.VideoWriter in lib/core/base.py:301 for any codec an encoder can read    */
+/*           from a pipe (`ffmpeg -f yuv4mpegpipe -i - -c:v libx264 out.mp4`)              */
+/* ------------------------------------------------------------------------------------ */
+/* j6 backwards.  The host half (pr_yuv_enc_plan; csrc/y4m_host.cc, no device) makes the matrix integers; the device half
+ * (pr_yuv_encode, csrc/yuv_enc.hip) turns RGB frames into the frames of a stream, ready to be written behind a stream header.
+ * tests/yuv_enc_ref.py restates this section in numpy.  No ABI bump: functions and structs were added.
+ *
+ * Stream bytes.  For F frames of a picture out_W x out_H the output is F (6 + frame_bytes) bytes: per frame "FRAME\n", the Y
+ *   plane, the U plane, the V plane, with j6's sizes for out_W x out_H (cw = (out_W + 1) / 2 for 420 and 422, ch =
+ *   (out_H + 1) / 2 for 420, no chroma planes for mono).  Frames follow one another without padding, so the buffer is a chunk of
+ *   a valid stream: pr_y4m_index accepts it.
+ * Padding.  out_H is H or H + 1, out_W is W or W + 1 (encoders want even sides).  A position outside the source reads the
+ *   nearest source pixel (edge replication), for luma and for every chroma tap.
+ * Matrix.  Kr, Kb as in j6.  Limited range: sy = 219 / 255, sc = 224 / 255, yo = 16; full range: sy = sc = 1, yo = 0.
+ *   pr_yuv_enc_plan computes in double and rounds to nearest even (rne):
+ *     KY = rne(sy 65536)   kyr = rne(Kr sy 65536)   kyb = rne(Kb sy 65536)   kyg = KY - kyr - kyb
+ *     kc = rne(sc 32768)   kur = rne(Kr / (2 (1 - Kb)) sc 65536)   kug = kc - kur
+ *                          kvb = rne(Kb / (2 (1 - Kr)) sc 65536)   kvg = kc - kvb
+ *   (601 limited: 16829, 33039, 6416; 28784; 9714, 19070; 4681, 24103.)  The luma row sums to KY exactly and both chroma rows
+ *   to zero: every grey gives U = V = 128 exactly, white Y = 235 (255 in full range), black 16 (0).
+ * Samples, in int32, one rounding a sample, the shift arithmetic (floor):
+ *     Y = yo + ((kyr R + kyg G + kyb B + 2^15) >> 16)
+ *   Chroma from tap sums Rs, Gs, Bs whose weights sum to T, the taps' indices clamped to the padded picture:
+ *     444        the pixel itself                                                     T = 1
+ *     420jpeg    the 2 x 2 block (rows 2 j, 2 j + 1, columns 2 i, 2 i + 1), 1 each      T = 4
+ *     422        columns 2 i - 1, 2 i, 2 i + 1 of the row, weights 1, 2, 1             T = 4
+ *     420mpeg2   those three columns on rows 2 j and 2 j + 1                           T = 8
+ *     U = clamp8(128 + ((kc Bs - kur Rs - kug Gs + T 2^15) >> (16 + log2 T)))
+ *     V = clamp8(128 + ((kc Rs - kvg Gs - kvb Bs + T 2^15) >> (16 + log2 T)))
+ *   No sum exceeds 7e7 in magnitude.  bgr != 0: the input's first channel is B.
+ * Accuracy (tests/test_y4m_write_cpu.py, over all 2^24 colours): every sample lies within 0.51 of the float64 evaluation of
+ *   the same taps and the exact matrix.  A 444 round trip through j6 (pr_yuv_frames, same matrix and range) returns every colour
+ *   within 1 level in full range; in limited range within 1 level for R and G and within 2 for B.  For the subsampled layouts
+ *   that holds for flat-colour frames (the subsampling is then the identity); nothing more is promised for them.  These are
+ *   this project's own bits; swscale's are not promised. */
+typedef struct pr_yuv_enc_coeffs { /* pr_yuv_enc_plan's integers */
+  int32_t kyr, kyg, kyb;
+  int32_t kc;
+  int32_t kur, kug;
+  int32_t kvb, kvg;
+  int32_t yo;
+} pr_yuv_enc_coeffs;
+
+/* Fills *plan_host for matrix PR_YUV_601 | PR_YUV_709 and full_range 0 | 1; PR_ERR_INVALID by name for anything else or a null
+ * pointer, before anything is written.  No device call. */
+int pr_yuv_enc_plan(int matrix, int full_range, pr_yuv_enc_coeffs* plan_host);
+
+/* Device pointers: src u8[F,H,W,3] (any alignment), dst u8[F (6 + frame_bytes)] (any alignment: the call's output is one flat
+ * run written in aligned dwords, with byte stores only for the up to three bytes at either end; a dword may hold the tail of
+ * V, a FRAME header and the next frame's first Y samples).  plan: pr_yuv_enc_plan's integers, by value; chroma: PR_Y4M_C*.
+ * Reads only src, writes every byte of dst and nothing else.  Argument errors (null pointers, a side outside
+ * 1..PR_RESIZE_MAX_SIDE, out_H - H or out_W - W outside 0..1, an unknown chroma, F < 0, more bytes than a grid of 2^31 - 1
+ * blocks writes) return PR_ERR_INVALID by name before any device work; F = 0 returns PR_OK.  Asynchronous on `stream`, no
+ * allocation, no copy, no synchronisation (capturable). */
+typedef struct pr_yuv_enc_args {
+  const uint8_t* src;
+  uint8_t* dst;
+  pr_yuv_enc_coeffs plan;
+  int F, H, W;
+  int out_H, out_W;
+  int chroma;
+  int bgr;
+} pr_yuv_enc_args;
+int pr_yuv_encode(const pr_yuv_enc_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

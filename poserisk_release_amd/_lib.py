@@ -97,6 +97,17 @@ class YuvArgs(C.Structure):
                [("plan", YuvCoeffs)] + [(n, C.c_int) for n in ("F", "H", "W", "chroma", "bgr", "h", "w", "mode")]
 
 
+class YuvEncCoeffs(C.Structure):
+    """pr_yuv_enc_coeffs (include/poserisk_hip.h, pr_yuv_enc_plan)."""
+    _fields_ = [(n, C.c_int32) for n in ("kyr", "kyg", "kyb", "kc", "kur", "kug", "kvb", "kvg", "yo")]
+
+
+class YuvEncArgs(C.Structure):
+    """pr_yuv_enc_args (include/poserisk_hip.h, pr_yuv_encode)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("plan", YuvEncCoeffs)] + \
+               [(n, C.c_int) for n in ("F", "H", "W", "out_H", "out_W", "chroma", "bgr")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -181,6 +192,8 @@ SIGNATURES = {
     "pr_y4m_index": (_I, [_P, C.c_int64, C.POINTER(Y4mInfo), _P, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "pr_yuv_plan": (_I, [_I, _I, C.POINTER(YuvCoeffs)]),
     "pr_yuv_frames": (_I, [C.POINTER(YuvArgs), _P]),
+    "pr_yuv_enc_plan": (_I, [_I, _I, C.POINTER(YuvEncCoeffs)]),
+    "pr_yuv_encode": (_I, [C.POINTER(YuvEncArgs), _P]),
 }
 
 _lib = None

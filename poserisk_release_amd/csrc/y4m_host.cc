@@ -1,6 +1,7 @@
 // Host half of the YUV4MPEG2 reader (include/poserisk_hip.h, section j6): the stream header, the walk over the FRAME headers
-// of a chunk, and the colour matrix's integers.  No device call and no HIP header: tests/test_y4m_native.py builds this file
-// with g++ under sanitizers.  Every refusal is decided before an output is written.
+// of a chunk, and the colour matrix's integers; and of the writer (section j7): the forward matrix's integers.  No device call
+// and no HIP header: tests/test_y4m_native.py and tests/test_y4m_write_native.py build this file with g++ under sanitizers.
+// Every refusal is decided before an output is written.
 #include <algorithm>
 #include <cmath>
 #include <initializer_list>
@@ -210,6 +211,28 @@ extern "C" int pr_yuv_plan(int matrix, int full_range, pr_yuv_coeffs* plan) {
   plan->cbu = (int32_t)std::nearbyint(2.0 * (1.0 - kb) * sc * 65536.0);
   plan->cgu = (int32_t)std::nearbyint(2.0 * kb * (1.0 - kb) / kg * sc * 65536.0);
   plan->cgv = (int32_t)std::nearbyint(2.0 * kr * (1.0 - kr) / kg * sc * 65536.0);
+  plan->yo = full_range ? 0 : 16;
+  return PR_OK;
+}
+
+// Section j7: the integers of the forward matrix.  The green luma weight and the green chroma weights are what is left of
+// the rows' sums, so that a grey pixel has no chroma and white and black land on the range's ends exactly.
+extern "C" int pr_yuv_enc_plan(int matrix, int full_range, pr_yuv_enc_coeffs* plan) {
+  using namespace pr;
+  PR_REQUIRE(matrix == PR_YUV_601 || matrix == PR_YUV_709, "pr_yuv_enc_plan: matrix = %d (PR_YUV_601 = 0 or PR_YUV_709 = 1)", matrix);
+  PR_REQUIRE(full_range == 0 || full_range == 1, "pr_yuv_enc_plan: full_range = %d (0 or 1)", full_range);
+  PR_REQUIRE(plan, "pr_yuv_enc_plan: null plan_host");
+  const double kr = matrix == PR_YUV_601 ? 0.299 : 0.2126, kb = matrix == PR_YUV_601 ? 0.114 : 0.0722;
+  const double sy = full_range ? 1.0 : 219.0 / 255.0, sc = full_range ? 1.0 : 224.0 / 255.0;
+  const int32_t ky = (int32_t)std::nearbyint(sy * 65536.0);
+  plan->kyr = (int32_t)std::nearbyint(kr * sy * 65536.0);
+  plan->kyb = (int32_t)std::nearbyint(kb * sy * 65536.0);
+  plan->kyg = ky - plan->kyr - plan->kyb;
+  plan->kc = (int32_t)std::nearbyint(sc * 32768.0);
+  plan->kur = (int32_t)std::nearbyint(kr / (2.0 * (1.0 - kb)) * sc * 65536.0);
+  plan->kug = plan->kc - plan->kur;
+  plan->kvb = (int32_t)std::nearbyint(kb / (2.0 * (1.0 - kr)) * sc * 65536.0);
+  plan->kvg = plan->kc - plan->kvb;
   plan->yo = full_range ? 0 : 16;
   return PR_OK;
 }

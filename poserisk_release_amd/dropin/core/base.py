@@ -145,12 +145,28 @@ class Predictor:
         # how write_gpu_video and the mesh writer store their frames: args.video_codec, else cfg.DATASET.gpu_video_codec.  ''
         # (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded on the GPU
         # (jpeg.encode_frames) into <TITLE>_video.avi / <TITLE>_mesh.avi (mjpeg.AviWriter), with or without cv2; 'png' = lossless,
-        # encoded on the GPU (png.encode_frames) into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2
+        # encoded on the GPU (png.encode_frames) into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2;
+        # 'y4m' = converted to Y'CbCr on the GPU (y4m.encode_frames) into <TITLE>_video.y4m / <TITLE>_mesh.y4m, or, with the
+        # video_encoder knob, piped to that command, which writes <TITLE>_video.mp4 / <TITLE>_mesh.mp4 in the codec it names
         knob = getattr(args, 'video_codec', None)
         self.gpu_video_codec = str(knob if knob is not None else cfg.DATASET.get('gpu_video_codec', '') or '')
-        if self.gpu_video_codec not in ('', 'mjpeg', 'png'):
-            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg' "
-                             "or 'png'")
+        if self.gpu_video_codec not in ('', 'mjpeg', 'png', 'y4m'):
+            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg', "
+                             "'png' or 'y4m' (any other codec: 'y4m' with the video_encoder knob)")
+        # args.video_encoder, else cfg.DATASET.video_encoder ('' = off): a command line with {output} that reads YUV4MPEG2 on its
+        # standard input; it implies the 'y4m' codec.  video_encoder_ext ('.mp4') ends the file's name, video_chroma the layout
+        knob = getattr(args, 'video_encoder', None)
+        self.video_encoder = str(knob if knob is not None else cfg.DATASET.get('video_encoder', '') or '')
+        knob = getattr(args, 'video_encoder_ext', None)
+        self.video_encoder_ext = str(knob if knob is not None else cfg.DATASET.get('video_encoder_ext', '.mp4') or '.mp4')
+        self.video_chroma = str(cfg.DATASET.get('video_chroma', '420mpeg2') or '420mpeg2')
+        if self.video_encoder:
+            if '{output}' not in self.video_encoder:
+                raise ValueError(f"video_encoder {self.video_encoder!r} must be a command line containing {{output}}")
+            if self.gpu_video_codec not in ('', 'y4m'):
+                raise ValueError(f"video_encoder is fed YUV4MPEG2: it goes with gpu_video_codec 'y4m' (or ''), not "
+                                 f"{self.gpu_video_codec!r}")
+            self.gpu_video_codec = 'y4m'
         self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
         # load_front_end's case 3c: args.video_decoder, else cfg.DATASET.video_decoder ('' = off): a command line with {input}
         # whose standard output is read as YUV4MPEG2
@@ -441,6 +457,33 @@ class Predictor:
                     fh.write(data)
         return write, lambda: path
 
+    def _y4m_writer(self, stem, width, height, fps, bgr):
+        """-> (write(images u8[b,H,W,3] CUDA), close() -> path): the images converted to Y'CbCr on the GPU (y4m.encode_frames:
+        cfg.DATASET.yuv_matrix, limited range, video_chroma, odd sides of a subsampled layout padded to even) and written as a
+        YUV4MPEG2 stream to `stem`.y4m -- or, with the video_encoder knob, to that command's standard input, {output} replaced
+        by `stem` + video_encoder_ext.  Never a shell; close() raises RuntimeError naming a failed encoder's status."""
+        import shlex
+        from poserisk_release_amd import y4m
+        matrix = str(cfg.DATASET.get('yuv_matrix', '601'))
+        if matrix == 'auto':
+            matrix = '709' if height > 576 else '601'
+        how = dict(width=width, height=height, fps=fps, chroma=self.video_chroma, matrix=matrix, full_range=False, bgr=bgr,
+                   pad_even=self.video_chroma in ('420jpeg', '420mpeg2', '422'))
+        if self.video_encoder:
+            path = stem + self.video_encoder_ext
+            writer = y4m.Writer(command=[a.replace('{output}', path) for a in shlex.split(self.video_encoder)], **how)
+        else:
+            path = stem + '.y4m'
+            writer = y4m.Writer(path, **how)
+
+        def close(failed=False):
+            if failed:
+                writer.abort()                              # reaps the child, raises nothing over the caller's error
+            else:
+                writer.close()
+            return path
+        return writer.put, close
+
     def _mesh_writer(self, frames, output_path, title, bgr, fps):
         """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): <output>/<TITLE>_mesh.mp4 where cv2 is importable,
         else <output>/<TITLE>_mesh/%09d.png (frame number); with gpu_video_codec 'mjpeg' <output>/<TITLE>_mesh.avi either way,
@@ -451,6 +494,10 @@ class Predictor:
         if self.gpu_video_codec == 'mjpeg':
             put, close = self._mjpeg_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh.avi"),
                                             int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
+            return (lambda fr, img: put(img)), close
+        if self.gpu_video_codec == 'y4m':
+            put, close = self._y4m_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh"),
+                                          int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
             return (lambda fr, img: put(img)), close
         try:
             import cv2
@@ -491,7 +538,8 @@ class Predictor:
         poserisk_release_amd.video (pr_compose_video) from the arrays score_frames returned.  <output>/<TITLE>_video.mp4 where
         cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame; with
         gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there; with
-        'png' <output>/<TITLE>_video/%09d.png, encoded on the GPU (lossless), whether or not cv2 is there.  With
+        'png' <output>/<TITLE>_video/%09d.png, encoded on the GPU (lossless), whether or not cv2 is there; with 'y4m'
+        <output>/<TITLE>_video.y4m, or through the video_encoder knob's command <TITLE>_video.mp4 (_y4m_writer).  With
         the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
         parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
         that the mesh output is written from the same rendering.  Returns the path written."""
@@ -528,6 +576,15 @@ class Predictor:
             finally:                                # also when encoding raises: the index is written, the headers patched
                 path = close()
             return path
+        if self.gpu_video_codec == 'y4m':
+            put, close = self._y4m_writer(osp.join(output_path, title + '_video'), resize_w + panel_w, canvas_h, fps, bgr)
+            try:
+                for canvases in batches:
+                    put(canvases)
+            except BaseException:
+                close(failed=True)
+                raise
+            return close()
         if self.gpu_video_codec == 'png':
             put, close = self._png_writer(osp.join(output_path, title + '_video'), bgr)
             i = 0

@@ -27,8 +27,16 @@ absent from the reference and all optional:
     cfg.DATASET.gpu_video_codec  '' (default: the two outputs above as they are) | 'mjpeg': <TITLE>_video.avi and <TITLE>_mesh.avi,
                               baseline JPEG frames encoded on the GPU (pr_jpeg_encode) in a Motion-JPEG AVI written in Python,
                               with or without cv2 | 'png': <TITLE>_video/%09d.png and <TITLE>_mesh/%09d.png, lossless frames
-                              encoded on the GPU (pr_png_encode), with or without cv2 (args.video_codec overrides it); any other
-                              name raises
+                              encoded on the GPU (pr_png_encode), with or without cv2 | 'y4m': <TITLE>_video.y4m and
+                              <TITLE>_mesh.y4m, YUV4MPEG2 converted on the GPU (pr_yuv_encode), with or without cv2
+                              (args.video_codec overrides it); any other name raises
+    cfg.DATASET.video_encoder  '' (off) | a command line containing {output}, e.g. `ffmpeg -v error -y -f yuv4mpegpipe -i -
+                              -c:v libx264 -pix_fmt yuv420p {output}`: implies gpu_video_codec 'y4m'; the stream is piped to it as
+                              a child process (no shell) and the files are <TITLE>_video and <TITLE>_mesh + video_encoder_ext
+                              (args.video_encoder overrides it); a failing command raises RuntimeError naming its exit status
+    cfg.DATASET.video_encoder_ext  '.mp4': the ending of the files that command writes
+    cfg.DATASET.video_chroma  '420mpeg2' | '420jpeg' | '422' | '444' | 'mono': the layout of that stream; the matrix is yuv_matrix,
+                              the range limited, odd sides of a subsampled layout are padded to even by replication
     cfg.DATASET.gpu_video_quality  the JPEG quality of those frames, 1..100 (90)
     cfg.DATASET.front_max_w, front_max_h  800, 450: the reference's front-end rule for a Motion-JPEG AVI input (wider than
                               front_max_w -> that width, else higher than front_max_h -> that height; 0 switches an arm off),
@@ -106,7 +114,8 @@ def _defaults(root):
                     'hip_batch_size': 64, 'hip_lanes': 2, 'hip_world_size': 0,
                     'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
                     'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True,
-                    'yuv_matrix': '601', 'video_decoder': ''},
+                    'yuv_matrix': '601', 'video_decoder': '', 'video_encoder': '', 'video_encoder_ext': '.mp4',
+                    'video_chroma': '420mpeg2'},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

@@ -1,4 +1,4 @@
-"""YUV4MPEG2 (`.y4m`) video read on the GPU: the raw planar stream that `ffmpeg -f yuv4mpegpipe`, mpv, GStreamer's y4menc, x264
+"""YUV4MPEG2 (`.y4m`) video read and written on the GPU: the raw planar stream that `ffmpeg -f yuv4mpegpipe`, mpv, GStreamer's y4menc, x264
 and the AV1 tools read and write, so any codec a decoder can pipe out reaches the front end without touching a disk and without
 being recompressed.  The contract is in include/poserisk_hip.h (section j6); the host half (csrc/y4m_host.cc) reads the
 syntax, the device half (csrc/yuv.hip) does chroma upsampling, the colour matrix and the front end's downscale in one kernel.
@@ -9,8 +9,12 @@ syntax, the device half (csrc/yuv.hip) does chroma upsampling, the colour matrix
     yuv_frames     a chunk on the device + payload offsets -> u8[F,h,w,3] on the device (pr_yuv_frames)
     decode         a Reader, a path or bytes -> u8[F,h,w,3] on the device
     write          planes -> a stream (for tests and users; no GPU work)
+    stream_header  the stream header line
+    encode_frames  u8[F,H,W,3] on the device -> the frames' stream bytes on the device (pr_yuv_encode; section j7, csrc/yuv_enc.hip)
+    Writer         RGB frames on the device -> a path, a binary file object, "-" (standard output) or an encoder child process
 
-    ffmpeg -i clip.mp4 -f yuv4mpegpipe -pix_fmt yuv420p - | python -m poserisk_release_amd.frontend prepare - frames_dir"""
+    ffmpeg -i clip.mp4 -f yuv4mpegpipe -pix_fmt yuv420p - | python -m poserisk_release_amd.frontend prepare - frames_dir
+    y4m.Writer(command=["ffmpeg", "-y", "-f", "yuv4mpegpipe", "-i", "-", "-c:v", "libx264", "out.mp4"], width=W, height=H)"""
 import collections
 import ctypes as C
 import io
@@ -305,7 +309,6 @@ def decode(src, device, matrix="601", full_range=None, bgr=False, size=None, fus
 def write(dst, Y, U=None, V=None, fps=30.0, chroma="420jpeg", full_range=None, frame_fields=b""):
     """Planes -> a YUV4MPEG2 stream.  Y u8[F,H,W]; U, V u8[F,ch,cw] (None for chroma "mono"); fps a number or (num, den);
     full_range True | False writes XCOLORRANGE, None leaves it out.  `dst` is a path or a binary file object.  No GPU work."""
-    import fractions
     Y = np.ascontiguousarray(Y, np.uint8)
     F, H, W = Y.shape
     if chroma not in CHROMAS:
@@ -316,14 +319,10 @@ def write(dst, Y, U=None, V=None, fps=30.0, chroma="420jpeg", full_range=None, f
         U, V = np.ascontiguousarray(U, np.uint8), np.ascontiguousarray(V, np.uint8)
         if U.shape != (F, ch, cw) or V.shape != (F, ch, cw):
             raise ValueError(f"{chroma} planes of {W} x {H} frames must be {[F, ch, cw]}, got {list(U.shape)} and {list(V.shape)}")
-    num, den = fps if isinstance(fps, tuple) else fractions.Fraction(float(fps)).limit_denominator(1001).as_integer_ratio()
-    head = f"YUV4MPEG2 W{W} H{H} F{num}:{den} Ip A1:1 C{chroma}"
-    if full_range is not None:
-        head += " XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")
     own = isinstance(dst, (str, os.PathLike))
     f = open(dst, "wb") if own else dst
     try:
-        f.write(head.encode() + b"\n")
+        f.write(stream_header(W, H, fps, chroma, full_range))
         for k in range(F):
             f.write(b"FRAME" + frame_fields + b"\n" + Y[k].tobytes())
             if chroma != "mono":
@@ -331,3 +330,216 @@ def write(dst, Y, U=None, V=None, fps=30.0, chroma="420jpeg", full_range=None, f
     finally:
         if own:
             f.close()
+
+
+# ---- the writer (include/poserisk_hip.h, section j7) ---------------------------------------------------------------------------
+def stream_header(W, H, fps=30.0, chroma="420jpeg", full_range=None):
+    """The stream header line, its '\\n' included.  fps a number or (num, den); full_range True | False writes XCOLORRANGE, None
+    leaves it out."""
+    import fractions
+    if chroma not in CHROMAS:
+        raise ValueError(f"chroma {chroma!r} is not one of {CHROMAS}")
+    num, den = fps if isinstance(fps, tuple) else fractions.Fraction(float(fps)).limit_denominator(1001).as_integer_ratio()
+    head = f"YUV4MPEG2 W{W} H{H} F{num}:{den} Ip A1:1 C{chroma}"
+    if full_range is not None:
+        head += " XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")
+    return head.encode() + b"\n"
+
+
+def yuv_enc_plan(matrix, full_range):
+    """pr_yuv_enc_plan -> (kyr, kyg, kyb, kc, kur, kug, kvb, kvg, yo)."""
+    if matrix not in MATRICES:
+        raise ValueError(f"matrix {matrix!r} is not known: '601' or '709'")
+    plan = _lib.YuvEncCoeffs()
+    _lib.check(_lib.load().pr_yuv_enc_plan(MATRICES[matrix], int(bool(full_range)), C.byref(plan)), "pr_yuv_enc_plan")
+    return tuple(getattr(plan, name) for name, _ in _lib.YuvEncCoeffs._fields_)
+
+
+def encoded_size(W, H, chroma="420mpeg2", pad_even=False):
+    """-> (out_W, out_H, bytes a frame takes in the stream: "FRAME\\n" and its planes).  pad_even rounds both sides up to even."""
+    if chroma not in CHROMAS:
+        raise ValueError(f"chroma {chroma!r} is not one of {CHROMAS}")
+    W, H = int(W), int(H)
+    ow, oh = (W + (W & 1), H + (H & 1)) if pad_even else (W, H)
+    cw = (ow + 1) // 2 if chroma in ("420jpeg", "420mpeg2", "422") else ow
+    ch = (oh + 1) // 2 if chroma in ("420jpeg", "420mpeg2") else oh
+    return ow, oh, 6 + ow * oh + (0 if chroma == "mono" else 2 * cw * ch)
+
+
+def encode_frames(frames, chroma="420mpeg2", matrix="601", full_range=False, bgr=False, pad_even=False, out=None):
+    """pr_yuv_encode: `frames` u8[F,H,W,3] on the device (RGB; BGR with bgr=True) -> u8[F, 6 + frame_bytes] on the device, the
+    frames of a YUV4MPEG2 stream one after the other ("FRAME\\n", Y, U, V), ready to be written behind stream_header(out_W,
+    out_H, ...).  pad_even pads odd sides by one replicated row / column (encoded_size gives the sizes).  Asynchronous on the
+    current stream; with `out` given it allocates and synchronises nothing."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+        raise _lib.PoseRiskHipError("encode_frames: the conversion runs on the GPU only (no CPU fallback)")
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError(f"encode_frames: frames must be a contiguous uint8 [F,H,W,3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    device, (F, H, W) = frames.device, (int(s) for s in frames.shape[:3])
+    ow, oh, size = encoded_size(W, H, chroma, pad_even)
+    a = _lib.YuvEncArgs()
+    a.plan = _lib.YuvEncCoeffs(*yuv_enc_plan(matrix, full_range))
+    a.F, a.H, a.W, a.out_H, a.out_W, a.chroma, a.bgr = F, H, W, oh, ow, CHROMAS.index(chroma), int(bool(bgr))
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty((F, size), dtype=torch.uint8, device=device)
+        _check_out(out, (F, size), device, "encode_frames")
+        a.src, a.dst = frames.data_ptr(), out.data_ptr()
+        _lib.check(_lib.load().pr_yuv_encode(C.byref(a), torch.cuda.current_stream(device).cuda_stream), "pr_yuv_encode")
+    return out
+
+
+class Writer:
+    """A YUV4MPEG2 stream of `width` x `height` RGB frames, converted on the GPU (encode_frames), to `dst`: a path, a binary file
+    object, "-" (standard output), or -- with dst None and command=[argv] -- a child process fed on its standard input, for
+    example ["ffmpeg", "-v", "error", "-y", "-f", "yuv4mpegpipe", "-i", "-", "-c:v", "libx264", "out.mp4"].  The stream header is
+    written on construction; .out_width and .out_height are the stream's sides (pad_even rounds odd ones up).
+
+    put(frames) converts a batch, starts its download into one of two pinned buffers and writes the PREVIOUS batch while this
+    one converts; close() writes what is left and closes what the writer opened.  Never a shell and never this process's own
+    program; a child is reaped whatever happens.  A command that cannot be started, a write that fails with a broken pipe and
+    a non-zero exit status raise RuntimeError naming the command, the status and the tail of the child's standard error."""
+
+    def __init__(self, dst=None, width=None, height=None, fps=30.0, chroma="420mpeg2", matrix="601", full_range=False, bgr=False,
+                 pad_even=False, command=None):
+        import shlex
+        import subprocess
+        import tempfile
+        if (dst is None) == (command is None):
+            raise ValueError("y4m.Writer: give either dst (a path, a binary file object or '-') or command=[argv]")
+        if matrix not in MATRICES:
+            raise ValueError(f"matrix {matrix!r} is not known: '601' or '709'")
+        self.width, self.height = int(width), int(height)
+        self.out_width, self.out_height, self.frame_size = encoded_size(self.width, self.height, chroma, pad_even)
+        self.chroma, self.matrix, self.full_range, self.bgr, self.pad_even = chroma, matrix, bool(full_range), bool(bgr), bool(pad_even)
+        self.frames_written = 0
+        self._child = self._err = self._f = None
+        self._own = self._closed = False
+        self._pinned, self._staged, self._pending, self._which = [None, None], None, None, 0
+        if command is not None:
+            argv = [os.fspath(a) for a in command]
+            self._shown = " ".join(shlex.quote(a) for a in argv)
+            self._err = tempfile.TemporaryFile()
+            try:
+                self._child = subprocess.Popen(argv, stdin=subprocess.PIPE, stdout=subprocess.DEVNULL, stderr=self._err)
+            except OSError as e:
+                self._err.close()
+                self._closed = True
+                raise RuntimeError(f"the video encoder `{self._shown}` could not be started: {e}") from e
+            self._f = self._child.stdin
+        elif isinstance(dst, (str, os.PathLike)) and os.fspath(dst) != "-":
+            self._f, self._own = open(dst, "wb"), True
+        elif isinstance(dst, (str, os.PathLike)):
+            self._f = sys.stdout.buffer
+        else:
+            self._f = dst
+        self._write(stream_header(self.out_width, self.out_height, fps, chroma, self.full_range))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, kind, *exc):
+        if kind is None:
+            self.close()
+        else:
+            self.abort()                              # the caller's exception stands; the child is reaped all the same
+
+    def abort(self):
+        """Gives up what is queued, closes the sink and reaps a child without raising for its status: for a caller that is
+        already handling an error of its own."""
+        self._finish(raising=False)
+
+    def _write(self, data):
+        try:
+            self._f.write(data)
+        except (BrokenPipeError, ConnectionResetError) as e:
+            if self._child is None:
+                raise
+            self._finish(failure=f"it closed its standard input after {self.frames_written} frames ({e.strerror or e})")
+
+    def _flush(self):
+        if self._pending is not None:
+            event, view, frames = self._pending
+            self._pending = None
+            event.synchronize()
+            self._write(memoryview(view))
+            self.frames_written += frames
+
+    def put_stream_bytes(self, data, frames=0):
+        """Host only: writes `data` (bytes-like: whole frames as encode_frames lays them out) behind what put has queued.
+        What put itself ends in, so a test without a GPU drives the same path."""
+        if self._closed:
+            raise ValueError("y4m.Writer: closed")
+        self._flush()
+        self._write(memoryview(data))
+        self.frames_written += int(frames)
+
+    def put(self, frames):
+        """frames u8[F,height,width,3] on the device.  Returns after the PREVIOUS batch's bytes are written; this batch's are
+        written by the next put or by close."""
+        if self._closed:
+            raise ValueError("y4m.Writer: closed")
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+            raise _lib.PoseRiskHipError("y4m.Writer.put: the conversion runs on the GPU only (no CPU fallback)")
+        if tuple(frames.shape[1:]) != (self.height, self.width, 3):
+            raise ValueError(f"y4m.Writer.put: frames must be [F,{self.height},{self.width},3], got {tuple(frames.shape)}")
+        F = int(frames.shape[0])
+        if F == 0:
+            return
+        device = frames.device
+        with torch.cuda.device(device):
+            if self._staged is None or self._staged.shape[0] < F or self._staged.device != device:
+                self._staged = torch.empty((F, self.frame_size), dtype=torch.uint8, device=device)
+            host = self._pinned[self._which]
+            if host is None or host.shape[0] < F:
+                host = self._pinned[self._which] = torch.empty((F, self.frame_size), dtype=torch.uint8, pin_memory=True)
+            encode_frames(frames.contiguous(), self.chroma, self.matrix, self.full_range, self.bgr, self.pad_even, out=self._staged[:F])
+            host[:F].copy_(self._staged[:F], non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(device))
+        self._flush()                                 # the previous batch: written while this one converts and downloads
+        self._pending = (event, host[:F].numpy().reshape(-1), F)
+        self._which ^= 1
+
+    def close(self):
+        """Writes what is left, closes what the writer opened; for a child closes its standard input and waits for it."""
+        if self._closed:
+            return
+        self._flush()
+        self._finish()
+
+    def _finish(self, failure=None, raising=True):
+        """Closes the sink and reaps the child; raises RuntimeError for a failed child (unless raising is False)."""
+        if self._closed:
+            return
+        self._closed = True
+        self._pending = None
+        import subprocess
+        if self._child is None:
+            if self._own:
+                self._f.close()
+            else:
+                try:
+                    self._f.flush()
+                except (AttributeError, ValueError):
+                    pass
+            return
+        try:
+            self._f.close()                           # flushes: a child that is gone answers with a broken pipe here too
+        except (BrokenPipeError, ConnectionResetError) as e:
+            failure = failure or f"it closed its standard input after {self.frames_written} frames ({e.strerror or e})"
+        except OSError:
+            pass
+        try:
+            status = self._child.wait(timeout=5 if failure is not None or not raising else 600)
+        except subprocess.TimeoutExpired:
+            self._child.kill()
+            status = self._child.wait()
+            failure = failure or "it did not end after its standard input was closed"
+        self._err.seek(0)
+        tail = self._err.read()[-2000:].decode("utf-8", "replace").strip()
+        self._err.close()
+        if raising and (failure is not None or status != 0):
+            raise RuntimeError(f"the video encoder `{self._shown}` failed with exit status {status}"
+                               + (f": {failure}" if failure is not None else "")
+                               + (f"; its standard error ends: {tail}" if tail else ""))
