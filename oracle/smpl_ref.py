@@ -46,7 +46,8 @@ class SMPLModel:
                  parents=SMPL_PARENTS, model_betas=None):
         self.v_template = np.asarray(v_template, F32).reshape(-1, 3)          # [V,3]
         V = self.v_template.shape[0]
-        self.shapedirs = np.asarray(shapedirs, F32).reshape(V, 3, -1)          # [V,3,10]
+        sd = np.asarray(shapedirs, F32)
+        self.shapedirs = sd.reshape(V, 3, sd.size // (3 * V))                  # [V,3,10] (any count, none included)
         self.posedirs = np.asarray(posedirs, F32).reshape(V, 3, -1)            # [V,3,207]
         self.J_regressor = np.asarray(J_regressor, F32)                        # [J,V]
         self.weights = np.asarray(weights, F32)                                # [V,J]

@@ -60,11 +60,15 @@ __global__ void smpl_flags(const float* __restrict__ betas, long nb, const float
     any_t = 0;
   }
   __syncthreads();
+  // torch.norm(x) == 0 sums float32 squares: a value counts only if its square does not round to zero, that is if
+  // |x| > 2^-75 (x^2 = 2^-150 is the tie between 0 and the smallest denormal, and goes to 0).  Spelled as a comparison
+  // of magnitudes so that the answer does not hang on the device's denormal mode; the negated <= lets a NaN count.
+  constexpr float kSquareVanishes = 0x1p-75f;
   int lb = 0, lt = 0;
   if (betas)
-    for (long i = threadIdx.x; i < nb; i += blockDim.x) lb |= (betas[i] != 0.f);
+    for (long i = threadIdx.x; i < nb; i += blockDim.x) lb |= !(fabsf(betas[i]) <= kSquareVanishes);
   if (trans)
-    for (long i = threadIdx.x; i < nt; i += blockDim.x) lt |= (trans[i] != 0.f);
+    for (long i = threadIdx.x; i < nt; i += blockDim.x) lt |= !(fabsf(trans[i]) <= kSquareVanishes);
   if (lb) atomicOr(&any_b, 1);
   if (lt) atomicOr(&any_t, 1);
   __syncthreads();
@@ -195,9 +199,13 @@ __global__ __launch_bounds__(64) void smpl_pose(const PoseArgs a) {
     if (a.joints) {
       float* jo = a.joints + ((long)b * kJ + lane) * 3;
       if (a.joint_cam_mode) {  // coord_utils.py:16-17: (joints * 1000) - root
-        jo[0] = G[lane][3] * 1000.f - G[0][3] * 1000.f;
-        jo[1] = G[lane][7] * 1000.f - G[0][7] * 1000.f;
-        jo[2] = G[lane][11] * 1000.f - G[0][11] * 1000.f;
+        // Both products rounded, as in the reference.  Left to the compiler this contracts to fma(joint, 1000, -(root * 1000)),
+        // which keeps the first product exact: the root's own row, and every joint that coincides with the root, then comes
+        // out as the rounding error of root * 1000 (about 1e-6 mm) instead of 0.
+#pragma clang fp contract(off)
+        const float jx = G[lane][3] * 1000.f, jy = G[lane][7] * 1000.f, jz = G[lane][11] * 1000.f;
+        const float rx = G[0][3] * 1000.f, ry = G[0][7] * 1000.f, rz = G[0][11] * 1000.f;
+        jo[0] = jx - rx; jo[1] = jy - ry; jo[2] = jz - rz;
       } else {
         jo[0] = G[lane][3] + ox; jo[1] = G[lane][7] + oy; jo[2] = G[lane][11] + oz;
       }

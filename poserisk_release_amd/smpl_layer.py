@@ -30,7 +30,7 @@ class SMPLLayer:
                        shapedirs=_f32(model["shapedirs"]), posedirs=_f32(model["posedirs"]),
                        J_regressor=_f32(model["J_regressor"]), weights=_f32(model["weights"]))
         V = self._m["v_template"].shape[0]
-        self._m["shapedirs"] = self._m["shapedirs"].reshape(V, 3, -1)
+        self._m["shapedirs"] = self._m["shapedirs"].reshape(V, 3, self._m["shapedirs"].size // (3 * V))    # (-1 cannot stand for 0)
         self._m["posedirs"] = self._m["posedirs"].reshape(V, 3, -1)
         self.num_verts = V
         self.kintree_parents = [int(p) for p in np.asarray(model["parents"]).reshape(-1)]

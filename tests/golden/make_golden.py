@@ -126,6 +126,27 @@ def gen_smpl():
     np.savez_compressed(os.path.join(HERE, "rodrigues.npz"), axisang=v, rotmat=r)
 
 
+def gen_smpl_sweep():
+    """smpl_sweep.npz: the reference's SMPL_Layer on the small models of tests/smpl_cases.py -- the centring branch, a
+    translation given / zero / absent, large and exactly periodic angles, betas and trans whose squares underflow, other
+    kinematic trees and weight counts.  Inputs and outputs are stored; the models come from their seeds."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import smpl_cases
+    out = {}
+    for name, spec in smpl_cases.FIXTURES.items():
+        layer = _ref_smpl_layer(smpl_cases.fixture_model(name))
+        layer.center_idx = spec["center_idx"]
+        pose, betas, trans = smpl_cases.fixture_inputs(name)
+        args = [torch.tensor(pose), torch.tensor(betas)] + ([torch.tensor(trans)] if trans is not None else [])
+        with torch.no_grad():
+            v, j = layer(*args)
+        out[f"{name}_pose"], out[f"{name}_betas"] = pose, betas
+        if trans is not None:
+            out[f"{name}_trans"] = trans
+        out[f"{name}_verts"], out[f"{name}_joints"] = v.numpy(), j.numpy()
+    np.savez_compressed(os.path.join(HERE, "smpl_sweep.npz"), **out)
+
+
 def gen_euler():
     import coord_utils
     rot = synth.rotmats(40, seed=5)
@@ -292,6 +313,7 @@ def gen_driver_loop():
 if __name__ == "__main__":
     _reference_paths()
     gen_smpl()
+    gen_smpl_sweep()
     gen_euler()
     gen_scores()
     gen_driver_loop()
