@@ -1377,6 +1377,131 @@ typedef struct pr_yuv_enc_args {
 } pr_yuv_enc_args;
 int pr_yuv_encode(const pr_yuv_enc_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* j8  person detector: YOLOv3 (Darknet-53 + three heads) and its post-processing          */
+/* replaces: the detector half of multi_person_tracker's MPT(...)(image_folder),           */
+/*           lib/core/base.py:38-46,59 (detector_type='yolo', yolo_img_size=416,            */
+/*           detection_threshold=0.1); the SORT half is host Python (sort.py)               */
+/* ------------------------------------------------------------------------------------ */
+/* multi_person_tracker and its `yolov3` package are cloned by the reference at install time and are NOT part of the reference
+ * tree: nothing pins their bits.  Everything in this section is this project's own contract, modelled on them; a choice marked
+ * [unpinned] was taken from memory of the upstream code, not from a file that can be compared.  No ABI bump: functions were added
+ * (j3's precedent).
+ *
+ * Network.  The fixed topology of darknet's yolov3.cfg: 107 layers (0..106), 75 convolutions, 23 shortcuts, routes -4 | -1,61 |
+ *   -4 | -1,36, two nearest x2 upsamples, heads at layers 82 / 94 / 106 with strides 32 / 16 / 8.  Every convolution but the three
+ *   255-channel head layers is conv (no bias) + BatchNorm + leaky ReLU of slope 0.1 (v > 0 ? v : 0.1f * v); the head layers are
+ *   conv + bias, linear.  Padding is k / 2.  A shortcut adds AFTER the activation and applies none to the sum:
+ *   y = leaky(conv + b) + res, evaluated in that order in fp32.  Head channel = anchor * 85 + (x, y, w, h, obj, 80 classes).
+ *   The input is S_h x S_w, each a multiple of 32 (default 416 x 416, the reference's yolo_img_size).  fp32 only, on
+ *   v_mfma_f32_32x32x2_f32; activations NHWC.
+ * Weights.  weights_host is the float body of a darknet weight file, unchanged (62 001 757 floats for the 80-class network): per
+ *   BatchNorm convolution beta[O], gamma[O], running mean[O], running var[O], then the weights OIHW; per head convolution
+ *   bias[255], then the weights OIHW.  BatchNorm is folded in float64: scale = gamma / sqrt(var + bn_eps), w' = (float)(w *
+ *   scale), b' = (float)(beta - mean * scale).  bn_eps is an argument; the value to pass for weights used with the PyTorch port
+ *   is 1e-5 (nn.BatchNorm2d's default [unpinned]); darknet itself uses 1e-6.
+ * Packed layout (pr_det_fold_pack; what the kernel reads): per convolution bias f32[cout_pad], then w f32[cout_pad][kpad] with
+ *   k = (kh * ksize + kw) * cin_pad + ci, zero where padded; cin_pad = cin rounded up to 4, cout_pad = cout rounded up to 64,
+ *   kpad = ksize^2 * cin_pad rounded up to 32. */
+#define PR_DET_NUM_LAYERS 107
+#define PR_DET_MAX_CAND 1024   /* candidates that take part in NMS, per frame */
+enum { PR_DET_CONV = 0, PR_DET_SHORTCUT = 1, PR_DET_ROUTE = 2, PR_DET_UPSAMPLE = 3, PR_DET_YOLO = 4 };
+enum { PR_DET_STATUS_CAND_OVERFLOW = 1, /* more than PR_DET_MAX_CAND candidates: the best PR_DET_MAX_CAND took part */
+       PR_DET_STATUS_DET_OVERFLOW = 2   /* more than max_det boxes survived NMS: the best max_det were written */ };
+typedef struct pr_det_layer {
+  int32_t type;           /* PR_DET_* */
+  int32_t cin, cout;      /* channels in and out, unpadded (a route's: the sum of its sources) */
+  int32_t ksize, stride;  /* convolution; upsample: stride 2 */
+  int32_t bn;             /* convolution: 1 = BatchNorm + leaky 0.1, 0 = bias, linear */
+  int32_t from0, from1;   /* ABSOLUTE layer indices, -1 = none.  shortcut: the layer added to the one in front; route: its sources */
+  int32_t down;           /* the output grid is (S_h / down) x (S_w / down) */
+  int32_t cin_pad, cout_pad, kpad;
+  int64_t weight_offset;  /* convolution: floats into the darknet body where its parameters begin, else -1 */
+  int64_t pack_offset;    /* convolution: floats into the packed blob where its bias begins, else -1 */
+} pr_det_layer;
+
+/* Host only, no device call (csrc/det_host.cc).  The first n_layers (1..107) of the table; a truncated table folds and packs
+ * like the whole one.  pr_det_weight_floats / pr_det_packed_floats: the darknet floats the first n_layers read and the floats
+ * they pack to (0 for n_layers outside 1..107).  pr_det_fold_pack refuses by name a null pointer, a count that is not exactly
+ * those, and bn_eps outside (0, 1). */
+int pr_det_topology(int n_layers, pr_det_layer* layers_host);
+size_t pr_det_weight_floats(int n_layers);
+size_t pr_det_packed_floats(int n_layers);
+int pr_det_fold_pack(int n_layers, const float* weights_host, size_t n_floats, double bn_eps, float* packed_host,
+                     size_t packed_floats);
+
+/* Handle.  pr_det_create folds, packs and uploads the weights and allocates every activation buffer for max_batch frames of
+ * S_h x S_w (through the internal fence where POSERISK_FENCE is set; every tensor stays below 2 GiB, else PR_ERR_INVALID), the
+ * candidate list of the post-processing and the input canvas of pr_det_detect; n_floats must be
+ * pr_det_weight_floats(107).  Allocates, copies, synchronises: refused under a declared stream capture, like the other
+ * handles' create and destroy.  (max_det, an argument of pr_det_postprocess / pr_det_detect, is the capacity of their outputs:
+ * 1..PR_DET_MAX_CAND.)  Queries: pr_det_input_size, pr_det_max_batch, pr_det_grid (the grid of layer `layer`'s output and its channels). */
+typedef struct pr_det pr_det_t;
+int pr_det_create(int device, const float* weights_host, size_t n_floats, int S_h, int S_w, int max_batch, double bn_eps,
+                  pr_det_t** out);
+int pr_det_destroy(pr_det_t* h);
+int pr_det_input_size(const pr_det_t* h, int* S_h, int* S_w);
+int pr_det_max_batch(const pr_det_t* h);
+int pr_det_grid(const pr_det_t* h, int layer, int* gh, int* gw, int* channels);
+
+/* The device entries below are asynchronous on `stream`, allocate nothing, copy nothing to or from the host and do not
+ * synchronise (capturable); each refuses its arguments by name (PR_ERR_INVALID; B above max_batch: PR_ERR_CAPACITY) before any
+ * device work; B = 0 returns PR_OK.
+ *
+ * pr_det_letterbox: frames_dev u8[B,H,W,3] (RGB, or BGR with bgr != 0) -> x_dev f32[B,S_h,S_w,4], channels R, G, B, 0.
+ *   Sizes, all in integers: with the tighter axis chosen by W * S_h >= H * S_w (the width binds) or not (the height binds),
+ *     width binds:   w' = S_w,  h' = min(S_h, max(1, (2 * H * S_w + W) / (2 * W)))        round_half_up(H * S_w / W)
+ *     height binds:  h' = S_h,  w' = min(S_w, max(1, (2 * W * S_h + H) / (2 * H)))        round_half_up(W * S_h / H)
+ *   i.e. w' = min(S_w, max(1, round_half_up(W r))), h' likewise, r = min(S_w / W, S_h / H) as an exact fraction (a frame smaller
+ *   than the input is enlarged) [unpinned: the upstream letterbox rounds W r in floating point].
+ *   The h' x w' image is exactly pr_resize_frames' output with pr_resize_plan(H, W, h', w')'s tables and mode (section j3; the
+ *   kernel evaluates the same tap expressions per pixel: the position as a double product and a double difference rounded
+ *   separately, to float once).  It lies at ox = (S_w - w') / 2, oy = (S_h - h') / 2 (floor) on a canvas of 128; every value is
+ *   (float)u8 * (1.f / 255.f).  H, W in 1..PR_RESIZE_MAX_SIDE.
+ *
+ * pr_det_network: x_dev f32[B,S_h,S_w,4] -> the three head tensors head{32,16,8}_dev f32[B,gh,gw,255], gh = S_h / stride.
+ * pr_det_network_until: the output of layer `layer` (0..106) as act_dev f32[B,gh,gw,C] (pr_det_grid): a convolution's (with its
+ *   activation, without the shortcut behind it), a shortcut's sum, an upsample's, a route's concatenation (sources in the
+ *   route's order), a yolo layer's = the head convolution's output unchanged.  (pr_hmr_encode_until's precedent.)
+ *
+ * pr_det_postprocess: the three head tensors -> per frame at most max_det person boxes: boxes_dev f32[B,max_det,4] (x1, y1, x2,
+ *   y2 in letterbox pixels), scores_dev f32[B,max_det], count_dev i32[B], status_dev i32[B] (PR_DET_STATUS_* bits); rows
+ *   beyond count are zero.
+ *   Decode, per cell (head, anchor a, row cy, column cx), each expression in float64 on the fp32 head values and rounded to fp32
+ *   once, sigma(t) = 1 / (1 + exp(-t)):
+ *     bx = (sigma(tx) + cx) * stride   by = (sigma(ty) + cy) * stride   bw = anchor_w * exp(tw)   bh = anchor_h * exp(th)
+ *     obj = sigma(to)   score = sigma(to) * sigma(tc0)
+ *   anchors (pixels) (10,13) (16,30) (33,23) (30,61) (62,45) (59,119) (116,90) (156,198) (373,326), masks 6-8 / 3-5 / 0-2 for
+ *   strides 32 / 16 / 8.  A cell is a candidate iff obj >= conf_thres (obj as fp32, conf_thres as given) and the largest of its
+ *   80 class values tc (the lowest index on ties; sigma is monotonic, the values themselves are compared) is class 0.
+ *   Order: score descending (as fp32), then the flat index ((head 32, 16, 8) / anchor / cy / cx, cx fastest) ascending; frames
+ *   are independent.  The first PR_DET_MAX_CAND take part; more set PR_DET_STATUS_CAND_OVERFLOW.
+ *   Box corners, fp32: x1 = bx - 0.5f * bw, x2 = bx + 0.5f * bw, y alike (a product, then a sum; never fused).
+ *   Greedy NMS in that order: a candidate is dropped iff an earlier KEPT one has IoU > nms_thres with it.  IoU in fp32, each
+ *   operation rounded, never fused, on continuous coordinates:
+ *     iw = max(min(ax2, bx2) - max(ax1, bx1), 0)   ih alike   inter = iw * ih
+ *     area = (x2 - x1) * (y2 - y1)                  IoU = inter / ((area_a + area_b) - inter)      (0 / 0 counts as no overlap)
+ *   Class-agnostic by construction: only class 0 is kept [unpinned: upstream runs NMS per class over all 80].
+ *
+ * pr_det_detect: frames_dev u8[B,H,W,3] -> letterbox, network, post-processing as above, then each box mapped to the frame:
+ *   x = (x_letterbox - ox) / (w' / W) evaluated as (x - (float)ox) * ((float)W / (float)w'), y alike with (float)H / (float)h',
+ *   then clipped to [0, W] and [0, H]: the scale actually used per axis.  Outputs as pr_det_postprocess'. */
+/* The detector's convolution alone (csrc/det_conv.hip; parity tests and timing against pr_conv2d_nhwc): x_dev f32[B,H,W,Cin]
+ * (Cin a multiple of 4), packed_dev = ONE convolution in the packed layout above (bias f32[cout_pad], then w
+ * f32[cout_pad][kpad], folded by the caller), res_dev f32[B,Ho,Wo,Cout] or NULL (added after the activation) -> y_dev
+ * f32[B,Ho,Wo,Cout] = leaky(conv + b) [+ res] (leaky = 0: linear); ksize 1 | 3, stride 1 | 2, padding ksize / 2, any Cout.  All
+ * device pointers; asynchronous, no allocation (capturable); refusals by name, a tensor of 2 GiB or more included. */
+int pr_det_conv_nhwc(const float* x_dev, const float* packed_dev, const float* res_dev, float* y_dev, int B, int H, int W, int Cin,
+                     int Cout, int ksize, int stride, int leaky, void* stream);
+int pr_det_letterbox(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, int bgr, float* x_dev, void* stream);
+int pr_det_network(pr_det_t* h, const float* x_dev, int B, float* head32_dev, float* head16_dev, float* head8_dev, void* stream);
+int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, float* act_dev, void* stream);
+int pr_det_postprocess(pr_det_t* h, const float* head32_dev, const float* head16_dev, const float* head8_dev, int B,
+                       float conf_thres, float nms_thres, int max_det, float* boxes_dev, float* scores_dev, int32_t* count_dev,
+                       int32_t* status_dev, void* stream);
+int pr_det_detect(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, int bgr, float conf_thres, float nms_thres,
+                  int max_det, float* boxes_dev, float* scores_dev, int32_t* count_dev, int32_t* status_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

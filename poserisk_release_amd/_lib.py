@@ -108,6 +108,12 @@ class YuvEncArgs(C.Structure):
                [(n, C.c_int) for n in ("F", "H", "W", "out_H", "out_W", "chroma", "bgr")]
 
 
+class DetLayer(C.Structure):
+    """pr_det_layer (include/poserisk_hip.h, section j8: the detector's topology table)."""
+    _fields_ = [(n, C.c_int32) for n in ("type", "cin", "cout", "ksize", "stride", "bn", "from0", "from1", "down", "cin_pad", "cout_pad",
+                                          "kpad")] + [("weight_offset", C.c_int64), ("pack_offset", C.c_int64)]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -194,6 +200,21 @@ SIGNATURES = {
     "pr_yuv_frames": (_I, [C.POINTER(YuvArgs), _P]),
     "pr_yuv_enc_plan": (_I, [_I, _I, C.POINTER(YuvEncCoeffs)]),
     "pr_yuv_encode": (_I, [C.POINTER(YuvEncArgs), _P]),
+    "pr_det_topology": (_I, [_I, C.POINTER(DetLayer)]),
+    "pr_det_weight_floats": (C.c_size_t, [_I]),
+    "pr_det_packed_floats": (C.c_size_t, [_I]),
+    "pr_det_fold_pack": (_I, [_I, _P, C.c_size_t, C.c_double, _P, C.c_size_t]),
+    "pr_det_create": (_I, [_I, _P, C.c_size_t, _I, _I, _I, C.c_double, C.POINTER(_P)]),
+    "pr_det_destroy": (_I, [_P]),
+    "pr_det_input_size": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "pr_det_max_batch": (_I, [_P]),
+    "pr_det_grid": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "pr_det_conv_nhwc": (_I, [_P, _P, _P, _P] + [_I] * 8 + [_P]),
+    "pr_det_letterbox": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "pr_det_network": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "pr_det_network_until": (_I, [_P, _P, _I, _I, _P, _P]),
+    "pr_det_postprocess": (_I, [_P, _P, _P, _P, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
+    "pr_det_detect": (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,22 @@
+// The detector's convolution (det_conv.hip): fp32 MFMA implicit GEMM on NHWC, y = leaky(x * w + b) [+ res] or linear.
+#pragma once
+#include "common.h"
+
+namespace pr {
+
+struct DetConvProblem {
+  const float* x = nullptr;     // [B,H,W,Cin], Cin % 4 == 0
+  const float* w = nullptr;     // packed [cout_pad][kpad], k = (kh * ksize + kw) * Cin + ci (include/poserisk_hip.h, j8)
+  const float* bias = nullptr;  // [cout_pad]
+  const float* res = nullptr;   // [M,Cout] or nullptr: added AFTER the activation
+  float* y = nullptr;           // [M,Cout]
+  int B = 0, H = 0, W = 0, Cin = 0, Ho = 0, Wo = 0, Cout = 0, cout_pad = 0, kpad = 0, ksize = 1, stride = 1;
+  int leaky = 1;                // 1: v > 0 ? v : 0.1f * v, 0: linear
+  long M() const { return (long)B * Ho * Wo; }
+  double flops() const { return 2.0 * (double)M() * Cout * ksize * ksize * Cin; }
+};
+
+// Asynchronous on `stream`; refuses by name what the kernel does not cover (a tensor of 2 GiB or more included).
+int det_conv_launch(const DetConvProblem& p, hipStream_t stream);
+
+}  // namespace pr

@@ -1,0 +1,269 @@
+"""The person detector (include/poserisk_hip.h, section j8): YOLOv3 on the GPU, the half of multi_person_tracker that finds
+people (lib/core/base.py:38-46,59); sort.py is the half that follows them.
+
+    yolo_layers()    the topology of darknet's yolov3.cfg as a list of dicts, in pure Python (synth.yolo_weights and
+                     tests/det_ref.py walk it; tests compare it with the library's own table, pr_det_topology)
+    load_darknet     a darknet weight file -> its float body, checked against the topology
+    save_darknet     the reverse (what the tests and synth use to make a file)
+    Detector         the handle: letterbox, network, network_until, postprocess, detect_raw on device tensors, and
+                     detect(frames) -> one array of boxes per frame
+
+`img_size` is (S_h, S_w), rows first, each a multiple of 32: (416, 416) is the reference's yolo_img_size; (256, 416) suits
+800 x 450 frames at 0.62 of the work."""
+import ctypes as C
+import warnings
+
+import numpy as np
+
+from . import _lib
+
+CONV, SHORTCUT, ROUTE, UPSAMPLE, YOLO = range(5)
+NUM_LAYERS = 107
+WEIGHT_FLOATS = 62001757
+HEAD_LAYERS = (82, 94, 106)
+STRIDES = (32, 16, 8)
+ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
+ANCHOR_MASKS = ((6, 7, 8), (3, 4, 5), (0, 1, 2))
+MAX_CAND = 1024
+STATUS_CAND_OVERFLOW, STATUS_DET_OVERFLOW = 1, 2
+
+
+def yolo_layers():
+    """[{type, cin, cout, ksize, stride, bn, from (absolute indices), down}] for layers 0..106."""
+    L = []
+
+    def add(type, **kw):
+        prev = L[-1] if L else {"cout": 3, "down": 1}
+        d = {"type": type, "cin": prev["cout"], "cout": prev["cout"], "ksize": 0, "stride": 0, "bn": 0, "from": (), "down": prev["down"]}
+        d.update(kw)
+        L.append(d)
+
+    def conv(filters, k, stride=1, bn=1):
+        add(CONV, cout=filters, ksize=k, stride=stride, bn=bn, down=(L[-1]["down"] if L else 1) * stride)
+
+    def block(planes, n):
+        for _ in range(n):
+            conv(planes // 2, 1), conv(planes, 3), add(SHORTCUT, **{"from": (len(L) - 3,)})
+
+    def route(*src):
+        add(ROUTE, cin=sum(L[s]["cout"] for s in src), cout=sum(L[s]["cout"] for s in src), down=L[src[0]]["down"], **{"from": src})
+
+    def neck(planes):
+        for _ in range(3):
+            conv(planes, 1), conv(2 * planes, 3)
+        conv(255, 1, bn=0), add(YOLO)
+
+    conv(32, 3)
+    for planes, n in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
+        conv(planes, 3, 2), block(planes, n)
+    neck(512)
+    route(len(L) - 4), conv(256, 1), add(UPSAMPLE, stride=2, down=L[-1]["down"] // 2), route(len(L) - 1, 61)
+    neck(256)
+    route(len(L) - 4), conv(128, 1), add(UPSAMPLE, stride=2, down=L[-1]["down"] // 2), route(len(L) - 1, 36)
+    neck(128)
+    assert len(L) == NUM_LAYERS
+    return L
+
+
+def weight_floats(layers=None):
+    """Floats of the darknet body the layers read: per BatchNorm convolution 4 O + O I k k, per head convolution O + O I k k."""
+    layers = yolo_layers() if layers is None else layers
+    return sum(l["cout"] * (4 if l["bn"] else 1) + l["cout"] * l["cin"] * l["ksize"] ** 2 for l in layers if l["type"] == CONV)
+
+
+def load_darknet(path):
+    """A darknet weight file -> its float body f32[62001757], unchanged.  Header: major, minor, revision as int32, then `seen`
+    as int64 when major * 10 + minor >= 2, else int32.  A header that is not one, or a body of another length than the
+    topology's, is refused by name."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    if len(blob) < 16:
+        raise ValueError(f"{path!r}: {len(blob)} bytes are no darknet weight file (the header alone has 16 or 20)")
+    major, minor, revision = (int(v) for v in np.frombuffer(blob, "<i4", 3))
+    if not (0 <= major <= 100 and 0 <= minor <= 1000 and 0 <= revision <= 100000):
+        raise ValueError(f"{path!r}: bad darknet header (version {major}.{minor}.{revision})")
+    head = 12 + (8 if major * 10 + minor >= 2 else 4)
+    body = blob[head:]
+    if len(body) != 4 * WEIGHT_FLOATS:
+        raise ValueError(f"{path!r}: the body holds {len(body) / 4:g} floats, YOLOv3 with 80 classes holds {WEIGHT_FLOATS} "
+                         f"(header version {major}.{minor}.{revision}, {head} bytes)")
+    return np.frombuffer(body, "<f4").astype(np.float32, copy=False)
+
+
+def save_darknet(path, weights, version=(0, 2, 0), seen=0):
+    weights = np.ascontiguousarray(weights, "<f4")
+    with open(path, "wb") as f:
+        f.write(np.asarray(version, "<i4").tobytes())
+        f.write(np.asarray([seen], "<i8" if version[0] * 10 + version[1] >= 2 else "<i4").tobytes())
+        f.write(weights.tobytes())
+
+
+def topology(n_layers=NUM_LAYERS):
+    """pr_det_topology -> a list of dicts (the library's own table, packed offsets included)."""
+    arr = (_lib.DetLayer * n_layers)()
+    _lib.check(_lib.load().pr_det_topology(int(n_layers), arr), "pr_det_topology")
+    return [{n: getattr(a, n) for n, _ in _lib.DetLayer._fields_} for a in arr]
+
+
+def fold_pack(weights, n_layers=NUM_LAYERS, bn_eps=1e-5):
+    """pr_det_fold_pack on the host -> the packed blob f32[pr_det_packed_floats(n_layers)]."""
+    lib = _lib.load()
+    weights = np.ascontiguousarray(weights, np.float32)
+    out = np.empty(lib.pr_det_packed_floats(int(n_layers)), np.float32)
+    _lib.check(lib.pr_det_fold_pack(int(n_layers), weights.ctypes.data_as(C.c_void_p), weights.size, float(bn_eps),
+                                    out.ctypes.data_as(C.c_void_p), out.size), "pr_det_fold_pack")
+    return out
+
+
+def letterbox_geometry(H, W, S_h, S_w):
+    """(h', w', ox, oy) of the header's integer rule."""
+    if W * S_h >= H * S_w:
+        w2, h2 = S_w, min(S_h, max(1, (2 * H * S_w + W) // (2 * W)))
+    else:
+        h2, w2 = S_h, min(S_w, max(1, (2 * W * S_h + H) // (2 * H)))
+    return h2, w2, (S_w - w2) // 2, (S_h - h2) // 2
+
+
+class Detector:
+    """weights: a darknet file's path or its float body.  Every method works on CUDA tensors of `device`, asynchronously on
+    the current stream; detect() alone copies to the host."""
+
+    def __init__(self, weights, img_size=(416, 416), device=None, max_batch=8, bn_eps=1e-5, max_det=100):
+        import torch
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PoseRiskHipError("Detector: the detector runs on the GPU only (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        body = load_darknet(weights) if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__") else weights
+        body = np.ascontiguousarray(body, np.float32)
+        self.S_h, self.S_w = (int(img_size), int(img_size)) if np.isscalar(img_size) else (int(img_size[0]), int(img_size[1]))
+        self.max_batch, self.max_det = int(max_batch), int(max_det)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            lib = _lib.declare_stream(self.device)
+            _lib.check(lib.pr_det_create(self.device.index, body.ctypes.data_as(C.c_void_p), body.size, self.S_h, self.S_w,
+                                         self.max_batch, float(bn_eps), C.byref(self._h)), "pr_det_create")
+        self.grids = [(self.S_h // s, self.S_w // s) for s in STRIDES]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            import torch
+            with torch.cuda.device(self.device):
+                torch.cuda.synchronize(self.device)
+                _lib.check(_lib.declare_stream(self.device).pr_det_destroy(self._h), "pr_det_destroy")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _check(self, t, dtype, what):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor on {self.device}")
+        return t
+
+    def _out(self, out, shape, dtype, what):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(out.shape)}")
+        return self._check(out, dtype, what)
+
+    def layer_shape(self, layer):
+        gh, gw, ch = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.load().pr_det_grid(self._h, int(layer), C.byref(gh), C.byref(gw), C.byref(ch)), "pr_det_grid")
+        return gh.value, gw.value, ch.value
+
+    def letterbox(self, frames, bgr=False, out=None):
+        """u8[B,H,W,3] -> f32[B,S_h,S_w,4] (R, G, B, 0)."""
+        import torch
+        self._check(frames, torch.uint8, "frames")
+        B, H, W, _ = frames.shape
+        out = self._out(out, (B, self.S_h, self.S_w, 4), torch.float32, "out")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pr_det_letterbox(self._h, frames.data_ptr(), B, H, W, int(bool(bgr)), out.data_ptr(), self._stream()),
+                       "pr_det_letterbox")
+        return out
+
+    def network(self, x, out=None):
+        """f32[B,S_h,S_w,4] -> the three head tensors f32[B,gh,gw,255] (strides 32, 16, 8)."""
+        import torch
+        self._check(x, torch.float32, "x")
+        B = x.shape[0]
+        outs = [self._out(None if out is None else out[i], (B, gh, gw, 255), torch.float32, f"out[{i}]") for i, (gh, gw) in enumerate(self.grids)]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pr_det_network(self._h, x.data_ptr(), B, outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                                                  self._stream()), "pr_det_network")
+        return outs
+
+    def network_until(self, x, layer, out=None):
+        import torch
+        self._check(x, torch.float32, "x")
+        B = x.shape[0]
+        out = self._out(out, (B,) + self.layer_shape(layer), torch.float32, "out")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pr_det_network_until(self._h, x.data_ptr(), B, int(layer), out.data_ptr(), self._stream()),
+                       "pr_det_network_until")
+        return out
+
+    def _post_outs(self, B, max_det, out):
+        import torch
+        out = out or {}
+        return (self._out(out.get("boxes"), (B, max_det, 4), torch.float32, "boxes"), self._out(out.get("scores"), (B, max_det), torch.float32, "scores"),
+                self._out(out.get("count"), (B,), torch.int32, "count"), self._out(out.get("status"), (B,), torch.int32, "status"))
+
+    def postprocess(self, heads, conf_thres=0.1, nms_thres=0.4, max_det=None, out=None):
+        """The three head tensors -> (boxes f32[B,max_det,4] in letterbox pixels, scores f32[B,max_det], count i32[B], status i32[B])."""
+        import torch
+        for i, t in enumerate(heads):
+            self._check(t, torch.float32, f"heads[{i}]")
+        B = heads[0].shape[0]
+        max_det = self.max_det if max_det is None else int(max_det)
+        boxes, scores, count, status = self._post_outs(B, max_det, out)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pr_det_postprocess(self._h, heads[0].data_ptr(), heads[1].data_ptr(), heads[2].data_ptr(), B,
+                                                      float(conf_thres), float(nms_thres), max_det, boxes.data_ptr(), scores.data_ptr(),
+                                                      count.data_ptr(), status.data_ptr(), self._stream()), "pr_det_postprocess")
+        return boxes, scores, count, status
+
+    def detect_raw(self, frames, bgr=False, conf_thres=0.1, nms_thres=0.4, max_det=None, out=None):
+        """u8[B,H,W,3], B <= max_batch -> postprocess' outputs with the boxes in FRAME pixels."""
+        import torch
+        self._check(frames, torch.uint8, "frames")
+        B, H, W, _ = frames.shape
+        max_det = self.max_det if max_det is None else int(max_det)
+        boxes, scores, count, status = self._post_outs(B, max_det, out)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pr_det_detect(self._h, frames.data_ptr(), B, H, W, int(bool(bgr)), float(conf_thres), float(nms_thres),
+                                                 max_det, boxes.data_ptr(), scores.data_ptr(), count.data_ptr(), status.data_ptr(),
+                                                 self._stream()), "pr_det_detect")
+        return boxes, scores, count, status
+
+    def detect(self, frames, bgr=False, conf_thres=0.1, nms_thres=0.4):
+        """u8[F,H,W,3] (a CUDA tensor, or numpy: uploaded) -> a list of F arrays f32[n,5] (x1, y1, x2, y2, score) in frame pixels,
+        best score first; runs in chunks of max_batch.  A frame with more than MAX_CAND candidates (the best MAX_CAND took
+        part) or more than max_det boxes is reported with a warning naming it, never cut silently."""
+        import torch
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        frames = frames.to(self.device).contiguous()
+        results = []
+        for lo in range(0, frames.shape[0], self.max_batch):
+            part = frames[lo:lo + self.max_batch]
+            boxes, scores, count, status = (t.cpu().numpy() for t in self.detect_raw(part, bgr, conf_thres, nms_thres))
+            for i in range(part.shape[0]):
+                if status[i]:
+                    warnings.warn(f"detector: frame {lo + i}: " + ("more than %d candidates above conf_thres %g" % (MAX_CAND, conf_thres)
+                                  if status[i] & STATUS_CAND_OVERFLOW else "more than %d boxes after NMS" % self.max_det), RuntimeWarning)
+                n = int(count[i])
+                results.append(np.concatenate([boxes[i, :n], scores[i, :n, None]], axis=1).astype(np.float32))
+        return results

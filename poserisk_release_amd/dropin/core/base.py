@@ -627,13 +627,15 @@ class Predictor:
                                    frame=self.debug_frame)
 
     # ---- main/run.py:31  predictor(args.input, args.info, args.output) -----------------------------------
-    @staticmethod
-    def _folder_sidecars(folder):
+    def _folder_sidecars(self, folder, frames=None):
         """What every frame folder carries beside its frames -> (fps, tracking): `fps.txt` (optional, 30.0 without it) and
-        `tracking.pkl`."""
+        `tracking.pkl`; without that file and with cfg.TRACKER.weights set, the built-in tracker's dict for `frames`."""
         import pickle
-        with open(osp.join(folder, 'tracking.pkl'), 'rb') as f:
-            tracking = pickle.load(f)
+        if frames is not None and self._tracker_weights() and not osp.isfile(osp.join(folder, 'tracking.pkl')):
+            tracking = self.track_frames(frames, bgr=False)
+        else:
+            with open(osp.join(folder, 'tracking.pkl'), 'rb') as f:
+                tracking = pickle.load(f)
         fps_file = osp.join(folder, 'fps.txt')
         fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
         return fps, tracking
@@ -671,14 +673,17 @@ class Predictor:
              is started as a fresh child process (shlex.split, no shell), its standard output is read as YUV4MPEG2 exactly as
              3b reads a file, and it is always reaped.  A child that exits non-zero or writes no stream header raises
              RuntimeError naming the command, the exit status and the tail of its standard error;
+          With cfg.TRACKER.weights set (off, '', by default) the tracking of cases 3, 3b and 3c comes from this package's own
+          detector and tracker (`track_frames`: YOLOv3 on the GPU + SORT) after the dict given and the sidecar and before
+          multi_person_tracker, and the folders of cases 1, 2 and 2b are accepted without `tracking.pkl`;
           4. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
              frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
              written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
              the same JPEG-decoded pixels as the reference's CropDataset."""
         if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'frames.npy')):
             frames = np.load(osp.join(input_path, 'frames.npy'))
-            return (frames, False) + self._folder_sidecars(input_path)
-        if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'tracking.pkl')):
+            return (frames, False) + self._folder_sidecars(input_path, frames)
+        if osp.isdir(input_path) and (osp.isfile(osp.join(input_path, 'tracking.pkl')) or self._tracker_weights()):
             from poserisk_release_amd import jpeg, png
             names = png.list_frames(input_path)
             if names and not any(n.lower().endswith(('.jpg', '.jpeg')) for n in os.listdir(input_path)):
@@ -688,7 +693,7 @@ class Predictor:
                 if bad:
                     raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
                                        + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
-                return (frames, False) + self._folder_sidecars(input_path)
+                return (frames, False) + self._folder_sidecars(input_path, frames)
             names = jpeg.list_frames(input_path)
             if names:
                 paths = [osp.join(input_path, n) for n in names]
@@ -699,7 +704,7 @@ class Predictor:
                 if bad:
                     raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
                                        + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
-                return (frames, False) + self._folder_sidecars(input_path)
+                return (frames, False) + self._folder_sidecars(input_path, frames)
         not_mjpeg = None
         if osp.isfile(input_path):
             from poserisk_release_amd import mjpeg
@@ -813,9 +818,34 @@ class Predictor:
                                + (f"; its standard error ends: {tail}" if tail else ''))
         return return_value
 
+    # ---- the built-in tracker (cfg.TRACKER; off while its weights are '') --------------------------------------------------
+    @staticmethod
+    def _tracker_weights():
+        return str(cfg.get('TRACKER', {}).get('weights', '') or '')
+
+    def track_frames(self, frames, bgr=False):
+        """frames u8[F,H,W,3] (device tensor or numpy) -> multi_person_tracker's dict, by this package's own detector
+        (poserisk_release_amd.detector, YOLOv3 on the GPU) and tracker (poserisk_release_amd.sort).  No person found anywhere
+        raises RuntimeError naming the threshold used."""
+        from poserisk_release_amd import detector, sort
+        t = cfg.TRACKER
+        det = getattr(self, '_detector', None)
+        key = (self._tracker_weights(), tuple(t.img_size), int(t.batch))
+        if det is None or getattr(self, '_detector_key', None) != key:
+            det = detector.Detector(key[0], img_size=key[1], device=self.device, max_batch=key[2])
+            self._detector, self._detector_key = det, key
+        dets = det.detect(frames, bgr=bgr, conf_thres=float(t.conf_thres), nms_thres=float(t.nms_thres))
+        tracking = sort.track_frames(dets, max_age=int(t.max_age), min_hits=int(t.min_hits), iou_thres=float(t.iou_thres))
+        if not tracking:
+            raise RuntimeError(f"the built-in tracker found no person track in {len(dets)} frames ({sum(len(d) for d in dets)} "
+                               f"detections at conf_thres {float(t.conf_thres):g}, nms_thres {float(t.nms_thres):g}; a track needs "
+                               f"{int(t.min_hits)} consecutive hits)")
+        return tracking
+
     def _tracking_for(self, frames, fps, input_path, output_path, tracking_results=None):
         """The second half of cases 3, 3b and 3c: the tracking of a video file's decoded, downscaled `frames`, in this order: the
-        `tracking_results` given, `<stem>.tracking.pkl`, multi_person_tracker where importable, else the named error."""
+        `tracking_results` given, `<stem>.tracking.pkl`, the built-in tracker where cfg.TRACKER.weights names a weight file,
+        multi_person_tracker where importable, else the named error."""
         import pickle
         import shutil
         from poserisk_release_amd import frontend, jpeg
@@ -825,6 +855,8 @@ class Predictor:
         if osp.isfile(sidecar):
             with open(sidecar, 'rb') as f:
                 return frames, False, fps, pickle.load(f)
+        if self._tracker_weights():
+            return frames, False, fps, self.track_frames(frames, bgr=False)
         try:
             from multi_person_tracker import MPT
         except ImportError as e:

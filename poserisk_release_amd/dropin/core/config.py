@@ -53,6 +53,13 @@ absent from the reference and all optional:
                               -pix_fmt yuv420p -`: a regular file that is neither a Motion-JPEG AVI nor a YUV4MPEG2 file is decoded
                               by running it as a child process (no shell) and reading its standard output as YUV4MPEG2
                               (args.video_decoder overrides it)
+    cfg.TRACKER               the built-in person detector and tracker (poserisk_release_amd.detector: YOLOv3 on the GPU,
+                              poserisk_release_amd.sort: SORT on the host).  All of it is inert while `weights` is '':
+                              weights '' | the path of a darknet yolov3.weights file; img_size (416, 416) = (rows, columns) of the
+                              network input, multiples of 32 ((256, 416) suits 800 x 450 frames); conf_thres 0.1 (the reference's
+                              detection_threshold); nms_thres 0.4; max_age 1, min_hits 3, iou_thres 0.3 (SORT); batch 8 frames a call.
+                              With weights set, a video file's tracking comes from it after the tracking given and the sidecar
+                              and before multi_person_tracker, and a frame folder without tracking.pkl is accepted
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -123,6 +130,8 @@ def _defaults(root):
                  'precision': 'fp32', 'conv_form': 'default'},
         'AUG': {'flip': False, 'rotate_factor': 0},
         'TEST': {},
+        'TRACKER': {'weights': '', 'img_size': (416, 416), 'conf_thres': 0.1, 'nms_thres': 0.4, 'max_age': 1, 'min_hits': 3,
+                    'iou_thres': 0.3, 'batch': 8},
     }
 
 

@@ -211,6 +211,28 @@ def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_by
     return int(frames.shape[0]), (int(frames.shape[2]), int(frames.shape[1])), fps
 
 
+def track(path, weights, out=None, device=None, img_size=(416, 416), conf_thres=0.1, nms_thres=0.4, max_age=1, min_hits=3, iou_thres=0.3,
+          batch=8, max_w=800, max_h=450, matrix="601"):
+    """A Motion-JPEG AVI or a YUV4MPEG2 stream (read_video's inputs) -> `out` (default `<stem>.tracking.pkl` beside the video):
+    multi_person_tracker's dict, boxes in the downscaled frames' coordinates, made by this package's own detector (YOLOv3 on the
+    GPU, `weights` = a darknet yolov3.weights file) and SORT.  Returns (out, the dict, number of frames)."""
+    import pickle
+    from . import detector, sort
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    frames, _ = read_video(path, device, max_w=max_w, max_h=max_h, progressive=True, matrix=matrix)
+    det = detector.Detector(weights, img_size=img_size, device=device, max_batch=batch)
+    dets = det.detect(frames, conf_thres=conf_thres, nms_thres=nms_thres)
+    det.close()
+    tracking = sort.track_frames(dets, max_age=max_age, min_hits=min_hits, iou_thres=iou_thres)
+    if not tracking:
+        raise RuntimeError(f"{path!r}: no person track in {len(dets)} frames ({sum(len(d) for d in dets)} detections at conf_thres "
+                           f"{conf_thres:g}, nms_thres {nms_thres:g}; a track needs {min_hits} consecutive hits)")
+    out = out or os.path.splitext(os.fspath(path))[0] + ".tracking.pkl"
+    with open(out, "wb") as f:
+        pickle.dump(tracking, f)
+    return out, tracking, len(dets)
+
+
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m poserisk_release_amd.frontend")
@@ -224,7 +246,21 @@ def main(argv=None):
     p.add_argument("--gpu", type=int, default=0)
     p.add_argument("--matrix", choices=("601", "709", "auto"), default="601",
                    help="the colour matrix of a YUV4MPEG2 input (auto: 709 above 576 rows); a Motion-JPEG AVI ignores it")
+    t = sub.add_parser("track", help="Motion-JPEG AVI or .y4m file -> <stem>.tracking.pkl by the built-in detector (YOLOv3) and SORT")
+    t.add_argument("video")
+    t.add_argument("out", nargs="?", default=None)
+    t.add_argument("--weights", required=True, help="a darknet yolov3.weights file")
+    t.add_argument("--img-size", type=int, nargs=2, default=(416, 416), metavar=("ROWS", "COLUMNS"))
+    t.add_argument("--conf-thres", type=float, default=0.1)
+    t.add_argument("--nms-thres", type=float, default=0.4)
+    t.add_argument("--batch", type=int, default=8)
+    t.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.command == "track":
+        out, tracking, n = track(a.video, a.weights, a.out, device=torch.device("cuda", a.gpu), img_size=tuple(a.img_size),
+                                 conf_thres=a.conf_thres, nms_thres=a.nms_thres, batch=a.batch)
+        print(f"{out}: {len(tracking)} tracks over {n} frames")
+        return
     n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h,
                              progressive=True, matrix=a.matrix)
     print(f"{a.out_dir}: {n} frames of {w} x {h} at {fps:g} frames/s; add tracking.pkl (multi_person_tracker's dict) to score it")

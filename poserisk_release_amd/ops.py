@@ -140,6 +140,21 @@ def conv2d_nhwc(x, w_oihw, bias=None, residual=None, stride=1, pad=0, relu=False
         stride, pad, int(relu), tile_cfg, bf, repeats, ms, _stream(x.device)), "pr_conv2d_nhwc", y, repeats)
 
 
+def det_conv_nhwc(x, packed, cout, ksize, stride=1, leaky=True, residual=None, out=None):
+    """The detector's convolution alone (pr_det_conv_nhwc, csrc/det_conv.hip): x f32[B,H,W,Cin] CUDA, `packed` ONE convolution in
+    pr_det_fold_pack's layout on the device (bias[cout_pad], then w[cout_pad][kpad]) -> f32[B,Ho,Wo,cout] = leaky(conv + b)
+    [+ residual]; padding ksize // 2.  Asynchronous; allocates nothing with `out` given."""
+    _need_cuda(x, "det_conv_nhwc")
+    B, H, W, Cin = x.shape
+    pad = ksize // 2
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    y = _out(out, (B, Ho, Wo, cout), torch.float32, x.device)
+    _lib.check(_lib.load().pr_det_conv_nhwc(x.data_ptr(), packed.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                            y.data_ptr(), B, H, W, Cin, int(cout), int(ksize), int(stride), int(bool(leaky)),
+                                            _stream(x.device)), "pr_det_conv_nhwc")
+    return y
+
+
 def conv1x1_dual_nhwc(x1, w1, x2, w2, bias=None, stride2=1, relu=False, tile_cfg=-1, precision="fp32", out=None):
     """relu(x1*W1 + x2[::stride2, ::stride2]*W2 + bias) as one dual-source GEMM (a first Bottleneck's conv3 with its
     downsample branch summed in).  x1 [B,Ho,Wo,C1], x2 [B,H2,W2,C2] CUDA, w1 [Cout,C1], w2 [Cout,C2] numpy."""

@@ -165,6 +165,34 @@ def closed_body(V=6890, seed=7):
     return v.astype(np.float32), f
 
 
+def yolo_weights(seed=11):
+    """The float body of a darknet YOLOv3 weight file, f32[62001757], whose outputs stay sane: the trained file is a download
+    (multi_person_tracker fetches it), absent here.  Plain He weights let the 23 residual sums grow the activations to
+    rms ~ 70 and |t| ~ 150 at the heads; these choices keep the heads near rms 2 with some person candidates:
+    He-normal weights over the fan-out (as hmr_state_dict), with gain 0.3 on the 3x3 convolution of each residual block;
+    BatchNorm gamma = 1, beta ~ N(0, 0.1^2), mean ~ N(0, 0.1^2), var ~ U(0.5, 1.5); head weights N(0, 0.6^2 / fan_in), head
+    bias 0 for the box, -3 for the objectness, +3 for class 0 and -1 for the other classes (class 0 has to beat 79 others for
+    a person candidate to exist: about a dozen a frame at 64 x 96 with conf_thres 0.1)."""
+    from .detector import CONV, SHORTCUT, yolo_layers
+    rng = np.random.Generator(np.random.PCG64(seed))
+    layers = yolo_layers()
+    parts = []
+    for i, l in enumerate(layers):
+        if l["type"] != CONV:
+            continue
+        fan_in, fan_out = l["cin"] * l["ksize"] ** 2, l["cout"] * l["ksize"] ** 2
+        shape = (l["cout"], l["cin"], l["ksize"], l["ksize"])
+        if l["bn"]:
+            gain = 0.3 if i + 1 < len(layers) and layers[i + 1]["type"] == SHORTCUT else 1.0
+            parts += [rng.normal(0.0, 0.1, l["cout"]), np.ones(l["cout"]), rng.normal(0.0, 0.1, l["cout"]), rng.uniform(0.5, 1.5, l["cout"])]
+            parts.append(rng.standard_normal(shape, dtype=np.float32) * np.float32(gain * np.sqrt(2.0 / fan_out)))
+        else:
+            bias = np.zeros((3, 85))
+            bias[:, 4], bias[:, 5], bias[:, 6:] = -3.0, 3.0, -1.0
+            parts += [bias, rng.standard_normal(shape, dtype=np.float32) * np.float32(0.6 / np.sqrt(fan_in))]
+    return np.concatenate([np.asarray(p, np.float32).ravel() for p in parts])
+
+
 DEFAULT_INFO = {  # main/default_information.json
     "REBA": {"Legs_bilateral_weight_bearing/walking": 0, "Sitting": 0, "Load/Force Score": 0,
              "Arm_supported_leaning_L": 0, "Arm_supported_leaning_R": 0, "Coupling": 0, "Activity_Score": 0},

@@ -1,6 +1,7 @@
 """Tracker hand-off: what `DataProcessing.__call__` does with multi_person_tracker's output
 before the crops are cut (lib/core/base.py:47-74, lib/utils/funcs_utils.py:55-64).  Pure host logic on small
-arrays; MPT itself (YOLOv3 + SORT) stays outside this package.
+arrays.  MPT itself stays outside this package; detector.py (YOLOv3 on the GPU) and sort.py (SORT) are this package's own
+stand-in for it, opt-in through cfg.TRACKER, and return the same dict.
 
 tracking_results: {person_id: {'bbox': f32[n,4] (cx,cy,w,h), 'frames': int[n]}}  (MPT output_format='dict').
 """
