@@ -829,7 +829,7 @@ int pr_jpeg_decode_scans(const pr_jpeg_scans_args* args, void* workspace, size_t
 /* ------------------------------------------------------------------------------------ */
 /* j2  u8[F,H,W,3] on the device -> baseline JPEG files, byte-exact with libjpeg          */
 /* replaces: cv2.VideoWriter / one PNG per frame behind the composed canvases             */
-/*           (write_gpu_video, _mesh_writer): only compressed bytes leave the device      */
+/*           (write_gpu_video, sinks.py): only compressed bytes leave the device          */
 /* ------------------------------------------------------------------------------------ */
 /* The inverse of j1.  The host half (pr_jpeg_encode_plan, csrc/jpeg_host.cc, no device) derives the tables and writes the
  * header bytes; the device half (pr_jpeg_encode, csrc/jpeg_enc.hip) does everything else.  No ABI bump: functions were added.
@@ -1095,7 +1095,7 @@ int pr_png_decode(const pr_png_args* args, void* workspace, size_t workspace_byt
 /* ------------------------------------------------------------------------------------ */
 /* j5  u8[F,H,W,3] on the device -> PNG files: filters, run-length deflate, dynamic codes  */
 /* replaces: the raw download + Pillow save of one PNG per frame behind the composed       */
-/*           canvases (write_gpu_video, _mesh_writer): only compressed bytes leave         */
+/*           canvases (write_gpu_video, sinks.py): only compressed bytes leave             */
 /* ------------------------------------------------------------------------------------ */
 /* The lossless counterpart of j2 and the inverse of j4.  The host half (pr_png_encode_plan, csrc/png_enc_host.cc, no device)
  * writes the fixed bytes and the CRC power table; the device half (pr_png_encode, csrc/png_enc.hip over

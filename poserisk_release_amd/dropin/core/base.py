@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from poserisk_release_amd import pipeline as pl
-from poserisk_release_amd import synth
+from poserisk_release_amd import sinks, synth
 from poserisk_release_amd.hmr import hmr
 
 from core.config import cfg
@@ -110,6 +110,20 @@ def default_information():
     return synth.DEFAULT_INFO
 
 
+def _knob(args, name, key, default):
+    """`args.<name>` when the caller's namespace has one that is not None, else cfg.DATASET.<key>, else (absent or empty) `default`."""
+    knob = getattr(args, name, None)
+    return knob if knob is not None else cfg.DATASET.get(key, default) or default
+
+
+def _jpeg_options():                                   # what every jpeg.decode_files call of the front end takes from cfg.DATASET
+    return dict(entropy=cfg.DATASET.get('jpeg_entropy', 'auto'), progressive=bool(cfg.DATASET.get('jpeg_progressive', True)))
+
+
+def _front_limits():                                   # the front end's downscale rule (frontend.target_size) from cfg.DATASET
+    return dict(max_w=cfg.DATASET.get('front_max_w', 800), max_h=cfg.DATASET.get('front_max_h', 450))
+
+
 class Predictor:
     def __init__(self, args, spin_model=None, smpl_model=None, batch_size=None, spin_checkpoint=None,
                  smpl_mean_params=None):
@@ -137,28 +151,23 @@ class Predictor:
         self.debugging = debug
         self.debug_frame = getattr(args, 'debug_frame', -1)
         # the mesh overlay (render_overlay): args.render_mesh, else cfg.DATASET.render_mesh (False; $POSERISK_CFG can set it)
-        knob = getattr(args, 'render_mesh', None)
-        self.render_mesh = bool(knob if knob is not None else cfg.DATASET.get('render_mesh', False))
+        self.render_mesh = bool(_knob(args, 'render_mesh', 'render_mesh', False))
         # the annotated score video composed on the GPU (write_gpu_video): args.gpu_video, else cfg.DATASET.gpu_video (False)
-        knob = getattr(args, 'gpu_video', None)
-        self.gpu_video = bool(knob if knob is not None else cfg.DATASET.get('gpu_video', False))
-        # how write_gpu_video and the mesh writer store their frames: args.video_codec, else cfg.DATASET.gpu_video_codec.  ''
-        # (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded on the GPU
-        # (jpeg.encode_frames) into <TITLE>_video.avi / <TITLE>_mesh.avi (mjpeg.AviWriter), with or without cv2; 'png' = lossless,
-        # encoded on the GPU (png.encode_frames) into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2;
-        # 'y4m' = converted to Y'CbCr on the GPU (y4m.encode_frames) into <TITLE>_video.y4m / <TITLE>_mesh.y4m, or, with the
-        # video_encoder knob, piped to that command, which writes <TITLE>_video.mp4 / <TITLE>_mesh.mp4 in the codec it names
-        knob = getattr(args, 'video_codec', None)
-        self.gpu_video_codec = str(knob if knob is not None else cfg.DATASET.get('gpu_video_codec', '') or '')
-        if self.gpu_video_codec not in ('', 'mjpeg', 'png', 'y4m'):
+        self.gpu_video = bool(_knob(args, 'gpu_video', 'gpu_video', False))
+        # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
+        # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
+        # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
+        # into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2; 'y4m' = converted to Y'CbCr on the GPU into
+        # <TITLE>_video.y4m / <TITLE>_mesh.y4m, or, with the video_encoder knob, piped to that command, which writes
+        # <TITLE>_video.mp4 / <TITLE>_mesh.mp4 in the codec it names
+        self.gpu_video_codec = str(_knob(args, 'video_codec', 'gpu_video_codec', ''))
+        if self.gpu_video_codec not in sinks.CODECS:
             raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg', "
                              "'png' or 'y4m' (any other codec: 'y4m' with the video_encoder knob)")
         # args.video_encoder, else cfg.DATASET.video_encoder ('' = off): a command line with {output} that reads YUV4MPEG2 on its
         # standard input; it implies the 'y4m' codec.  video_encoder_ext ('.mp4') ends the file's name, video_chroma the layout
-        knob = getattr(args, 'video_encoder', None)
-        self.video_encoder = str(knob if knob is not None else cfg.DATASET.get('video_encoder', '') or '')
-        knob = getattr(args, 'video_encoder_ext', None)
-        self.video_encoder_ext = str(knob if knob is not None else cfg.DATASET.get('video_encoder_ext', '.mp4') or '.mp4')
+        self.video_encoder = str(_knob(args, 'video_encoder', 'video_encoder', ''))
+        self.video_encoder_ext = str(_knob(args, 'video_encoder_ext', 'video_encoder_ext', '.mp4'))
         self.video_chroma = str(cfg.DATASET.get('video_chroma', '420mpeg2') or '420mpeg2')
         if self.video_encoder:
             if '{output}' not in self.video_encoder:
@@ -170,8 +179,7 @@ class Predictor:
         self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
         # load_front_end's case 3c: args.video_decoder, else cfg.DATASET.video_decoder ('' = off): a command line with {input}
         # whose standard output is read as YUV4MPEG2
-        knob = getattr(args, 'video_decoder', None)
-        self.video_decoder = str(knob if knob is not None else cfg.DATASET.get('video_decoder', '') or '')
+        self.video_decoder = str(_knob(args, 'video_decoder', 'video_decoder', ''))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
             self.debug_joints = None
@@ -188,12 +196,8 @@ class Predictor:
         and no process group yet, this rank joins one over RCCL (`nccl`) on the GPU $LOCAL_RANK names -- main/run.py:26
         narrows CUDA_VISIBLE_DEVICES to --gpu first, so `--gpu 0,1,...` has to list a GPU per rank.  A mismatch between
         what was asked for and what the launcher started is an error, never a silent single-GPU run."""
-        import os
         import torch.distributed as dist
-        want = getattr(args, 'world_size', None)
-        if want is None:
-            want = cfg.DATASET.get('hip_world_size', 0)
-        want = int(want or 0)
+        want = int(_knob(args, 'world_size', 'hip_world_size', 0))
         launched = int(os.environ.get('WORLD_SIZE', '1'))
         if dist.is_available() and dist.is_initialized():
             have = dist.get_world_size()
@@ -411,126 +415,18 @@ class Predictor:
                                  face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
             yield fidx[i:j], img
 
-    def _mjpeg_writer(self, path, width, height, fps, bgr):
-        """-> (write(images u8[b,H,W,3] CUDA), close() -> path): the images encoded to baseline JPEG on the GPU at
-        gpu_video_quality (4:2:0, a restart marker per MCU row) and stored as Motion-JPEG in `path`: only the files' bytes
-        leave the device.  A frame that overflows its default slot is encoded again with the slot no file exceeds.  close()
-        returns `path`, the first file; past 1 GiB the frames continue in <name>.001.avi, ... beside it (mjpeg.AviWriter)."""
-        from poserisk_release_amd import jpeg, mjpeg
-        avi = mjpeg.AviWriter(path, width, height, fps)
-
-        def write(images):
-            images = images.contiguous()
-            buf, nbytes, status = jpeg.encode_frames(images, quality=self.gpu_video_quality, bgr=bgr)
-            files = jpeg.download_files(buf, nbytes)
-            for i in np.nonzero(status.cpu().numpy())[0]:
-                cap = jpeg.encode_bound(height, width)
-                buf1, nbytes1, status1 = jpeg.encode_frames(images[i:i + 1], quality=self.gpu_video_quality, bgr=bgr, capacity=cap)
-                if int(status1[0]):
-                    raise RuntimeError(f"jpeg.encode_frames: status {int(status1[0])} for a frame with the largest slot")
-                files[i] = jpeg.download_files(buf1, nbytes1)[0]
-            for data in files:
-                avi.write(data)
-        return write, lambda: (avi.close(), path)[1]
-
-    def _png_writer(self, path, bgr):
-        """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): the images encoded to PNG on the GPU (adaptive
-        filters, run-length deflate; png.encode_frames) and written as `path`/%09d.png by frame number: only the files' bytes
-        leave the device.  A slot holds half the raw size, which rendered canvases stay far below; a frame that overflows it
-        (noise does) is encoded again alone with the slot no file exceeds."""
-        import os
-        from poserisk_release_amd import png
-        os.makedirs(path, exist_ok=True)
-
-        def write(numbers, images):
-            images = images.contiguous()
-            H, W = int(images.shape[1]), int(images.shape[2])
-            buf, nbytes, status = png.encode_frames(images, bgr=bgr, capacity=min(png.encode_bound(H, W), 4096 + H * W * 3 // 2))
-            files = png.download_files(buf, nbytes)
-            for i in np.nonzero(status.cpu().numpy())[0]:
-                buf1, nbytes1, status1 = png.encode_frames(images[i:i + 1], bgr=bgr, capacity=png.encode_bound(H, W))
-                if int(status1[0]):
-                    raise RuntimeError(f"png.encode_frames: status {int(status1[0])} for a frame with the largest slot")
-                files[i] = png.download_files(buf1, nbytes1)[0]
-            for f, data in zip(numbers, files):
-                with open(osp.join(path, '{0:09d}.png'.format(int(f))), 'wb') as fh:
-                    fh.write(data)
-        return write, lambda: path
-
-    def _y4m_writer(self, stem, width, height, fps, bgr):
-        """-> (write(images u8[b,H,W,3] CUDA), close() -> path): the images converted to Y'CbCr on the GPU (y4m.encode_frames:
-        cfg.DATASET.yuv_matrix, limited range, video_chroma, odd sides of a subsampled layout padded to even) and written as a
-        YUV4MPEG2 stream to `stem`.y4m -- or, with the video_encoder knob, to that command's standard input, {output} replaced
-        by `stem` + video_encoder_ext.  Never a shell; close() raises RuntimeError naming a failed encoder's status."""
-        import shlex
-        from poserisk_release_amd import y4m
-        matrix = str(cfg.DATASET.get('yuv_matrix', '601'))
-        if matrix == 'auto':
-            matrix = '709' if height > 576 else '601'
-        how = dict(width=width, height=height, fps=fps, chroma=self.video_chroma, matrix=matrix, full_range=False, bgr=bgr,
-                   pad_even=self.video_chroma in ('420jpeg', '420mpeg2', '422'))
-        if self.video_encoder:
-            path = stem + self.video_encoder_ext
-            writer = y4m.Writer(command=[a.replace('{output}', path) for a in shlex.split(self.video_encoder)], **how)
-        else:
-            path = stem + '.y4m'
-            writer = y4m.Writer(path, **how)
-
-        def close(failed=False):
-            if failed:
-                writer.abort()                              # reaps the child, raises nothing over the caller's error
-            else:
-                writer.close()
-            return path
-        return writer.put, close
-
-    def _mesh_writer(self, frames, output_path, title, bgr, fps):
-        """-> (write(frame numbers, images u8[b,H,W,3] CUDA), close() -> path): <output>/<TITLE>_mesh.mp4 where cv2 is importable,
-        else <output>/<TITLE>_mesh/%09d.png (frame number); with gpu_video_codec 'mjpeg' <output>/<TITLE>_mesh.avi either way,
-        with 'png' <output>/<TITLE>_mesh/%09d.png encoded on the GPU either way."""
-        import os
-        if self.gpu_video_codec == 'png':
-            return self._png_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh"), bgr)
-        if self.gpu_video_codec == 'mjpeg':
-            put, close = self._mjpeg_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh.avi"),
-                                            int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
-            return (lambda fr, img: put(img)), close
-        if self.gpu_video_codec == 'y4m':
-            put, close = self._y4m_writer(osp.join(output_path, f"{title if title is not None else 'MESH'}_mesh"),
-                                          int(frames.shape[2]), int(frames.shape[1]), fps, bgr)
-            return (lambda fr, img: put(img)), close
-        try:
-            import cv2
-        except ImportError:
-            cv2 = None
-        name = f"{title if title is not None else 'MESH'}_mesh"
-        if cv2 is not None:
-            path = osp.join(output_path, name + '.mp4')
-            H, W = int(frames.shape[1]), int(frames.shape[2])
-            vw = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*'mp4v'), float(fps), (W, H))
-
-            def write(fr, img):
-                for im in img.cpu().numpy():
-                    vw.write(im if bgr else im[..., ::-1])
-            return write, lambda: (vw.release(), path)[1]
-        path = osp.join(output_path, name)
-        os.makedirs(path, exist_ok=True)
-
-        def write(fr, img):
-            for f, im in zip(fr, img.cpu().numpy()):
-                _save_png(osp.join(path, '{0:09d}.png'.format(int(f))), im[..., ::-1] if bgr else im)
-        return write, lambda: path
+    def _open_sink(self, output_path, name, frame_size, fps, bgr):
+        """<output>/<name>: the sink of the gpu_video_codec knob (poserisk_release_amd/sinks.py) for frames of (height, width) =
+        `frame_size`, with this Predictor's other knobs."""
+        return sinks.open_sink(self.gpu_video_codec, osp.join(output_path, name), int(frame_size[1]), int(frame_size[0]), fps, bgr,
+                               quality=self.gpu_video_quality, chroma=self.video_chroma, encoder=self.video_encoder,
+                               encoder_ext=self.video_encoder_ext, matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
 
     def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
         """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
         frame.  Returns the path written."""
-        write, close = self._mesh_writer(frames, output_path, title, bgr, fps)
-        try:
-            for fr, img in self.render_overlay(out, frames, title, bgr):
-                write(fr, img)
-        finally:
-            path = close()
-        return path
+        sink = self._open_sink(output_path, f"{title if title is not None else 'MESH'}_mesh", frames.shape[1:3], fps, bgr)
+        return sinks.write_all(sink, self.render_overlay(out, frames, title, bgr))
 
     # ---- base.py:284-327 on the GPU (the gpu_video knob) ---------------------------------------------------------
     def write_gpu_video(self, out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
@@ -539,11 +435,10 @@ class Predictor:
         cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame; with
         gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there; with
         'png' <output>/<TITLE>_video/%09d.png, encoded on the GPU (lossless), whether or not cv2 is there; with 'y4m'
-        <output>/<TITLE>_video.y4m, or through the video_encoder knob's command <TITLE>_video.mp4 (_y4m_writer).  With
+        <output>/<TITLE>_video.y4m, or through the video_encoder knob's command <TITLE>_video.mp4 (sinks.Y4mSink).  With
         the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
         parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
         that the mesh output is written from the same rendering.  Returns the path written."""
-        import os
         from poserisk_release_amd import video
         frames = torch.as_tensor(frames)
         if frames.device.type != 'cuda':
@@ -567,51 +462,13 @@ class Predictor:
                 if mesh_sink is not None:
                     mesh_sink(numbers, images)
                 return numbers, images
-        batches = video.annotated_frames(frames, draw, self.batch_size, overlay=overlay)
-        if self.gpu_video_codec == 'mjpeg':
-            put, close = self._mjpeg_writer(osp.join(output_path, title + '_video.avi'), resize_w + panel_w, canvas_h, fps, bgr)
-            try:
-                for canvases in batches:
-                    put(canvases)
-            finally:                                # also when encoding raises: the index is written, the headers patched
-                path = close()
-            return path
-        if self.gpu_video_codec == 'y4m':
-            put, close = self._y4m_writer(osp.join(output_path, title + '_video'), resize_w + panel_w, canvas_h, fps, bgr)
-            try:
-                for canvases in batches:
-                    put(canvases)
-            except BaseException:
-                close(failed=True)
-                raise
-            return close()
-        if self.gpu_video_codec == 'png':
-            put, close = self._png_writer(osp.join(output_path, title + '_video'), bgr)
+
+        def batches():                                  # one canvas per video frame, numbered 0 .. n_frames - 1
             i = 0
-            for canvases in batches:
-                put(range(i, i + int(canvases.shape[0])), canvases)
+            for canvases in video.annotated_frames(frames, draw, self.batch_size, overlay=overlay):
+                yield range(i, i + int(canvases.shape[0])), canvases
                 i += int(canvases.shape[0])
-            return close()
-        try:
-            import cv2
-        except ImportError:
-            cv2 = None
-        if cv2 is not None:
-            path = osp.join(output_path, title + '_video.mp4')
-            vw = cv2.VideoWriter(path, 0x7634706d, float(fps), (resize_w + panel_w, canvas_h))
-            for canvases in batches:
-                for im in canvases.cpu().numpy():
-                    vw.write(im if bgr else np.ascontiguousarray(im[..., ::-1]))
-            vw.release()
-            return path
-        path = osp.join(output_path, title + '_video')
-        os.makedirs(path, exist_ok=True)
-        i = 0
-        for canvases in batches:
-            for im in canvases.cpu().numpy():
-                _save_png(osp.join(path, '{0:09d}.png'.format(i)), im[..., ::-1] if bgr else im)
-                i += 1
-        return path
+        return sinks.write_all(self._open_sink(output_path, title + '_video', (canvas_h, resize_w + panel_w), fps, bgr), batches())
 
     # ---- base.py:273-282 ------------------------------------------------------------------------------------
     def visualize_joint_cam_mesh(self, debug_result, joint_cam, frames, output_path):
@@ -685,39 +542,27 @@ class Predictor:
             return (frames, False) + self._folder_sidecars(input_path, frames)
         if osp.isdir(input_path) and (osp.isfile(osp.join(input_path, 'tracking.pkl')) or self._tracker_weights()):
             from poserisk_release_amd import jpeg, png
-            names = png.list_frames(input_path)
-            if names and not any(n.lower().endswith(('.jpg', '.jpeg')) for n in os.listdir(input_path)):
-                paths = [osp.join(input_path, n) for n in names]
-                frames, status = png.decode_files(paths, self.device)
-                bad = png.bad_frames(paths, status)
-                if bad:
-                    raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
-                                       + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
-                return (frames, False) + self._folder_sidecars(input_path, frames)
-            names = jpeg.list_frames(input_path)
+            module, opts = jpeg, _jpeg_options()
+            if png.list_frames(input_path) and not any(n.lower().endswith(('.jpg', '.jpeg')) for n in os.listdir(input_path)):
+                module, opts = png, {}
+            names = module.list_frames(input_path)
             if names:
-                paths = [osp.join(input_path, n) for n in names]
-                progressive = bool(cfg.DATASET.get('jpeg_progressive', True))
-                frames, status = jpeg.decode_files(paths, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
-                                                   progressive=progressive)
-                bad = jpeg.bad_frames(paths, status, progressive=progressive)
-                if bad:
-                    raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
-                                       + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+                frames = self._decode_frames(module, [osp.join(input_path, n) for n in names], **opts)
                 return (frames, False) + self._folder_sidecars(input_path, frames)
         not_mjpeg = None
         if osp.isfile(input_path):
-            from poserisk_release_amd import mjpeg
+            from poserisk_release_amd import mjpeg, y4m
             if mjpeg.is_avi(input_path):
                 try:
                     reader = mjpeg.AviReader(input_path)
                 except ValueError as e:
                     not_mjpeg = e                              # an AVI, but not one to read here: cv2 may still open it
                 else:
-                    return self._avi_front_end(reader, input_path, output_path, tracking_results)
-            from poserisk_release_amd import y4m
+                    return self._video_front_end(reader, input_path, output_path, tracking_results, **_jpeg_options())
             if y4m.is_y4m(input_path):
-                return self._y4m_front_end(y4m.Reader(input_path), input_path, output_path, tracking_results)
+                with y4m.Reader(input_path) as reader:
+                    return self._video_front_end(reader, input_path, output_path, tracking_results,
+                                                 matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
             if self.video_decoder:
                 return self._decoder_front_end(input_path, output_path, tracking_results)
         try:
@@ -756,66 +601,50 @@ class Predictor:
         shutil.rmtree(image_path, ignore_errors=True)
         return frames, True, fps, tracking
 
-    def _avi_front_end(self, reader, input_path, output_path, tracking_results=None):
-        """load_front_end's case 3: `reader` is the mjpeg.AviReader of `input_path`."""
-        from poserisk_release_amd import frontend
-        frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
-                                          max_h=cfg.DATASET.get('front_max_h', 450),
-                                          entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
-                                          progressive=bool(cfg.DATASET.get('jpeg_progressive', True)))
-        return self._tracking_for(frames, fps, input_path, output_path, tracking_results)
+    def _decode_frames(self, module, paths, written_to=None, **opts):
+        """`paths` (files, or their bytes) decoded by `module` (jpeg | png: decode_files with `opts`) -> the frames on the device.  The
+        first bad frame raises RuntimeError naming its file -- for bytes written to a tracker's folder `written_to`, its number there."""
+        frames, status = module.decode_files(paths, self.device, **opts)
+        bad = module.bad_frames(paths, status, **{k: opts[k] for k in ('progressive',) if k in opts})
+        if bad and written_to is not None:
+            raise RuntimeError(f"{written_to!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")
+        if bad:
+            raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
+                               + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
+        return frames
 
-    def _y4m_front_end(self, reader, input_path, output_path, tracking_results=None):
-        """load_front_end's cases 3b and 3c: `reader` is the y4m.Reader of `input_path` or of a decoder's standard output."""
+    def _video_front_end(self, reader, input_path, output_path, tracking_results=None, **opts):
+        """load_front_end's cases 3, 3b and 3c: `reader` is the mjpeg.AviReader of `input_path` (`opts`: the JPEG options), or the
+        y4m.Reader of `input_path` or of a decoder's standard output (`opts`: the colour matrix)."""
         from poserisk_release_amd import frontend
-        with reader:
-            frames, fps = frontend.read_video(reader, self.device, max_w=cfg.DATASET.get('front_max_w', 800),
-                                              max_h=cfg.DATASET.get('front_max_h', 450),
-                                              matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+        frames, fps = frontend.read_video(reader, self.device, **_front_limits(), **opts)
         return self._tracking_for(frames, fps, input_path, output_path, tracking_results)
 
     def _decoder_front_end(self, input_path, output_path, tracking_results=None):
         """load_front_end's case 3c: self.video_decoder, with {input} replaced, runs as a child process whose standard output
         is read as YUV4MPEG2.  Never a shell and never this process's own program; the child is reaped whatever happens."""
         import shlex
-        import subprocess
-        import tempfile
-        from poserisk_release_amd import y4m
+        from poserisk_release_amd import _child, y4m
         if '{input}' not in self.video_decoder:
             raise ValueError(f"video_decoder {self.video_decoder!r} must be a command line containing {{input}}")
-        argv = [a.replace('{input}', input_path) for a in shlex.split(self.video_decoder)]
-        shown = ' '.join(shlex.quote(a) for a in argv)
+        child = _child.Child([a.replace('{input}', input_path) for a in shlex.split(self.video_decoder)],
+                             f"{input_path!r}: the video decoder", feed=False)
         failure, read_to_the_end = None, False
-        with tempfile.TemporaryFile() as err:
+        try:
             try:
-                child = subprocess.Popen(argv, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=err)
-            except OSError as e:
-                raise RuntimeError(f"{input_path!r}: the video decoder `{shown}` could not be started: {e}") from e
-            try:
+                reader = y4m.Reader(child.pipe)
+            except ValueError as e:
+                failure = f"it wrote no YUV4MPEG2 stream header ({e})"
+            else:
                 try:
-                    reader = y4m.Reader(child.stdout)
-                except ValueError as e:
-                    failure = f"wrote no YUV4MPEG2 stream header ({e})"
-                else:
-                    try:
-                        return_value = self._y4m_front_end(reader, input_path, output_path, tracking_results)
-                        read_to_the_end = True
-                    except ValueError as e:                     # the stream broke off: the child's status says why
-                        failure = str(e)
-            finally:
-                child.stdout.close()                            # a child still writing gets EPIPE and ends by itself
-                try:
-                    status = child.wait(timeout=60 if read_to_the_end else 5)
-                except subprocess.TimeoutExpired:
-                    child.kill()
-                    status = child.wait()
-            err.seek(0)
-            tail = err.read()[-2000:].decode('utf-8', 'replace').strip()
-        if failure is not None or status != 0:
-            raise RuntimeError(f"{input_path!r}: the video decoder `{shown}` failed with exit status {status}"
-                               + (f": it {failure}" if failure is not None and failure.startswith('wrote no') else
-                                  f": {failure}" if failure is not None else '')
-                               + (f"; its standard error ends: {tail}" if tail else ''))
+                    return_value = self._video_front_end(reader, input_path, output_path, tracking_results,
+                                                         matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+                    read_to_the_end = True
+                except ValueError as e:                         # the stream broke off: the child's status says why
+                    failure = str(e)
+        finally:
+            child.pipe.close()                  # a child still writing gets EPIPE and ends by itself; its status raises nothing
+            child.finish(60 if read_to_the_end else 5, failure, raising=read_to_the_end or failure is not None)    # over another error
         return return_value
 
     # ---- the built-in tracker (cfg.TRACKER; off while its weights are '') --------------------------------------------------
@@ -873,12 +702,7 @@ class Predictor:
             tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
                           output_format='dict', yolo_img_size=416)
             tracking = tracker(image_path)
-            progressive = bool(cfg.DATASET.get('jpeg_progressive', True))
-            frames, status = jpeg.decode_files(files, self.device, entropy=cfg.DATASET.get('jpeg_entropy', 'auto'),
-                                               progressive=progressive)
-            bad = jpeg.bad_frames(files, status, progressive=progressive)
-            if bad:
-                raise RuntimeError(f"{image_path!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")
+            frames = self._decode_frames(jpeg, files, written_to=image_path, **_jpeg_options())
         finally:
             shutil.rmtree(image_path, ignore_errors=True)
         return frames, False, fps, tracking
@@ -918,7 +742,6 @@ class Predictor:
         the reference's own: `load_front_end`) -> crops, pose, scores on the GPU -> `reba_result.txt` /
         `rula_result.txt`, `<TITLE>_score.png`, `<TITLE>_video.mp4` (OpenCV drawing: only where cv2 is importable; with
         the gpu_video knob composed on the GPU instead, see write_gpu_video) and with `args.debug` the CSV logs under <output>/debug.  Returns the dict of `score_frames` plus `fps`."""
-        import os
         from poserisk_release_amd import reports
         os.makedirs(output_path, exist_ok=True)
         world, rank = pl.world_and_rank()
@@ -956,7 +779,7 @@ class Predictor:
                 title = 'REBA' if 'reba' in out else ('RULA' if 'rula' in out else None)
                 for _, img in self.render_overlay(one, frames, title, bgr):
                     im = img[0].cpu().numpy()
-                    _save_png(osp.join(debug_path, 'mesh_overlay.png'), im[..., ::-1] if bgr else im)
+                    sinks.save_png(osp.join(debug_path, 'mesh_overlay.png'), im[..., ::-1] if bgr else im)
             print("\n Debug files are saved in : ", debug_path)
             return out
         pose_str = reports.pose_to_str(out['result'])
@@ -972,11 +795,13 @@ class Predictor:
             reports.save_score_plot(output_path, title, timestamp, scores)      # base.py:254-262
             if getattr(self, 'visualize', True) and self.gpu_video:            # base.py:156,173 on the GPU
                 if self.render_mesh:                # one rendering of the mesh feeds both outputs
-                    sink, close = self._mesh_writer(frames, output_path, title, bgr, fps)
+                    mesh = self._open_sink(output_path, title + '_mesh', frames.shape[1:3], fps, bgr)
                     try:
-                        self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=sink)
-                    finally:
-                        close()
+                        self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=mesh.put)
+                    except BaseException:
+                        mesh.abort()                    # the video's error stands; a mesh encoder child is reaped all the same
+                        raise
+                    mesh.close()
                     mesh_written = True
                 else:
                     self.write_gpu_video(out, frames, output_path, title, bgr, fps)
@@ -993,13 +818,3 @@ class Predictor:
             if self.debugging:
                 reports.save_score_csv(debug_path, title, timestamp, scores, scorer.eval_items, logs, scorer.log)
         return out
-
-
-def _save_png(path, rgb):
-    """u8[H,W,3] RGB -> PNG with Pillow, else matplotlib."""
-    try:
-        from PIL import Image
-        Image.fromarray(np.ascontiguousarray(rgb)).save(path)
-    except ImportError:
-        import matplotlib.image
-        matplotlib.image.imsave(path, np.ascontiguousarray(rgb))

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, jpeg, mjpeg
+from . import _lib, _media, jpeg, mjpeg
 
 MODE_COPY, MODE_HALF, MODE_LINEAR = 0, 1, 2
 MAX_CHUNK = 1024
@@ -44,20 +44,12 @@ def resize_plan(H, W, h, w):
     return xofs, xcoef, yofs, ycoef, int(mode[0])
 
 
-_plans = {}
-
-
-def _device_plan(key, device):
-    """The uploaded tables of (H, W, h, w) on `device` -> (u8 tensor [xofs | yofs | xcoef | ycoef], mode): made once, kept.
-    As jpeg._device_plan: the first call of a size pair waits for its copy, every further call only looks it up."""
-    plan = _plans.get((key, device))
-    if plan is None:
+def _resize_tables(key, device):
+    """The uploaded tables of key = (H, W, h, w) on `device` -> (u8 tensor [xofs | yofs | xcoef | ycoef], mode)."""
+    def make():
         xofs, xcoef, yofs, ycoef, mode = resize_plan(*key)
-        host = torch.from_numpy(np.frombuffer(xofs.tobytes() + yofs.tobytes() + xcoef.tobytes() + ycoef.tobytes(), np.uint8).copy())
-        tables = host.to(device)
-        torch.cuda.current_stream(device).synchronize()
-        plan = _plans[(key, device)] = (tables, mode)
-    return plan
+        return xofs.tobytes() + yofs.tobytes() + xcoef.tobytes() + ycoef.tobytes(), mode
+    return _media.device_plan(("resize",) + key, device, make)
 
 
 def resize_frames(frames, h, w, out=None):
@@ -71,7 +63,7 @@ def resize_frames(frames, h, w, out=None):
     device, (F, H, W, _) = frames.device, frames.shape
     h, w = int(h), int(w)
     with torch.cuda.device(device):
-        tables, mode = _device_plan((H, W, h, w), device)
+        tables, mode = _resize_tables((H, W, h, w), device)
         if out is None:
             out = torch.empty((F, h, w, 3), dtype=torch.uint8, device=device)
         if tuple(out.shape) != (F, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
@@ -138,11 +130,7 @@ def read_video(path, device, max_w=800, max_h=450, bgr=False, max_bytes=16 << 30
     and the reason; a file that is no Motion-JPEG AVI raises ValueError (mjpeg.AviReader).  `path` may be an AviReader already made.
     `entropy` is jpeg.decode_files' ("auto" | "serial" | "sync"), and so is `progressive`: False refuses a progressive frame by
     name, True decodes it (pr_jpeg_decode_scans)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PoseRiskHipError("read_video: decoding and resizing run on the GPU only (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _media.cuda_device(device, "read_video", "decoding and resizing run")
     y4m_reader = None if isinstance(path, mjpeg.AviReader) else _y4m_source(path)
     if y4m_reader is not None:
         return read_y4m(y4m_reader, device, max_w=max_w, max_h=max_h, bgr=bgr, max_bytes=max_bytes, matrix=matrix)
@@ -186,13 +174,11 @@ def write_frame_folder(frames, out_dir, quality=95, fps=None, bgr=False, chunk=6
     os.makedirs(out_dir, exist_ok=True)
     F, H, W, _ = frames.shape
     files = []
+    encode = lambda images, capacity: jpeg.encode_frames(images, quality=quality, subsampling="4:2:0", restart_rows=1, bgr=bgr,
+                                                         capacity=capacity)
     for lo in range(0, F, chunk):
-        part = frames[lo:lo + chunk]
-        buf, nbytes, status = jpeg.encode_frames(part, quality=quality, subsampling="4:2:0", restart_rows=1, bgr=bgr)
-        if bool(status.any()):                                   # a frame beyond the default slot: the size no file exceeds
-            buf, nbytes, status = jpeg.encode_frames(part, quality=quality, subsampling="4:2:0", restart_rows=1, bgr=bgr,
-                                                     capacity=jpeg.encode_bound(H, W, "4:2:0", -1))
-        for i, data in enumerate(jpeg.download_files(buf, nbytes), lo):
+        part = _media.encode_files(encode, frames[lo:lo + chunk], None, jpeg.encode_bound(H, W, "4:2:0", -1), "jpeg.encode_frames")
+        for i, data in enumerate(part, lo):
             with open(os.path.join(out_dir, "{0:09d}.jpg".format(i)), "wb") as f:
                 f.write(data)
             files.append(data)

@@ -17,7 +17,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _media
+from ._media import download_files   # noqa: F401  (buffer, nbytes) -> [bytes]: one shape of result for both encoders
 
 # pr_jpeg_frame, pr_jpeg_segment, pr_jpeg_hufftab / pr_jpeg_huff as numpy records (tests compare them with the C structs)
 FRAME_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"),
@@ -189,11 +190,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     such a call `bad_frames(..., progressive=True)` names the refusals."""
     if entropy not in ENTROPY:
         raise ValueError(f"decode_files: entropy = {entropy!r}: one of {ENTROPY}")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PoseRiskHipError("decode_files: the decoder runs on the GPU only (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _media.cuda_device(device, "decode_files", "the decoder runs")
     items = list(paths_or_bytes)
     F, chunk = len(items), max(int(chunk), 1)
     lib = _lib.load()
@@ -226,14 +223,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             if pinned is None or pinned.numel() < room:
                 pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
             host = pinned.numpy()
-            for p, a, b in zip(part, offsets[:-1], offsets[1:]):
-                if isinstance(p, (str, os.PathLike)):
-                    with open(p, "rb") as f:
-                        got = f.readinto(memoryview(host[a:b]))
-                    if got != b - a:
-                        raise OSError(f"{p!r} changed size while it was read")
-                else:
-                    host[a:b] = np.frombuffer(bytes(p), np.uint8)
+            _media.read_files(host, part, offsets)
             pst = np.zeros(n, np.int32)
             while True:
                 fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
@@ -348,22 +338,6 @@ def encode_bound(H, W, subsampling="4:2:0", restart_interval=-1):
     return int(_lib.load().pr_jpeg_encode_bound(int(H), int(W), hs, vs, int(restart_interval)))
 
 
-_plans = {}
-
-
-def _device_plan(key, device):
-    """The uploaded plan of (quality, subsampling, restart interval, H, W) on `device`: made once, kept.  The first call of a
-    parameter set copies the plan from pageable host memory and waits for the copy, so that every stream, then and later, finds
-    the plan complete; every further call only looks it up."""
-    plan = _plans.get((key, device))
-    if plan is None:
-        host = torch.from_numpy(np.frombuffer(encode_plan(*key).tobytes(), np.uint8).copy())
-        plan = host.to(device)
-        torch.cuda.current_stream(device).synchronize()
-        _plans[(key, device)] = plan
-    return plan
-
-
 def encode_frames(frames, quality=90, subsampling="4:2:0", restart_rows=1, bgr=False, capacity=None, out=None, workspace=None):
     """Encode u8[F,H,W,3] frames on the GPU (RGB, or BGR with bgr=True) to F baseline JPEG files: returns (buffer u8[F,cap],
     nbytes int32[F], status int32[F]), all on the device; file f is buffer[f, :nbytes[f]], header and EOI included.
@@ -373,7 +347,7 @@ def encode_frames(frames, quality=90, subsampling="4:2:0", restart_rows=1, bgr=F
     encode it again with capacity=encode_bound(H, W, subsampling, -1 if restart_rows else 0).  `out` = (buffer, nbytes, status)
     to write into caller-owned tensors; `workspace` = a u8 device tensor of at least encode_workspace_bytes(...) to reuse across
     calls on one stream (None allocates one per call).  Asynchronous on the current stream.  The first call of a parameter set
-    on a device uploads its plan and waits for that copy (_device_plan); every later call synchronises nothing, and with `out`
+    on a device uploads its plan and waits for that copy (_media.device_plan); every later call synchronises nothing, and with `out`
     and `workspace` given allocates nothing either, so it can be captured into a graph."""
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
         raise _lib.PoseRiskHipError("encode_frames: the encoder runs on the GPU only (no CPU fallback)")
@@ -388,7 +362,8 @@ def encode_frames(frames, quality=90, subsampling="4:2:0", restart_rows=1, bgr=F
     ri = -1 if restart_rows else 0
     lib = _lib.load()
     with torch.cuda.device(device):
-        plan = _device_plan((int(quality), subsampling, ri, H, W), device)
+        key = (int(quality), subsampling, ri, H, W)
+        plan, _ = _media.device_plan(("jpeg.encode",) + key, device, lambda: (encode_plan(*key).tobytes(), None))
         if capacity is None:
             capacity = min(encode_bound(H, W, subsampling, ri), 4096 + H * W * 3 // 2)
         capacity = int(capacity)
@@ -427,14 +402,3 @@ def encode_workspace_bytes(F, H, W, subsampling="4:2:0", restart_rows=1, capacit
     if capacity is None:
         capacity = min(encode_bound(H, W, subsampling, ri), 4096 + H * W * 3 // 2)
     return int(_lib.load().pr_jpeg_encode_workspace_bytes(int(F), int(H), int(W), hs, vs, ri, int(capacity)))
-
-
-def download_files(buffer, nbytes):
-    """[bytes] of an encode_frames result; only the used bytes cross to the host: the sizes first (one small copy), then the
-    slices buffer[f, :nbytes[f]] packed into one device tensor and copied once."""
-    n = nbytes.cpu().numpy().astype(np.int64)
-    if n.size == 0:
-        return []
-    packed = torch.cat([buffer[f, :k] for f, k in enumerate(n.tolist())]).cpu().numpy().tobytes()
-    ends = np.cumsum(n)
-    return [packed[e - k:e] for e, k in zip(ends, n)]

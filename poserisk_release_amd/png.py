@@ -13,8 +13,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from .jpeg import download_files   # noqa: F401  (buffer, nbytes) -> [bytes]: one shape of result for both encoders
+from . import _lib, _media
+from ._media import download_files   # noqa: F401  (buffer, nbytes) -> [bytes]: one shape of result for both encoders
 
 # pr_png_frame, pr_png_idat as numpy records (tests compare them with the C structs); a palette is 256 x 3 bytes
 FRAME_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("color_type", "<i4"), ("bpp", "<i4"), ("first_idat", "<i4"),
@@ -116,11 +116,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     buffer, the parser writes its descriptors behind them in the same buffer, and ONE asynchronous copy uploads it; the decode
     neither allocates nor synchronises (include/poserisk_hip.h, pr_png_decode).  The host waits for chunk k's upload (not its
     decode) before it reads chunk k + 1 into the buffer."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PoseRiskHipError("decode_files: the decoder runs on the GPU only (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _media.cuda_device(device, "decode_files", "the decoder runs")
     items = list(paths_or_bytes)
     F, chunk = len(items), max(int(chunk), 1)
     lib = _lib.load()
@@ -153,14 +149,7 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
             if pinned is None or pinned.numel() < room:
                 pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
             host = pinned.numpy()
-            for p, a, b in zip(part, offsets[:-1], offsets[1:]):
-                if isinstance(p, (str, os.PathLike)):
-                    with open(p, "rb") as f:
-                        got = f.readinto(memoryview(host[a:b]))
-                    if got != b - a:
-                        raise OSError(f"{p!r} changed size while it was read")
-                else:
-                    host[a:b] = np.frombuffer(bytes(p), np.uint8)
+            _media.read_files(host, part, offsets)
             pst = np.zeros(n, np.int32)
             while True:
                 fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
@@ -269,21 +258,6 @@ def encode_workspace_bytes(F, H, W):
     return int(_lib.load().pr_png_encode_workspace_bytes(int(F), int(H), int(W)))
 
 
-_plans = {}
-
-
-def _device_plan(key, device):
-    """The uploaded plan of (filter, mode, H, W) on `device`: made once, kept.  The first call of a parameter set copies the plan
-    from pageable host memory and waits for the copy; every further call only looks it up."""
-    plan = _plans.get((key, device))
-    if plan is None:
-        host = torch.from_numpy(np.frombuffer(encode_plan(*key).tobytes(), np.uint8).copy())
-        plan = host.to(device)
-        torch.cuda.current_stream(device).synchronize()
-        _plans[(key, device)] = plan
-    return plan
-
-
 def encode_frames(frames, filter="adaptive", mode="rle", bgr=False, capacity=None, out=None, workspace=None):
     """Encode u8[F,H,W,3] frames on the GPU (RGB, or BGR with bgr=True) to F PNG files (colour type 2, depth 8): returns (buffer
     u8[F,cap], nbytes int32[F], status int32[F]), all on the device; file f is buffer[f, :nbytes[f]].  `filter` is a name of
@@ -302,7 +276,7 @@ def encode_frames(frames, filter="adaptive", mode="rle", bgr=False, capacity=Non
     device, (F, H, W, _) = frames.device, frames.shape
     lib = _lib.load()
     with torch.cuda.device(device):
-        plan = _device_plan((f, m, H, W), device)
+        plan, _ = _media.device_plan(("png.encode", f, m, H, W), device, lambda: (encode_plan(f, m, H, W).tobytes(), None))
         capacity = encode_bound(H, W) if capacity is None else int(capacity)
         if out is None:
             out = (torch.empty((F, capacity), dtype=torch.uint8, device=device), torch.empty(F, dtype=torch.int32, device=device),

@@ -24,7 +24,8 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _media
+from ._child import Child
 
 CHROMAS = ("420jpeg", "420mpeg2", "422", "444", "mono")        # index = PR_Y4M_C*
 MATRICES = {"601": 0, "709": 1}                                # PR_YUV_*
@@ -220,7 +221,7 @@ def yuv_frames(data, offsets, H, W, chroma, plan, bgr=False, size=None, out=None
     a.F, a.H, a.W, a.chroma, a.bgr = F, H, W, CHROMAS.index(chroma), int(bool(bgr))
     with torch.cuda.device(device):
         if size is not None:
-            tables, mode = frontend._device_plan((H, W, h, w), device)
+            tables, mode = frontend._resize_tables((H, W, h, w), device)
             base = tables.data_ptr()
             a.xofs, a.xcoef, a.yofs, a.ycoef = base, base + 4 * w + 4 * h, base + 4 * w, base + 8 * w + 4 * h
             a.h, a.w, a.mode = h, w, mode
@@ -247,11 +248,7 @@ def decode(src, device, matrix="601", full_range=None, bgr=False, size=None, fus
     chunk by chunk (`chunk` frames, else what max_bytes allows, at most 256) into pinned memory, uploaded and converted while
     the next chunk is read.  A regular file's result is sized from its length; a pipe's chunks are concatenated once."""
     from . import frontend
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PoseRiskHipError("y4m.decode: the conversion runs on the GPU only (no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _media.cuda_device(device, "y4m.decode", "the conversion runs")
     if isinstance(src, (bytes, bytearray, memoryview)):
         src = io.BytesIO(bytes(src))
     reader = src if isinstance(src, Reader) else Reader(src)
@@ -402,9 +399,6 @@ class Writer:
 
     def __init__(self, dst=None, width=None, height=None, fps=30.0, chroma="420mpeg2", matrix="601", full_range=False, bgr=False,
                  pad_even=False, command=None):
-        import shlex
-        import subprocess
-        import tempfile
         if (dst is None) == (command is None):
             raise ValueError("y4m.Writer: give either dst (a path, a binary file object or '-') or command=[argv]")
         if matrix not in MATRICES:
@@ -413,20 +407,12 @@ class Writer:
         self.out_width, self.out_height, self.frame_size = encoded_size(self.width, self.height, chroma, pad_even)
         self.chroma, self.matrix, self.full_range, self.bgr, self.pad_even = chroma, matrix, bool(full_range), bool(bgr), bool(pad_even)
         self.frames_written = 0
-        self._child = self._err = self._f = None
+        self._child = self._f = None
         self._own = self._closed = False
         self._pinned, self._staged, self._pending, self._which = [None, None], None, None, 0
         if command is not None:
-            argv = [os.fspath(a) for a in command]
-            self._shown = " ".join(shlex.quote(a) for a in argv)
-            self._err = tempfile.TemporaryFile()
-            try:
-                self._child = subprocess.Popen(argv, stdin=subprocess.PIPE, stdout=subprocess.DEVNULL, stderr=self._err)
-            except OSError as e:
-                self._err.close()
-                self._closed = True
-                raise RuntimeError(f"the video encoder `{self._shown}` could not be started: {e}") from e
-            self._f = self._child.stdin
+            self._child = Child([os.fspath(a) for a in command], "the video encoder", feed=True)
+            self._f = self._child.pipe
         elif isinstance(dst, (str, os.PathLike)) and os.fspath(dst) != "-":
             self._f, self._own = open(dst, "wb"), True
         elif isinstance(dst, (str, os.PathLike)):
@@ -514,7 +500,6 @@ class Writer:
             return
         self._closed = True
         self._pending = None
-        import subprocess
         if self._child is None:
             if self._own:
                 self._f.close()
@@ -530,16 +515,4 @@ class Writer:
             failure = failure or f"it closed its standard input after {self.frames_written} frames ({e.strerror or e})"
         except OSError:
             pass
-        try:
-            status = self._child.wait(timeout=5 if failure is not None or not raising else 600)
-        except subprocess.TimeoutExpired:
-            self._child.kill()
-            status = self._child.wait()
-            failure = failure or "it did not end after its standard input was closed"
-        self._err.seek(0)
-        tail = self._err.read()[-2000:].decode("utf-8", "replace").strip()
-        self._err.close()
-        if raising and (failure is not None or status != 0):
-            raise RuntimeError(f"the video encoder `{self._shown}` failed with exit status {status}"
-                               + (f": {failure}" if failure is not None else "")
-                               + (f"; its standard error ends: {tail}" if tail else ""))
+        self._child.finish(5 if failure is not None or not raising else 600, failure, raising)

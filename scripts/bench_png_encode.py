@@ -6,7 +6,7 @@ picture with three bits of noise a sample: a camera's frame as the mesh writer s
      allocated once), warmed up, the median of the rounds;
   b  compose + encode + download of the used bytes (png.download_files), wall clock with a synchronisation at the end
      (canvases only: the noisy frames have no compose step, theirs is encode + download);
-  c  today's path: download of the raw frames, then one PNG per frame through Pillow (dropin/core/base.py's _save_png), wall clock;
+  c  today's path: download of the raw frames, then one PNG per frame through Pillow (poserisk_release_amd/sinks.py's save_png), wall clock;
   d  Pillow on 16 threads from host memory at compress_level 1 and at its default, wall clock;
   e  bytes per frame of each of the above and of pr_jpeg_encode at quality 90.
 No threshold: the figures are reported as they are, the rows where the GPU loses to (d) included.
@@ -30,7 +30,6 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "scripts"))
 
 from poserisk_release_amd import _lib, jpeg, png  # noqa: E402
-from poserisk_release_amd import dropin  # noqa: E402
 import bench_jpeg_encode as bj  # noqa: E402
 import bench_video  # noqa: E402
 
@@ -102,8 +101,7 @@ def measure(kind, B, dev, rounds):
         return rec
     host = images.cpu().numpy()
     assert all(np.array_equal(np.asarray(Image.open(io.BytesIO(f)).convert("RGB")), im) for f, im in zip(files[:4], host[:4]))
-    dropin.install()
-    from core.base import _save_png                               # what write_gpu_video calls per frame today
+    from poserisk_release_amd.sinks import save_png as _save_png   # what write_gpu_video's Pillow sink calls per frame
     with tempfile.TemporaryDirectory() as tmp:
         def path_c():
             compose()
