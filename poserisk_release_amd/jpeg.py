@@ -4,9 +4,9 @@ lib/core/base.py:47-56, read back by CropDataset with cv2.imread).  The contract
 the marker parser is csrc/jpeg_host.cc (host, no device), everything else csrc/jpeg.hip.
 
 `list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
-go through ONE pinned buffer and ONE upload, then pr_jpeg_decode.  Progressive files and files whose components come in
-several scans (section j1b; csrc/jpeg_scans_host.cc, csrc/jpeg_scans.hip) are opt-in: `parse_scans` is their host half,
-`decode_files(progressive=True)` sends a chunk that holds one to pr_jpeg_decode_scans.
+go through ONE pinned buffer and ONE upload (_media.decode_chunks), then pr_jpeg_decode.  Progressive files and files whose
+components come in several scans (section j1b; csrc/jpeg_scans_host.cc, csrc/jpeg_scans.hip) are opt-in: `parse_scans` is their
+host half, `decode_files(progressive=True)` sends a chunk that holds one to pr_jpeg_decode_scans.
 
 The inverse direction (section j2; csrc/jpeg_enc.hip): `encode_frames` turns u8 frames on the device into complete baseline
 JPEG files in per-frame slots, byte for byte what libjpeg writes with the standard tables; `download_files` brings only the
@@ -80,12 +80,6 @@ def list_frames(directory):
     return [n for n in names if n.lower().endswith(_EXT)]
 
 
-def _packed(blobs):
-    offsets = np.zeros(len(blobs) + 1, np.int64)
-    np.cumsum([len(b) for b in blobs], out=offsets[1:])
-    return offsets
-
-
 def _parse_into(data, offsets, H, W, frames, segs, huff, pstatus):
     """pr_jpeg_parse into caller-owned numpy arrays -> (status code, counts int32[4] = segments, table sets, H, W)."""
     counts = np.zeros(4, np.int32)
@@ -98,8 +92,7 @@ def _parse_into(data, offsets, H, W, frames, segs, huff, pstatus):
 def parse(blobs, H=0, W=0):
     """Host half on a list of bytes objects: (frames FRAME_DTYPE[F], segments SEGMENT_DTYPE[S], huff HUFF_DTYPE[T],
     parse_status int32[F], H, W, offsets int64[F+1]).  Refused frames have parse_status != 0 (refusal_name gives the words)."""
-    offsets = _packed(blobs)
-    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    offsets, data = _media.pack(blobs)
     F = len(blobs)
     frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
     seg_cap, huff_cap = 64 + 2 * F, 4
@@ -128,8 +121,7 @@ def parse_scans(blobs, H=0, W=0):
     everything `parse` accepts) on a list of bytes objects: `parse`'s tuple (frames, segments, huff, parse_status, H, W,
     offsets) followed by scans SCAN_DTYPE[N], segment_scan int32[S] (segment i belongs to scans[segment_scan[i]]), the number
     of levels and the number of frames with more than one scan.  scan_refusal_name gives a refusal's words."""
-    offsets = _packed(blobs)
-    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    offsets, data = _media.pack(blobs)
     F = len(blobs)
     frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
     seg_cap, huff_cap, scan_cap = 64 + 16 * F, 4 + F, 16 * F
@@ -166,10 +158,6 @@ def sync_workspace_bytes(F, H, W, data_bytes, n_segments, sync_opts=None):
     return int(_lib.load().pr_jpeg_sync_workspace_bytes(int(F), int(H), int(W), int(data_bytes), int(n_segments), _sync_opts(sync_opts)))
 
 
-def _align(n, a=256):
-    return (n + a - 1) // a * a
-
-
 def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, entropy="auto", stats=False, sync_opts=None,
                  progressive=False):
     """Decode F baseline JPEG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread
@@ -193,129 +181,72 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     device = _media.cuda_device(device, "decode_files", "the decoder runs")
     items = list(paths_or_bytes)
     F, chunk = len(items), max(int(chunk), 1)
-    lib = _lib.load()
-    H, W, seg_per_frame, scan_per_frame, huff_room = 0, 0, 2, (10 if progressive else 0), 0
-    frames_out = status = pinned = ws = uploaded = first_refusal = sync_stats = None
-    opts = _sync_opts(sync_opts)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device)
-        for lo in range(0, F, chunk):
-            part = items[lo:lo + chunk]
-            n = len(part)
-            sizes = [os.path.getsize(p) if isinstance(p, (str, os.PathLike)) else len(p) for p in part]
-            offsets = np.zeros(n + 1, np.int64)
-            np.cumsum(sizes, out=offsets[1:])
-            total, seg_room, scan_room, huff_room = int(offsets[-1]), 64 + seg_per_frame * n, scan_per_frame * n, max(huff_room, n)
-            # [file bytes | frames | segments | (segments' scans | scans |) table sets]: the parser reads the bytes where they lie
-            # and writes beside them; the two arrays in brackets are empty without `progressive`
-            o_fr = _align(max(total, 1))
-            o_seg = _align(o_fr + n * FRAME_DTYPE.itemsize)
+    lib, opts = _lib.load(), _sync_opts(sync_opts)
+    # what a frame needed so far: these only grow, so that later chunks start from what an earlier one needed (a folder one
+    # encoder wrote has one restart interval)
+    seg_per_frame, scan_per_frame, huff_room, sync_stats = 2, (10 if progressive else 0), 0, None
 
-            def layout():
-                o_ss = _align(o_seg + seg_room * SEGMENT_DTYPE.itemsize)
-                o_sc = _align(o_ss + (seg_room * 4 if progressive else 0))
-                o_huff = _align(o_sc + scan_room * SCAN_DTYPE.itemsize)
-                return o_ss, o_sc, o_huff, o_huff + huff_room * HUFF_DTYPE.itemsize
-            o_ss, o_sc, o_huff, room = layout()
-            if uploaded is not None:
-                uploaded.synchronize()                           # the previous chunk has left the buffer
-                uploaded = None
-            if pinned is None or pinned.numel() < room:
-                pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
-            host = pinned.numpy()
-            _media.read_files(host, part, offsets)
-            pst = np.zeros(n, np.int32)
-            while True:
-                fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
-                segs = host[o_seg:o_seg + seg_room * SEGMENT_DTYPE.itemsize].view(SEGMENT_DTYPE)
-                huff = host[o_huff:o_huff + huff_room * HUFF_DTYPE.itemsize].view(HUFF_DTYPE)
-                if progressive:
-                    seg_scan = host[o_ss:o_ss + seg_room * 4].view(np.int32)
-                    scans = host[o_sc:o_sc + scan_room * SCAN_DTYPE.itemsize].view(SCAN_DTYPE)
-                    rc, counts = _parse_scans_into(host[:max(total, 1)], offsets, H, W, fr, segs, seg_scan, huff, scans, pst)
-                else:
-                    rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, segs, huff, pst)
-                if rc != -4:                                     # PR_ERR_CAPACITY: more restart segments than guessed
-                    _lib.check(rc, "pr_jpeg_parse_scans" if progressive else "pr_jpeg_parse")
-                    break
-                # parse again where the bytes lie, with the room the parser asked for; later chunks start from what this one
-                # needed a frame (a folder one encoder wrote has one restart interval)
-                seg_room = int(counts[0])
-                seg_per_frame = max(seg_per_frame, -(-seg_room // n))
-                if progressive:
-                    scan_room, huff_room = max(scan_room, int(counts[4])), max(huff_room, int(counts[1]))
-                    scan_per_frame = max(scan_per_frame, -(-scan_room // n))
-                o_ss, o_sc, o_huff, room = layout()
-                if pinned.numel() < room:
-                    bigger = torch.empty(room, dtype=torch.uint8).pin_memory()
-                    bigger[:total] = pinned[:total]
-                    pinned, host = bigger, bigger.numpy()
-            n_segs, n_huff = int(counts[0]), int(counts[1])
-            if H == 0 and pst.any() and first_refusal is None:
-                first_refusal = (lo + int(np.nonzero(pst)[0][0]), scan_refusal_name(pst[np.nonzero(pst)[0][0]]))
-            if H == 0 and counts[2]:
-                H, W = int(counts[2]), int(counts[3])
-                frames_out = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
-                if tuple(frames_out.shape) != (F, H, W, 3) or frames_out.dtype != torch.uint8 or not frames_out.is_contiguous() \
-                        or frames_out.device != device:
-                    raise ValueError(f"out must be a contiguous uint8 {[F, H, W, 3]} tensor on {device}")
-                status = torch.full((F,), ST_REFUSED, dtype=torch.int32, device=device)   # chunks before the first size
-                sync_stats = torch.zeros((F, 4), dtype=torch.int32, device=device) if stats else None
-                frames_out[:lo].zero_()
-            if H == 0:
-                continue                                         # nothing accepted so far: no size to decode at
-            used = o_huff + n_huff * HUFF_DTYPE.itemsize
-            dev = torch.empty(used, dtype=torch.uint8, device=device)
-            dev.copy_(pinned[:used], non_blocking=True)          # the chunk's one upload
-            uploaded = torch.cuda.Event()
-            uploaded.record(stream)
-            ok = fr[pst == 0]
-            multi = progressive and int(counts[6]) > 0
-            sync = not multi and (entropy == "sync" or (entropy == "auto" and bool((ok["restart_interval"] == 0).any())))
-            need = sync_workspace_bytes(n, H, W, total, n_segs, sync_opts) if sync else workspace_bytes(n, H, W)
-            if sync and need == 0:
-                raise _lib.PoseRiskHipError(f"decode_files: sync_opts = {sync_opts!r}: subseq_bytes is a multiple of 4 in 16..4096 "
-                                            "(or 0 for the default), max_rounds 1..64")
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=device)
-            base = dev.data_ptr()
-            args = _lib.JpegArgs(base, base + o_fr, base + o_seg, base + o_huff, frames_out[lo:lo + n].data_ptr(),
-                                 status[lo:lo + n].data_ptr(), total, n, H, W, n_segs, n_huff, int(bool(bgr)))
-            if multi:
-                sargs = _lib.JpegScansArgs(args, base + o_sc, base + o_ss, int(counts[4]), int(counts[5]))
-                _lib.check(lib.pr_jpeg_decode_scans(sargs, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode_scans")
-            elif sync:
-                st_ptr = sync_stats[lo:lo + n].data_ptr() if stats else None
-                _lib.check(lib.pr_jpeg_decode_sync(args, opts, st_ptr, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode_sync")
-            else:
-                _lib.check(lib.pr_jpeg_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_jpeg_decode")
-            dev.record_stream(stream)
-            ws.record_stream(stream)
-        if uploaded is not None:
-            uploaded.synchronize()
-    if frames_out is None:
-        if first_refusal:
-            raise _lib.PoseRiskHipError(f"decode_files: no frame was accepted; frame {first_refusal[0]}: {first_refusal[1]}")
-        frames_out = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
-        status = torch.zeros(0, dtype=torch.int32, device=device)
-        sync_stats = torch.zeros((0, 4), dtype=torch.int32, device=device)
-    return (frames_out, status, sync_stats) if stats else (frames_out, status)
+    def rooms(n):
+        """[frames | segments | segments' scans | scans | table sets]; the two in the middle stay empty without `progressive`."""
+        nonlocal huff_room
+        huff_room = max(huff_room, n)
+        seg_room = 64 + seg_per_frame * n
+        return [n, seg_room, seg_room if progressive else 0, scan_per_frame * n, huff_room]
+
+    def regrow(n, room, counts):   # more restart segments (scans, table sets) than guessed
+        nonlocal seg_per_frame, scan_per_frame, huff_room
+        seg_room, scan_room = int(counts[0]), room[3]
+        seg_per_frame = max(seg_per_frame, -(-seg_room // n))
+        if progressive:
+            scan_room, huff_room = max(scan_room, int(counts[4])), max(huff_room, int(counts[1]))
+            scan_per_frame = max(scan_per_frame, -(-scan_room // n))
+        return [n, seg_room, seg_room if progressive else 0, scan_room, huff_room]
+
+    def parse_chunk(data, offsets, H, W, views, pst):
+        fr, segs, seg_scan, scans, huff = (v.view(t) for v, t in zip(views, (FRAME_DTYPE, SEGMENT_DTYPE, np.int32, SCAN_DTYPE, HUFF_DTYPE)))
+        if progressive:
+            return _parse_scans_into(data, offsets, H, W, fr, segs, seg_scan, huff, scans, pst)
+        return _parse_into(data, offsets, H, W, fr, segs, huff, pst)
+
+    def sized(H, W):
+        nonlocal sync_stats
+        sync_stats = torch.zeros((F, 4), dtype=torch.int32, device=device) if stats else None
+
+    def decode(c):
+        """serial, sync or scans for this chunk, from what the parser counted and the accepted frames' restart intervals"""
+        o_fr, o_seg, o_ss, o_sc, o_huff = (c.base + o for o in c.at)
+        n_segs, n_huff = int(c.counts[0]), int(c.counts[1])
+        ok = c.views[0].view(FRAME_DTYPE)[c.pstatus == 0]
+        multi = progressive and int(c.counts[6]) > 0
+        sync = not multi and (entropy == "sync" or (entropy == "auto" and bool((ok["restart_interval"] == 0).any())))
+        need = sync_workspace_bytes(c.n, c.H, c.W, c.total, n_segs, sync_opts) if sync else workspace_bytes(c.n, c.H, c.W)
+        if sync and need == 0:
+            raise _lib.PoseRiskHipError(f"decode_files: sync_opts = {sync_opts!r}: subseq_bytes is a multiple of 4 in 16..4096 "
+                                        "(or 0 for the default), max_rounds 1..64")
+        args = _lib.JpegArgs(c.base, o_fr, o_seg, o_huff, c.out, c.status, c.total, c.n, c.H, c.W, n_segs, n_huff, int(bool(bgr)))
+        if multi:
+            sargs = _lib.JpegScansArgs(args, o_sc, o_ss, int(c.counts[4]), int(c.counts[5]))
+            return need, lambda *ws: _lib.check(lib.pr_jpeg_decode_scans(sargs, *ws), "pr_jpeg_decode_scans")
+        if sync:
+            st_ptr = sync_stats[c.lo:c.lo + c.n].data_ptr() if stats else None
+            return need, lambda *ws: _lib.check(lib.pr_jpeg_decode_sync(args, opts, st_ptr, *ws), "pr_jpeg_decode_sync")
+        return need, lambda *ws: _lib.check(lib.pr_jpeg_decode(args, *ws), "pr_jpeg_decode")
+
+    frames_out, status = _media.decode_chunks(
+        items, device, out, cut=lambda lo: [_media.size(p) for p in items[lo:lo + chunk]], rooms=rooms, regrow=regrow,
+        itemsizes=[FRAME_DTYPE.itemsize, SEGMENT_DTYPE.itemsize, 4, SCAN_DTYPE.itemsize, HUFF_DTYPE.itemsize], parse=parse_chunk,
+        parser="pr_jpeg_parse_scans" if progressive else "pr_jpeg_parse", used=1, sized=sized, decode=decode,
+        refusal_name=scan_refusal_name, refused=ST_REFUSED)
+    if not stats:
+        return frames_out, status
+    return frames_out, status, sync_stats if F else torch.zeros((0, 4), dtype=torch.int32, device=device)
 
 
 def bad_frames(paths_or_bytes, status, progressive=False):
     """[(frame index, reason)] for every frame of a decode_files call whose status is non-zero (one device -> host copy; a
     refused frame's file is parsed again on its own to name the parser's reason: with progressive=True, as the call was made,
     by the scan-aware parser)."""
-    items, st, out = list(paths_or_bytes), status.cpu().numpy(), []
-    for i in np.nonzero(st)[0]:
-        why = status_text(int(st[i]))
-        if st[i] & ST_REFUSED:
-            p = items[i]
-            blob = open(p, "rb").read() if isinstance(p, (str, os.PathLike)) else bytes(p)
-            _, _, _, pst, h, w, *_ = parse_scans([blob]) if progressive else parse([blob])
-            why = scan_refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
-        out.append((int(i), why))
-    return out
+    return _media.bad_frames(paths_or_bytes, status, status_text, parse_scans if progressive else parse, scan_refusal_name, ST_REFUSED)
 
 
 def encode_plan(quality, subsampling, restart_interval, H, W):

@@ -6,7 +6,8 @@ csrc/png_host.cc (host, no device), everything else csrc/png.hip over csrc/png_d
 The other direction -- `encode_frames`, u8 frames on the device to PNG files, section j5 -- is at the end of this file.
 
 `list_frames` orders a folder, `parse` is the host half, `decode_files` the whole thing: file bytes and descriptors of a chunk
-go through ONE pinned buffer and ONE upload, then pr_png_decode (gather, inflate, unfilter + Adler-32 + colour)."""
+go through ONE pinned buffer and ONE upload (_media.decode_chunks), then pr_png_decode (gather, inflate, unfilter + Adler-32 +
+colour)."""
 import ctypes as C
 import os
 
@@ -63,9 +64,7 @@ def _parse_into(data, offsets, H, W, frames, idat, palettes, pstatus):
 def parse(blobs, H=0, W=0):
     """Host half on a list of bytes objects: (frames FRAME_DTYPE[F], idat IDAT_DTYPE[N], palettes u8[P, 256, 3], parse_status
     int32[F], H, W, offsets int64[F+1]).  Refused frames have parse_status != 0 (refusal_name gives the words)."""
-    offsets = np.zeros(len(blobs) + 1, np.int64)
-    np.cumsum([len(b) for b in blobs], out=offsets[1:])
-    data = np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\0", np.uint8)
+    offsets, data = _media.pack(blobs)
     F = len(blobs)
     frames, pstatus = np.zeros(F, FRAME_DTYPE), np.zeros(F, np.int32)
     idat_cap, pal_cap = 16 + 2 * F, 1
@@ -84,14 +83,6 @@ def workspace_bytes(F, H, W, data_bytes):
     return int(_lib.load().pr_png_workspace_bytes(int(F), int(H), int(W), int(data_bytes)))
 
 
-def _align(n, a=256):
-    return (n + a - 1) // a * a
-
-
-def _size(p):
-    return os.path.getsize(p) if isinstance(p, (str, os.PathLike)) else len(p)
-
-
 def _peek_size(items):
     """(H, W) of the first item that starts like a PNG (its IHDR's numbers, unchecked: only chunks are sized by them)."""
     for p in items:
@@ -107,6 +98,16 @@ def _peek_size(items):
     return 0, 0
 
 
+def cut_chunk(sizes, lo, chunk, per_frame, max_bytes):
+    """How many of the files of `sizes` (bytes each) from `lo` on form the next chunk: at most `chunk`, and only as many as keep
+    the chunk's workspace and output (`per_frame` bytes a frame, the files' bytes, 32) within `max_bytes`; at least one."""
+    n, total = 0, 0
+    while lo + n < len(sizes) and n < chunk and (n == 0 or (n + 1) * per_frame + total + sizes[lo + n] + 32 <= max_bytes):
+        total += sizes[lo + n]
+        n += 1
+    return n
+
+
 def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=None, max_bytes=DEFAULT_MAX_BYTES):
     """Decode F PNG files (paths, or bytes objects) of one size to u8[F,H,W,3] on `device` (RGB, or BGR as cv2.imread gives with
     bgr=True; gray replicated, alpha dropped).  Returns (frames, status int32[F] on the device): status[f] != 0 marks a frame
@@ -118,105 +119,42 @@ def decode_files(paths_or_bytes, device, bgr=False, chunk=DEFAULT_CHUNK, out=Non
     decode) before it reads chunk k + 1 into the buffer."""
     device = _media.cuda_device(device, "decode_files", "the decoder runs")
     items = list(paths_or_bytes)
-    F, chunk = len(items), max(int(chunk), 1)
+    chunk = max(int(chunk), 1)
     lib = _lib.load()
-    sizes = [_size(p) for p in items]
-    H, W = 0, 0
+    sizes = [_media.size(p) for p in items]
     h0, w0 = _peek_size(items)
     per_frame = (h0 * (1 + 4 * w0) + 16 + 16) + h0 * w0 * 3      # workspace without the files' bytes, and the output
-    frames_out = status = pinned = ws = uploaded = first_refusal = None
-    idat_per_frame = 2
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device)
-        lo = 0
-        while lo < F:
-            n, total = 0, 0
-            while lo + n < F and n < chunk and (n == 0 or (n + 1) * per_frame + total + sizes[lo + n] + 32 <= max_bytes):
-                total += sizes[lo + n]
-                n += 1
-            part = items[lo:lo + n]
-            offsets = np.zeros(n + 1, np.int64)
-            np.cumsum(sizes[lo:lo + n], out=offsets[1:])
-            idat_room, pal_room = 16 + idat_per_frame * n, n
-            # [file bytes | frames | palettes | IDAT ranges]: the parser reads the bytes where they lie and writes beside them
-            o_fr = _align(max(total, 1))
-            o_pal = _align(o_fr + n * FRAME_DTYPE.itemsize)
-            o_idat = _align(o_pal + pal_room * PALETTE_BYTES)
-            room = o_idat + idat_room * IDAT_DTYPE.itemsize
-            if uploaded is not None:
-                uploaded.synchronize()                           # the previous chunk has left the buffer
-                uploaded = None
-            if pinned is None or pinned.numel() < room:
-                pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
-            host = pinned.numpy()
-            _media.read_files(host, part, offsets)
-            pst = np.zeros(n, np.int32)
-            while True:
-                fr = host[o_fr:o_fr + n * FRAME_DTYPE.itemsize].view(FRAME_DTYPE)
-                pal = host[o_pal:o_pal + pal_room * PALETTE_BYTES]
-                idat = host[o_idat:o_idat + idat_room * IDAT_DTYPE.itemsize].view(IDAT_DTYPE)
-                rc, counts = _parse_into(host[:max(total, 1)], offsets, H, W, fr, idat, pal, pst)
-                if rc != -4:                                     # PR_ERR_CAPACITY: more IDAT chunks than guessed
-                    _lib.check(rc, "pr_png_parse")
-                    break
-                idat_room = int(counts[0])
-                idat_per_frame = max(idat_per_frame, -(-idat_room // n))
-                room = o_idat + idat_room * IDAT_DTYPE.itemsize
-                if pinned.numel() < room:
-                    bigger = torch.empty(room, dtype=torch.uint8).pin_memory()
-                    bigger[:total] = pinned[:total]
-                    pinned, host = bigger, bigger.numpy()
-            n_idat, n_pal = int(counts[0]), int(counts[1])
-            if H == 0 and pst.any() and first_refusal is None:
-                first_refusal = (lo + int(np.nonzero(pst)[0][0]), refusal_name(pst[np.nonzero(pst)[0][0]]))
-            if H == 0 and counts[2]:
-                H, W = int(counts[2]), int(counts[3])
-                frames_out = out if out is not None else torch.empty((F, H, W, 3), dtype=torch.uint8, device=device)
-                if tuple(frames_out.shape) != (F, H, W, 3) or frames_out.dtype != torch.uint8 or not frames_out.is_contiguous() \
-                        or frames_out.device != device:
-                    raise ValueError(f"out must be a contiguous uint8 {[F, H, W, 3]} tensor on {device}")
-                status = torch.full((F,), ST_REFUSED, dtype=torch.int32, device=device)   # chunks before the first size
-                frames_out[:lo].zero_()
-                per_frame = (H * (1 + 4 * W) + 32) + H * W * 3
-            if H != 0:
-                used = o_idat + n_idat * IDAT_DTYPE.itemsize
-                dev = torch.empty(used, dtype=torch.uint8, device=device)
-                dev.copy_(pinned[:used], non_blocking=True)      # the chunk's one upload
-                uploaded = torch.cuda.Event()
-                uploaded.record(stream)
-                need = workspace_bytes(n, H, W, total)
-                if ws is None or ws.numel() < need:
-                    ws = torch.empty(need, dtype=torch.uint8, device=device)
-                base = dev.data_ptr()
-                args = _lib.PngArgs(base, base + o_fr, base + o_idat, base + o_pal, frames_out[lo:lo + n].data_ptr(),
-                                    status[lo:lo + n].data_ptr(), total, n, H, W, n_idat, n_pal, int(bool(bgr)))
-                _lib.check(lib.pr_png_decode(args, ws.data_ptr(), ws.numel(), stream.cuda_stream), "pr_png_decode")
-                dev.record_stream(stream)
-                ws.record_stream(stream)
-            lo += n
-        if uploaded is not None:
-            uploaded.synchronize()
-    if frames_out is None:
-        if first_refusal:
-            raise _lib.PoseRiskHipError(f"decode_files: no frame was accepted; frame {first_refusal[0]}: {first_refusal[1]}")
-        frames_out = torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device)
-        status = torch.zeros(0, dtype=torch.int32, device=device)
-    return frames_out, status
+    idat_per_frame = 2                                           # what a frame needed so far: only ever grows
+
+    def rooms(n):   # [frames | palettes | IDAT ranges]
+        return [n, n, 16 + idat_per_frame * n]
+
+    def regrow(n, room, counts):   # more IDAT chunks than guessed
+        nonlocal idat_per_frame
+        idat_per_frame = max(idat_per_frame, -(-int(counts[0]) // n))
+        return [n, n, int(counts[0])]
+
+    def sized(H, W):
+        nonlocal per_frame
+        per_frame = (H * (1 + 4 * W) + 32) + H * W * 3
+
+    def decode(c):
+        o_fr, o_pal, o_idat = (c.base + o for o in c.at)
+        args = _lib.PngArgs(c.base, o_fr, o_idat, o_pal, c.out, c.status, c.total, c.n, c.H, c.W, int(c.counts[0]), int(c.counts[1]),
+                            int(bool(bgr)))
+        return workspace_bytes(c.n, c.H, c.W, c.total), lambda *ws: _lib.check(lib.pr_png_decode(args, *ws), "pr_png_decode")
+
+    return _media.decode_chunks(
+        items, device, out, cut=lambda lo: sizes[lo:lo + cut_chunk(sizes, lo, chunk, per_frame, max_bytes)],
+        itemsizes=[FRAME_DTYPE.itemsize, PALETTE_BYTES, IDAT_DTYPE.itemsize], rooms=rooms, regrow=regrow,
+        parse=lambda data, offsets, H, W, v, pst: _parse_into(data, offsets, H, W, v[0].view(FRAME_DTYPE), v[2].view(IDAT_DTYPE), v[1], pst),
+        parser="pr_png_parse", used=0, sized=sized, decode=decode, refusal_name=refusal_name, refused=ST_REFUSED)
 
 
 def bad_frames(paths_or_bytes, status):
     """[(frame index, reason)] for every frame of a decode_files call whose status is non-zero (one device -> host copy; a
     refused frame's file is parsed again on its own to name the parser's reason)."""
-    items, st, out = list(paths_or_bytes), status.cpu().numpy(), []
-    for i in np.nonzero(st)[0]:
-        why = status_text(int(st[i]))
-        if st[i] & ST_REFUSED:
-            p = items[i]
-            blob = open(p, "rb").read() if isinstance(p, (str, os.PathLike)) else bytes(p)
-            _, _, _, pst, h, w, _ = parse([blob])
-            why = refusal_name(pst[0]) if pst[0] else f"its size {w}x{h} differs from the other frames of the call"
-        out.append((int(i), why))
-    return out
+    return _media.bad_frames(paths_or_bytes, status, status_text, parse, refusal_name, ST_REFUSED)
 
 
 # ---- the encoder (include/poserisk_hip.h, section j5): host half csrc/png_enc_host.cc, device half csrc/png_enc.hip ------------
