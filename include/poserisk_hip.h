@@ -1393,8 +1393,8 @@ int pr_yuv_encode(const pr_yuv_enc_args* args, void* stream);
  *   255-channel head layers is conv (no bias) + BatchNorm + leaky ReLU of slope 0.1 (v > 0 ? v : 0.1f * v); the head layers are
  *   conv + bias, linear.  Padding is k / 2.  A shortcut adds AFTER the activation and applies none to the sum:
  *   y = leaky(conv + b) + res, evaluated in that order in fp32.  Head channel = anchor * 85 + (x, y, w, h, obj, 80 classes).
- *   The input is S_h x S_w, each a multiple of 32 (default 416 x 416, the reference's yolo_img_size).  fp32 only, on
- *   v_mfma_f32_32x32x2_f32; activations NHWC.
+ *   The input is S_h x S_w, each a multiple of 32 (default 416 x 416, the reference's yolo_img_size).  fp32 on
+ *   v_mfma_f32_32x32x2_f32 by default (this paragraph and the next two), or bf16 (paragraph "bf16" below); activations NHWC.
  * Weights.  weights_host is the float body of a darknet weight file, unchanged (62 001 757 floats for the 80-class network): per
  *   BatchNorm convolution beta[O], gamma[O], running mean[O], running var[O], then the weights OIHW; per head convolution
  *   bias[255], then the weights OIHW.  BatchNorm is folded in float64: scale = gamma / sqrt(var + bn_eps), w' = (float)(w *
@@ -1402,7 +1402,26 @@ int pr_yuv_encode(const pr_yuv_enc_args* args, void* stream);
  *   is 1e-5 (nn.BatchNorm2d's default [unpinned]); darknet itself uses 1e-6.
  * Packed layout (pr_det_fold_pack; what the kernel reads): per convolution bias f32[cout_pad], then w f32[cout_pad][kpad] with
  *   k = (kh * ksize + kw) * cin_pad + ci, zero where padded; cin_pad = cin rounded up to 4, cout_pad = cout rounded up to 64,
- *   kpad = ksize^2 * cin_pad rounded up to 32. */
+ *   kpad = ksize^2 * cin_pad rounded up to 32.
+ *
+ * bf16.  A second precision beside fp32 (pr_det_create_p, precision = 1); fp32 stays the default and keeps its bits.
+ *   Weights: BatchNorm is folded in float64 exactly as above, giving w' and b' as float.  For every convolution but layer 0, w' is
+ *   then rounded to bfloat16, round to nearest even, as an integer operation on the float's bits (NaN stays NaN; past the
+ *   largest bf16 becomes infinity, as the device conversion does); the bias stays fp32.  Packed layout
+ *   (pr_det_fold_pack_bf16) per convolution: bias f32[cout_pad], then w bf16[cout_pad][kpad] (layer 0: w f32[cout_pad][kpad],
+ *   as above); k, cin_pad, cout_pad and kpad by the rules above, counted in elements (every Cin of the network but layer 0's is a
+ *   multiple of 32: nothing is padded in k).  A convolution's bias begins at the sum of the sizes of the convolutions in front of
+ *   it, in BYTES, which is a multiple of 16.
+ *   Layer 0 (3 x 3, 4 -> 32, on the fp32 letterbox) is computed exactly as in fp32 -- fp32 operands and weights on
+ *   v_mfma_f32_32x32x2_f32 -- and only its output is rounded to bf16 when stored: u8 / 255 is not representable in 8 mantissa
+ *   bits, K = 36 does not fit the bf16 loader, and the layer is 0.6 % of the FLOP.  pr_det_letterbox is unchanged.
+ *   Every other convolution takes bf16 operands on v_mfma_f32_32x32x16_bf16 and accumulates in fp32 in one fixed k order per
+ *   output, independent of B.  Epilogue in fp32, never fused: v = leaky(acc + b); where a shortcut follows, v = v + (float)res;
+ *   then v is rounded to bf16 ONCE.  A shortcut's tensor is bf16(leaky(acc + b) + res), not the sum of two rounded values;
+ *   pr_det_network_until on the convolution in front of a shortcut gives bf16(leaky(acc + b)).
+ *   The three head convolutions (81, 93, 105) read bf16 and write fp32, linear, un-rounded: pr_det_postprocess, the decode in
+ *   float64, ranking, NMS and the map back to the frame are the same code for both precisions.
+ *   Routes, upsamples and yolo layers move bf16 bits unchanged. */
 #define PR_DET_NUM_LAYERS 107
 #define PR_DET_MAX_CAND 1024   /* candidates that take part in NMS, per frame */
 enum { PR_DET_CONV = 0, PR_DET_SHORTCUT = 1, PR_DET_ROUTE = 2, PR_DET_UPSAMPLE = 3, PR_DET_YOLO = 4 };
@@ -1429,6 +1448,11 @@ size_t pr_det_weight_floats(int n_layers);
 size_t pr_det_packed_floats(int n_layers);
 int pr_det_fold_pack(int n_layers, const float* weights_host, size_t n_floats, double bn_eps, float* packed_host,
                      size_t packed_floats);
+/* The bf16 layout (paragraph "bf16" above): its size in bytes (0 for n_layers outside 1..107) and the fold; the same refusals by
+ * name, with packed_bytes in place of packed_floats.  packed_host needs no alignment. */
+size_t pr_det_packed_bytes_bf16(int n_layers);
+int pr_det_fold_pack_bf16(int n_layers, const float* weights_host, size_t n_floats, double bn_eps, void* packed_host,
+                          size_t packed_bytes);
 
 /* Handle.  pr_det_create folds, packs and uploads the weights and allocates every activation buffer for max_batch frames of
  * S_h x S_w (through the internal fence where POSERISK_FENCE is set; every tensor stays below 2 GiB, else PR_ERR_INVALID), the
@@ -1439,6 +1463,14 @@ int pr_det_fold_pack(int n_layers, const float* weights_host, size_t n_floats, d
 typedef struct pr_det pr_det_t;
 int pr_det_create(int device, const float* weights_host, size_t n_floats, int S_h, int S_w, int max_batch, double bn_eps,
                   pr_det_t** out);
+/* pr_det_create_p: the same with a precision: 0 = fp32 (what pr_det_create passes), 1 = bf16 (paragraph "bf16": activation
+ * buffers of 2-byte elements, the head tensors' of 4); anything else is refused by name.  pr_det_precision: the handle's (-1 for
+ * NULL).  pr_det_elem_bytes: bytes of one element of layer `layer`'s output, as pr_det_network_until writes it: 4, or on a bf16
+ * handle 2 for every layer but 81, 82, 93, 94, 105 and 106 (0 for NULL or a layer outside 0..106). */
+int pr_det_create_p(int device, const float* weights_host, size_t n_floats, int S_h, int S_w, int max_batch, double bn_eps,
+                    int precision, pr_det_t** out);
+int pr_det_precision(const pr_det_t* h);
+int pr_det_elem_bytes(const pr_det_t* h, int layer);
 int pr_det_destroy(pr_det_t* h);
 int pr_det_input_size(const pr_det_t* h, int* S_h, int* S_w);
 int pr_det_max_batch(const pr_det_t* h);
@@ -1462,7 +1494,9 @@ int pr_det_grid(const pr_det_t* h, int layer, int* gh, int* gw, int* channels);
  * pr_det_network: x_dev f32[B,S_h,S_w,4] -> the three head tensors head{32,16,8}_dev f32[B,gh,gw,255], gh = S_h / stride.
  * pr_det_network_until: the output of layer `layer` (0..106) as act_dev f32[B,gh,gw,C] (pr_det_grid): a convolution's (with its
  *   activation, without the shortcut behind it), a shortcut's sum, an upsample's, a route's concatenation (sources in the
- *   route's order), a yolo layer's = the head convolution's output unchanged.  (pr_hmr_encode_until's precedent.)
+ *   route's order), a yolo layer's = the head convolution's output unchanged.  (pr_hmr_encode_until's precedent.)  On a bf16
+ *   handle act_dev holds bf16 bits, or fp32 for layers 81, 82, 93, 94, 105 and 106 (pr_det_elem_bytes); pr_det_network's and
+ *   pr_det_postprocess' head tensors are fp32 on both.
  *
  * pr_det_postprocess: the three head tensors -> per frame at most max_det person boxes: boxes_dev f32[B,max_det,4] (x1, y1, x2,
  *   y2 in letterbox pixels), scores_dev f32[B,max_det], count_dev i32[B], status_dev i32[B] (PR_DET_STATUS_* bits); rows
@@ -1493,9 +1527,14 @@ int pr_det_grid(const pr_det_t* h, int layer, int* gh, int* gw, int* channels);
  * device pointers; asynchronous, no allocation (capturable); refusals by name, a tensor of 2 GiB or more included. */
 int pr_det_conv_nhwc(const float* x_dev, const float* packed_dev, const float* res_dev, float* y_dev, int B, int H, int W, int Cin,
                      int Cout, int ksize, int stride, int leaky, void* stream);
+/* The bf16 convolution alone (csrc/det_conv_bf16.hip): x_dev bf16[B,H,W,Cin] (Cin a multiple of 8), packed_dev = ONE
+ * convolution as bias f32[cout_pad], then w bf16[cout_pad][kpad], res_dev bf16[B,Ho,Wo,Cout] or NULL -> y_dev bf16[B,Ho,Wo,Cout],
+ * or f32 with out_f32 != 0, = round(leaky(acc + b) [+ (float)res]), rounded once (not at all for f32).  Otherwise as above. */
+int pr_det_conv_nhwc_bf16(const void* x_dev, const void* packed_dev, const void* res_dev, void* y_dev, int B, int H, int W, int Cin,
+                          int Cout, int ksize, int stride, int leaky, int out_f32, void* stream);
 int pr_det_letterbox(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, int bgr, float* x_dev, void* stream);
 int pr_det_network(pr_det_t* h, const float* x_dev, int B, float* head32_dev, float* head16_dev, float* head8_dev, void* stream);
-int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, float* act_dev, void* stream);
+int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, void* act_dev, void* stream);
 int pr_det_postprocess(pr_det_t* h, const float* head32_dev, const float* head16_dev, const float* head8_dev, int B,
                        float conf_thres, float nms_thres, int max_det, float* boxes_dev, float* scores_dev, int32_t* count_dev,
                        int32_t* status_dev, void* stream);

@@ -204,6 +204,12 @@ SIGNATURES = {
     "pr_det_weight_floats": (C.c_size_t, [_I]),
     "pr_det_packed_floats": (C.c_size_t, [_I]),
     "pr_det_fold_pack": (_I, [_I, _P, C.c_size_t, C.c_double, _P, C.c_size_t]),
+    "pr_det_packed_bytes_bf16": (C.c_size_t, [_I]),
+    "pr_det_fold_pack_bf16": (_I, [_I, _P, C.c_size_t, C.c_double, _P, C.c_size_t]),
+    "pr_det_create_p": (_I, [_I, _P, C.c_size_t, _I, _I, _I, C.c_double, _I, C.POINTER(_P)]),
+    "pr_det_precision": (_I, [_P]),
+    "pr_det_elem_bytes": (_I, [_P, _I]),
+    "pr_det_conv_nhwc_bf16": (_I, [_P, _P, _P, _P] + [_I] * 9 + [_P]),
     "pr_det_create": (_I, [_I, _P, C.c_size_t, _I, _I, _I, C.c_double, C.POINTER(_P)]),
     "pr_det_destroy": (_I, [_P]),
     "pr_det_input_size": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),

@@ -13,9 +13,11 @@
 
 struct pr_det {
   int device = 0, S_h = 0, S_w = 0, max_batch = 0, fence = 0;
+  int precision = 0;                       // 0: fp32, 1: the bf16 contract (activations bf16, head tensors fp32)
   pr::DetPlan plan;
-  float* packed = nullptr;                 // the folded weights, pr_det_fold_pack's layout
-  std::vector<float*> slots;               // activation buffers, max_batch frames of plan.slot_floats each
+  float* packed = nullptr;                 // the folded weights: pr_det_fold_pack's layout, or pr_det_fold_pack_bf16's
+  std::vector<int64_t> pack_off_bf16;      // bf16: per layer the byte offset of its bias in `packed`
+  std::vector<float*> slots;               // activation buffers, max_batch frames of plan.slot_frame_bytes each
   std::vector<size_t> slot_bytes;
   float* canvas = nullptr;                 // pr_det_detect's letterboxed input, f32[max_batch,S_h,S_w,4]
   float* cand = nullptr;                   // f32[max_batch][cells][6]: score, flat index (as int bits), x1, y1, x2, y2
@@ -140,7 +142,7 @@ __global__ void __launch_bounds__(kDetThreads) det_concat_kernel(ConcatParams p)
 }
 
 int concat_launch(const float* a, const float* b, float* out, int B, int gh, int gw, int Ca, int Cb, int sa, hipStream_t stream) {
-  PR_REQUIRE(Ca % 4 == 0 && Cb % 4 == 0 && Ca > 0, "detector: concat of %d + %d channels", Ca, Cb);
+  PR_REQUIRE(Ca % 4 == 0 && Cb % 4 == 0 && Ca > 0, "detector: concat of %d + %d 4-byte words a pixel", Ca, Cb);
   ConcatParams p{a, b, out, B, gh, gw, Ca, Cb, sa};
   const long blocks = ceil_div((long)B * gh * gw * ((Ca + Cb) / 4), (long)kDetThreads);
   hipLaunchKernelGGL(det_concat_kernel, dim3((unsigned)blocks), dim3(kDetThreads), 0, stream, p);
@@ -264,9 +266,13 @@ float* placed(const pr_det* h, int slot, size_t bytes) {
   if (h->fence != 2 || bytes > h->slot_bytes[slot]) return reinterpret_cast<float*>(base);
   return reinterpret_cast<float*>(base + (h->slot_bytes[slot] - bytes) / 16 * 16);
 }
+size_t tensor_bytes(const pr_det* h, int layer, int B) {
+  const auto& P = h->plan;
+  return (size_t)B * P.gh[layer] * P.gw[layer] * P.layers[layer].cout * P.elem_bytes[layer];
+}
 float* tensor_of(const pr_det* h, int layer, int B) {
   const auto& P = h->plan;
-  return placed(h, P.slot[layer], (size_t)B * P.gh[layer] * P.gw[layer] * P.layers[layer].cout * sizeof(float));
+  return placed(h, P.slot[layer], tensor_bytes(h, layer, B));
 }
 
 template <typename T>
@@ -279,7 +285,7 @@ int det_alloc(pr_det* h, T** out, size_t bytes, size_t frame_bytes, const char* 
 }
 
 int det_build(pr_det* h, const float* weights_host, size_t n_floats, double bn_eps) {
-  PR_TRY(det_plan(h->S_h, h->S_w, &h->plan));
+  PR_TRY(det_plan(h->S_h, h->S_w, &h->plan, h->precision));
   const auto& P = h->plan;
   const size_t lim = 0x7fffffffu;
   for (int l = 0; l < kDetLayers; ++l)
@@ -287,18 +293,23 @@ int det_build(pr_det* h, const float* weights_host, size_t n_floats, double bn_e
                    (size_t)h->max_batch * h->S_h * h->S_w * 4 * sizeof(float) <= lim,
                "pr_det_create: %d frames of %d x %d make an activation tensor of 2 GiB or more; lower max_batch", h->max_batch, h->S_w,
                h->S_h);
-  const size_t packed_floats = pr_det_packed_floats(kDetLayers);
-  std::vector<float> packed(packed_floats);
-  PR_TRY(pr_det_fold_pack(kDetLayers, weights_host, n_floats, bn_eps, packed.data(), packed_floats));
-  PR_TRY(det_alloc(h, &h->packed, packed_floats * sizeof(float), 0, "packed weights"));
-  PR_HIP(hipMemcpy(h->packed, packed.data(), packed_floats * sizeof(float), hipMemcpyHostToDevice));
-  h->slots.resize(P.slot_floats.size());
-  h->slot_bytes.resize(P.slot_floats.size());
-  for (size_t s = 0; s < P.slot_floats.size(); ++s) {
+  const size_t packed_bytes = h->precision ? pr_det_packed_bytes_bf16(kDetLayers) : pr_det_packed_floats(kDetLayers) * sizeof(float);
+  std::vector<float> packed(packed_bytes / sizeof(float));      // both layouts are whole floats long
+  if (h->precision) {
+    PR_TRY(pr_det_fold_pack_bf16(kDetLayers, weights_host, n_floats, bn_eps, packed.data(), packed_bytes));
+    det_pack_offsets_bf16(kDetLayers, &h->pack_off_bf16);
+  } else {
+    PR_TRY(pr_det_fold_pack(kDetLayers, weights_host, n_floats, bn_eps, packed.data(), packed.size()));
+  }
+  PR_TRY(det_alloc(h, &h->packed, packed_bytes, 0, "packed weights"));
+  PR_HIP(hipMemcpy(h->packed, packed.data(), packed_bytes, hipMemcpyHostToDevice));
+  h->slots.resize(P.slot_frame_bytes.size());
+  h->slot_bytes.resize(P.slot_frame_bytes.size());
+  for (size_t s = 0; s < P.slot_frame_bytes.size(); ++s) {
     char name[32];
     snprintf(name, sizeof name, "act[%zu]", s);
-    h->slot_bytes[s] = (P.slot_floats[s] * h->max_batch * sizeof(float) + 255) / 256 * 256;
-    PR_TRY(det_alloc(h, &h->slots[s], h->slot_bytes[s], P.slot_floats[s] * sizeof(float), name));
+    h->slot_bytes[s] = (P.slot_frame_bytes[s] * h->max_batch + 255) / 256 * 256;
+    PR_TRY(det_alloc(h, &h->slots[s], h->slot_bytes[s], P.slot_frame_bytes[s], name));
   }
   h->cells = 0;
   for (int i = 0; i < 3; ++i) h->cells += 3 * P.gh[kHeadLayer[i]] * P.gw[kHeadLayer[i]];
@@ -318,12 +329,30 @@ int det_walk(pr_det* h, const float* x, int B, int until, float* const* heads, h
     const pr_det_layer& c = L[l];
     if (c.type == PR_DET_CONV) {
       const bool fused = l + 1 <= until && L[l + 1].type == PR_DET_SHORTCUT;
+      if (h->precision && l > 0) {      // bf16 operands; layer 0 stays on the fp32 kernel below and only stores bf16
+        DetConvBf16Problem q;
+        q.x = tensor_of(h, l - 1, B);
+        q.B = B, q.H = P.gh[l - 1], q.W = P.gw[l - 1];
+        q.Cin = c.cin_pad, q.Ho = P.gh[l], q.Wo = P.gw[l], q.Cout = c.cout, q.cout_pad = c.cout_pad, q.kpad = c.kpad;
+        q.ksize = c.ksize, q.stride = c.stride, q.leaky = c.bn, q.out_f32 = P.elem_bytes[l] == 4;
+        const char* blob = reinterpret_cast<const char*>(h->packed) + h->pack_off_bf16[l];
+        q.bias = reinterpret_cast<const float*>(blob);
+        q.w = blob + (size_t)c.cout_pad * 4;
+        q.res = fused ? tensor_of(h, L[l + 1].from0, B) : nullptr;
+        q.y = tensor_of(h, l, B);
+        if (heads)
+          for (int i = 0; i < 3; ++i)
+            if (l == kHeadLayer[i]) q.y = heads[i];
+        PR_TRY(det_conv_bf16_launch(q, stream));
+        if (fused) ++l;
+        continue;
+      }
       DetConvProblem p;
       p.x = l == 0 ? x : tensor_of(h, l - 1, B);
       p.B = B, p.H = l == 0 ? h->S_h : P.gh[l - 1], p.W = l == 0 ? h->S_w : P.gw[l - 1];
       p.Cin = c.cin_pad, p.Ho = P.gh[l], p.Wo = P.gw[l], p.Cout = c.cout, p.cout_pad = c.cout_pad, p.kpad = c.kpad;
-      p.ksize = c.ksize, p.stride = c.stride, p.leaky = c.bn;
-      p.bias = h->packed + c.pack_offset;
+      p.ksize = c.ksize, p.stride = c.stride, p.leaky = c.bn, p.out_bf16 = h->precision;
+      p.bias = h->packed + c.pack_offset;      // layer 0 begins both blobs and has the same layout in both
       p.w = p.bias + c.cout_pad;
       p.res = fused ? tensor_of(h, L[l + 1].from0, B) : nullptr;
       p.y = tensor_of(h, l, B);
@@ -333,19 +362,22 @@ int det_walk(pr_det* h, const float* x, int B, int until, float* const* heads, h
       PR_TRY(det_conv_launch(p, stream));
       if (fused) ++l;
     } else if (c.type == PR_DET_UPSAMPLE) {
+      // the copy kernel moves 16-byte chunks of 4-byte words: two bf16 channels make one word (channels are multiples of 8)
+      const int cw = h->precision ? 2 : 1;
       // with the concatenation behind it wanted too, the upsampled tensor is never written: one kernel fills the route's
       const bool into = l + 1 <= until && L[l + 1].type == PR_DET_ROUTE && L[l + 1].from0 == l && L[l + 1].from1 >= 0;
       if (into) {
         const int o = l + 1;
-        PR_TRY(concat_launch(tensor_of(h, l - 1, B), tensor_of(h, L[o].from1, B), tensor_of(h, o, B), B, P.gh[o], P.gw[o], c.cout,
-                             L[L[o].from1].cout, 1, stream));
+        PR_TRY(concat_launch(tensor_of(h, l - 1, B), tensor_of(h, L[o].from1, B), tensor_of(h, o, B), B, P.gh[o], P.gw[o], c.cout / cw,
+                             L[L[o].from1].cout / cw, 1, stream));
         ++l;
       } else {
-        PR_TRY(concat_launch(tensor_of(h, l - 1, B), nullptr, tensor_of(h, l, B), B, P.gh[l], P.gw[l], c.cout, 0, 1, stream));
+        PR_TRY(concat_launch(tensor_of(h, l - 1, B), nullptr, tensor_of(h, l, B), B, P.gh[l], P.gw[l], c.cout / cw, 0, 1, stream));
       }
     } else if (c.type == PR_DET_ROUTE && c.from1 >= 0) {
-      PR_TRY(concat_launch(tensor_of(h, c.from0, B), tensor_of(h, c.from1, B), tensor_of(h, l, B), B, P.gh[l], P.gw[l], L[c.from0].cout,
-                           L[c.from1].cout, 0, stream));
+      const int cw = h->precision ? 2 : 1;
+      PR_TRY(concat_launch(tensor_of(h, c.from0, B), tensor_of(h, c.from1, B), tensor_of(h, l, B), B, P.gh[l], P.gw[l],
+                           L[c.from0].cout / cw, L[c.from1].cout / cw, 0, stream));
     } else {
       PR_REQUIRE(c.type != PR_DET_SHORTCUT, "detector: internal error, the shortcut at layer %d has no convolution in front", l);
     }
@@ -405,8 +437,15 @@ int check_frames(const void* frames, int H, int W, const char* what) {
 extern "C" {
 
 int pr_det_create(int device, const float* weights_host, size_t n_floats, int S_h, int S_w, int max_batch, double bn_eps, pr_det_t** out) {
+  return pr_det_create_p(device, weights_host, n_floats, S_h, S_w, max_batch, bn_eps, 0, out);
+}
+
+// the messages keep pr_det_create's name: it is the fp32 entry's text, and the bf16 handle is refused for the same reasons
+int pr_det_create_p(int device, const float* weights_host, size_t n_floats, int S_h, int S_w, int max_batch, double bn_eps, int precision,
+                    pr_det_t** out) {
   using namespace pr;
   PR_REQUIRE(out, "pr_det_create: null out");
+  PR_REQUIRE(precision == 0 || precision == 1, "pr_det_create_p: precision = %d, must be 0 (fp32) or 1 (bf16)", precision);
   PR_REQUIRE(weights_host, "pr_det_create: null weights_host");
   PR_REQUIRE(n_floats == pr_det_weight_floats(kDetLayers), "pr_det_create: n_floats = %zu, but the network holds %zu", n_floats,
              pr_det_weight_floats(kDetLayers));
@@ -423,7 +462,7 @@ int pr_det_create(int device, const float* weights_host, size_t n_floats, int S_
   DeviceGuard g(device);
   PR_TRY(refuse_under_declared_capture("pr_det_create"));
   std::unique_ptr<pr_det> h(new pr_det);
-  h->device = device, h->S_h = S_h, h->S_w = S_w, h->max_batch = max_batch;
+  h->device = device, h->S_h = S_h, h->S_w = S_w, h->max_batch = max_batch, h->precision = precision;
   h->fence = fence_mode_from_env();
   const int st = det_build(h.get(), weights_host, n_floats, bn_eps);
   if (st != PR_OK) {
@@ -451,6 +490,12 @@ int pr_det_input_size(const pr_det_t* h, int* S_h, int* S_w) {
 }
 
 int pr_det_max_batch(const pr_det_t* h) { return h ? h->max_batch : 0; }
+
+int pr_det_precision(const pr_det_t* h) { return h ? h->precision : -1; }
+
+int pr_det_elem_bytes(const pr_det_t* h, int layer) {
+  return h && layer >= 0 && layer < pr::kDetLayers ? h->plan.elem_bytes[layer] : 0;
+}
 
 int pr_det_grid(const pr_det_t* h, int layer, int* gh, int* gw, int* channels) {
   using namespace pr;
@@ -481,6 +526,28 @@ int pr_det_conv_nhwc(const float* x_dev, const float* packed_dev, const float* r
   return det_conv_launch(p, (hipStream_t)stream);
 }
 
+int pr_det_conv_nhwc_bf16(const void* x_dev, const void* packed_dev, const void* res_dev, void* y_dev, int B, int H, int W, int Cin, int Cout,
+                          int ksize, int stride, int leaky, int out_f32, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(x_dev, "pr_det_conv_nhwc_bf16: null x_dev");
+  PR_REQUIRE(packed_dev, "pr_det_conv_nhwc_bf16: null packed_dev");
+  PR_REQUIRE(y_dev, "pr_det_conv_nhwc_bf16: null y_dev");
+  PR_REQUIRE(B >= 0 && Cout >= 1 && Cout <= 65536, "pr_det_conv_nhwc_bf16: B %d, Cout %d", B, Cout);
+  PR_REQUIRE(Cin >= 8 && Cin <= 65536 && Cin % 8 == 0, "pr_det_conv_nhwc_bf16: Cin = %d, must be a multiple of 8 in 8..65536", Cin);
+  PR_REQUIRE(ksize == 1 || ksize == 3, "pr_det_conv_nhwc_bf16: ksize = %d, must be 1 or 3", ksize);
+  PR_REQUIRE(stride == 1 || stride == 2, "pr_det_conv_nhwc_bf16: stride = %d, must be 1 or 2", stride);
+  PR_REQUIRE(H >= 1 && W >= 1 && H <= 65536 && W <= 65536, "pr_det_conv_nhwc_bf16: H %d, W %d", H, W);
+  if (B == 0) return PR_OK;
+  DetConvBf16Problem p;
+  p.x = x_dev, p.res = res_dev, p.y = y_dev, p.B = B, p.H = H, p.W = W, p.Cin = Cin, p.Cout = Cout, p.ksize = ksize, p.stride = stride;
+  p.leaky = leaky != 0, p.out_f32 = out_f32 != 0;
+  p.Ho = (H + 2 * (ksize / 2) - ksize) / stride + 1, p.Wo = (W + 2 * (ksize / 2) - ksize) / stride + 1;
+  p.cout_pad = (Cout + kDetCoutTile - 1) / kDetCoutTile * kDetCoutTile;
+  p.kpad = (ksize * ksize * Cin + kDetKTile - 1) / kDetKTile * kDetKTile;
+  p.bias = static_cast<const float*>(packed_dev), p.w = static_cast<const char*>(packed_dev) + (size_t)p.cout_pad * 4;
+  return det_conv_bf16_launch(p, (hipStream_t)stream);
+}
+
 int pr_det_letterbox(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, int bgr, float* x_dev, void* stream) {
   using namespace pr;
   PR_TRY(check_common(h, B, "pr_det_letterbox"));
@@ -502,7 +569,7 @@ int pr_det_network(pr_det_t* h, const float* x_dev, int B, float* head32_dev, fl
   return det_walk(h, x_dev, B, kDetLayers - 1, heads, (hipStream_t)stream);
 }
 
-int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, float* act_dev, void* stream) {
+int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, void* act_dev, void* stream) {
   using namespace pr;
   PR_TRY(check_common(h, B, "pr_det_network_until"));
   PR_REQUIRE(x_dev, "pr_det_network_until: null x_dev");
@@ -510,8 +577,7 @@ int pr_det_network_until(pr_det_t* h, const float* x_dev, int B, int layer, floa
   PR_REQUIRE(layer >= 0 && layer < kDetLayers, "pr_det_network_until: layer = %d, must lie in 0..%d", layer, kDetLayers - 1);
   if (B == 0) return PR_OK;
   PR_TRY(det_walk(h, x_dev, B, layer, nullptr, (hipStream_t)stream));
-  const size_t bytes = (size_t)B * h->plan.gh[layer] * h->plan.gw[layer] * h->plan.layers[layer].cout * sizeof(float);
-  PR_HIP(hipMemcpyAsync(act_dev, tensor_of(h, layer, B), bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  PR_HIP(hipMemcpyAsync(act_dev, tensor_of(h, layer, B), tensor_bytes(h, layer, B), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return PR_OK;
 }
 

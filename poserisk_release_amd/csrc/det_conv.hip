@@ -35,6 +35,8 @@ __device__ __forceinline__ float det_act(float acc, float b, int leaky) {
   return (leaky && !(v > 0.f)) ? 0.1f * v : v;
 }
 
+// kOutBf16: y is bf16, each value rounded once when stored (layer 0 of a bf16 handle); false is the fp32 kernel, unchanged
+template <bool kOutBf16>
 __global__ void __launch_bounds__(kThreads) det_conv_kernel(DetConvProblem p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   __shared__ __attribute__((aligned(16))) float sW[kBN * kRow];
@@ -112,7 +114,7 @@ __global__ void __launch_bounds__(kThreads) det_conv_kernel(DetConvProblem p) {
 
   // epilogue: acc[4 q + j] = channel n0 + 32 wn + 8 q + 4 (lane >> 5) + j of pixel m0 + 32 wm + (lane & 31)
   const int pix = m0 + wm * 32 + (lane & 31);
-  const int ybytes = M * p.Cout * 4;
+  const int ybytes = M * p.Cout * (kOutBf16 ? 2 : 4);
   const auto ysrc = make_rsrc(p.y, ybytes);
   const auto rsrc = make_rsrc(p.res ? p.res : p.y, ybytes);
   const bool vec = (p.Cout & 3) == 0;
@@ -123,7 +125,20 @@ __global__ void __launch_bounds__(kThreads) det_conv_kernel(DetConvProblem p) {
     f32x4 v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = det_act(acc[4 * q + j], b[j], p.leaky);
-    if (vec) {
+    if constexpr (kOutBf16) {      // no residual (the launcher refuses one): 8 bytes a run, or 2 bytes a value where Cout % 4 != 0
+      const unsigned lo = pack_bf16x2(v[0], v[1]), hi = pack_bf16x2(v[2], v[3]);
+      if (vec) {
+        const unsigned off = (pix < M && c < p.Cout) ? ((unsigned)pix * (unsigned)p.Cout + (unsigned)c) * 2u : kOOB;
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{lo, hi}, ysrc, off, 0, 0);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned off = (pix < M && c + j < p.Cout) ? ((unsigned)pix * (unsigned)p.Cout + (unsigned)(c + j)) * 2u : kOOB;
+          const unsigned word = j < 2 ? lo : hi;
+          __builtin_amdgcn_raw_buffer_store_b16((unsigned short)((j & 1) ? word >> 16 : word & 0xffffu), ysrc, off, 0, 0);
+        }
+      }
+    } else if (vec) {
       const unsigned off = (pix < M && c < p.Cout) ? ((unsigned)pix * (unsigned)p.Cout + (unsigned)c) * 4u : kOOB;
       if (p.res) {
         const f32x4 r = load4(rsrc, off);
@@ -163,7 +178,12 @@ int det_conv_launch(const DetConvProblem& p, hipStream_t stream) {
   PR_REQUIRE((long)p.B * p.H * p.W * p.Cin * 4 <= lim && p.M() * p.Cout * 4 <= lim && (long)p.cout_pad * p.kpad * 4 <= lim,
              "det_conv: a tensor of 2 GiB or more (B %d, %d x %d x %d -> %d x %d x %d)", p.B, p.H, p.W, p.Cin, p.Ho, p.Wo, p.Cout);
   const dim3 grid((unsigned)ceil_div(p.M(), (long)kBM), (unsigned)(p.cout_pad / kBN));
-  hipLaunchKernelGGL(det_conv_kernel, grid, dim3(kThreads), 0, stream, p);
+  if (p.out_bf16) {
+    PR_REQUIRE(!p.res, "det_conv: a residual with bf16 output is not covered");
+    hipLaunchKernelGGL(det_conv_kernel<true>, grid, dim3(kThreads), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL(det_conv_kernel<false>, grid, dim3(kThreads), 0, stream, p);
+  }
   return check_launch("det_conv_kernel");
 }
 

@@ -90,6 +90,25 @@ const std::vector<pr_det_layer>& full_table() {
 
 bool det_n_ok(int n) { return n >= 1 && n <= kDetLayers; }
 
+// One convolution folded in float64: bias[o] = b', put(o * kpad + tap * cin_pad + ci, w') for every weight (OIHW in the body)
+template <typename Put>
+void fold_conv(const pr_det_layer& c, const float* src, double bn_eps, float* bias, Put put) {
+  const float* wsrc = src + (size_t)c.cout * (c.bn ? 4 : 1);
+  const int kk = c.ksize * c.ksize;
+  for (int o = 0; o < c.cout; ++o) {
+    double scale = 1.0, shift = src[o];                              // head: bias, weights as they are
+    if (c.bn) {                                                      // darknet order: beta, gamma, mean, var
+      const double beta = src[o], gamma = src[c.cout + o], mean = src[2 * c.cout + o], var = src[3 * c.cout + o];
+      scale = gamma / std::sqrt(var + bn_eps);
+      shift = beta - mean * scale;
+    }
+    bias[o] = (float)shift;
+    for (int ci = 0; ci < c.cin; ++ci)
+      for (int t2 = 0; t2 < kk; ++t2)
+        put((size_t)o * c.kpad + (size_t)t2 * c.cin_pad + ci, (float)(wsrc[((size_t)o * c.cin + ci) * kk + t2] * scale));
+  }
+}
+
 }  // namespace
 
 void det_topology(int n_layers, std::vector<pr_det_layer>* out) {
@@ -97,7 +116,19 @@ void det_topology(int n_layers, std::vector<pr_det_layer>* out) {
   out->assign(t.begin(), t.begin() + n_layers);
 }
 
-int det_plan(int S_h, int S_w, DetPlan* plan) {
+void det_pack_offsets_bf16(int n_layers, std::vector<int64_t>* out) {
+  const auto& t = full_table();
+  out->assign(n_layers, -1);
+  int64_t off = 0;
+  for (int l = 0; l < n_layers; ++l) {
+    if (t[l].type != PR_DET_CONV) continue;
+    (*out)[l] = off;                                      // layer 0 keeps fp32 weights: it runs on the fp32 MFMA
+    off += (int64_t)t[l].cout_pad * 4 + (int64_t)t[l].cout_pad * t[l].kpad * (l == 0 ? 4 : 2);
+  }
+}
+
+int det_plan(int S_h, int S_w, DetPlan* plan, int precision) {
+  PR_REQUIRE(precision == 0 || precision == 1, "detector: precision = %d, must be 0 (fp32) or 1 (bf16)", precision);
   PR_REQUIRE(S_h >= 32 && S_w >= 32 && S_h % 32 == 0 && S_w % 32 == 0 && S_h <= 4096 && S_w <= 4096,
              "detector: the network input %d x %d (S_w x S_h) must be multiples of 32 in 32..4096", S_w, S_h);
   det_topology(kDetLayers, &plan->layers);
@@ -125,6 +156,10 @@ int det_plan(int S_h, int S_w, DetPlan* plan) {
   plan->slot.assign(n, -1);
   plan->gh.resize(n), plan->gw.resize(n);
   plan->slot_floats.clear();
+  plan->slot_frame_bytes.clear();
+  plan->elem_bytes.assign(n, precision == 1 ? 2 : 4);
+  for (int l = 0; l < n; ++l)      // a head convolution writes fp32 in either precision; the yolo layer behind it is its view
+    if (L[l].type == PR_DET_YOLO) plan->elem_bytes[l] = plan->elem_bytes[l - 1] = 4;
   std::vector<char> busy;
   for (int l = 0; l < n; ++l) {
     plan->gh[l] = S_h / L[l].down, plan->gw[l] = S_w / L[l].down;
@@ -134,10 +169,11 @@ int det_plan(int S_h, int S_w, DetPlan* plan) {
     } else {                                            // the output's buffer is taken BEFORE the inputs' are released
       size_t s = 0;
       while (s < busy.size() && busy[s]) ++s;
-      if (s == busy.size()) busy.push_back(0), plan->slot_floats.push_back(0);
+      if (s == busy.size()) busy.push_back(0), plan->slot_floats.push_back(0), plan->slot_frame_bytes.push_back(0);
       busy[s] = 1;
       plan->slot[l] = (int)s;
       plan->slot_floats[s] = std::max(plan->slot_floats[s], floats);
+      plan->slot_frame_bytes[s] = std::max(plan->slot_frame_bytes[s], floats * plan->elem_bytes[l]);
     }
     for (int t = 0; t <= l; ++t)
       if (store[t] == t && last[t] == l) busy[plan->slot[t]] = 0;
@@ -194,23 +230,54 @@ int pr_det_fold_pack(int n_layers, const float* weights_host, size_t n_floats, d
   for (int l = 0; l < n_layers; ++l) {
     const pr_det_layer& c = t[l];
     if (c.type != PR_DET_CONV) continue;
-    const float* src = weights_host + c.weight_offset;
     float* bias = packed_host + c.pack_offset;
     float* w = bias + c.cout_pad;
-    const float* wsrc = src + (size_t)c.cout * (c.bn ? 4 : 1);
-    const int kk = c.ksize * c.ksize;
-    for (int o = 0; o < c.cout; ++o) {
-      double scale = 1.0, shift = src[o];                              // head: bias, weights as they are
-      if (c.bn) {                                                      // darknet order: beta, gamma, mean, var
-        const double beta = src[o], gamma = src[c.cout + o], mean = src[2 * c.cout + o], var = src[3 * c.cout + o];
-        scale = gamma / std::sqrt(var + bn_eps);
-        shift = beta - mean * scale;
-      }
-      bias[o] = (float)shift;
-      for (int ci = 0; ci < c.cin; ++ci)
-        for (int t2 = 0; t2 < kk; ++t2)                                // OIHW -> k = tap * cin_pad + ci
-          w[(size_t)o * c.kpad + (size_t)t2 * c.cin_pad + ci] = (float)(wsrc[((size_t)o * c.cin + ci) * kk + t2] * scale);
+    fold_conv(c, weights_host + c.weight_offset, bn_eps, bias, [&](size_t i, float v) { w[i] = v; });
+  }
+  return PR_OK;
+}
+
+size_t pr_det_packed_bytes_bf16(int n_layers) {
+  using namespace pr;
+  if (!det_n_ok(n_layers)) return 0;
+  size_t n = 0;
+  const auto& t = full_table();
+  for (int l = 0; l < n_layers; ++l)
+    if (t[l].type == PR_DET_CONV) n += (size_t)t[l].cout_pad * 4 + (size_t)t[l].cout_pad * t[l].kpad * (l == 0 ? 4 : 2);
+  return n;
+}
+
+int pr_det_fold_pack_bf16(int n_layers, const float* weights_host, size_t n_floats, double bn_eps, void* packed_host, size_t packed_bytes) {
+  using namespace pr;
+  PR_REQUIRE(det_n_ok(n_layers), "pr_det_fold_pack_bf16: n_layers = %d, must lie in 1..%d", n_layers, kDetLayers);
+  PR_REQUIRE(weights_host, "pr_det_fold_pack_bf16: null weights_host");
+  PR_REQUIRE(packed_host, "pr_det_fold_pack_bf16: null packed_host");
+  PR_REQUIRE(n_floats == pr_det_weight_floats(n_layers), "pr_det_fold_pack_bf16: n_floats = %zu, but the first %d layers hold %zu", n_floats,
+             n_layers, pr_det_weight_floats(n_layers));
+  PR_REQUIRE(packed_bytes == pr_det_packed_bytes_bf16(n_layers),
+             "pr_det_fold_pack_bf16: packed_bytes = %zu, but the first %d layers pack to %zu", packed_bytes, n_layers,
+             pr_det_packed_bytes_bf16(n_layers));
+  PR_REQUIRE(bn_eps > 0 && bn_eps < 1, "pr_det_fold_pack_bf16: bn_eps = %g, must lie in (0, 1)", bn_eps);
+  memset(packed_host, 0, packed_bytes);
+  const auto& t = full_table();
+  std::vector<int64_t> off;
+  det_pack_offsets_bf16(n_layers, &off);
+  std::vector<float> bias;
+  for (int l = 0; l < n_layers; ++l) {
+    const pr_det_layer& c = t[l];
+    if (c.type != PR_DET_CONV) continue;
+    char* base = static_cast<char*>(packed_host) + off[l];       // memcpy throughout: packed_host is only byte-aligned for us
+    char* w = base + (size_t)c.cout_pad * 4;
+    bias.assign(c.cout_pad, 0.f);
+    if (l == 0) {
+      fold_conv(c, weights_host + c.weight_offset, bn_eps, bias.data(), [&](size_t i, float v) { memcpy(w + 4 * i, &v, 4); });
+    } else {
+      fold_conv(c, weights_host + c.weight_offset, bn_eps, bias.data(), [&](size_t i, float v) {
+        const uint16_t r = bf16_rne(v);
+        memcpy(w + 2 * i, &r, 2);
+      });
     }
+    memcpy(base, bias.data(), (size_t)c.cout_pad * 4);
   }
   return PR_OK;
 }

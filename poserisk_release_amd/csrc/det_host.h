@@ -24,7 +24,21 @@ struct DetPlan {
   std::vector<int> slot;                   // per layer: the buffer of its output (a view's is its source's)
   std::vector<size_t> slot_floats;         // per buffer: floats of one frame of the largest tensor it holds
   std::vector<int> gh, gw;                 // per layer: its output's grid
+  std::vector<int> elem_bytes;             // per layer: bytes of one element of its output (4; bf16: 2, the head tensors 4)
+  std::vector<size_t> slot_frame_bytes;    // per buffer: bytes of one frame of the largest tensor it holds
 };
-int det_plan(int S_h, int S_w, DetPlan* plan);
+// precision 0: fp32 throughout; 1: the bf16 contract of section j8 (the same liveness walk with an element size per tensor)
+int det_plan(int S_h, int S_w, DetPlan* plan, int precision = 0);
+
+// bf16 pack (section j8, "bf16"): where each layer's bias begins in pr_det_fold_pack_bf16's blob, in BYTES (-1: no convolution)
+void det_pack_offsets_bf16(int n_layers, std::vector<int64_t>* out);
+// fp32 -> bf16 bits, round to nearest even on the integer; NaN stays NaN (quiet), past the largest bf16 becomes infinity
+inline uint16_t bf16_rne(float v) {
+  uint32_t u;
+  memcpy(&u, &v, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
 
 }  // namespace pr

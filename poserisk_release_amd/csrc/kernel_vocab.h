@@ -12,6 +12,7 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
 using i16x2 = __attribute__((ext_vector_type(2))) short;
 using i16x8 = __attribute__((ext_vector_type(8))) short;

@@ -5,7 +5,8 @@ people (lib/core/base.py:38-46,59); sort.py is the half that follows them.
                      tests/det_ref.py walk it; tests compare it with the library's own table, pr_det_topology)
     load_darknet     a darknet weight file -> its float body, checked against the topology
     save_darknet     the reverse (what the tests and synth use to make a file)
-    Detector         the handle: letterbox, network, network_until, postprocess, detect_raw on device tensors, and
+    fold_pack_bf16   the bf16 contract's packed blob (pr_det_fold_pack_bf16), as bytes
+    Detector         the handle (precision "fp32" | "bf16"): letterbox, network, network_until, postprocess, detect_raw on device tensors, and
                      detect(frames) -> one array of boxes per frame
 
 `img_size` is (S_h, S_w), rows first, each a multiple of 32: (416, 416) is the reference's yolo_img_size; (256, 416) suits
@@ -25,6 +26,7 @@ STRIDES = (32, 16, 8)
 ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326))
 ANCHOR_MASKS = ((6, 7, 8), (3, 4, 5), (0, 1, 2))
 MAX_CAND = 1024
+PRECISIONS = {"fp32": 0, "bf16": 1}
 STATUS_CAND_OVERFLOW, STATUS_DET_OVERFLOW = 1, 2
 
 
@@ -115,6 +117,24 @@ def fold_pack(weights, n_layers=NUM_LAYERS, bn_eps=1e-5):
     return out
 
 
+def fold_pack_bf16(weights, n_layers=NUM_LAYERS, bn_eps=1e-5):
+    """pr_det_fold_pack_bf16 on the host -> the packed blob u8[pr_det_packed_bytes_bf16(n_layers)]: per convolution bias f32[cout_pad],
+    then w bf16[cout_pad][kpad] (layer 0: w f32), BatchNorm folded in float64 and rounded to nearest even."""
+    lib = _lib.load()
+    weights = np.ascontiguousarray(weights, np.float32)
+    out = np.empty(lib.pr_det_packed_bytes_bf16(int(n_layers)), np.uint8)
+    _lib.check(lib.pr_det_fold_pack_bf16(int(n_layers), weights.ctypes.data_as(C.c_void_p), weights.size, float(bn_eps),
+                                         out.ctypes.data_as(C.c_void_p), out.size), "pr_det_fold_pack_bf16")
+    return out
+
+
+def check_precision(precision):
+    """'fp32' | 'bf16' -> the library's flag; anything else raises naming the two."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"detector precision {precision!r} unknown: one of 'fp32', 'bf16'")
+    return PRECISIONS[precision]
+
+
 def letterbox_geometry(H, W, S_h, S_w):
     """(h', w', ox, oy) of the header's integer rule."""
     if W * S_h >= H * S_w:
@@ -126,10 +146,13 @@ def letterbox_geometry(H, W, S_h, S_w):
 
 class Detector:
     """weights: a darknet file's path or its float body.  Every method works on CUDA tensors of `device`, asynchronously on
-    the current stream; detect() alone copies to the host."""
+    the current stream; detect() alone copies to the host.  precision: 'fp32' (default) or 'bf16' (include/poserisk_hip.h, j8,
+    paragraph "bf16": bf16 activations and weights, fp32 accumulation, fp32 head tensors; inputs and outputs keep their types)."""
 
-    def __init__(self, weights, img_size=(416, 416), device=None, max_batch=8, bn_eps=1e-5, max_det=100):
+    def __init__(self, weights, img_size=(416, 416), device=None, max_batch=8, bn_eps=1e-5, max_det=100, precision="fp32"):
         import torch
+        self.precision = precision
+        flag = check_precision(precision)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise _lib.PoseRiskHipError("Detector: the detector runs on the GPU only (no CPU fallback)")
@@ -142,8 +165,8 @@ class Detector:
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             lib = _lib.declare_stream(self.device)
-            _lib.check(lib.pr_det_create(self.device.index, body.ctypes.data_as(C.c_void_p), body.size, self.S_h, self.S_w,
-                                         self.max_batch, float(bn_eps), C.byref(self._h)), "pr_det_create")
+            _lib.check(lib.pr_det_create_p(self.device.index, body.ctypes.data_as(C.c_void_p), body.size, self.S_h, self.S_w,
+                                           self.max_batch, float(bn_eps), flag, C.byref(self._h)), "pr_det_create_p")
         self.grids = [(self.S_h // s, self.S_w // s) for s in STRIDES]
 
     def close(self):
@@ -183,6 +206,12 @@ class Detector:
         _lib.check(_lib.load().pr_det_grid(self._h, int(layer), C.byref(gh), C.byref(gw), C.byref(ch)), "pr_det_grid")
         return gh.value, gw.value, ch.value
 
+    def layer_dtype(self, layer):
+        """The dtype network_until returns for `layer`: torch.float32, or on a bf16 handle torch.bfloat16 for every layer but the
+        head convolutions and their yolo layers."""
+        import torch
+        return torch.bfloat16 if _lib.load().pr_det_elem_bytes(self._h, int(layer)) == 2 else torch.float32
+
     def letterbox(self, frames, bgr=False, out=None):
         """u8[B,H,W,3] -> f32[B,S_h,S_w,4] (R, G, B, 0)."""
         import torch
@@ -209,7 +238,7 @@ class Detector:
         import torch
         self._check(x, torch.float32, "x")
         B = x.shape[0]
-        out = self._out(out, (B,) + self.layer_shape(layer), torch.float32, "out")
+        out = self._out(out, (B,) + self.layer_shape(layer), self.layer_dtype(layer), "out")
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pr_det_network_until(self._h, x.data_ptr(), B, int(layer), out.data_ptr(), self._stream()),
                        "pr_det_network_until")
@@ -267,3 +296,63 @@ class Detector:
                 n = int(count[i])
                 results.append(np.concatenate([boxes[i, :n], scores[i, :n, None]], axis=1).astype(np.float32))
         return results
+
+
+def compare(weights, clip, img_size=(416, 416), device=None, batch=8, conf_thres=0.1, nms_thres=0.4, match_iou=0.5, report=print):
+    """Both precisions on one clip (a video file frontend.read_video reads, or frames u8[F,H,W,3]): per frame and in total the boxes kept by both
+    (greedy matching by IoU >= match_iou, best first), the boxes kept by one only, and the largest corner distance of matched
+    boxes in frame pixels.  The way to find out how far the bf16 detector agrees with fp32 on TRAINED weights: nobody has
+    measured that (no trained yolov3.weights exists where this package is built and tested)."""
+    import torch
+    from . import frontend
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    frames = frontend.read_video(clip, device, progressive=True)[0] if isinstance(clip, (str, bytes)) or hasattr(clip, "__fspath__") else clip
+    dets = {}
+    for precision in ("fp32", "bf16"):
+        d = Detector(weights, img_size=img_size, device=device, max_batch=batch, precision=precision)
+        dets[precision] = d.detect(frames, conf_thres=conf_thres, nms_thres=nms_thres)
+        d.close()
+    total = {"both": 0, "fp32_only": 0, "bf16_only": 0, "max_corner_px": 0.0}
+    rows = []
+    for f, (a, b) in enumerate(zip(dets["fp32"], dets["bf16"])):
+        free, both, worst = list(range(len(b))), 0, 0.0
+        for box in a:
+            best, best_iou = -1, match_iou
+            for j in free:
+                iw = min(box[2], b[j][2]) - max(box[0], b[j][0])
+                ih = min(box[3], b[j][3]) - max(box[1], b[j][1])
+                inter = max(iw, 0.0) * max(ih, 0.0)
+                union = (box[2] - box[0]) * (box[3] - box[1]) + (b[j][2] - b[j][0]) * (b[j][3] - b[j][1]) - inter
+                iou = inter / union if union > 0 else 0.0
+                if iou >= best_iou:
+                    best, best_iou = j, iou
+            if best >= 0:
+                free.remove(best)
+                both += 1
+                worst = max(worst, float(np.abs(box[:4] - b[best][:4]).max()))
+        row = {"frame": f, "both": both, "fp32_only": len(a) - both, "bf16_only": len(free), "max_corner_px": worst}
+        rows.append(row)
+        report("frame %(frame)d: both %(both)d, fp32 only %(fp32_only)d, bf16 only %(bf16_only)d, max corner distance %(max_corner_px).3f px" % row)
+        for k in ("both", "fp32_only", "bf16_only"):
+            total[k] += row[k]
+        total["max_corner_px"] = max(total["max_corner_px"], worst)
+    report("total over %d frames: both %d, fp32 only %d, bf16 only %d, max corner distance %.3f px"
+           % (len(rows), total["both"], total["fp32_only"], total["bf16_only"], total["max_corner_px"]))
+    return rows, total
+
+
+if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m poserisk_release_amd.detector")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    c = sub.add_parser("compare", help="run the fp32 and the bf16 detector on a clip and report how far their boxes agree")
+    c.add_argument("clip")
+    c.add_argument("--weights", required=True, help="a darknet yolov3.weights file")
+    c.add_argument("--img-size", type=int, nargs=2, default=(416, 416), metavar=("ROWS", "COLUMNS"))
+    c.add_argument("--conf-thres", type=float, default=0.1)
+    c.add_argument("--nms-thres", type=float, default=0.4)
+    c.add_argument("--batch", type=int, default=8)
+    c.add_argument("--gpu", type=int, default=0)
+    a = ap.parse_args()
+    import torch
+    compare(a.weights, a.clip, tuple(a.img_size), torch.device("cuda", a.gpu), a.batch, a.conf_thres, a.nms_thres)

@@ -659,9 +659,10 @@ class Predictor:
         from poserisk_release_amd import detector, sort
         t = cfg.TRACKER
         det = getattr(self, '_detector', None)
-        key = (self._tracker_weights(), tuple(t.img_size), int(t.batch))
+        key = (self._tracker_weights(), tuple(t.img_size), int(t.batch), str(t.get('precision', 'fp32')))
+        detector.check_precision(key[3])        # 'fp32' | 'bf16', anything else raises naming the two
         if det is None or getattr(self, '_detector_key', None) != key:
-            det = detector.Detector(key[0], img_size=key[1], device=self.device, max_batch=key[2])
+            det = detector.Detector(key[0], img_size=key[1], device=self.device, max_batch=key[2], precision=key[3])
             self._detector, self._detector_key = det, key
         dets = det.detect(frames, bgr=bgr, conf_thres=float(t.conf_thres), nms_thres=float(t.nms_thres))
         tracking = sort.track_frames(dets, max_age=int(t.max_age), min_hits=int(t.min_hits), iou_thres=float(t.iou_thres))

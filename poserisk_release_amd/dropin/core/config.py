@@ -57,7 +57,9 @@ absent from the reference and all optional:
                               poserisk_release_amd.sort: SORT on the host).  All of it is inert while `weights` is '':
                               weights '' | the path of a darknet yolov3.weights file; img_size (416, 416) = (rows, columns) of the
                               network input, multiples of 32 ((256, 416) suits 800 x 450 frames); conf_thres 0.1 (the reference's
-                              detection_threshold); nms_thres 0.4; max_age 1, min_hits 3, iou_thres 0.3 (SORT); batch 8 frames a call.
+                              detection_threshold); nms_thres 0.4; max_age 1, min_hits 3, iou_thres 0.3 (SORT); batch 8 frames a call;
+                              precision 'fp32' (default) | 'bf16' (the detector on the bf16 MFMAs: `TRACKER: {precision: bf16}`;
+                              its agreement with fp32 on trained weights is unmeasured).
                               With weights set, a video file's tracking comes from it after the tracking given and the sidecar
                               and before multi_person_tracker, and a frame folder without tracking.pkl is accepted
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
@@ -131,7 +133,7 @@ def _defaults(root):
         'AUG': {'flip': False, 'rotate_factor': 0},
         'TEST': {},
         'TRACKER': {'weights': '', 'img_size': (416, 416), 'conf_thres': 0.1, 'nms_thres': 0.4, 'max_age': 1, 'min_hits': 3,
-                    'iou_thres': 0.3, 'batch': 8},
+                    'iou_thres': 0.3, 'batch': 8, 'precision': 'fp32'},
     }
 
 

@@ -198,15 +198,16 @@ def prepare(path, out_dir, quality=95, device=None, max_w=800, max_h=450, max_by
 
 
 def track(path, weights, out=None, device=None, img_size=(416, 416), conf_thres=0.1, nms_thres=0.4, max_age=1, min_hits=3, iou_thres=0.3,
-          batch=8, max_w=800, max_h=450, matrix="601"):
+          batch=8, max_w=800, max_h=450, matrix="601", precision="fp32"):
     """A Motion-JPEG AVI or a YUV4MPEG2 stream (read_video's inputs) -> `out` (default `<stem>.tracking.pkl` beside the video):
     multi_person_tracker's dict, boxes in the downscaled frames' coordinates, made by this package's own detector (YOLOv3 on the
-    GPU, `weights` = a darknet yolov3.weights file) and SORT.  Returns (out, the dict, number of frames)."""
+    GPU, `weights` = a darknet yolov3.weights file; precision 'fp32' | 'bf16') and SORT.  Returns (out, the dict, number of frames)."""
     import pickle
     from . import detector, sort
+    detector.check_precision(precision)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     frames, _ = read_video(path, device, max_w=max_w, max_h=max_h, progressive=True, matrix=matrix)
-    det = detector.Detector(weights, img_size=img_size, device=device, max_batch=batch)
+    det = detector.Detector(weights, img_size=img_size, device=device, max_batch=batch, precision=precision)
     dets = det.detect(frames, conf_thres=conf_thres, nms_thres=nms_thres)
     det.close()
     tracking = sort.track_frames(dets, max_age=max_age, min_hits=min_hits, iou_thres=iou_thres)
@@ -241,10 +242,12 @@ def main(argv=None):
     t.add_argument("--nms-thres", type=float, default=0.4)
     t.add_argument("--batch", type=int, default=8)
     t.add_argument("--gpu", type=int, default=0)
+    t.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="the detector's arithmetic (bf16: faster; its agreement "
+                   "with fp32 on trained weights is unmeasured: python -m poserisk_release_amd.detector compare)")
     a = ap.parse_args(argv)
     if a.command == "track":
         out, tracking, n = track(a.video, a.weights, a.out, device=torch.device("cuda", a.gpu), img_size=tuple(a.img_size),
-                                 conf_thres=a.conf_thres, nms_thres=a.nms_thres, batch=a.batch)
+                                 conf_thres=a.conf_thres, nms_thres=a.nms_thres, batch=a.batch, precision=a.precision)
         print(f"{out}: {len(tracking)} tracks over {n} frames")
         return
     n, (w, h), fps = prepare(a.video, a.out_dir, quality=a.quality, device=torch.device("cuda", a.gpu), max_w=a.max_w, max_h=a.max_h,

@@ -155,6 +155,25 @@ def det_conv_nhwc(x, packed, cout, ksize, stride=1, leaky=True, residual=None, o
     return y
 
 
+def det_conv_nhwc_bf16(x, packed, cout, ksize, stride=1, leaky=True, residual=None, out_dtype=torch.bfloat16, out=None):
+    """The detector's bf16 convolution alone (pr_det_conv_nhwc_bf16, csrc/det_conv_bf16.hip): x bf16[B,H,W,Cin] CUDA (Cin a
+    multiple of 8), `packed` ONE convolution as bytes on the device (bias f32[cout_pad], then w bf16[cout_pad][kpad]), residual
+    bf16 -> out_dtype (torch.bfloat16 | torch.float32) [B,Ho,Wo,cout] = round(leaky(conv + b) [+ residual]), rounded once."""
+    _need_cuda(x, "det_conv_nhwc_bf16")
+    if x.dtype != torch.bfloat16 or (residual is not None and residual.dtype != torch.bfloat16) or not x.is_contiguous():
+        raise ValueError("det_conv_nhwc_bf16: x and residual must be contiguous torch.bfloat16 tensors")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"det_conv_nhwc_bf16: out_dtype {out_dtype} unknown: torch.bfloat16 or torch.float32")
+    B, H, W, Cin = x.shape
+    pad = ksize // 2
+    Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+    y = _out(out, (B, Ho, Wo, cout), out_dtype, x.device)
+    _lib.check(_lib.load().pr_det_conv_nhwc_bf16(x.data_ptr(), packed.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                                 y.data_ptr(), B, H, W, Cin, int(cout), int(ksize), int(stride), int(bool(leaky)),
+                                                 int(out_dtype == torch.float32), _stream(x.device)), "pr_det_conv_nhwc_bf16")
+    return y
+
+
 def conv1x1_dual_nhwc(x1, w1, x2, w2, bias=None, stride2=1, relu=False, tile_cfg=-1, precision="fp32", out=None):
     """relu(x1*W1 + x2[::stride2, ::stride2]*W2 + bias) as one dual-source GEMM (a first Bottleneck's conv3 with its
     downsample branch summed in).  x1 [B,Ho,Wo,C1], x2 [B,H2,W2,C2] CUDA, w1 [Cout,C1], w2 [Cout,C2] numpy."""
