@@ -1426,7 +1426,8 @@ int pr_yuv_encode(const pr_yuv_enc_args* args, void* stream);
 #define PR_DET_MAX_CAND 1024   /* candidates that take part in NMS, per frame */
 enum { PR_DET_CONV = 0, PR_DET_SHORTCUT = 1, PR_DET_ROUTE = 2, PR_DET_UPSAMPLE = 3, PR_DET_YOLO = 4 };
 enum { PR_DET_STATUS_CAND_OVERFLOW = 1, /* more than PR_DET_MAX_CAND candidates: the best PR_DET_MAX_CAND took part */
-       PR_DET_STATUS_DET_OVERFLOW = 2   /* more than max_det boxes survived NMS: the best max_det were written */ };
+       PR_DET_STATUS_DET_OVERFLOW = 2,  /* more than max_det boxes survived NMS: the best max_det were written */
+       PR_DET_STATUS_NONFINITE = 4      /* a head value that is not finite took a cell out (paragraph "Non-finite head values") */ };
 typedef struct pr_det_layer {
   int32_t type;           /* PR_DET_* */
   int32_t cin, cout;      /* channels in and out, unpadded (a route's: the sum of its sources) */
@@ -1516,10 +1517,20 @@ int pr_det_grid(const pr_det_t* h, int layer, int* gh, int* gw, int* channels);
  *     iw = max(min(ax2, bx2) - max(ax1, bx1), 0)   ih alike   inter = iw * ih
  *     area = (x2 - x1) * (y2 - y1)                  IoU = inter / ((area_a + area_b) - inter)      (0 / 0 counts as no overlap)
  *   Class-agnostic by construction: only class 0 is kept [unpinned: upstream runs NMS per class over all 80].
+ *   Non-finite head values.  The frame's status gets PR_DET_STATUS_NONFINITE where a cell's objectness logit to is NaN, or where
+ *   a cell passes the candidate test above and its fp32 score or any of its four fp32 corners is not finite (NaN or +-inf: a
+ *   NaN tx, ty or tc0, an infinite tw, a tw whose box overflows fp32 only).  Such a cell is never a candidate: it takes no part in
+ *   the order or in NMS and does not count towards PR_DET_MAX_CAND, so every candidate's score and corners are finite.  A NaN
+ *   among the other 79 class values never beats class 0: the test is "no c in 1..79 has tc[c] > tc[0]", false for every
+ *   comparison with a NaN, and sets no bit.
  *
  * pr_det_detect: frames_dev u8[B,H,W,3] -> letterbox, network, post-processing as above, then each box mapped to the frame:
  *   x = (x_letterbox - ox) / (w' / W) evaluated as (x - (float)ox) * ((float)W / (float)w'), y alike with (float)H / (float)h',
- *   then clipped to [0, W] and [0, H]: the scale actually used per axis.  Outputs as pr_det_postprocess'. */
+ *   then clipped to [0, W] and [0, H]: the scale actually used per axis.  Outputs as pr_det_postprocess'.
+ * pr_det_unmap: that map alone, in place and without a handle (the same launcher pr_det_detect calls; what the tests compare
+ *   bit for bit): boxes_dev f32[B,max_det,4] in letterbox pixels of an S_h x S_w input (ox, oy, w', h' by pr_det_letterbox's
+ *   rule for H x W frames) -> frame pixels, for the rows below count_dev[b]; a row at or beyond count_dev[b] is left as it is.
+ *   B in 0..4096, max_det in 1..PR_DET_MAX_CAND, H and W in 1..PR_RESIZE_MAX_SIDE, S_h and S_w multiples of 32 in 32..4096. */
 /* The detector's convolution alone (csrc/det_conv.hip; parity tests and timing against pr_conv2d_nhwc): x_dev f32[B,H,W,Cin]
  * (Cin a multiple of 4), packed_dev = ONE convolution in the packed layout above (bias f32[cout_pad], then w
  * f32[cout_pad][kpad], folded by the caller), res_dev f32[B,Ho,Wo,Cout] or NULL (added after the activation) -> y_dev
@@ -1540,6 +1551,7 @@ int pr_det_postprocess(pr_det_t* h, const float* head32_dev, const float* head16
                        int32_t* status_dev, void* stream);
 int pr_det_detect(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, int bgr, float conf_thres, float nms_thres,
                   int max_det, float* boxes_dev, float* scores_dev, int32_t* count_dev, int32_t* status_dev, void* stream);
+int pr_det_unmap(float* boxes_dev, const int32_t* count_dev, int B, int max_det, int H, int W, int S_h, int S_w, void* stream);
 
 #ifdef __cplusplus
 }

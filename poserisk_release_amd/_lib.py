@@ -221,6 +221,7 @@ SIGNATURES = {
     "pr_det_network_until": (_I, [_P, _P, _I, _I, _P, _P]),
     "pr_det_postprocess": (_I, [_P, _P, _P, _P, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
     "pr_det_detect": (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
+    "pr_det_unmap": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

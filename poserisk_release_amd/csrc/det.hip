@@ -21,7 +21,7 @@ struct pr_det {
   std::vector<size_t> slot_bytes;
   float* canvas = nullptr;                 // pr_det_detect's letterboxed input, f32[max_batch,S_h,S_w,4]
   float* cand = nullptr;                   // f32[max_batch][cells][6]: score, flat index (as int bits), x1, y1, x2, y2
-  int32_t* cand_count = nullptr;           // i32[max_batch]
+  int32_t* cand_count = nullptr;           // i32[2][max_batch]: the candidate counts, then the decode kernel's status flags
   int cells = 0;                           // candidates a frame can have: 3 * (sum of the three grids)
   std::vector<void*> allocs;
 };
@@ -159,7 +159,12 @@ struct HeadSet {
 
 __device__ __forceinline__ double sigmoid64(double t) { return 1.0 / (1.0 + exp(-t)); }
 
-__global__ void __launch_bounds__(kDetThreads) det_decode_kernel(HeadSet hs, float conf_thres, float* cand, int32_t* cand_count) {
+__device__ __forceinline__ bool finite32(float v) { return fabsf(v) <= 3.402823466e+38f; }      // false for NaN and +-inf
+
+// cand_flag[b] collects PR_DET_STATUS_NONFINITE (zeroed with cand_count; det_nms_kernel folds it into the status): a cell that
+// raises it returns before the append, so every appended score and corner is finite.
+__global__ void __launch_bounds__(kDetThreads) det_decode_kernel(HeadSet hs, float conf_thres, float* cand, int32_t* cand_count,
+                                                                 int32_t* cand_flag) {
   const int flat = blockIdx.x * kDetThreads + threadIdx.x;
   const int b = blockIdx.y;
   if (flat >= hs.cells) return;
@@ -168,6 +173,10 @@ __global__ void __launch_bounds__(kDetThreads) det_decode_kernel(HeadSet hs, flo
   const int r = flat - hs.base[hd];
   const int a = r / (gh * gw), cy = (r / gw) % gh, cx = r % gw;
   const float* t = hs.t[hd] + (((long)b * gh + cy) * gw + cx) * 255 + a * 85;
+  if (t[4] != t[4]) {      // a NaN objectness logit: neither above nor below the threshold
+    atomicOr(cand_flag + b, PR_DET_STATUS_NONFINITE);
+    return;
+  }
   const double so = sigmoid64((double)t[4]);
   if (!((float)so >= conf_thres)) return;
   const float c0 = t[5];
@@ -179,10 +188,15 @@ __global__ void __launch_bounds__(kDetThreads) det_decode_kernel(HeadSet hs, flo
   const float bw = (float)((double)kAnchors[an][0] * exp((double)t[2])), bh = (float)((double)kAnchors[an][1] * exp((double)t[3]));
   const float score = (float)(so * sigmoid64((double)c0));
   const float hw = 0.5f * bw, hh = 0.5f * bh;
+  const float x1 = bx - hw, y1 = by - hh, x2 = bx + hw, y2 = by + hh;
+  if (!(finite32(score) && finite32(x1) && finite32(y1) && finite32(x2) && finite32(y2))) {
+    atomicOr(cand_flag + b, PR_DET_STATUS_NONFINITE);
+    return;
+  }
   const int slot = atomicAdd(cand_count + b, 1);
   if (slot >= hs.cells) return;      // cannot happen: a cell appends once
   float* o = cand + ((long)b * hs.cells + slot) * 6;
-  o[0] = score, o[1] = __int_as_float(flat), o[2] = bx - hw, o[3] = by - hh, o[4] = bx + hw, o[5] = by + hh;
+  o[0] = score, o[1] = __int_as_float(flat), o[2] = x1, o[3] = y1, o[4] = x2, o[5] = y2;
 }
 
 // ---- order, NMS, output: one workgroup a frame ---------------------------------------------------------------------
@@ -193,15 +207,19 @@ __device__ __forceinline__ float det_iou(f32x4 a, f32x4 b) {
   return inter / ((aa + ab) - inter);
 }
 
-__global__ void __launch_bounds__(kNmsThreads) det_nms_kernel(const float* cand, const int32_t* cand_count, int cells, float nms_thres,
-                                                              int max_det, float* boxes, float* scores, int32_t* count, int32_t* status) {
+__global__ void __launch_bounds__(kNmsThreads) det_nms_kernel(const float* cand, const int32_t* cand_count, const int32_t* cand_flag,
+                                                              int cells, float nms_thres, int max_det, float* boxes, float* scores,
+                                                              int32_t* count, int32_t* status) {
   __shared__ f32x4 sbox[PR_DET_MAX_CAND];
   __shared__ float sscore[PR_DET_MAX_CAND];
   __shared__ int srem[PR_DET_MAX_CAND];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = min(max(cand_count[b], 0), cells);
   const float* cb = cand + (long)b * cells * 6;
-  // rank = how many candidates come first in (score descending, flat index ascending): a total order, so ranks are distinct
+  // rank = how many candidates come first in (score descending, flat index ascending).  Ranks are distinct: the decode kernel
+  // appends no score that is NaN, so of two candidates' scores one is greater or they are equal, and no two candidates share a
+  // flat index (a cell appends once): exactly one of two candidates comes before the other, the relation is transitive, and
+  // the n ranks are 0..n-1, each once.  Every slot below m = min(n, MAX_CAND) is therefore written exactly once.
   for (int i = tid; i < n; i += kNmsThreads) {
     const float si = cb[6 * i];
     const int fi = __float_as_int(cb[6 * i + 1]);
@@ -243,7 +261,8 @@ __global__ void __launch_bounds__(kNmsThreads) det_nms_kernel(const float* cand,
   }
   if (tid == 0) {
     count[b] = nout;
-    status[b] = (n > PR_DET_MAX_CAND ? PR_DET_STATUS_CAND_OVERFLOW : 0) | (kept > max_det ? PR_DET_STATUS_DET_OVERFLOW : 0);
+    status[b] = (n > PR_DET_MAX_CAND ? PR_DET_STATUS_CAND_OVERFLOW : 0) | (kept > max_det ? PR_DET_STATUS_DET_OVERFLOW : 0) |
+                (cand_flag[b] & PR_DET_STATUS_NONFINITE);
   }
 }
 
@@ -252,10 +271,20 @@ __global__ void __launch_bounds__(kDetThreads) det_unmap_kernel(float* boxes, co
                                                                 float oy, float sx, float sy, float W, float H) {
   const long g = (long)blockIdx.x * kDetThreads + threadIdx.x;
   if (g >= n_boxes) return;
-  if ((int)(g % max_det) >= count[g / max_det]) return;      // a row beyond count stays zero
+  if ((int)(g % max_det) >= count[g / max_det]) return;      // a row beyond count stays as it is (pr_det_detect: zero)
   float* q = boxes + 4 * g;
   q[0] = fminf(fmaxf((q[0] - ox) * sx, 0.f), W), q[2] = fminf(fmaxf((q[2] - ox) * sx, 0.f), W);
   q[1] = fminf(fmaxf((q[1] - oy) * sy, 0.f), H), q[3] = fminf(fmaxf((q[3] - oy) * sy, 0.f), H);
+}
+
+// pr_det_detect's last step and pr_det_unmap: B * max_det <= 4096 * 1024 boxes, a thread each
+int unmap_launch(float* boxes, const int32_t* count, int B, int max_det, int H, int W, int S_h, int S_w, hipStream_t stream) {
+  int h2, w2, ox, oy;
+  letterbox_geometry(H, W, S_h, S_w, &h2, &w2, &ox, &oy);
+  const long n_boxes = (long)B * max_det;
+  hipLaunchKernelGGL(det_unmap_kernel, dim3((unsigned)ceil_div(n_boxes, (long)kDetThreads)), dim3(kDetThreads), 0, stream, boxes, count,
+                     n_boxes, max_det, (float)ox, (float)oy, (float)W / (float)w2, (float)H / (float)h2, (float)W, (float)H);
+  return check_launch("det_unmap_kernel");
 }
 
 // ---- the handle ----------------------------------------------------------------------------------------------------
@@ -316,7 +345,7 @@ int det_build(pr_det* h, const float* weights_host, size_t n_floats, double bn_e
   PR_TRY(det_alloc(h, &h->canvas, (size_t)h->max_batch * h->S_h * h->S_w * 4 * sizeof(float), (size_t)h->S_h * h->S_w * 4 * sizeof(float),
                    "canvas"));
   PR_TRY(det_alloc(h, &h->cand, (size_t)h->max_batch * h->cells * 6 * sizeof(float), (size_t)h->cells * 6 * sizeof(float), "candidates"));
-  PR_TRY(det_alloc(h, &h->cand_count, (size_t)h->max_batch * sizeof(int32_t), 0, "candidate counts"));
+  PR_TRY(det_alloc(h, &h->cand_count, (size_t)2 * h->max_batch * sizeof(int32_t), 0, "candidate counts"));
   PR_HIP(hipDeviceSynchronize());
   return PR_OK;
 }
@@ -395,12 +424,13 @@ int det_post(pr_det* h, const float* const* heads, int B, float conf_thres, floa
     hs.base[i] = hs.cells;
     hs.cells += 3 * hs.gh[i] * hs.gw[i];
   }
-  PR_HIP(hipMemsetAsync(h->cand_count, 0, (size_t)B * sizeof(int32_t), stream));
+  int32_t* cand_flag = h->cand_count + h->max_batch;
+  PR_HIP(hipMemsetAsync(h->cand_count, 0, (size_t)2 * h->max_batch * sizeof(int32_t), stream));
   hipLaunchKernelGGL(det_decode_kernel, dim3((unsigned)ceil_div(hs.cells, kDetThreads), (unsigned)B), dim3(kDetThreads), 0, stream, hs,
-                     conf_thres, h->cand, h->cand_count);
+                     conf_thres, h->cand, h->cand_count, cand_flag);
   PR_TRY(check_launch("det_decode_kernel"));
   hipLaunchKernelGGL(det_nms_kernel, dim3((unsigned)B), dim3(kNmsThreads), 0, stream, (const float*)h->cand,
-                     (const int32_t*)h->cand_count, hs.cells, nms_thres, max_det, boxes, scores, count, status);
+                     (const int32_t*)h->cand_count, (const int32_t*)cand_flag, hs.cells, nms_thres, max_det, boxes, scores, count, status);
   return check_launch("det_nms_kernel");
 }
 
@@ -607,12 +637,20 @@ int pr_det_detect(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, i
   PR_TRY(det_walk(h, h->canvas, B, kDetLayers - 1, nullptr, s));
   const float* const heads[3] = {tensor_of(h, kHeadLayer[0], B), tensor_of(h, kHeadLayer[1], B), tensor_of(h, kHeadLayer[2], B)};
   PR_TRY(det_post(h, heads, B, conf_thres, nms_thres, max_det, boxes_dev, scores_dev, count_dev, status_dev, s));
-  int h2, w2, ox, oy;
-  letterbox_geometry(H, W, h->S_h, h->S_w, &h2, &w2, &ox, &oy);
-  const long n_boxes = (long)B * max_det;
-  hipLaunchKernelGGL(det_unmap_kernel, dim3((unsigned)ceil_div(n_boxes, (long)kDetThreads)), dim3(kDetThreads), 0, s, boxes_dev,
-                     (const int32_t*)count_dev, n_boxes, max_det, (float)ox, (float)oy, (float)W / (float)w2, (float)H / (float)h2, (float)W, (float)H);
-  return check_launch("det_unmap_kernel");
+  return unmap_launch(boxes_dev, count_dev, B, max_det, H, W, h->S_h, h->S_w, s);
+}
+
+int pr_det_unmap(float* boxes_dev, const int32_t* count_dev, int B, int max_det, int H, int W, int S_h, int S_w, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(boxes_dev, "pr_det_unmap: null boxes_dev");
+  PR_REQUIRE(count_dev, "pr_det_unmap: null count_dev");
+  PR_REQUIRE(B >= 0 && B <= 4096, "pr_det_unmap: B = %d, must lie in 0..4096", B);
+  PR_REQUIRE(max_det >= 1 && max_det <= PR_DET_MAX_CAND, "pr_det_unmap: max_det = %d, must lie in 1..%d", max_det, PR_DET_MAX_CAND);
+  PR_TRY(check_frames(boxes_dev, H, W, "pr_det_unmap"));
+  PR_REQUIRE(S_h >= 32 && S_w >= 32 && S_h % 32 == 0 && S_w % 32 == 0 && S_h <= 4096 && S_w <= 4096,
+             "pr_det_unmap: the network input %d x %d (S_w x S_h) must be multiples of 32 in 32..4096", S_w, S_h);
+  if (B == 0) return PR_OK;
+  return unmap_launch(boxes_dev, count_dev, B, max_det, H, W, S_h, S_w, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -27,7 +27,23 @@ ANCHORS = ((10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90
 ANCHOR_MASKS = ((6, 7, 8), (3, 4, 5), (0, 1, 2))
 MAX_CAND = 1024
 PRECISIONS = {"fp32": 0, "bf16": 1}
-STATUS_CAND_OVERFLOW, STATUS_DET_OVERFLOW = 1, 2
+STATUS_CAND_OVERFLOW, STATUS_DET_OVERFLOW, STATUS_NONFINITE = 1, 2, 4
+
+
+def status_text(status, conf_thres, max_det):
+    """A frame's status word -> what happened to it, every set bit named ('' for 0; a bit this module does not know by its number)."""
+    status = int(status)
+    parts = []
+    if status & STATUS_CAND_OVERFLOW:
+        parts.append("more than %d candidates above conf_thres %g" % (MAX_CAND, conf_thres))
+    if status & STATUS_DET_OVERFLOW:
+        parts.append("more than %d boxes after NMS" % max_det)
+    if status & STATUS_NONFINITE:
+        parts.append("a head value that is not finite (NaN or infinite) took at least one cell out")
+    rest = status & ~(STATUS_CAND_OVERFLOW | STATUS_DET_OVERFLOW | STATUS_NONFINITE)
+    if rest:
+        parts.append("unknown status bits 0x%x" % rest)
+    return "; ".join(parts)
 
 
 def yolo_layers():
@@ -142,6 +158,23 @@ def letterbox_geometry(H, W, S_h, S_w):
     else:
         h2, w2 = S_h, min(S_w, max(1, (2 * W * S_h + H) // (2 * H)))
     return h2, w2, (S_w - w2) // 2, (S_h - h2) // 2
+
+
+def unmap(boxes, count, frame_size, img_size):
+    """pr_det_unmap, in place: boxes f32[B,max_det,4] (CUDA, letterbox pixels of an img_size = (S_h, S_w) input) -> frame pixels of
+    frame_size = (H, W) frames, clipped, for the rows below count i32[B]; the other rows are left as they are.  The map
+    detect_raw ends with, without a handle.  -> boxes."""
+    import torch
+    for t, dtype, what in ((boxes, torch.float32, "boxes"), (count, torch.int32, "count")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous {dtype} CUDA tensor")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or tuple(count.shape) != (boxes.shape[0],) or count.device != boxes.device:
+        raise ValueError(f"boxes must be [B, max_det, 4] and count [B] on one device, got {tuple(boxes.shape)} and {tuple(count.shape)}")
+    (H, W), (S_h, S_w) = frame_size, img_size
+    with torch.cuda.device(boxes.device):
+        _lib.check(_lib.load().pr_det_unmap(boxes.data_ptr(), count.data_ptr(), boxes.shape[0], boxes.shape[1], int(H), int(W), int(S_h), int(S_w),
+                                    torch.cuda.current_stream(boxes.device).cuda_stream), "pr_det_unmap")
+    return boxes
 
 
 class Detector:
@@ -280,7 +313,8 @@ class Detector:
     def detect(self, frames, bgr=False, conf_thres=0.1, nms_thres=0.4):
         """u8[F,H,W,3] (a CUDA tensor, or numpy: uploaded) -> a list of F arrays f32[n,5] (x1, y1, x2, y2, score) in frame pixels,
         best score first; runs in chunks of max_batch.  A frame with more than MAX_CAND candidates (the best MAX_CAND took
-        part) or more than max_det boxes is reported with a warning naming it, never cut silently."""
+        part), more than max_det boxes or a cell taken out by a head value that is not finite is reported with a warning naming
+        it (status_text), never cut silently."""
         import torch
         if not isinstance(frames, torch.Tensor):
             frames = torch.from_numpy(np.ascontiguousarray(frames))
@@ -291,8 +325,7 @@ class Detector:
             boxes, scores, count, status = (t.cpu().numpy() for t in self.detect_raw(part, bgr, conf_thres, nms_thres))
             for i in range(part.shape[0]):
                 if status[i]:
-                    warnings.warn(f"detector: frame {lo + i}: " + ("more than %d candidates above conf_thres %g" % (MAX_CAND, conf_thres)
-                                  if status[i] & STATUS_CAND_OVERFLOW else "more than %d boxes after NMS" % self.max_det), RuntimeWarning)
+                    warnings.warn(f"detector: frame {lo + i}: " + status_text(status[i], conf_thres, self.max_det), RuntimeWarning)
                 n = int(count[i])
                 results.append(np.concatenate([boxes[i, :n], scores[i, :n, None]], axis=1).astype(np.float32))
         return results

@@ -111,50 +111,79 @@ def _sigmoid(t):
     return 1.0 / (1.0 + np.exp(-t))
 
 
-def decode(heads, dtype=np.float64):
+def _decode_head(v, hd, dtype, out):
+    """One head's cells (v f32[anchor,cy,cx,85]) -> obj, score, box [n,4], each expression in `dtype`, then obj, score and the box
+    terms converted to `out` and the corners formed there (a product, then a sum)."""
+    gh, gw = v.shape[1:3]
+    vd = v.astype(dtype)
+    cy, cx = np.meshgrid(np.arange(gh), np.arange(gw), indexing="ij")
+    stride = dtype(STRIDES[hd])
+    an = np.array([ANCHORS[k] for k in ANCHOR_MASKS[hd]], dtype)
+    bx = ((_sigmoid(vd[..., 0]) + cx[None].astype(dtype)) * stride).astype(out)
+    by = ((_sigmoid(vd[..., 1]) + cy[None].astype(dtype)) * stride).astype(out)
+    bw = (an[:, 0, None, None] * np.exp(vd[..., 2])).astype(out)
+    bh = (an[:, 1, None, None] * np.exp(vd[..., 3])).astype(out)
+    so = _sigmoid(vd[..., 4])
+    sc = (so * _sigmoid(vd[..., 5])).astype(out)
+    hw, hh = bw * out(0.5), bh * out(0.5)
+    return so.astype(out).ravel(), sc.ravel(), np.stack([bx - hw, by - hh, bx + hw, by + hh], -1).reshape(-1, 4)
+
+
+def decode(heads, dtype=np.float64, out=None):
     """heads: three f32[B,gh,gw,255] -> per frame a dict of arrays over ALL cells in flat order (head, anchor, cy, cx):
-    obj, score, person (bool: the argmax class is 0), box [n,4] (x1, y1, x2, y2), each expression in `dtype`."""
+    obj, score, box [n,4] (x1, y1, x2, y2), each expression in `dtype`; `out` (default: `dtype`) is the type they are converted to
+    before the corners are formed: decode(heads, np.float64, np.float32) is the header's contract to the letter (float64
+    expressions rounded to fp32 once, fp32 corners).
+    person (bool): no other class value is greater than class 0's -- tc[c] > tc[0] for no c, which a NaN among the other 79 never
+    satisfies and which every comparison with a NaN tc[0] fails (that cell passes; its score is NaN).
+    nan_obj (bool): the objectness logit is NaN.  finite (bool): the CONTRACT's fp32 score and four fp32 corners are all finite,
+    whatever `dtype` is: what select() leaves out and nonfinite() reports is the same for every dtype."""
     B = heads[0].shape[0]
+    out = dtype if out is None else out
     frames = []
     for b in range(B):
-        obj, score, person, boxes = [], [], [], []
+        obj, score, person, boxes, nan_obj, finite = [], [], [], [], [], []
         for hd, t in enumerate(heads):
             gh, gw = t.shape[1:3]
             v = np.asarray(t[b], np.float32).reshape(gh, gw, 3, 85).transpose(2, 0, 1, 3)      # anchor, cy, cx, 85
-            vd = v.astype(dtype)
-            cy, cx = np.meshgrid(np.arange(gh), np.arange(gw), indexing="ij")
-            stride = dtype(STRIDES[hd])
-            bx = (_sigmoid(vd[..., 0]) + cx[None].astype(dtype)) * stride
-            by = (_sigmoid(vd[..., 1]) + cy[None].astype(dtype)) * stride
-            an = np.array([ANCHORS[k] for k in ANCHOR_MASKS[hd]], dtype)
-            bw = an[:, 0, None, None] * np.exp(vd[..., 2])
-            bh = an[:, 1, None, None] * np.exp(vd[..., 3])
-            so = _sigmoid(vd[..., 4])
-            sc = so * _sigmoid(vd[..., 5])
-            obj.append(so.ravel()), score.append(sc.ravel())
-            person.append((np.argmax(v[..., 5:], axis=-1) == 0).ravel())                       # lowest index on ties
-            hw, hh = bw * dtype(0.5), bh * dtype(0.5)                                         # the corners: a product, then a sum
-            boxes.append(np.stack([bx - hw, by - hh, bx + hw, by + hh], -1).reshape(-1, 4))
+            with np.errstate(all="ignore"):
+                so, sc, box = _decode_head(v, hd, dtype, out)
+                _, sc32, box32 = _decode_head(v, hd, np.float64, np.float32)
+            obj.append(so), score.append(sc), boxes.append(box)
+            person.append((~np.any(v[..., 6:] > v[..., 5:6], axis=-1)).ravel())
+            nan_obj.append(np.isnan(v[..., 4]).ravel())
+            finite.append(np.isfinite(sc32) & np.isfinite(box32).all(axis=1))
         frames.append({"obj": np.concatenate(obj), "score": np.concatenate(score), "person": np.concatenate(person),
-                       "box": np.concatenate(boxes)})
+                       "box": np.concatenate(boxes), "nan_obj": np.concatenate(nan_obj), "finite": np.concatenate(finite)})
     return frames
+
+
+def candidates(cells, conf_thres):
+    """-> (bool over all cells: passes the candidate test and is finite; the frame's PR_DET_STATUS_NONFINITE: an objectness logit
+    is NaN, or a cell passes the test with a score or corner that is not finite in fp32)."""
+    with np.errstate(invalid="ignore"):
+        passes = (cells["obj"] >= cells["obj"].dtype.type(conf_thres)) & cells["person"] & ~cells["nan_obj"]
+    return passes & cells["finite"], bool(cells["nan_obj"].any() or (passes & ~cells["finite"]).any())
 
 
 def iou(a, b):
     """The contract's IoU of box a with boxes b [n,4], in the arrays' dtype."""
     z = a.dtype.type(0)
-    iw = np.maximum(np.minimum(a[2], b[:, 2]) - np.maximum(a[0], b[:, 0]), z)
-    ih = np.maximum(np.minimum(a[3], b[:, 3]) - np.maximum(a[1], b[:, 1]), z)
-    inter = iw * ih
-    union = ((a[2] - a[0]) * (a[3] - a[1]) + (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) - inter
-    with np.errstate(divide="ignore", invalid="ignore"):
+    with np.errstate(all="ignore"):      # 0 / 0 (two empty boxes) and an area past the format's largest: NaN or 0, no overlap
+        iw = np.maximum(np.minimum(a[2], b[:, 2]) - np.maximum(a[0], b[:, 0]), z)
+        ih = np.maximum(np.minimum(a[3], b[:, 3]) - np.maximum(a[1], b[:, 1]), z)
+        inter = iw * ih
+        union = ((a[2] - a[0]) * (a[3] - a[1]) + (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) - inter
         return inter / union
 
 
 def select(cells, conf_thres, nms_thres, max_cand=MAX_CAND):
     """One frame's decode() dict -> (flat indices of the candidates in order, cut at max_cand; flat indices kept by the greedy
-    NMS, in order; overflow flag; every pair's IoU among the participants, for the margin assertions)."""
-    cand = np.nonzero((cells["obj"] >= cells["obj"].dtype.type(conf_thres)) & cells["person"])[0]
+    NMS, in order; overflow flag; every pair's IoU among the participants, for the margin assertions).
+    Candidates: candidates() -- a cell a non-finite head value took out is none and does not count towards max_cand.  Order: score
+    descending, then the flat index ascending.  The first max_cand take part.  A participant is dropped iff an earlier KEPT one has
+    IoU > nms_thres with it (thresholds in the boxes' dtype); a NaN IoU (0 / 0: two empty boxes) is greater than nothing."""
+    cand = np.nonzero(candidates(cells, conf_thres)[0])[0]
     order = cand[np.lexsort((cand, -cells["score"][cand]))]
     overflow = order.size > max_cand
     order = order[:max_cand]

@@ -132,3 +132,113 @@ def test_reference_letterbox_and_nms_are_sane():
     order2, kept2, overflow2, _ = det_ref.select(cells[2], dc.CONF, dc.NMS)
     assert overflow2 and order2.size == detector.MAX_CAND
     assert det_ref.select(cells[1], dc.CONF, dc.NMS)[0].size == 0
+
+
+# ---- the post-processing reference on the contract's edges: hand-derived numbers (tests/test_detector_gpu.py, section 3b) ---------
+def _contract(cells, conf=0.1, nms=0.4):
+    c = det_ref.decode(dc.edge_heads(cells), np.float64, np.float32)[0]
+    return c, det_ref.select(c, conf, nms)
+
+
+def test_reference_ious_of_the_crafted_cells_are_the_hand_derived_ones():
+    c, _ = _contract({dc.EDGE_A: {}, dc.EDGE_B: {}, dc.EDGE_C: {}, dc.EDGE_B16: {}, dc.EDGE_ANCHOR_PAIR[0]: {}, dc.EDGE_ANCHOR_PAIR[1]: {}})
+    box = lambda cell: c["box"][dc.flat_index(cell)]
+    assert c["box"].dtype == np.float32 and c["score"].dtype == np.float32
+    assert box(dc.EDGE_A).tolist() == [-42.0, 3.0, 74.0, 93.0] and box(dc.EDGE_B).tolist() == [-10.0, 3.0, 106.0, 93.0]
+    assert box(dc.EDGE_B16).tolist() == [10.5, -19.5, 69.5, 99.5]
+    assert c["score"][dc.flat_index(dc.EDGE_A)] == np.float32(0.25) and c["obj"][dc.flat_index(dc.EDGE_A)] == np.float32(0.5)
+    iou = lambda p, q: det_ref.iou(box(p), box(q)[None])[0]
+    assert iou(dc.EDGE_A, dc.EDGE_B) == dc.EDGE_IOU_1 == np.float32(7560) / np.float32(13320)
+    assert iou(dc.EDGE_A, dc.EDGE_C) == dc.EDGE_IOU_2 == np.float32(4680) / np.float32(16200) and abs(float(dc.EDGE_IOU_2) - 0.289) < 1e-3
+    assert iou(dc.EDGE_B, dc.EDGE_B16) == np.float32(5310) / np.float32(12151) > np.float32(0.4)
+    assert iou(*dc.EDGE_ANCHOR_PAIR) == np.float32(1350) / np.float32(3270) > np.float32(0.4)
+
+
+def test_reference_selection_on_the_edges():
+    flat = dc.flat_index
+    abc = {dc.EDGE_A: {"tc0": 0.0}, dc.EDGE_B: {"tc0": -1.0}, dc.EDGE_C: {"tc0": -2.0}}
+    _, (order, kept, overflow, _) = _contract(abc)
+    assert order.tolist() == [flat(dc.EDGE_A), flat(dc.EDGE_B), flat(dc.EDGE_C)] and not overflow
+    assert kept.tolist() == [flat(dc.EDGE_A), flat(dc.EDGE_C)]              # B fell to A; C overlaps A by 0.289 only, and B was not kept
+    # ties: the lower flat index first, whatever order the cells were named in, across heads and across anchors
+    for first, second in ((dc.EDGE_A, dc.EDGE_B), (dc.EDGE_B, dc.EDGE_B16), dc.EDGE_ANCHOR_PAIR):
+        assert flat(first) < flat(second)
+        _, (order, kept, _, _) = _contract({second: {}, first: {}})
+        assert order.tolist() == [flat(first), flat(second)] and kept.tolist() == [flat(first)]
+        assert _contract({second: {}, first: {}}, nms=1.0)[1][1].tolist() == [flat(first), flat(second)]
+    # strictly greater: at the IoU itself both stay, one ulp below it the later one goes
+    two = {dc.EDGE_A: {"tc0": 0.0}, dc.EDGE_B: {"tc0": -1.0}}
+    assert _contract(two, nms=float(dc.EDGE_IOU_1))[1][1].size == 2
+    assert _contract(two, nms=float(np.nextafter(dc.EDGE_IOU_1, np.float32(0))))[1][1].size == 1
+    # greater or equal: objectness 0.5 at conf_thres 0.5
+    assert _contract({dc.EDGE_B: {}}, conf=0.5)[1][0].size == 1
+    assert _contract({dc.EDGE_B: {}}, conf=float(np.nextafter(np.float32(0.5), np.float32(1))))[1][0].size == 0
+    # 0 / 0 is no overlap
+    hd, _, cy, cx = dc.EDGE_B
+    empty = {"box": (0, 0, -200, -200), "tc0": -1.0}
+    c, (order, kept, _, ious) = _contract({(hd, 0, cy, cx): empty, (hd, 1, cy, cx): empty}, nms=0.0)
+    assert kept.size == 2 and np.isnan(ious[0, 1]) and c["box"][order[0]].tolist() == [48.0] * 4
+
+
+def test_reference_takes_non_finite_cells_out_and_reports_them():
+    flat = dc.flat_index(dc.EDGE_B)
+    for spec, out, bit in (({"to": np.nan}, True, True), ({"tc0": np.nan}, True, True), ({"box": (0, 0, np.inf, 0)}, True, True),
+                           ({"box": (0, 0, 89, 0)}, True, True), ({"box": (np.nan, 0, 0, 0)}, True, True), ({"box": (0, 0, 80, 0)}, False, False),
+                           ({"to": -8.0, "box": (np.nan, 0, 0, 0)}, True, False)):       # below the threshold: no candidate, no bit
+        heads = dc.edge_heads({dc.EDGE_B: spec, dc.EDGE_A: {}})
+        for dtype in (np.float64, np.float32):
+            c = det_ref.decode(heads, dtype)[0]
+            cand, nonfinite = det_ref.candidates(c, 0.1)
+            assert (not cand[flat]) == out and nonfinite == bit, (spec, dtype)
+            assert det_ref.select(c, 0.1, 0.4)[0].tolist() == [dc.flat_index(dc.EDGE_A)] + ([] if out else [flat])
+    # a NaN among the other classes never beats class 0
+    heads = dc.edge_heads({dc.EDGE_B: {}})
+    hd, a, cy, cx = dc.EDGE_B
+    heads[hd][0, cy, cx, a * 85 + 5 + 7] = np.nan
+    c = det_ref.decode(heads)[0]
+    assert c["person"][flat]
+    cand, nonfinite = det_ref.candidates(c, 0.1)
+    assert cand[flat] and cand.sum() == 1 and not nonfinite
+
+
+def test_cut_heads_hold_what_the_cut_tests_need():
+    M = detector.MAX_CAND
+    for n, tie in ((M, False), (M + 1, False), (M + 1, True)):
+        heads, pick = dc.cut_heads(n, tie)
+        c = det_ref.decode(heads, np.float64, np.float32)[0]
+        order, kept, overflow, _ = det_ref.select(c, 0.1, 1.0)
+        assert len(set(pick)) == n and det_ref.candidates(c, 0.1)[0].sum() == n and overflow == (n > M)
+        assert order.size == M and np.array_equal(order, kept)
+        s = np.sort(c["score"][[dc.flat_index(p) for p in pick]])
+        assert (np.diff(s)[1 if tie else 0:] > 1e-5).all() and (s[0] == s[1]) == tie
+
+
+def test_status_text_names_every_set_bit():
+    texts = [detector.status_text(s, 0.1, 100) for s in range(8)]
+    assert texts[0] == ""
+    names = {detector.STATUS_CAND_OVERFLOW: "more than 1024 candidates above conf_thres 0.1", detector.STATUS_DET_OVERFLOW: "more than 100 boxes after NMS",
+             detector.STATUS_NONFINITE: "not finite"}
+    assert sorted(names) == [1, 2, 4]
+    for s in range(8):
+        for bit, name in names.items():
+            assert (name in texts[s]) == bool(s & bit), (s, bit, texts[s])
+        assert texts[s].count(";") == max(0, bin(s).count("1") - 1) and "unknown" not in texts[s]
+    assert "unknown status bits 0x8" in detector.status_text(9, 0.1, 100) and "candidates" in detector.status_text(9, 0.1, 100)
+
+
+def test_unmap_symbol_and_status_bit_are_declared_bound_and_exported():
+    import os
+    import re
+    from conftest import REPO
+    hdr = open(os.path.join(REPO, "include", "poserisk_hip.h")).read()
+    lib = detector._lib.load()
+    assert re.search(r"\bpr_det_unmap\s*\(", hdr) and "pr_det_unmap" in detector._lib.SIGNATURES and hasattr(lib, "pr_det_unmap")
+    assert lib.pr_det_unmap.argtypes == detector._lib.SIGNATURES["pr_det_unmap"][1]
+    assert re.search(r"PR_DET_STATUS_NONFINITE\s*=\s*4\b", hdr) and detector.STATUS_NONFINITE == 4
+    assert lib.pr_abi_version() == detector._lib.ABI_VERSION      # a function was added: no ABI bump
+    # refusals come before any device work: they need no GPU
+    for args, name in (((None, 1, 2, 4, 54, 96, 64, 96), "null boxes_dev"), ((1, None, 2, 4, 54, 96, 64, 96), "null count_dev"),
+                       ((1, 1, 4097, 4, 54, 96, 64, 96), "B = 4097"), ((1, 1, 2, 1025, 54, 96, 64, 96), "max_det = 1025"),
+                       ((1, 1, 2, 4, 54, 0, 64, 96), "frames of 0 x 54"), ((1, 1, 2, 4, 54, 96, 64, 100), "multiples of 32")):
+        with pytest.raises(detector._lib.PoseRiskHipError, match="pr_det_unmap: .*" + name):
+            detector._lib.check(lib.pr_det_unmap(*args, None), "pr_det_unmap")

@@ -173,20 +173,262 @@ def test_postprocess_reports_more_boxes_than_max_det(gpu_device):
         det.postprocess(heads, 1.5, dc.NMS, 5)
 
 
+# ---- 3b. post-processing ON its contract's edges: ties, thresholds met exactly, empty boxes, the cut, non-finite values -------------
+# No margins here (_assert_margins is for the tolerance tests above): the crafted cells have tx = ty = tw = th = 0, so their boxes
+# and IoUs are exact in fp32 and the reference is the contract to the letter, det_ref.decode(heads, float64, float32).
+def _run_post(det, heads, conf, nms, max_det, device):
+    B = heads[0].shape[0]
+    outs = gb.run_guarded(lambda i, o: det.postprocess([i["h0"], i["h1"], i["h2"]], conf, nms, max_det, out=o),
+                          {f"h{k}": torch.from_numpy(np.ascontiguousarray(h)) for k, h in enumerate(heads)},
+                          {"boxes": ((B, max_det, 4), torch.float32), "scores": ((B, max_det), torch.float32), "count": ((B,), torch.int32),
+                           "status": ((B,), torch.int32)}, device=device)
+    return [outs[k].cpu().numpy() for k in ("boxes", "scores", "count", "status")]
+
+
+def _edge_reference(heads, conf, nms):
+    """Per frame: the contract's kept flat indices in order, its fp32 boxes (exact where the box logits are 0), the float64 scores and
+    the tolerance for them (the score_tol rule: 4 x |float32 evaluation - float64|), and the status word without DET_OVERFLOW."""
+    c64, c32, cc = det_ref.decode(heads, np.float64), det_ref.decode(heads, np.float32), det_ref.decode(heads, np.float64, np.float32)
+    out = []
+    for a, f, c in zip(c64, c32, cc):
+        order, kept, overflow, _ = det_ref.select(c, conf, nms)
+        status = (detector.STATUS_CAND_OVERFLOW if overflow else 0) | (detector.STATUS_NONFINITE if det_ref.candidates(c, conf)[1] else 0)
+        out.append({"order": order, "kept": kept, "status": status, "box32": c["box"][kept], "box": a["box"][kept], "score": a["score"][kept],
+                    "box_tol": 4 * float(np.abs(f["box"][kept].astype(np.float64) - a["box"][kept]).max()) if kept.size else 0.0,
+                    "score_tol": 4 * float(np.abs(f["score"][kept].astype(np.float64) - a["score"][kept]).max()) if kept.size else 0.0})
+    return out
+
+
+def _assert_edge(got, ref, b, what, exact_boxes=True):
+    boxes, scores, count, status = got
+    n = int(count[b])
+    assert n == ref["kept"].size, f"{what} frame {b}: {n} boxes, the contract keeps {ref['kept'].size} (cells {ref['kept'].tolist()[:8]})"
+    assert int(status[b]) == ref["status"], (what, b, int(status[b]), ref["status"])
+    if n:
+        if exact_boxes:
+            assert np.array_equal(boxes[b, :n], ref["box32"]), f"{what} frame {b}: boxes\n{boxes[b, :n]}\nfor\n{ref['box32']}"
+        else:
+            eb = float(np.abs(boxes[b, :n].astype(np.float64) - ref["box"]).max())
+            print(f"[edge] {what} frame {b} boxes: {eb:.3e} px (tolerance {ref['box_tol']:g})")
+            assert eb <= ref["box_tol"], (what, b, eb, ref["box_tol"])
+        es = float(np.abs(scores[b, :n].astype(np.float64) - ref["score"]).max())
+        print(f"[edge] {what} frame {b} scores: {es:.3e} (tolerance {ref['score_tol']:g})")
+        assert es <= ref["score_tol"], (what, b, es, ref["score_tol"])
+    assert not boxes[b, n:].any() and not scores[b, n:].any(), f"{what} frame {b}: rows beyond count are not zero"
+
+
+def _edge_case(gpu_device, cells, conf, nms, want_kept, what, max_det=16):
+    """Run the named cells; the kept cells, in order, must be `want_kept` by the contract reference AND on the GPU."""
+    det = _detector(gpu_device, dc.POST_SIZE)
+    heads = dc.edge_heads(cells)
+    ref = _edge_reference(heads, conf, nms)[0]
+    assert ref["kept"].tolist() == [dc.flat_index(c) for c in want_kept], (what, ref["kept"].tolist())
+    got = _run_post(det, heads, conf, nms, max_det, gpu_device)
+    _assert_edge(got, ref, 0, what)
+    return got, ref
+
+
+def test_nms_drops_only_above_the_threshold_never_at_it(gpu_device):
+    cells = {dc.EDGE_A: {"tc0": 0.0}, dc.EDGE_B: {"tc0": -1.0}}
+    at = float(dc.EDGE_IOU_1)
+    below = float(np.nextafter(dc.EDGE_IOU_1, np.float32(0)))
+    assert np.float32(at) == dc.EDGE_IOU_1 and np.float32(below) < dc.EDGE_IOU_1
+    _edge_case(gpu_device, cells, 0.1, at, [dc.EDGE_A, dc.EDGE_B], "IoU == nms_thres")
+    _edge_case(gpu_device, cells, 0.1, below, [dc.EDGE_A], "IoU one ulp above nms_thres")
+
+
+def test_objectness_equal_to_the_threshold_is_a_candidate(gpu_device):
+    cells = {dc.EDGE_B: {}}
+    above = float(np.nextafter(np.float32(0.5), np.float32(1)))
+    got, _ = _edge_case(gpu_device, cells, 0.5, 0.4, [dc.EDGE_B], "obj == conf_thres")
+    assert got[2][0] == 1
+    got, _ = _edge_case(gpu_device, cells, above, 0.4, [], "obj one ulp below conf_thres")
+    assert got[2][0] == 0
+
+
+TIE_PAIRS = {"one column apart": (dc.EDGE_A, dc.EDGE_B), "head 32 and head 16": (dc.EDGE_B, dc.EDGE_B16), "two anchors of a cell": dc.EDGE_ANCHOR_PAIR}
+
+
+@pytest.mark.parametrize("pair", TIE_PAIRS, ids=[k.replace(" ", "-") for k in TIE_PAIRS])
+def test_equal_scores_are_ordered_by_the_flat_index(gpu_device, pair):
+    first, second = TIE_PAIRS[pair]
+    assert dc.flat_index(first) < dc.flat_index(second)
+    cells = {second: {}, first: {}}
+    got, ref = _edge_case(gpu_device, cells, 0.1, 0.4, [first], pair)
+    assert got[1][0, 0] == np.float32(0.25)
+    got, ref = _edge_case(gpu_device, cells, 0.1, 1.0, [first, second], pair + ", nms_thres = 1")
+    assert got[1][0, 0] == got[1][0, 1] == np.float32(0.25)
+
+
+def test_only_a_kept_box_suppresses(gpu_device):
+    cells = {dc.EDGE_A: {"tc0": 0.0}, dc.EDGE_B: {"tc0": -1.0}, dc.EDGE_C: {"tc0": -2.0}}
+    _edge_case(gpu_device, cells, 0.1, 0.4, [dc.EDGE_A, dc.EDGE_C], "A > B > C")
+
+
+@pytest.mark.parametrize("nms", (0.4, 0.0))
+def test_empty_boxes_overlap_nothing(gpu_device, nms):
+    hd, _, cy, cx = dc.EDGE_B
+    e0, e1, big = (hd, 0, cy, cx), (hd, 1, cy, cx), (hd, 2, cy, cx)
+    empty = {"box": (0, 0, -200, -200), "tc0": -1.0}
+    got, ref = _edge_case(gpu_device, {e0: empty, e1: empty}, 0.1, nms, [e0, e1], "two empty boxes: 0 / 0")
+    assert np.array_equal(got[0][0, :2], np.array([[48, 48, 48, 48]] * 2, np.float32))
+    # inside the 373 x 326 box of the same cell, which is kept first: IoU 0 / area = 0
+    got, ref = _edge_case(gpu_device, {e0: empty, e1: empty, big: {}}, 0.1, nms, [big, e0, e1], "empty boxes inside a kept one")
+    assert np.array_equal(got[0][0, 0], np.array([48 - 186.5, 48 - 163, 48 + 186.5, 48 + 163], np.float32))
+
+
+@pytest.mark.parametrize("n,tie", ((detector.MAX_CAND, False), (detector.MAX_CAND + 1, False), (detector.MAX_CAND + 1, True)),
+                         ids=("exactly-MAX_CAND", "one-more", "one-more-tied-at-the-cut"))
+def test_the_cut_at_max_cand(gpu_device, n, tie):
+    """nms_thres = 1 keeps every participant, so the output IS the list of those that took part, in order."""
+    M = detector.MAX_CAND
+    det = _detector(gpu_device, dc.POST_SIZE)
+    heads, pick = dc.cut_heads(n, tie)
+    ref = _edge_reference(heads, 0.1, 1.0)[0]
+    flats = np.array([dc.flat_index(c) for c in pick])
+    score = det_ref.decode(heads)[0]["score"]
+    by_rank = flats[np.lexsort((flats, -score[flats]))]
+    assert ref["kept"].size == M and np.array_equal(ref["kept"], by_rank[:M])
+    assert ref["status"] == (detector.STATUS_CAND_OVERFLOW if n > M else 0)
+    if tie:      # ranks M - 1 and M hold one score: the lower flat index takes part
+        assert score[by_rank[M - 1]] == score[by_rank[M]] and by_rank[M - 1] < by_rank[M]
+    got = _run_post(det, heads, 0.1, 1.0, M, gpu_device)
+    _assert_edge(got, ref, 0, f"cut {n} tie {tie}", exact_boxes=False)
+
+
+def test_frames_are_independent_and_runs_reproduce(gpu_device):
+    det = _detector(gpu_device, dc.POST_SIZE)
+    heads = dc.crafted_heads(*dc.POST_SIZE)
+    M = detector.MAX_CAND
+    whole = _run_post(det, heads, dc.CONF, dc.NMS, M, gpu_device)
+    again = _run_post(det, heads, dc.CONF, dc.NMS, M, gpu_device)
+    for name, a, b in zip(("boxes", "scores", "count", "status"), whole, again):
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"{name}: a second run of the same call gives other bits"
+    for b in range(3):
+        alone = _run_post(det, [h[b:b + 1] for h in heads], dc.CONF, dc.NMS, M, gpu_device)
+        for name, a, w in zip(("boxes", "scores", "count", "status"), alone, whole):
+            assert np.array_equal(a[0].view(np.uint32), w[b].view(np.uint32)), f"frame {b} {name}: alone is not what it is in a batch of 3"
+
+
+def _poison(kind):
+    """Three copies of crafted_heads' frame 0, frame 1 poisoned in its best kept cell -> (clean heads, poisoned heads)."""
+    clean = [np.repeat(h[:1], 3, axis=0) for h in dc.crafted_heads(*dc.POST_SIZE)]
+    cells = det_ref.decode([h[:1] for h in clean], np.float64, np.float32)[0]
+    flat = int(det_ref.select(cells, dc.CONF, dc.NMS)[1][0])
+    hd, a, cy, cx = dc.all_cells()[flat]
+    assert dc.flat_index((hd, a, cy, cx)) == flat
+    bad = [h.copy() for h in clean]
+    channel, value = {"to-nan": (4, np.nan), "tc0-nan": (5, np.nan), "tw-inf": (2, np.inf), "tw-89": (2, 89.0), "tx-nan": (0, np.nan),
+                      "class7-nan": (5 + 7, np.nan)}[kind]
+    bad[hd][1, cy, cx, a * 85 + channel] = value
+    return clean, bad, flat
+
+
+@pytest.mark.parametrize("kind", ("to-nan", "tc0-nan", "tw-inf", "tw-89", "tx-nan", "class7-nan"))
+def test_a_non_finite_head_value_takes_its_cell_out_and_is_reported(gpu_device, kind):
+    det = _detector(gpu_device, dc.POST_SIZE)
+    clean, bad, flat = _poison(kind)
+    M = detector.MAX_CAND
+    ref_clean, ref = _edge_reference(clean, dc.CONF, dc.NMS), _edge_reference(bad, dc.CONF, dc.NMS)
+    harmless = kind == "class7-nan"
+    assert (flat in ref[1]["kept"]) == harmless and ref[1]["status"] == (0 if harmless else detector.STATUS_NONFINITE)
+    assert flat in ref_clean[1]["order"] and (flat in ref[1]["order"]) == harmless
+    assert np.array_equal(ref[0]["kept"], ref_clean[0]["kept"]) and ref[0]["status"] == ref[2]["status"] == 0
+    if kind == "tw-89":      # finite in float64, infinite in fp32 only
+        assert np.isfinite(det_ref.decode([h[1:2] for h in bad])[0]["box"][flat]).all()
+    want = _run_post(det, clean, dc.CONF, dc.NMS, M, gpu_device)
+    got = _run_post(det, bad, dc.CONF, dc.NMS, M, gpu_device)
+    again = _run_post(det, bad, dc.CONF, dc.NMS, M, gpu_device)
+    for name, g, w, r in zip(("boxes", "scores", "count", "status"), got, want, again):
+        assert np.array_equal(g.view(np.uint32), r.view(np.uint32)), f"{name}: a second run gives other bits"
+        for b in (0, 2):
+            assert np.array_equal(g[b].view(np.uint32), w[b].view(np.uint32)), f"frame {b} {name}: changed by a value in frame 1"
+    assert not want[3].any() and got[3][0] == 0 and got[3][2] == 0
+    _assert_edge(got, ref[1], 1, kind, exact_boxes=False)
+    if harmless:
+        assert np.array_equal(got[0][1].view(np.uint32), want[0][1].view(np.uint32)) and got[3][1] == 0
+
+
+# ---- 3c. the map back to the frame, alone ---------------------------------------------------------------------------------------
+def test_unmap_geometries_cover_both_bars_and_both_scale_directions():
+    geo = [(H, W) + detector.letterbox_geometry(H, W, S_h, S_w) for H, W, S_h, S_w in dc.UNMAP_GEOMETRIES]      # H, W, h', w', ox, oy
+    assert {c[1:5] for c in dc.LETTERBOX_CASES} <= set(dc.UNMAP_GEOMETRIES)
+    assert {(1080, 1920, 416, 416), (1920, 1080, 416, 416), (1, 1, 32, 32)} <= set(dc.UNMAP_GEOMETRIES)
+    assert any(max(g[:2]) == 4096 for g in dc.UNMAP_GEOMETRIES)                       # PR_RESIZE_MAX_SIDE
+    assert any(ox > 0 and oy == 0 for *_, ox, oy in geo) and any(oy > 0 and ox == 0 for *_, ox, oy in geo)
+    sx = [np.float32(W) / np.float32(w2) for H, W, h2, w2, ox, oy in geo]
+    sy = [np.float32(H) / np.float32(h2) for H, W, h2, w2, ox, oy in geo]
+    assert max(sx) > 1 and min(sx) < 1 and max(sy) > 1 and min(sy) < 1 and any(a != b for a, b in zip(sx, sy))
+
+
+@pytest.mark.parametrize("geometry", dc.UNMAP_GEOMETRIES, ids=lambda g: "x".join(str(v) for v in g))
+def test_unmap_alone_is_bit_exact(gpu_device, geometry):
+    """A subtraction, a multiplication by one rounded fp32 quotient and two clamps, each rounded, none fusable: equality."""
+    H, W, S_h, S_w = geometry
+    h2, w2, ox, oy = detector.letterbox_geometry(H, W, S_h, S_w)
+    boxes, kinds = dc.unmap_boxes(h2, w2, ox, oy, S_h, S_w)
+    count = np.array(dc.UNMAP_COUNTS, np.int32)
+    want = boxes.copy()
+    for b, n in enumerate(count):
+        want[b, :n] = det_ref.unmap(boxes[b, :n], H, W, S_h, S_w, np.float32)
+    assert want.dtype == np.float32
+    # what the reference itself says of the crafted rows: a box inside a padding bar comes out empty, on the frame's edge
+    f0 = want[0]
+    assert (f0[kinds["bar_x"], 0] == f0[kinds["bar_x"], 2]).all() and f0[kinds["bar_x"], 0].tolist() == [0.0, float(W)]
+    assert (f0[kinds["bar_y"], 1] == f0[kinds["bar_y"], 3]).all() and f0[kinds["bar_y"], 1].tolist() == [0.0, float(H)]
+    assert f0[kinds["corners"][0]].tolist() == [0.0, 0.0, float(W), float(H)]
+    assert (f0[kinds["inside"], 2] > f0[kinds["inside"], 0]).all() and (f0[kinds["inside"], 3] > f0[kinds["inside"], 1]).all()
+    assert (f0[:, 0::2] >= 0).all() and (f0[:, 0::2] <= W).all() and (f0[:, 1::2] >= 0).all() and (f0[:, 1::2] <= H).all()
+    ins = {"boxes": torch.from_numpy(boxes), "count": torch.from_numpy(count)}
+    got = {}
+
+    def run(i, o):
+        detector.unmap(i["boxes"], i["count"], (H, W), (S_h, S_w))
+        got["boxes"] = i["boxes"].cpu().numpy()
+
+    gb.run_guarded(run, ins, {}, device=gpu_device, mutated=("boxes",))
+    g = got["boxes"]
+    for b, n in enumerate(count):
+        assert np.array_equal(g[b, n:].view(np.uint32), boxes[b, n:].view(np.uint32)), f"frame {b}: a row at or beyond count {n} was touched"
+    bad = np.argwhere(g.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, (f"{len(bad)} values differ, first (frame, row, corner) {bad[0].tolist()}: {g[tuple(bad[0])]!r} for "
+                           f"{want[tuple(bad[0])]!r} from {boxes[tuple(bad[0])]!r}")
+
+
+def test_unmap_refuses_by_name(gpu_device):
+    boxes = torch.zeros((2, 4, 4), device=gpu_device)
+    count = torch.zeros((2,), dtype=torch.int32, device=gpu_device)
+    lib = detector._lib.load()
+    for args, name in (((None, count.data_ptr(), 2, 4, 54, 96, 64, 96), "null boxes_dev"), ((boxes.data_ptr(), None, 2, 4, 54, 96, 64, 96), "null count_dev"),
+                       ((boxes.data_ptr(), count.data_ptr(), -1, 4, 54, 96, 64, 96), "B = -1"),
+                       ((boxes.data_ptr(), count.data_ptr(), 2, 0, 54, 96, 64, 96), "max_det = 0"),
+                       ((boxes.data_ptr(), count.data_ptr(), 2, 4, 0, 96, 64, 96), "frames of 96 x 0"),
+                       ((boxes.data_ptr(), count.data_ptr(), 2, 4, 54, 4097, 64, 96), "frames of 4097 x 54"),
+                       ((boxes.data_ptr(), count.data_ptr(), 2, 4, 54, 96, 48, 96), "multiples of 32")):
+        with pytest.raises(detector._lib.PoseRiskHipError, match="pr_det_unmap: .*" + name):
+            detector._lib.check(lib.pr_det_unmap(*args, None), "pr_det_unmap")
+    detector._lib.check(lib.pr_det_unmap(boxes.data_ptr(), count.data_ptr(), 0, 4, 54, 96, 64, 96, None), "pr_det_unmap")      # B = 0: PR_OK
+    with pytest.raises(ValueError, match="boxes must be"):
+        detector.unmap(boxes[:, :, :3].contiguous(), count, (54, 96), (64, 96))
+
+
 # ---- 4. pr_det_detect end to end ------------------------------------------------------------------------------------------------
-def test_detect_end_to_end_against_the_chained_references(gpu_device):
+@pytest.mark.parametrize("case", dc.DETECT_CASES, ids=lambda c: f"{c[0]}x{c[1]}" + ("-bgr" if c[2] else ""))
+def test_detect_end_to_end_against_the_chained_references(gpu_device, case):
     S_h, S_w = dc.DETECT_SIZE
-    H, W = dc.DETECT_FRAME
+    H, W, bgr = case
     B = 3
     det = _detector(gpu_device, dc.DETECT_SIZE)
     frames = dc.frames(dc.DETECT_SEED, B, H, W)
-    x = det_ref.letterbox(frames, S_h, S_w)
+    x = det_ref.letterbox(frames, S_h, S_w, bgr)
+    h2, w2, ox, oy = detector.letterbox_geometry(H, W, S_h, S_w)
+    in_a_bar = 0
     chains = {}
     for name, tdt, ndt in (("f64", torch.float64, np.float64), ("f32", torch.float32, np.float32)):
         o = det_ref.forward(dc.weights(), x, tdt)
         chains[name] = det_ref.decode([o[l].astype(np.float32) for l in detector.HEAD_LAYERS], ndt)
     M = 256
-    outs = gb.run_guarded(lambda i, o: det.detect_raw(i["frames"], False, dc.CONF, dc.NMS, M, out=o), {"frames": torch.from_numpy(frames)},
+    outs = gb.run_guarded(lambda i, o: det.detect_raw(i["frames"], bgr, dc.CONF, dc.NMS, M, out=o), {"frames": torch.from_numpy(frames)},
                           {"boxes": ((B, M, 4), torch.float32), "scores": ((B, M), torch.float32), "count": ((B,), torch.int32),
                            "status": ((B,), torch.int32)}, device=gpu_device)
     boxes, scores, count, status = (outs[k].cpu().numpy() for k in ("boxes", "scores", "count", "status"))
@@ -202,6 +444,8 @@ def test_detect_end_to_end_against_the_chained_references(gpu_device):
             continue
         _, kept32, _, _ = det_ref.select(f, dc.CONF, dc.NMS)
         assert np.array_equal(kept, kept32), f"frame {b}: the float32 chain keeps another set"
+        lb = a["box"][kept]
+        in_a_bar += int(((lb[:, 2] <= ox) | (lb[:, 0] >= ox + w2) | (lb[:, 3] <= oy) | (lb[:, 1] >= oy + h2)).sum())
         want = det_ref.unmap(a["box"][kept], H, W, S_h, S_w, np.float64)
         yard = det_ref.unmap(f["box"][kept], H, W, S_h, S_w, np.float32).astype(np.float64)
         assert int(count[b]) == kept.size and status[b] == 0, (b, int(count[b]), kept.size)
@@ -209,12 +453,14 @@ def test_detect_end_to_end_against_the_chained_references(gpu_device):
             tb, ts = 4 * float(np.abs(yard - want).max()), 4 * float(np.abs(f["score"][kept].astype(np.float64) - a["score"][kept]).max())
             eb = float(np.abs(boxes[b, :kept.size].astype(np.float64) - want).max())
             es = float(np.abs(scores[b, :kept.size].astype(np.float64) - a["score"][kept]).max())
-            measured(f"det detect frame {b} boxes", eb, tb, "px")
-            measured(f"det detect frame {b} scores", es, ts)
+            measured(f"det detect {H}x{W}{' bgr' if bgr else ''} frame {b} boxes", eb, tb, "px")
+            measured(f"det detect {H}x{W}{' bgr' if bgr else ''} frame {b} scores", es, ts)
             assert eb <= tb and es <= ts, (b, eb, tb, es, ts)
             compared += kept.size
     assert total >= 20 and compared > 0, (total, compared)
     assert left_out <= 0.02 * total, f"{left_out} of {total} reference candidates left out"
+    if (H, W) == (97, 41):      # the clip has work: kept boxes wholly inside a padding bar, which come out empty on the frame's edge
+        assert in_a_bar >= 1, "no reference box lies wholly inside a padding bar"
 
 
 # ---- 5. the Predictor with the built-in tracker ---------------------------------------------------------------------------------
