@@ -11,7 +11,7 @@ What is imported from the reference, unmodified (sys.path ordered as main/__init
   * coord_utils  -> get_joint_cam, axis_angle_to_euler_angle, rotationMatrixToEulerAngles
     (it does `import cv2`; OpenCV is absent here, so oracle.rodrigues_cv.Rodrigues is installed as
     the `cv2` module: the Euler arithmetic is the reference's, the Rodrigues part is ours)
-  * reba.REBA, rula.RULA  -> scores and log_score
+  * reba.REBA, rula.RULA  -> scores and log_score (scores.npz; score_probes.npz over the probe set of tests/score_cases.py)
   * core.base  -> Predictor.get_pose_estimation_results (base.py:211-240) and Predictor.post_processing
     (base.py:242-271), called UNBOUND on a plain namespace holding oracle.hmr_ref as `spin_model` (SPIN's source is not in
     the tree) and the synthetic SMPL holder.  `import core.base` needs modules the container lacks -- easydict,
@@ -231,6 +231,41 @@ def gen_scores():
         np.savez_compressed(os.path.join(HERE, f"scores.pose.{i}.npz"), pose=pose[s:s + 1500])
 
 
+def gen_score_probes(out_dir=HERE):
+    """score_probes.npz: the reference's REBA(False) / RULA(False) over every (pose block, info) pair of tests/score_cases.py
+    -- every rule-class product, every special value, every table cell under shifts that cross table C.  Poses, infos and
+    pairs are stored beside the results, so the fixture is self-contained data; results are int8 in the kernels' column
+    order, one row per (pair, pose), pairs in order."""
+    from reba import REBA
+    from rula import RULA
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import score_cases
+    pose, blocks, infos, pairs = score_cases.build()
+    jc = np.zeros((len(pose), 24, 3), np.float32)
+
+    def ints(s):
+        return [int(x) for x in s.split(",")]
+
+    reba, rula = [], []
+    for block, i in pairs:
+        a, b = blocks[block]
+        for d in REBA(False)(pose[a:b], jc[a:b], infos[i]):
+            reba.append([d["score"], *d["log_score"][:3], *ints(d["log_score"][3]), *ints(d["log_score"][4]),
+                         *ints(d["log_score"][5])])
+        for d in RULA(False)(pose[a:b], jc[a:b], infos[i]):
+            rula.append([d["score"], *ints(d["log_score"][0]), *ints(d["log_score"][1]), *ints(d["log_score"][2]),
+                         *ints(d["log_score"][3]), *d["log_score"][4:]])
+    reba, rula = np.array(reba, np.int64), np.array(rula, np.int64)
+    assert np.abs(reba).max() < 128 and np.abs(rula).max() < 128
+    np.savez_compressed(os.path.join(out_dir, "score_probes.npz"), infos_json=np.array(json.dumps(infos)),
+                        blocks_json=np.array(json.dumps(blocks)),
+                        pairs=np.array([[*blocks[b], i] for b, i in pairs], np.int32),
+                        pair_blocks_json=np.array(json.dumps([b for b, _ in pairs])),
+                        reba=reba.astype(np.int8), rula=rula.astype(np.int8), pose=pose)
+    # few distinct doubles: the poses compress to a tenth, so the one file stays far below 1 MiB and needs no row chunks
+    assert os.path.getsize(os.path.join(out_dir, "score_probes.npz")) < 1 << 20
+
+
 def _import_reference_core_base():
     """`import core.base` as main/run.py:7 reaches it, with empty modules standing where the container lacks a package."""
     os.environ.setdefault("MPLBACKEND", "Agg")
@@ -316,6 +351,7 @@ if __name__ == "__main__":
     gen_smpl_sweep()
     gen_euler()
     gen_scores()
+    gen_score_probes()
     gen_driver_loop()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
