@@ -535,6 +535,52 @@ typedef struct pr_compose_args {
 int pr_compose_video(const pr_compose_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* r3  people video: frame + every tracked person's box and tag + people panel, one call  */
+/*     a batch.  No counterpart in the reference, which draws one person; no ABI bump:    */
+/*     a function was added, no signature changed                                         */
+/* ------------------------------------------------------------------------------------ */
+/* People contract.  Integer-exact, so that tests/video_people_ref.py (numpy) reproduces every byte.
+ *
+ * Canvas, area resample, src_idx, status bit 0 and the limits on H, W, dst_w, dst_h, panel_w, C, S, CH, CW, adv and ascent:
+ *   r2's, word for word.
+ * Boxes, on the source BEFORE resampling.  box int32[N,K,4] = (x_min, y_min, x_max, y_max) and box_rgb u8[N,K,4] (channels 0,
+ *   1, 2 of the frames' order; [3] unused), 1 <= K <= PR_PEOPLE_MAX_BOXES.  Slot k of canvas n paints r2's outline (Chebyshev
+ *   distance 1 of the rectangle, clipped to the frame) in its own colour.  Slots are painted in index order, later over
+ *   earlier.  x_max < x_min means no box in that slot; a NULL box means no box in any slot (box_rgb may then be NULL too).
+ *   Corners may be any int32.
+ * Lines.  lines int32[N,L,5], text u8[N,L,C] and the atlas as in r2, 0 <= L <= PR_PEOPLE_MAX_LINES.  L_img (0 <= L_img <= L)
+ *   splits them in two groups:
+ *     [0, L_img)  tags.  The origin is in canvas coordinates.  A tag is drawn AFTER resampling over the image region, columns
+ *                 [0, dst_w): r2's coverage blend with bg_c = the resampled image byte (0 where the frame index is outside
+ *                 the range), then what earlier tags left.  A tag never touches the panel.
+ *     [L_img, L)  panel lines: r2's rule, r2's clipping to the panel, bg black.  A panel line never touches the image.
+ *   Lines apply in index order within each group; the two groups do not meet.
+ * Reduction.  With K = 1, L_img = 0 and box_rgb[n][0] equal to r2's box_rgb for every n, every output byte and status word
+ *   equals pr_compose_video's on the same remaining arguments.
+ *
+ * status, argument errors (PR_ERR_INVALID before any device work, `out` untouched), N = 0, asynchrony: r2's.  One launch, no
+ * workspace, no allocation, no synchronisation (capturable).  A canvas depends on no other canvas of the batch. */
+#define PR_PEOPLE_MAX_BOXES 16
+#define PR_PEOPLE_MAX_LINES 32
+typedef struct pr_compose_people_args {
+  const uint8_t* frames;    /* u8[n_frames,H,W,3] */
+  const int32_t* src_idx;   /* int32[N] or NULL */
+  const int32_t* box;       /* int32[N,K,4] or NULL */
+  const uint8_t* box_rgb;   /* u8[N,K,4] */
+  const int32_t* lines;     /* int32[N,L,5]  (may be NULL when L = 0, like text and atlas) */
+  const uint8_t* text;      /* u8[N,L,C] */
+  const uint8_t* atlas;     /* u8[S,96,CH,CW] */
+  uint8_t* out;             /* u8[N,dst_h,dst_w+panel_w,3] */
+  int32_t* status;          /* int32[N] or NULL */
+  int N, n_frames, H, W;
+  int dst_h, dst_w, panel_w;
+  int K, L, L_img, C, S, CH, CW;
+  int adv[PR_VIDEO_MAX_CLASSES], ascent[PR_VIDEO_MAX_CLASSES];
+} pr_compose_people_args;
+
+int pr_compose_people(const pr_compose_people_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* j1  baseline JPEG frames -> u8[F,H,W,3] on the device, bit-exact with libjpeg         */
 /* replaces: cv2.imread in CropDataset.__getitem__ data/demo_dataset.py:58-59 on the      */
 /*           <output>/tmp/%09d.jpg files the front end writes (lib/core/base.py:47-56)    */

@@ -45,6 +45,13 @@ class ComposeArgs(C.Structure):
                [("adv", C.c_int * 4), ("ascent", C.c_int * 4), ("box_rgb", C.c_uint8 * 4)]
 
 
+class ComposePeopleArgs(C.Structure):
+    """pr_compose_people_args (include/poserisk_hip.h, the people video)."""
+    _fields_ = [(n, C.c_void_p) for n in ("frames", "src_idx", "box", "box_rgb", "lines", "text", "atlas", "out", "status")] + \
+               [(n, C.c_int) for n in ("N", "n_frames", "H", "W", "dst_h", "dst_w", "panel_w", "K", "L", "L_img", "C", "S", "CH", "CW")] + \
+               [("adv", C.c_int * 4), ("ascent", C.c_int * 4)]
+
+
 class JpegArgs(C.Structure):
     """pr_jpeg_args (include/poserisk_hip.h, the JPEG decoder)."""
     _fields_ = [(n, C.c_void_p) for n in ("data", "frames", "segments", "huff", "out", "status")] + [("data_bytes", C.c_int64)] + \
@@ -169,6 +176,7 @@ SIGNATURES = {
     "pr_render_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_render_overlay": (_I, [C.POINTER(RenderArgs), _P, C.c_size_t, _P]),
     "pr_compose_video": (_I, [C.POINTER(ComposeArgs), _P]),
+    "pr_compose_people": (_I, [C.POINTER(ComposePeopleArgs), _P]),
     "pr_jpeg_parse": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
     "pr_jpeg_refusal_name": (C.c_char_p, [_I]),
     "pr_jpeg_workspace_bytes": (C.c_size_t, [_I, _I, _I]),

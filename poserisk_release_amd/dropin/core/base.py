@@ -154,6 +154,11 @@ class Predictor:
         self.render_mesh = bool(_knob(args, 'render_mesh', 'render_mesh', False))
         # the annotated score video composed on the GPU (write_gpu_video): args.gpu_video, else cfg.DATASET.gpu_video (False)
         self.gpu_video = bool(_knob(args, 'gpu_video', 'gpu_video', False))
+        # whom __call__ scores: args.persons, else cfg.DATASET.persons.  'target' (default): the reference's one person; 'all':
+        # every kept track in one pass (score_people), with person_<id>/, people.json and <TITLE>_people beside the target's outputs
+        self.persons = str(_knob(args, 'persons', 'persons', 'target'))
+        if self.persons not in ('target', 'all'):
+            raise ValueError(f"persons {self.persons!r} is not known: 'target' or 'all' (cfg.DATASET.persons / args.persons)")
         # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
         # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
         # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
@@ -375,6 +380,68 @@ class Predictor:
             out['bbox_scale'] = float(bbox_scale)
         return out
 
+    def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None):
+        """Decoded frames + tracker output -> the scores of EVERY person tracks.people_tracks keeps, in one pass over the model:
+        {'people': [out_0, out_1, ...], 'ids': [...], 'frames_total': F}, in people_tracks order (element 0 is the person
+        score_frames scores).  Each out_p holds what score_frames returns for that person alone -- result, joint_cam,
+        debug_result, reba, rula, frames, bboxes -- bit for bit: a frame's bits do not depend on its batch
+        (tests/test_encoder_batch_sweep.py), so the people share batches.  Every person's (frame index, box) rows are
+        concatenated, cut into batches of self.batch_size across person boundaries, cropped and run through
+        get_pose_estimation_results once, and split back by offsets; the scorers and the aggregation run per person on the
+        host.  With args.debug the dict also holds 'pose_logs', each person's rows of the scorers' angle logs.
+
+        Not supported, by name: several ranks (hip_world_size / args.world_size > 1) and the render_mesh knob
+        (pr_render_overlay draws one mesh per canvas)."""
+        from poserisk_release_amd import ops, tracks
+        world, _ = pl.world_and_rank()
+        if world > 1:
+            raise NotImplementedError(f"score_people runs on one rank, this process group has {world}: persons='all' does not go "
+                                      "with hip_world_size / args.world_size > 1")
+        if self.render_mesh:
+            raise NotImplementedError("score_people does not go with the render_mesh knob: pr_render_overlay draws one mesh per "
+                                      "canvas (cfg.DATASET.render_mesh / args.render_mesh)")
+        frames = torch.as_tensor(frames)
+        if frames.device.type != 'cuda':
+            frames = frames.to(self.device)
+        if bbox_scale is None:
+            bbox_scale = cfg.DATASET.bbox_scale
+        if add_info is None:
+            add_info = default_information()
+        elif isinstance(add_info, str):
+            with open(add_info, 'r') as f:
+                add_info = json.load(f)
+        people = tracks.people_tracks(tracking_results, frames.shape[0], cfg.DATASET.min_frame_ratio)
+        bboxes = np.concatenate([b.reshape(-1, 4) for _, b, _ in people]) if people else np.zeros((0, 4), np.float32)
+        fidx = np.concatenate([np.asarray(f).reshape(-1) for _, _, f in people]) if people else np.zeros((0,), np.int64)
+        if len(fidx) and (int(np.min(fidx)) < 0 or int(np.max(fidx)) >= frames.shape[0]):
+            raise ValueError(f"tracking results name frames {int(np.min(fidx))}..{int(np.max(fidx))} but only "
+                             f"{frames.shape[0]} frames were decoded (tracking.pkl does not belong to these frames)")
+
+        def batches():                                  # across person boundaries: sum(n_p) / batch_size launches, rounded up once
+            for i in range(0, len(fidx), self.batch_size):
+                j = min(i + self.batch_size, len(fidx))
+                yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
+        result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False)
+        outs, pose_logs, lo = [], [], 0
+        for _, box_p, frames_p in people:
+            hi = lo + len(frames_p)
+            out = dict(result=result[lo:hi], joint_cam=joint_cam[lo:hi], debug_result=debug_result[lo:hi])
+            logs_p = {}
+            for key, run, scorer in (('reba', self.run_reba, self.reba), ('rula', self.run_rula, self.rula)):
+                if run:
+                    seen = len(scorer.log)
+                    final, scores, logs = self.post_processing(scorer(out['result'], out['joint_cam'], add_info))
+                    out[key] = (final, scores, logs, scorer.action_level(final[4]))
+                    logs_p[key] = scorer.log[seen:]
+            out['frames'], out['bboxes'] = frames_p, box_p
+            outs.append(out)
+            pose_logs.append(logs_p)
+            lo = hi
+        people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': int(frames.shape[0])}
+        if self.debugging:
+            people_out['pose_logs'] = pose_logs
+        return people_out
+
     # ---- the mesh overlay (extends the --debug_frame mesh of base.py:273-282 to every track frame) -----------------
     def render_overlay(self, out, frames, title='REBA', bgr=False, alpha=0.6):
         """Yield (track frame numbers int[b], overlaid frames u8[b,H,W,3] CUDA) batch by batch: the fitted mesh of every
@@ -469,6 +536,68 @@ class Predictor:
                 yield range(i, i + int(canvases.shape[0])), canvases
                 i += int(canvases.shape[0])
         return sinks.write_all(self._open_sink(output_path, title + '_video', (canvas_h, resize_w + panel_w), fps, bgr), batches())
+
+    # ---- the persons='all' outputs (no counterpart in the reference, which describes one person) -----------------------------
+    def write_people_video(self, people_out, frames, output_path, title, bgr=False, fps=30.0):
+        """`<TITLE>_people`: every frame of the video at 720 px wide with every scored person's box and `#<id> <score>` tag in
+        the colour of that frame's action level, beside a panel that lists the people of the frame
+        (poserisk_release_amd.video.people_draw_list, pr_compose_people), from what score_people returned.  Written through
+        the sink of the gpu_video_codec knob, as write_gpu_video's.  Returns the path written."""
+        from poserisk_release_amd import video
+        frames = torch.as_tensor(frames)
+        if frames.device.type != 'cuda':
+            frames = frames.to(self.device)
+        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        scorer = self.reba if title.upper() == 'REBA' else self.rula
+        people = []
+        for pid, out in zip(people_out['ids'], people_out['people']):
+            scores = out[title.lower()][1]
+            acts = [scorer.action_level(s) for s in scores]
+            people.append(dict(id=pid, frames=out['frames'], bboxes=out['bboxes'], scores=scores, levels=[a[0] for a in acts],
+                               names=[a[1] for a in acts]))
+        canvas_h, resize_w, panel_w = video.canvas_size(H, W)
+        draw = video.people_draw_list(title, n_frames, people, canvas_h, resize_w, H, W, bgr=bgr)
+
+        def batches():                                  # one canvas per video frame, numbered 0 .. n_frames - 1
+            i = 0
+            for canvases in video.people_frames(frames, draw, self.batch_size):
+                yield range(i, i + int(canvases.shape[0])), canvases
+                i += int(canvases.shape[0])
+        return sinks.write_all(self._open_sink(output_path, title + '_people', (canvas_h, resize_w + panel_w), fps, bgr), batches())
+
+    def write_people_reports(self, people_out, output_path):
+        """<output>/person_<id>/ per scored person -- reba_result.txt / rula_result.txt and <TITLE>_score.png, with args.debug the
+        score, pose-evaluation and pose logs too, all by the functions that write the target's -- and <output>/people.json.
+        Returns the list people.json holds."""
+        from poserisk_release_amd import reports
+        plain = lambda v: v.item() if isinstance(v, np.generic) else v
+        num = lambda v: None if v is None or np.isnan(v) else float(v)        # top-10 % of fewer than 10 frames is NaN: null
+        n_frames, summary = people_out['frames_total'], []
+        for p, (pid, out) in enumerate(zip(people_out['ids'], people_out['people'])):
+            folder = osp.join(output_path, f'person_{pid}')
+            os.makedirs(folder, exist_ok=True)
+            fidx, boxes = np.asarray(out['frames']), np.asarray(out['bboxes'])
+            timestamp = (0, fidx, n_frames)
+            entry = dict(id=plain(pid), first_frame=int(fidx.min()) if fidx.size else None, last_frame=int(fidx.max()) if fidx.size else None,
+                         n_frames=int(fidx.size), mean_box_area=float((boxes[:, 2] * boxes[:, 3]).mean()) if fidx.size else None)
+            if self.debugging and self.debug_joints is not None:
+                reports.save_pose_log_csv(folder, timestamp, reports.pose_to_str(out['result']), self.debug_joints,
+                                          self.smpl_model.joints_name_upper)
+            for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
+                if title.lower() not in out:
+                    continue
+                final, scores, logs, (level, name) = out[title.lower()]
+                reports.save_score_plot(folder, title, timestamp, scores)
+                reports.write_result_txt(folder, title, final, level, name)
+                if self.debugging:
+                    reports.save_score_csv(folder, title, timestamp, scores, scorer.eval_items, logs,
+                                           people_out['pose_logs'][p][title.lower()])
+                entry[title] = dict(avg=num(final[0]), top50=num(final[1]), top10=num(final[2]), max=num(final[3]), mode=num(final[4]),
+                                    action_level=plain(level), action=name)
+            summary.append(entry)
+        with open(osp.join(output_path, 'people.json'), 'w') as f:
+            json.dump({'frames_total': n_frames, 'people': summary}, f, indent=1)
+        return summary
 
     # ---- base.py:273-282 ------------------------------------------------------------------------------------
     def visualize_joint_cam_mesh(self, debug_result, joint_cam, frames, output_path):
@@ -742,7 +871,10 @@ class Predictor:
         """The reference's entry point (base.py:126-209) around the accelerated path: front end (given, found or
         the reference's own: `load_front_end`) -> crops, pose, scores on the GPU -> `reba_result.txt` /
         `rula_result.txt`, `<TITLE>_score.png`, `<TITLE>_video.mp4` (OpenCV drawing: only where cv2 is importable; with
-        the gpu_video knob composed on the GPU instead, see write_gpu_video) and with `args.debug` the CSV logs under <output>/debug.  Returns the dict of `score_frames` plus `fps`."""
+        the gpu_video knob composed on the GPU instead, see write_gpu_video) and with `args.debug` the CSV logs under <output>/debug.  Returns the dict of `score_frames` plus `fps`.
+        With the persons knob at 'all' all of that is written for the target from score_people's element 0 (the model runs
+        once), then <output>/person_<id>/, <output>/people.json and, with gpu_video, <TITLE>_people (write_people_reports,
+        write_people_video); the dict returned also holds 'people', what score_people returned."""
         from poserisk_release_amd import reports
         os.makedirs(output_path, exist_ok=True)
         world, rank = pl.world_and_rank()
@@ -759,7 +891,14 @@ class Predictor:
                 add_info = json.load(f)
         else:
             add_info = default_information()                   # base.py:140-142
-        out = self.score_frames(frames, tracking_results, add_info, bgr=bgr)
+        people_out = None
+        if getattr(self, 'persons', 'target') == 'all':
+            # everybody in one pass; the target is element 0, bit for bit what score_frames returns, so the model runs once
+            people_out = self.score_people(frames, tracking_results, add_info, bgr=bgr)
+            out = dict(people_out['people'][0])
+            out['people'] = people_out
+        else:
+            out = self.score_frames(frames, tracking_results, add_info, bgr=bgr)
         out['fps'] = fps
         if rank != 0:
             # every rank holds all frames' results after the gather; the reports (result txt, plots, mp4, debug CSVs and
@@ -818,4 +957,12 @@ class Predictor:
                 self.write_mesh_overlay(out, frames, output_path, title, bgr, fps)
             if self.debugging:
                 reports.save_score_csv(debug_path, title, timestamp, scores, scorer.eval_items, logs, scorer.log)
+        if people_out is not None:
+            self.write_people_reports(people_out, output_path)
+            if getattr(self, 'visualize', True) and self.gpu_video:
+                for title in ('REBA', 'RULA'):
+                    if title.lower() in out:
+                        self.write_people_video(people_out, frames, output_path, title, bgr, fps)
+            elif getattr(self, 'visualize', True):
+                print("The people video (<TITLE>_people) is composed on the GPU only: it needs the gpu_video knob and is skipped")
         return out

@@ -27,6 +27,19 @@ def select_target_id(results):
     return int(np.argmax(np.array(areas)))
 
 
+def people_tracks(tracking_results, n_frames, min_frame_ratio=MIN_FRAME_RATIO):
+    """-> [(person_id, bbox f32[n,4], frames int[n])]: every track `filter_tracks` keeps (its "keep all if none qualifies"
+    rule included), by descending mean box area, ties in the dict's iteration order.  Element 0 is the track `target_track`
+    returns: the areas are select_target_id's own numbers and the sort is stable, as np.argmax takes the first maximum.  (No
+    counterpart in the reference, which scores one person.)"""
+    need = min(n_frames * min_frame_ratio, MIN_FRAME_CAP)
+    ids = [i for i, t in tracking_results.items() if np.asarray(t['frames']).shape[0] >= need] or list(tracking_results)
+    area = {i: (np.asarray(tracking_results[i]['bbox'])[:, 2] * np.asarray(tracking_results[i]['bbox'])[:, 3]).mean() for i in ids}
+    # np.argmax takes the first NaN (the mean of a track without frames) as the maximum: so does this order
+    return [(i, np.asarray(tracking_results[i]['bbox'], np.float32), np.asarray(tracking_results[i]['frames']))
+            for i in sorted(ids, key=lambda i: (0, 0.0) if np.isnan(area[i]) else (1, -area[i]))]
+
+
 def target_track(tracking_results, n_frames, min_frame_ratio=MIN_FRAME_RATIO):
     """-> (bbox f32[n,4], frames int[n]) of the person the reference scores (base.py:71-73)."""
     kept = filter_tracks(tracking_results, n_frames, min_frame_ratio)

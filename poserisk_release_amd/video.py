@@ -5,7 +5,11 @@ vis_utils.py:278-294) composed on the GPU (include/poserisk_hip.h, pr_compose_vi
 `draw_list` is the host half: the strings, origins, sizes, colours and box corners `reports.write_annotated_video` hands to
 OpenCV, per video frame.  `font_atlas` is the panel's font: a monospace coverage atlas in three sizes.  `compose` is the torch
 wrapper of the kernel, `annotated_frames` chains them batch by batch.  The Predictor's `write_gpu_video`
-(dropin/core/base.py) writes what it yields."""
+(dropin/core/base.py) writes what it yields.
+
+The people video (`<TITLE>_people`, the persons knob; no counterpart in the reference) is the second half of this file:
+`people_draw_list`, `compose_people` (pr_compose_people, csrc/compose_people.hip), `people_frames`, written by the Predictor's
+`write_people_video`."""
 import collections
 import os
 
@@ -107,14 +111,14 @@ def draw_list(title, n_frames, bboxes, timestamp, scores, joint_names, logs, can
     return DrawList(text, box)
 
 
-def pack_lines(text, L=None, C=None):
+def pack_lines(text, L=None, C=None, max_lines=MAX_LINES):
     """text (DrawList.text, or any per-canvas lists of (string, (x, y), class, colour)) -> lines int32[N,L,5], codes u8[N,L,C]
-    as pr_compose_video takes them.  Characters outside Latin-1 become '?'."""
+    as pr_compose_video takes them (max_lines=PEOPLE_MAX_LINES: as pr_compose_people does).  Characters outside Latin-1 become '?'."""
     n = len(text)
     L = max([len(t) for t in text] + [1]) if L is None else L
     C = max([len(s[0]) for t in text for s in t] + [1]) if C is None else C
-    if L > MAX_LINES:
-        raise ValueError(f"{L} lines per canvas: pr_compose_video takes at most {MAX_LINES}")
+    if L > max_lines:
+        raise ValueError(f"{L} lines per canvas: {'pr_compose_video' if max_lines == MAX_LINES else 'pr_compose_people'} takes at most {max_lines}")
     lines = np.zeros((n, L, LINE_INTS), np.int32)
     codes = np.zeros((n, L, C), np.uint8)
     for i, t in enumerate(text):
@@ -139,21 +143,11 @@ def _dev(x, dtype, dev, shape, what):
     return t
 
 
-def compose(frames, src_idx=None, box=None, lines=None, text=None, atlas=None, dst_h=None, dst_w=RESIZE_W, panel_w=PANEL_W,
-            box_rgb=GREEN, out=None, return_status=False):
-    """Compose N canvases on the GPU.
-
-    frames u8[n_frames,H,W,3] CUDA; src_idx int[N] or None (canvas n shows frame n, N = n_frames); box int[N,4] (x_min, y_min,
-    x_max, y_max; x_max < x_min: none) or None; lines int[N,L,5] + text u8[N,L,C] (pack_lines) or None (an empty panel);
-    atlas: Atlas or (cov u8[S,96,CH,CW], adv, ascent), default font_atlas(); dst_h default int(H * dst_w / W); box_rgb in the
-    frames' channel order.  Returns out u8[N,dst_h,dst_w+panel_w,3], and status int32[N] when asked for.
-
-    Arguments given as numpy arrays (or on another device) are uploaded on every call with a blocking copy -- a caller-supplied
-    numpy atlas included; only the default atlas is cached per device.  Pass CUDA tensors of the right dtype (int32 src_idx, box
-    and lines, uint8 text and atlas coverage) and `out` to make the call free of copies and allocation, which is what capturing
-    it into a graph needs."""
+def _canvas_args(who, frames, src_idx, lines, text, atlas, dst_h, dst_w, panel_w, out, return_status):
+    """The argument checks and uploads compose and compose_people share -> (frames, idx, ln, tx, cov, out, st, N, dst_h, L, C, S,
+    CH, CW, adv, ascent)."""
     if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
-        raise _lib.PoseRiskHipError("compose: frames must be a CUDA tensor (no CPU fallback)")
+        raise _lib.PoseRiskHipError(f"{who}: frames must be a CUDA tensor (no CPU fallback)")
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise ValueError("frames must be uint8 [n_frames,H,W,3]")
     dev = frames.device
@@ -166,7 +160,6 @@ def compose(frames, src_idx=None, box=None, lines=None, text=None, atlas=None, d
         N = idx.shape[0]
     else:
         idx, N = None, n_frames
-    bx = _dev(box, torch.int32, dev, (N, 4), "box") if box is not None else None
     if (lines is None) != (text is None):
         raise ValueError("lines and text come together (pack_lines)")
     ln = tx = cov = None
@@ -195,6 +188,26 @@ def compose(frames, src_idx=None, box=None, lines=None, text=None, atlas=None, d
     elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"out must be a contiguous uint8 {list(shape)} tensor on the frames' device")
     st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    return frames, idx, ln, tx, cov, out, st, N, dst_h, L, C, S, CH, CW, adv, ascent
+
+
+def compose(frames, src_idx=None, box=None, lines=None, text=None, atlas=None, dst_h=None, dst_w=RESIZE_W, panel_w=PANEL_W,
+            box_rgb=GREEN, out=None, return_status=False):
+    """Compose N canvases on the GPU.
+
+    frames u8[n_frames,H,W,3] CUDA; src_idx int[N] or None (canvas n shows frame n, N = n_frames); box int[N,4] (x_min, y_min,
+    x_max, y_max; x_max < x_min: none) or None; lines int[N,L,5] + text u8[N,L,C] (pack_lines) or None (an empty panel);
+    atlas: Atlas or (cov u8[S,96,CH,CW], adv, ascent), default font_atlas(); dst_h default int(H * dst_w / W); box_rgb in the
+    frames' channel order.  Returns out u8[N,dst_h,dst_w+panel_w,3], and status int32[N] when asked for.
+
+    Arguments given as numpy arrays (or on another device) are uploaded on every call with a blocking copy -- a caller-supplied
+    numpy atlas included; only the default atlas is cached per device.  Pass CUDA tensors of the right dtype (int32 src_idx, box
+    and lines, uint8 text and atlas coverage) and `out` to make the call free of copies and allocation, which is what capturing
+    it into a graph needs."""
+    frames, idx, ln, tx, cov, out, st, N, dst_h, L, C, S, CH, CW, adv, ascent = _canvas_args(
+        "compose", frames, src_idx, lines, text, atlas, dst_h, dst_w, panel_w, out, return_status)
+    dev, (n_frames, H, W, _) = frames.device, frames.shape
+    bx = _dev(box, torch.int32, dev, (N, 4), "box") if box is not None else None
     ptr = lambda t: t.data_ptr() if t is not None else None
     pad = lambda v: (_lib.C.c_int * 4)(*(list(v) + [0] * (4 - len(v))))
     args = _lib.ComposeArgs(frames.data_ptr(), ptr(idx), ptr(bx), ptr(ln), ptr(tx), ptr(cov), out.data_ptr(), ptr(st),
@@ -228,3 +241,121 @@ def annotated_frames(frames, draw, batch_size=64, atlas=None, overlay=None):
                 src[torch.as_tensor(np.asarray(numbers) - lo, device=src.device, dtype=torch.long)] = images
                 idx = None
         yield compose(src, idx, draw.box[lo:hi], lines, codes, atlas, dst_h, dst_w, panel_w)
+
+
+# ---- the people video (pr_compose_people): every tracked person's box and tag on the frame, a people panel beside it ----------
+PEOPLE_MAX_BOXES, PEOPLE_MAX_LINES = 16, 32     # PR_PEOPLE_MAX_BOXES, PR_PEOPLE_MAX_LINES
+PEOPLE_PANEL_ROWS = 14                          # people listed in the panel at most
+# Box, tag and panel-line colour by action level 1 .. 5 (REBA has five levels, RULA four), RGB: render.LEVEL_RGB's four, then a
+# purple for REBA's "very high risk"
+PEOPLE_LEVEL_RGB = ((40, 200, 60), (250, 220, 40), (250, 140, 20), (230, 30, 30), (170, 40, 200))
+TAG_GAP = 3                                     # px between a tag's baseline and the box's top edge
+TAG_H = FONT_PX[0]                              # rows a class-0 tag needs above its baseline to stay on the canvas
+PANEL_CHARS = (PANEL_W - 15) // 9               # class-0 characters between TEXT_X and the canvas edge (FONT_PX's comment: 9 px each)
+NO_LINE = ("", (0, 0), 0, (0, 0, 0))            # a slot that draws nothing (length 0)
+
+PeopleDraw = collections.namedtuple("PeopleDraw", "tags panel box box_rgb")     # per frame lists of lines; int32[F,K,4], u8[F,K,4]
+
+
+def people_draw_list(title, n_frames, people, canvas_h, dst_w, H, W, bgr=False):
+    """What the people video shows, per video frame, without drawing it: PeopleDraw(tags, panel, box, box_rgb).
+
+    people: one dict per person in tracks.people_tracks order, with 'id', 'frames' int[n], 'bboxes' f32[n,4] (cx, cy, w, h),
+    'scores' int[n], 'levels' int[n] (the action level of each frame's score, 1 .. 5; anything else counts as 1) and 'names'
+    (the action name of each frame's score).  A frame shows each person's OWN score of that frame: the `idx // 2 * 2` indexing
+    of draw_list is the single-target video's quirk (the reference's, Q21) and is not carried over.
+
+    Frame i draws the people whose track has frame i (the first row that names it), in the order given; more than
+    PEOPLE_MAX_BOXES of them: the 16 with the largest boxes (w * h of that frame, ties to the earlier person), still in the
+    order given.  Per person: box[i][k] = box_corners of the frame's box, box_rgb[i][k] = PEOPLE_LEVEL_RGB[level - 1] (swapped
+    with bgr), and the tag `#<id> <score>` in that colour at size class 0, its origin the box's top-left corner mapped to
+    the canvas, (floor(x_min dst_w / W), floor(y_min canvas_h / H)), its baseline TAG_GAP px above that corner -- or, where fewer
+    than TAG_H rows would be left above the baseline, TAG_GAP + TAG_H px below it.  The panel: `<TITLE> people: k` (k: the
+    people visible in the frame, all of them) in draw_list's score colour, then `#<id>  <score>  <action name>` per drawn
+    person in their colour, PEOPLE_PANEL_ROWS of them at most, cut to PANEL_CHARS characters, then draw_list's `frame: i`.
+    K = the most people drawn in one frame (at least 1); unused slots hold NO_BOX."""
+    text_x = dst_w + 15
+    where = [{int(f): r for r, f in reversed(list(enumerate(np.asarray(p['frames']).tolist())))} for p in people]
+    visible = [[(q, where[q][i]) for q in range(len(people)) if i in where[q]] for i in range(n_frames)]
+    K = max([min(len(v), PEOPLE_MAX_BOXES) for v in visible] + [1])
+    box = np.tile(np.array(NO_BOX, np.int32), (n_frames, K, 1))
+    box_rgb = np.zeros((n_frames, K, 4), np.uint8)
+    tags, panel = [], []
+    for i, vis in enumerate(visible):
+        shown = vis
+        if len(vis) > PEOPLE_MAX_BOXES:
+            area = [float(people[q]['bboxes'][r][2]) * float(people[q]['bboxes'][r][3]) for q, r in vis]
+            keep = sorted(sorted(range(len(vis)), key=lambda j: (-area[j], j))[:PEOPLE_MAX_BOXES])
+            shown = [vis[j] for j in keep]
+        t = []
+        lines = [(f"{title} people: {len(vis)}", (text_x, 35), 2, GREEN)]
+        for k, (q, r) in enumerate(shown):
+            p = people[q]
+            level = int(p['levels'][r]) if p['levels'][r] is not None else 1
+            rgb = PEOPLE_LEVEL_RGB[level - 1 if 1 <= level <= len(PEOPLE_LEVEL_RGB) else 0]
+            rgb = rgb[::-1] if bgr else rgb
+            corners = box_corners(p['bboxes'][r])
+            box[i, k], box_rgb[i, k, :3] = corners, rgb
+            x, y = corners[0] * dst_w // W, corners[1] * canvas_h // H
+            yb = y - TAG_GAP if y - TAG_GAP - TAG_H >= 0 else y + TAG_GAP + TAG_H
+            t.append((f"#{p['id']} {p['scores'][r]}", (x, yb), 0, rgb))
+            if k < PEOPLE_PANEL_ROWS:
+                lines.append((f"#{p['id']}  {p['scores'][r]}  {p['names'][r]}"[:PANEL_CHARS], (text_x, 70 + 24 * k), 0, rgb))
+        lines.append(("frame: " + str(i), (text_x, canvas_h - 14), 0, WHITE))
+        tags.append(t)
+        panel.append(lines)
+    return PeopleDraw(tags, panel, box, box_rgb)
+
+
+def compose_people(frames, src_idx=None, box=None, box_rgb=None, lines=None, text=None, L_img=0, atlas=None, dst_h=None,
+                   dst_w=RESIZE_W, panel_w=PANEL_W, out=None, return_status=False):
+    """Compose N people canvases on the GPU (pr_compose_people; the contract is section r3 of include/poserisk_hip.h).
+
+    As `compose`, with box int[N,K,4] and box_rgb u8[N,K,4] (a colour per slot, in the frames' channel order; [3] unused) in
+    place of one box and one colour, up to PEOPLE_MAX_LINES lines, and L_img: lines [0, L_img) are tags, drawn over the image
+    region; the others are panel lines.  Returns out u8[N,dst_h,dst_w+panel_w,3], and status int32[N] when asked for."""
+    frames, idx, ln, tx, cov, out, st, N, dst_h, L, C, S, CH, CW, adv, ascent = _canvas_args(
+        "compose_people", frames, src_idx, lines, text, atlas, dst_h, dst_w, panel_w, out, return_status)
+    dev, (n_frames, H, W, _) = frames.device, frames.shape
+    if (box is None) != (box_rgb is None):
+        raise ValueError("box and box_rgb come together")
+    bx = rgb = None
+    K = 1
+    if box is not None:
+        bx = _dev(box, torch.int32, dev, (N, None, 4), "box")
+        K = bx.shape[1]
+        rgb = _dev(box_rgb, torch.uint8, dev, (N, K, 4), "box_rgb")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    pad = lambda v: (_lib.C.c_int * 4)(*(list(v) + [0] * (4 - len(v))))
+    args = _lib.ComposePeopleArgs(frames.data_ptr(), ptr(idx), ptr(bx), ptr(rgb), ptr(ln), ptr(tx), ptr(cov), out.data_ptr(), ptr(st),
+                                  N, n_frames, H, W, dst_h, dst_w, panel_w, K, L, int(L_img), C, S, CH, CW, pad(adv), pad(ascent))
+    _lib.check(_lib.load().pr_compose_people(args, torch.cuda.current_stream(dev).cuda_stream), "pr_compose_people")
+    return (out, st) if return_status else out
+
+
+def pack_people(draw, lo, hi, n_tags=None, L=None, C=None):
+    """Frames [lo, hi) of a PeopleDraw -> (lines int32[n,L,5], codes u8[n,L,C], L_img) as pr_compose_people takes them: every
+    frame's tags padded with NO_LINE to n_tags slots (default: the box slots), then its panel lines."""
+    n_tags = draw.box.shape[1] if n_tags is None else n_tags
+    both = [list(t) + [NO_LINE] * (n_tags - len(t)) + list(p) for t, p in zip(draw.tags[lo:hi], draw.panel[lo:hi])]
+    lines, codes = pack_lines(both, L, C, max_lines=PEOPLE_MAX_LINES)
+    return lines, codes, n_tags
+
+
+def people_frames(frames, draw, batch_size=64, atlas=None):
+    """Yield the people canvases of the whole video in order, `batch_size` video frames at a time, as CUDA u8[b,dst_h,1000,3]
+    in the frames' channel order.  frames u8[F,H,W,3] CUDA; draw = people_draw_list(..., canvas_size(H, W)[0], RESIZE_W, H, W)."""
+    if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
+        raise _lib.PoseRiskHipError("people_frames: frames must be a CUDA tensor (no CPU fallback)")
+    F, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if len(draw.panel) != F:
+        raise ValueError(f"the draw list has {len(draw.panel)} frames, the video {F}")
+    dst_h, dst_w, panel_w = canvas_size(H, W)
+    n_tags = draw.box.shape[1]
+    L = n_tags + (max(len(p) for p in draw.panel) if F else 1)
+    C = max([len(s[0]) for group in (draw.tags, draw.panel) for t in group for s in t] + [1])
+    for lo in range(0, F, batch_size):
+        hi = min(lo + batch_size, F)
+        lines, codes, L_img = pack_people(draw, lo, hi, n_tags, L, C)
+        yield compose_people(frames, np.arange(lo, hi, dtype=np.int32), draw.box[lo:hi], draw.box_rgb[lo:hi], lines, codes, L_img,
+                             atlas, dst_h, dst_w, panel_w)
