@@ -110,6 +110,14 @@ def default_information():
     return synth.DEFAULT_INFO
 
 
+def _information(add_info):
+    """`add_info` as the scorers take it: None is default_information(), a string the path of a json file, a dict itself."""
+    if isinstance(add_info, str):
+        with open(add_info, 'r') as f:
+            return json.load(f)
+    return default_information() if add_info is None else add_info
+
+
 def _knob(args, name, key, default):
     """`args.<name>` when the caller's namespace has one that is not None, else cfg.DATASET.<key>, else (absent or empty) `default`."""
     knob = getattr(args, name, None)
@@ -122,6 +130,10 @@ def _jpeg_options():                                   # what every jpeg.decode_
 
 def _front_limits():                                   # the front end's downscale rule (frontend.target_size) from cfg.DATASET
     return dict(max_w=cfg.DATASET.get('front_max_w', 800), max_h=cfg.DATASET.get('front_max_h', 450))
+
+
+def _yuv_matrix():                                     # the Y'CbCr matrix the YUV4MPEG2 reader and sink take from cfg.DATASET
+    return str(cfg.DATASET.get('yuv_matrix', '601'))
 
 
 class Predictor:
@@ -308,28 +320,76 @@ class Predictor:
         return aggregate(scores), np.copy(scores), logs
 
     # ---- the accelerated half of __call__ (base.py:126-182 without tracking / reporting) ------------
+    def _on_device(self, frames):
+        """frames u8[F,H,W,3] (torch tensor or numpy) -> a CUDA tensor; one that is on a GPU already stays where it is."""
+        frames = torch.as_tensor(frames)
+        return frames if frames.device.type == 'cuda' else frames.to(self.device)
+
+    def _run_scorers(self, out, add_info):
+        """REBA / RULA and the aggregation over out['result'], out['joint_cam'] -> out['reba'], out['rula'] = (final, scores,
+        logs, level).  Returns {key: the rows this call added to that scorer's angle log} (none without args.debug)."""
+        added = {}
+        for key, run, scorer in (('reba', self.run_reba, self.reba), ('rula', self.run_rula, self.rula)):
+            if run:
+                seen = len(scorer.log)
+                final, scores, logs = self.post_processing(scorer(out['result'], out['joint_cam'], add_info))
+                out[key] = (final, scores, logs, scorer.action_level(final[4]))
+                added[key] = scorer.log[seen:]
+        return added
+
     def score_crops(self, crop_batches, add_info=None, n_total=None, with_smpl_params=False):
         """crops -> dict(result, joint_cam, reba=(final, scores, logs, level), rula=(...)).
         `n_total`: see get_pose_estimation_results (the batches are this rank's shard of n_total frames).
         `with_smpl_params`: the dict also holds rotmat, betas, cam and the add_info used (what render_overlay needs)."""
-        if add_info is None:
-            add_info = default_information()
-        elif isinstance(add_info, str):
-            with open(add_info, 'r') as f:
-                add_info = json.load(f)
+        add_info = _information(add_info)
         params = {} if with_smpl_params else None
         result, joint_cam, _, debug_result = self.get_pose_estimation_results(crop_batches, keep_images=False,
                                                                               n_total=n_total, smpl_params=params)
         out = dict(result=result, joint_cam=joint_cam, debug_result=debug_result)
         if with_smpl_params:
             out.update(params, add_info=add_info)
-        if self.run_reba:
-            final, scores, logs = self.post_processing(self.reba(result, joint_cam, add_info))
-            out['reba'] = (final, scores, logs, self.reba.action_level(final[4]))
-        if self.run_rula:
-            final, scores, logs = self.post_processing(self.rula(result, joint_cam, add_info))
-            out['rula'] = (final, scores, logs, self.rula.action_level(final[4]))
+        self._run_scorers(out, add_info)
         return out
+
+    def _score_tracks(self, frames, people, add_info, bgr, bbox_scale, shard=None, with_smpl_params=False):
+        """The one scoring pass under score_frames and score_people: people [(id, bboxes f32[n,4], frame indices int[n])] -> (a
+        dict per person as score_frames returns it, each person's rows of the scorers' angle logs).  Everybody's (frame index,
+        box) rows are concatenated, cut into batches of self.batch_size across person boundaries (sum(n_p) / batch_size launches,
+        rounded up once), cropped and run through get_pose_estimation_results once, and split back by offsets; the scorers and
+        the aggregation run per person on the host.  `shard(bboxes, fidx)`, a sharding caller's, runs after the range check ->
+        (lo, hi, n_total): the crops cover rows [lo, hi), this rank's, of the n_total the results are gathered to."""
+        from poserisk_release_amd import ops
+        frames = self._on_device(frames)
+        if bbox_scale is None:
+            bbox_scale = cfg.DATASET.bbox_scale                                   # base.py:121
+        add_info = _information(add_info)
+        bboxes = np.concatenate([b.reshape(-1, 4) for _, b, _ in people]) if people else np.zeros((0, 4), np.float32)
+        fidx = np.concatenate([np.asarray(f).reshape(-1) for _, _, f in people]) if people else np.zeros((0,), np.int64)
+        if len(fidx) and (int(np.min(fidx)) < 0 or int(np.max(fidx)) >= frames.shape[0]):
+            raise ValueError(f"tracking results name frames {int(np.min(fidx))}..{int(np.max(fidx))} but only "
+                             f"{frames.shape[0]} frames were decoded (tracking.pkl does not belong to these frames)")
+        lo, hi, n_total = shard(bboxes, fidx) if shard is not None else (0, len(fidx), None)
+
+        def batches():
+            for i in range(lo, hi, self.batch_size):
+                j = min(i + self.batch_size, hi)
+                yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
+        smpl = {} if with_smpl_params else None
+        result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False, n_total=n_total,
+                                                                              smpl_params=smpl)
+        outs, pose_logs, at = [], [], 0
+        for _, box_p, frames_p in people:
+            rows = slice(at, at + len(frames_p))
+            out = dict(result=result[rows], joint_cam=joint_cam[rows], debug_result=debug_result[rows])
+            if with_smpl_params:
+                out.update({k: v[rows] for k, v in smpl.items()}, add_info=add_info)
+            pose_logs.append(self._run_scorers(out, add_info))
+            out['frames'], out['bboxes'] = frames_p, box_p
+            if with_smpl_params:
+                out['bbox_scale'] = float(bbox_scale)
+            outs.append(out)
+            at = rows.stop
+        return outs, pose_logs
 
     def score_frames(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None):
         """Decoded frames + tracker output -> scores, all on the GPU (BASELINE config 5 without the detector).
@@ -339,60 +399,40 @@ class Predictor:
         frames: uint8[F,H,W,3] (torch CUDA tensor or numpy); tracking_results: multi_person_tracker's dict
         {id: {'bbox': [n,4] (cx,cy,w,h), 'frames': [n]}}.  Does what base.py:53-73 (track filter + target
         selection), demo_dataset.py:58-74 (crop) and base.py:126-182 (pose, scores) do."""
-        from poserisk_release_amd import ops, tracks
-        frames = torch.as_tensor(frames)
-        if frames.device.type != 'cuda':
-            frames = frames.to(self.device)
-        if bbox_scale is None:
-            bbox_scale = cfg.DATASET.bbox_scale                                   # base.py:121
-        bboxes, fidx = tracks.target_track(tracking_results, frames.shape[0], cfg.DATASET.min_frame_ratio)
-        if len(fidx) and (int(np.min(fidx)) < 0 or int(np.max(fidx)) >= frames.shape[0]):
-            raise ValueError(f"tracking results name frames {int(np.min(fidx))}..{int(np.max(fidx))} but only "
-                             f"{frames.shape[0]} frames were decoded (tracking.pkl does not belong to these frames)")
-        # one process per GPU: this rank crops and scores its contiguous shard of the track (SURVEY.md 8e)
-        world, rank = pl.world_and_rank()
-        if world > 1:
-            # the shard bounds and the gather's shapes follow from the track: a rank that selected another one (its own
-            # tracker run, another file) would hang the collective or gather rows that are not its frames -- compare first
-            import hashlib
-            import torch.distributed as dist
-            mine = (int(frames.shape[0]), len(fidx),
-                    hashlib.sha256(np.ascontiguousarray(fidx).tobytes() + np.ascontiguousarray(bboxes).tobytes()).hexdigest())
-            seen = [None] * world
-            dist.all_gather_object(seen, mine)
-            if any(s != seen[0] for s in seen):
-                raise RuntimeError(f"the ranks do not hold the same target track (frames, track length, digest per rank: "
-                                   f"{[s[:2] + (s[2][:8],) for s in seen]}): run the front end on one rank and broadcast its "
-                                   "output (Predictor.__call__ does), or pass every rank the same frames and tracking dict")
-        lo, hi = pl.shard_bounds(len(fidx), world, rank)
+        from poserisk_release_amd import tracks
+        target = (None,) + tracks.target_track(tracking_results, len(frames), cfg.DATASET.min_frame_ratio)
 
-        def batches():
-            for i in range(lo, hi, self.batch_size):
-                j = min(i + self.batch_size, hi)
-                yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
-        if with_smpl_params is None:
-            with_smpl_params = self.render_mesh
-        out = self.score_crops(batches(), add_info, n_total=len(fidx) if world > 1 else None,
-                               with_smpl_params=with_smpl_params)
-        out['frames'] = fidx
-        out['bboxes'] = bboxes
-        if with_smpl_params:
-            out['bbox_scale'] = float(bbox_scale)
-        return out
+        def shard(bboxes, fidx):
+            # one process per GPU: this rank crops and scores its contiguous shard of the track (SURVEY.md 8e)
+            world, rank = pl.world_and_rank()
+            if world > 1:
+                # the shard bounds and the gather's shapes follow from the track: a rank that selected another one (its own
+                # tracker run, another file) would hang the collective or gather rows that are not its frames -- compare first
+                import hashlib
+                import torch.distributed as dist
+                mine = (len(frames), len(fidx),
+                        hashlib.sha256(np.ascontiguousarray(fidx).tobytes() + np.ascontiguousarray(bboxes).tobytes()).hexdigest())
+                seen = [None] * world
+                dist.all_gather_object(seen, mine)
+                if any(s != seen[0] for s in seen):
+                    raise RuntimeError(f"the ranks do not hold the same target track (frames, track length, digest per rank: "
+                                       f"{[s[:2] + (s[2][:8],) for s in seen]}): run the front end on one rank and broadcast its "
+                                       "output (Predictor.__call__ does), or pass every rank the same frames and tracking dict")
+            return pl.shard_bounds(len(fidx), world, rank) + (len(fidx) if world > 1 else None,)
+        return self._score_tracks(frames, [target], add_info, bgr, bbox_scale, shard,
+                                  self.render_mesh if with_smpl_params is None else with_smpl_params)[0][0]
 
     def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None):
         """Decoded frames + tracker output -> the scores of EVERY person tracks.people_tracks keeps, in one pass over the model:
         {'people': [out_0, out_1, ...], 'ids': [...], 'frames_total': F}, in people_tracks order (element 0 is the person
         score_frames scores).  Each out_p holds what score_frames returns for that person alone -- result, joint_cam,
         debug_result, reba, rula, frames, bboxes -- bit for bit: a frame's bits do not depend on its batch
-        (tests/test_encoder_batch_sweep.py), so the people share batches.  Every person's (frame index, box) rows are
-        concatenated, cut into batches of self.batch_size across person boundaries, cropped and run through
-        get_pose_estimation_results once, and split back by offsets; the scorers and the aggregation run per person on the
-        host.  With args.debug the dict also holds 'pose_logs', each person's rows of the scorers' angle logs.
+        (tests/test_encoder_batch_sweep.py), so the people share batches (_score_tracks).  With args.debug the dict also holds
+        'pose_logs', each person's rows of the scorers' angle logs.
 
         Not supported, by name: several ranks (hip_world_size / args.world_size > 1) and the render_mesh knob
         (pr_render_overlay draws one mesh per canvas)."""
-        from poserisk_release_amd import ops, tracks
+        from poserisk_release_amd import tracks
         world, _ = pl.world_and_rank()
         if world > 1:
             raise NotImplementedError(f"score_people runs on one rank, this process group has {world}: persons='all' does not go "
@@ -400,47 +440,11 @@ class Predictor:
         if self.render_mesh:
             raise NotImplementedError("score_people does not go with the render_mesh knob: pr_render_overlay draws one mesh per "
                                       "canvas (cfg.DATASET.render_mesh / args.render_mesh)")
-        frames = torch.as_tensor(frames)
-        if frames.device.type != 'cuda':
-            frames = frames.to(self.device)
-        if bbox_scale is None:
-            bbox_scale = cfg.DATASET.bbox_scale
-        if add_info is None:
-            add_info = default_information()
-        elif isinstance(add_info, str):
-            with open(add_info, 'r') as f:
-                add_info = json.load(f)
-        people = tracks.people_tracks(tracking_results, frames.shape[0], cfg.DATASET.min_frame_ratio)
-        bboxes = np.concatenate([b.reshape(-1, 4) for _, b, _ in people]) if people else np.zeros((0, 4), np.float32)
-        fidx = np.concatenate([np.asarray(f).reshape(-1) for _, _, f in people]) if people else np.zeros((0,), np.int64)
-        if len(fidx) and (int(np.min(fidx)) < 0 or int(np.max(fidx)) >= frames.shape[0]):
-            raise ValueError(f"tracking results name frames {int(np.min(fidx))}..{int(np.max(fidx))} but only "
-                             f"{frames.shape[0]} frames were decoded (tracking.pkl does not belong to these frames)")
-
-        def batches():                                  # across person boundaries: sum(n_p) / batch_size launches, rounded up once
-            for i in range(0, len(fidx), self.batch_size):
-                j = min(i + self.batch_size, len(fidx))
-                yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
-        result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False)
-        outs, pose_logs, lo = [], [], 0
-        for _, box_p, frames_p in people:
-            hi = lo + len(frames_p)
-            out = dict(result=result[lo:hi], joint_cam=joint_cam[lo:hi], debug_result=debug_result[lo:hi])
-            logs_p = {}
-            for key, run, scorer in (('reba', self.run_reba, self.reba), ('rula', self.run_rula, self.rula)):
-                if run:
-                    seen = len(scorer.log)
-                    final, scores, logs = self.post_processing(scorer(out['result'], out['joint_cam'], add_info))
-                    out[key] = (final, scores, logs, scorer.action_level(final[4]))
-                    logs_p[key] = scorer.log[seen:]
-            out['frames'], out['bboxes'] = frames_p, box_p
-            outs.append(out)
-            pose_logs.append(logs_p)
-            lo = hi
-        people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': int(frames.shape[0])}
-        if self.debugging:
-            people_out['pose_logs'] = pose_logs
-        return people_out
+        n_frames = len(frames)
+        people = tracks.people_tracks(tracking_results, n_frames, cfg.DATASET.min_frame_ratio)
+        outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale)
+        people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': n_frames}
+        return dict(people_out, pose_logs=pose_logs) if self.debugging else people_out
 
     # ---- the mesh overlay (extends the --debug_frame mesh of base.py:273-282 to every track frame) -----------------
     def render_overlay(self, out, frames, title='REBA', bgr=False, alpha=0.6):
@@ -459,9 +463,7 @@ class Predictor:
             raise ValueError("the SMPL model has no faces to draw")
         scheme = None if title is None else str(title).upper()
         face_part = render.face_parts(layer.th_weights.numpy(), faces, scheme)
-        frames = torch.as_tensor(frames)
-        if frames.device.type != 'cuda':
-            frames = frames.to(self.device)
+        frames = self._on_device(frames)
         dev = frames.device
         faces_dev = torch.as_tensor(faces.astype(np.int32), device=dev)
         fidx, n = np.asarray(out['frames']), len(out['frames'])
@@ -487,13 +489,26 @@ class Predictor:
         `frame_size`, with this Predictor's other knobs."""
         return sinks.open_sink(self.gpu_video_codec, osp.join(output_path, name), int(frame_size[1]), int(frame_size[0]), fps, bgr,
                                quality=self.gpu_video_quality, chroma=self.video_chroma, encoder=self.video_encoder,
-                               encoder_ext=self.video_encoder_ext, matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+                               encoder_ext=self.video_encoder_ext, matrix=_yuv_matrix())
 
     def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
         """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
         frame.  Returns the path written."""
         sink = self._open_sink(output_path, f"{title if title is not None else 'MESH'}_mesh", frames.shape[1:3], fps, bgr)
         return sinks.write_all(sink, self.render_overlay(out, frames, title, bgr))
+
+    def _write_canvases(self, canvases, frames, output_path, name, bgr, fps):
+        """<output>/<name> through the sink of the gpu_video_codec knob: `canvases` yields the canvases of `frames`' video batch
+        by batch, one per video frame, numbered 0 .. n_frames - 1.  Returns the path written."""
+        from poserisk_release_amd import video
+        canvas_h, resize_w, panel_w = video.canvas_size(int(frames.shape[1]), int(frames.shape[2]))
+
+        def batches():
+            i = 0
+            for batch in canvases:
+                yield range(i, i + int(batch.shape[0])), batch
+                i += int(batch.shape[0])
+        return sinks.write_all(self._open_sink(output_path, name, (canvas_h, resize_w + panel_w), fps, bgr), batches())
 
     # ---- base.py:284-327 on the GPU (the gpu_video knob) ---------------------------------------------------------
     def write_gpu_video(self, out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
@@ -507,15 +522,12 @@ class Predictor:
         parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
         that the mesh output is written from the same rendering.  Returns the path written."""
         from poserisk_release_amd import video
-        frames = torch.as_tensor(frames)
-        if frames.device.type != 'cuda':
-            frames = frames.to(self.device)
+        frames = self._on_device(frames)
         n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         _, scores, logs, _ = out[title.lower()]
         items = (self.reba if title.upper() == 'REBA' else self.rula).eval_items
         fidx = np.asarray(out['frames'])
-        canvas_h, resize_w, panel_w = video.canvas_size(H, W)
-        draw = video.draw_list(title, n_frames, out['bboxes'], (0, fidx, n_frames), scores, items, logs, canvas_h)
+        draw = video.draw_list(title, n_frames, out['bboxes'], (0, fidx, n_frames), scores, items, logs, video.canvas_size(H, W)[0])
         overlay = None
         if self.render_mesh:
             def overlay(lo, hi):
@@ -529,13 +541,8 @@ class Predictor:
                 if mesh_sink is not None:
                     mesh_sink(numbers, images)
                 return numbers, images
-
-        def batches():                                  # one canvas per video frame, numbered 0 .. n_frames - 1
-            i = 0
-            for canvases in video.annotated_frames(frames, draw, self.batch_size, overlay=overlay):
-                yield range(i, i + int(canvases.shape[0])), canvases
-                i += int(canvases.shape[0])
-        return sinks.write_all(self._open_sink(output_path, title + '_video', (canvas_h, resize_w + panel_w), fps, bgr), batches())
+        return self._write_canvases(video.annotated_frames(frames, draw, self.batch_size, overlay=overlay), frames, output_path,
+                                    title + '_video', bgr, fps)
 
     # ---- the persons='all' outputs (no counterpart in the reference, which describes one person) -----------------------------
     def write_people_video(self, people_out, frames, output_path, title, bgr=False, fps=30.0):
@@ -544,9 +551,7 @@ class Predictor:
         (poserisk_release_amd.video.people_draw_list, pr_compose_people), from what score_people returned.  Written through
         the sink of the gpu_video_codec knob, as write_gpu_video's.  Returns the path written."""
         from poserisk_release_amd import video
-        frames = torch.as_tensor(frames)
-        if frames.device.type != 'cuda':
-            frames = frames.to(self.device)
+        frames = self._on_device(frames)
         n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         scorer = self.reba if title.upper() == 'REBA' else self.rula
         people = []
@@ -555,45 +560,50 @@ class Predictor:
             acts = [scorer.action_level(s) for s in scores]
             people.append(dict(id=pid, frames=out['frames'], bboxes=out['bboxes'], scores=scores, levels=[a[0] for a in acts],
                                names=[a[1] for a in acts]))
-        canvas_h, resize_w, panel_w = video.canvas_size(H, W)
+        canvas_h, resize_w, _ = video.canvas_size(H, W)
         draw = video.people_draw_list(title, n_frames, people, canvas_h, resize_w, H, W, bgr=bgr)
+        return self._write_canvases(video.people_frames(frames, draw, self.batch_size), frames, output_path, title + '_people',
+                                    bgr, fps)
 
-        def batches():                                  # one canvas per video frame, numbered 0 .. n_frames - 1
-            i = 0
-            for canvases in video.people_frames(frames, draw, self.batch_size):
-                yield range(i, i + int(canvases.shape[0])), canvases
-                i += int(canvases.shape[0])
-        return sinks.write_all(self._open_sink(output_path, title + '_people', (canvas_h, resize_w + panel_w), fps, bgr), batches())
+    def _write_reports(self, out, folder, debug_folder, n_frames, pose_logs, after_plot=lambda title: None, after_txt=lambda title: None):
+        """One scored person's files.  Into `folder`, per title scored: <TITLE>_score.png, then <title>_result.txt.  With args.debug
+        into `debug_folder`: pose_log.csv (the debug_joints) first, and per title, last, <TITLE>_score_log.csv and <TITLE>_eval_pose_log.csv
+        from pose_logs[<title>], rows of the scorer's angle log.  after_plot / after_txt: what __call__ writes in between (videos, mesh)."""
+        from poserisk_release_amd import reports
+        timestamp = (0, np.asarray(out['frames']), n_frames)           # base.py:130
+        if self.debugging and self.debug_joints is not None:
+            reports.save_pose_log_csv(debug_folder, timestamp, reports.pose_to_str(out['result']), self.debug_joints,
+                                      self.smpl_model.joints_name_upper)
+        for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
+            if title.lower() not in out:
+                continue
+            final, scores, logs, (level, name) = out[title.lower()]
+            reports.save_score_plot(folder, title, timestamp, scores)      # base.py:254-262
+            after_plot(title)
+            reports.write_result_txt(folder, title, final, level, name)
+            after_txt(title)
+            if self.debugging:
+                reports.save_score_csv(debug_folder, title, timestamp, scores, scorer.eval_items, logs, pose_logs[title.lower()])
 
     def write_people_reports(self, people_out, output_path):
         """<output>/person_<id>/ per scored person -- reba_result.txt / rula_result.txt and <TITLE>_score.png, with args.debug the
-        score, pose-evaluation and pose logs too, all by the functions that write the target's -- and <output>/people.json.
-        Returns the list people.json holds."""
-        from poserisk_release_amd import reports
+        score, pose-evaluation and pose logs too, all by the method that writes the target's (_write_reports) -- and
+        <output>/people.json.  Returns the list people.json holds."""
         plain = lambda v: v.item() if isinstance(v, np.generic) else v
         num = lambda v: None if v is None or np.isnan(v) else float(v)        # top-10 % of fewer than 10 frames is NaN: null
         n_frames, summary = people_out['frames_total'], []
         for p, (pid, out) in enumerate(zip(people_out['ids'], people_out['people'])):
             folder = osp.join(output_path, f'person_{pid}')
             os.makedirs(folder, exist_ok=True)
+            self._write_reports(out, folder, folder, n_frames, people_out['pose_logs'][p] if self.debugging else None)
             fidx, boxes = np.asarray(out['frames']), np.asarray(out['bboxes'])
-            timestamp = (0, fidx, n_frames)
             entry = dict(id=plain(pid), first_frame=int(fidx.min()) if fidx.size else None, last_frame=int(fidx.max()) if fidx.size else None,
                          n_frames=int(fidx.size), mean_box_area=float((boxes[:, 2] * boxes[:, 3]).mean()) if fidx.size else None)
-            if self.debugging and self.debug_joints is not None:
-                reports.save_pose_log_csv(folder, timestamp, reports.pose_to_str(out['result']), self.debug_joints,
-                                          self.smpl_model.joints_name_upper)
-            for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
-                if title.lower() not in out:
-                    continue
-                final, scores, logs, (level, name) = out[title.lower()]
-                reports.save_score_plot(folder, title, timestamp, scores)
-                reports.write_result_txt(folder, title, final, level, name)
-                if self.debugging:
-                    reports.save_score_csv(folder, title, timestamp, scores, scorer.eval_items, logs,
-                                           people_out['pose_logs'][p][title.lower()])
-                entry[title] = dict(avg=num(final[0]), top50=num(final[1]), top10=num(final[2]), max=num(final[3]), mode=num(final[4]),
-                                    action_level=plain(level), action=name)
+            for title in ('REBA', 'RULA'):
+                if title.lower() in out:
+                    final, _, _, (level, name) = out[title.lower()]
+                    entry[title] = dict(avg=num(final[0]), top50=num(final[1]), top10=num(final[2]), max=num(final[3]), mode=num(final[4]),
+                                        action_level=plain(level), action=name)
             summary.append(entry)
         with open(osp.join(output_path, 'people.json'), 'w') as f:
             json.dump({'frames_total': n_frames, 'people': summary}, f, indent=1)
@@ -691,7 +701,7 @@ class Predictor:
             if y4m.is_y4m(input_path):
                 with y4m.Reader(input_path) as reader:
                     return self._video_front_end(reader, input_path, output_path, tracking_results,
-                                                 matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+                                                 matrix=_yuv_matrix())
             if self.video_decoder:
                 return self._decoder_front_end(input_path, output_path, tracking_results)
         try:
@@ -767,7 +777,7 @@ class Predictor:
             else:
                 try:
                     return_value = self._video_front_end(reader, input_path, output_path, tracking_results,
-                                                         matrix=str(cfg.DATASET.get('yuv_matrix', '601')))
+                                                         matrix=_yuv_matrix())
                     read_to_the_end = True
                 except ValueError as e:                         # the stream broke off: the child's status says why
                     failure = str(e)
@@ -886,11 +896,7 @@ class Predictor:
                 frames, bgr, fps, tracking_results = self._front_end_on_rank0(input_path, output_path, world, rank, **given)
             else:
                 frames, bgr, fps, tracking_results = self.load_front_end(input_path, output_path, **given)
-        if info_path and osp.isfile(str(info_path)):
-            with open(info_path, 'r') as f:
-                add_info = json.load(f)
-        else:
-            add_info = default_information()                   # base.py:140-142
+        add_info = _information(info_path if info_path and osp.isfile(str(info_path)) else None)      # base.py:140-142
         people_out = None
         if getattr(self, 'persons', 'target') == 'all':
             # everybody in one pass; the target is element 0, bit for bit what score_frames returns, so the model runs once
@@ -922,18 +928,13 @@ class Predictor:
                     sinks.save_png(osp.join(debug_path, 'mesh_overlay.png'), im[..., ::-1] if bgr else im)
             print("\n Debug files are saved in : ", debug_path)
             return out
-        pose_str = reports.pose_to_str(out['result'])
-        if self.debugging and self.debug_joints is not None:
-            reports.save_pose_log_csv(debug_path, timestamp, pose_str, self.debug_joints, self.smpl_model.joints_name_upper)
-        if self.gpu_video and getattr(self, 'visualize', True):
+        show = getattr(self, 'visualize', True)
+        on_gpu = show and self.gpu_video
+        if on_gpu:
             frames = torch.as_tensor(frames).to(self.device)       # one upload for both titles' videos (and the mesh)
-        for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
-            if title.lower() not in out:
-                continue
-            final, scores, logs, (level, name) = out[title.lower()]
-            mesh_written = False
-            reports.save_score_plot(output_path, title, timestamp, scores)      # base.py:254-262
-            if getattr(self, 'visualize', True) and self.gpu_video:            # base.py:156,173 on the GPU
+
+        def videos(title):                                         # base.py:156,173: behind the title's plot
+            if on_gpu:
                 if self.render_mesh:                # one rendering of the mesh feeds both outputs
                     mesh = self._open_sink(output_path, title + '_mesh', frames.shape[1:3], fps, bgr)
                     try:
@@ -942,27 +943,28 @@ class Predictor:
                         mesh.abort()                    # the video's error stands; a mesh encoder child is reaped all the same
                         raise
                     mesh.close()
-                    mesh_written = True
                 else:
                     self.write_gpu_video(out, frames, output_path, title, bgr, fps)
-            elif getattr(self, 'visualize', True):                              # base.py:156,173 (OpenCV only)
+            elif show:                                             # ... (OpenCV only)
+                _, scores, logs, _ = out[title.lower()]
                 fr = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)   # once, host side
-                video = reports.write_annotated_video(output_path, title, fr if bgr else fr[..., ::-1], out['bboxes'],
-                                                      timestamp, fps, scores, scorer.eval_items, logs)
+                video = reports.write_annotated_video(output_path, title, fr if bgr else fr[..., ::-1], out['bboxes'], timestamp, fps,
+                                                      scores, (self.reba if title == 'REBA' else self.rula).eval_items, logs)
                 if video is None and not getattr(self, '_warned_no_cv2', False):
                     print("OpenCV (cv2) is not importable: the annotated mp4 is skipped, all other outputs are written")
                     self._warned_no_cv2 = True
-            reports.write_result_txt(output_path, title, final, level, name)
-            if self.render_mesh and not mesh_written:
+
+        def mesh_alone(title):                                     # behind the title's result txt
+            if self.render_mesh and not on_gpu:                    # with both knobs videos() has written the mesh
                 self.write_mesh_overlay(out, frames, output_path, title, bgr, fps)
-            if self.debugging:
-                reports.save_score_csv(debug_path, title, timestamp, scores, scorer.eval_items, logs, scorer.log)
+        # the scorers' whole angle logs, as the reference writes them (Q19: they are never cleared)
+        self._write_reports(out, output_path, debug_path, timestamp[2], {'reba': self.reba.log, 'rula': self.rula.log}, videos, mesh_alone)
         if people_out is not None:
             self.write_people_reports(people_out, output_path)
-            if getattr(self, 'visualize', True) and self.gpu_video:
+            if on_gpu:
                 for title in ('REBA', 'RULA'):
                     if title.lower() in out:
                         self.write_people_video(people_out, frames, output_path, title, bgr, fps)
-            elif getattr(self, 'visualize', True):
+            elif show:
                 print("The people video (<TITLE>_people) is composed on the GPU only: it needs the gpu_video knob and is skipped")
         return out

@@ -8,8 +8,8 @@ wrapper of the kernel, `annotated_frames` chains them batch by batch.  The Predi
 (dropin/core/base.py) writes what it yields.
 
 The people video (`<TITLE>_people`, the persons knob; no counterpart in the reference) is the second half of this file:
-`people_draw_list`, `compose_people` (pr_compose_people, csrc/compose_people.hip), `people_frames`, written by the Predictor's
-`write_people_video`."""
+`people_draw_list`, `compose_people` (pr_compose_people: the same kernel in csrc/compose.hip, of which pr_compose_video is the
+case of one box and no tags), `people_frames`, written by the Predictor's `write_people_video`."""
 import collections
 import os
 

@@ -1,11 +1,15 @@
 """Time scoring every tracked person.  Two measurements, one JSON line:
 
-(a) the people compositor (pr_compose_people, csrc/compose_people.hip): 64 canvases of 800x450 with K = 1, 4 and 16 people a
+(a) the people compositor (pr_compose_people, csrc/compose.hip): 64 canvases of 800x450 with K = 1, 4 and 16 people a
     frame (boxes, tags and a people panel from video.people_draw_list), against pr_compose_video on the same frames
     (scripts/bench_video.py's call) in the same process, alternating round by round -- and, as `compose_people_as_video`,
-    pr_compose_video's own box and nine-line panel through pr_compose_people (K = 1, L_img = 0): the same bytes out, so the
-    ratio of the two is what the shared structure costs.  The K = 1 people canvas itself has less text than the score panel.  Per variant: ms per batch, frames/s, the
-    bytes moved computed from the shapes and the share of the HBM streaming floor reached, as DESIGN.md 3.8 computes it.
+    pr_compose_video's own box and nine-line panel through pr_compose_people (K = 1, L_img = 0): the same bytes out.  That
+    pair runs at bench_video.py's second shape, 1920x1080, too (`compose_video_1920x1080`,
+    `compose_people_as_video_1920x1080`).  While the two entries had a kernel each, this pair was the gate for serving both
+    from one (profiles/compose_one_kernel.json); now that they share it, it shows that a colour in the parameter block costs
+    what a colour table does.  The K = 1 people canvas itself has less text than the score panel.  Per variant: ms per
+    batch, frames/s, the bytes moved computed from the shapes and the share of the HBM streaming floor reached, as DESIGN.md
+    3.8 computes it.
 (b) Predictor.score_people on a synthetic clip with 4 tracks of unequal length (synthetic weights), against the sum of 4
     Predictor.score_frames runs on single-track dicts: wall-clock ms, synchronised, median of the rounds.
 
@@ -137,6 +141,9 @@ def main():
     calls["compose_people_as_video"], same_bytes = reduction_call(single, frames, dev)
     for K in (1, 4, 16):
         calls[f"compose_people_K{K}"], _ = people_call(B, H, W, K, frames, dev)
+    single_hd, frames_hd, nbytes_hd = bench_video.compose_call(B, 1080, 1920, dev, seed=2)
+    calls["compose_video_1920x1080"] = single_hd
+    calls["compose_people_as_video_1920x1080"], same_bytes_hd = reduction_call(single_hd, frames_hd, dev)
     for call in calls.values():
         for _ in range(a.warmup):
             call()
@@ -146,15 +153,21 @@ def main():
         for k, call in calls.items():
             rounds[k].append(bench_video.time_ms(call, a.iters))
     med = {k: float(np.median(v)) for k, v in rounds.items()}
-    shape = lambda ms: {"ms_per_batch": round(ms, 4), "frames_per_s": round(B / ms * 1e3, 1), "bytes_per_batch": nbytes,
-                        "traffic_floor_ms": round(nbytes / HBM_BYTES_PER_S * 1e3, 4),
-                        "share_of_floor": round(nbytes / HBM_BYTES_PER_S * 1e3 / ms, 4),
-                        "over_compose_video": round(ms / med["compose_video"], 4)}
+    def shape(k):
+        hd = k.endswith("_1920x1080")
+        ms, nb, base = med[k], nbytes_hd if hd else nbytes, med["compose_video_1920x1080" if hd else "compose_video"]
+        return {"ms_per_batch": round(ms, 4), "frames_per_s": round(B / ms * 1e3, 1), "bytes_per_batch": nb,
+                "traffic_floor_ms": round(nb / HBM_BYTES_PER_S * 1e3, 4), "share_of_floor": round(nb / HBM_BYTES_PER_S * 1e3 / ms, 4),
+                "over_compose_video": round(ms / base, 4)}
+    # the people kernel serves pr_compose_video's workload when its median is within pr_compose_video's own spread of rounds
+    gate = {s: bool(med["compose_people_as_video" + s] <= med["compose_video" + s] + max(rounds["compose_video" + s])
+                    - min(rounds["compose_video" + s])) for s in ("", "_1920x1080")}
     ms, launches, rows = score_clip(dev, a.batch, a.rounds)
     smed = {k: float(np.median(v)) for k, v in ms.items()}
     rec = {"batch": B, "iters": a.iters, "rounds": a.rounds, "frame": [H, W],
-           **{k: shape(v) for k, v in med.items()},
-           "as_video_bytes_equal": same_bytes,
+           **{k: shape(k) for k in med},
+           "as_video_bytes_equal": same_bytes, "as_video_bytes_equal_1920x1080": same_bytes_hd,
+           "as_video_within_compose_video_spread": {"800x450": gate[""], "1920x1080": gate["_1920x1080"]},
            "as_video_within_10_percent_of_compose_video": bool(med["compose_people_as_video"] <= 1.10 * med["compose_video"]),
            "ms_per_round": {k: [round(x, 4) for x in v] for k, v in rounds.items()},
            "score": {"track_rows": rows, "batch_size": a.batch, "pipeline_launches": launches,

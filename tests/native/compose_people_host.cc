@@ -1,4 +1,4 @@
-// csrc/compose_people.hip on the host (see compose_host_shim.h): reads a case file, runs pr_compose_people, writes the canvases.
+// csrc/compose.hip on the host (see compose_host_shim.h): reads a case file, runs pr_compose_people, writes the canvases.
 //   case file: int32 header[24] = N n_frames H W dst_h dst_w panel_w K L L_img C S CH CW adv[4] ascent[4] has_src_idx has_box,
 //   then frames, src_idx, box, box_rgb, lines, text, atlas as raw bytes.
 //   usage: compose_people_host <case> <out> [output misalignment]
@@ -20,7 +20,7 @@ void set_error(const char* fmt, ...) {
 }
 }  // namespace pr
 
-#include "compose_people.hip"
+#include "compose.hip"
 
 static int validate() {
   // a valid 1-canvas call on exact-size buffers, then one field wrong at a time

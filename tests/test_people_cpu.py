@@ -248,6 +248,44 @@ def test_persons_all_adds_the_person_folders_and_people_json_and_leaves_the_rest
     assert doc["people"][2]["REBA"]["top10"] is None                      # 5 frames: no top 10 %
 
 
+def test_persons_all_with_debug_writes_every_persons_csvs_from_its_own_log_slice(tmp_path, monkeypatch):
+    smpl = types.SimpleNamespace(joints_name_upper=[f"J{i}" for i in range(22)] + ["L_HIP", "NECK"])
+    knobs = dict(debugging=True, debug_joints=["L_Hip", "Neck"], smpl_model=smpl)
+    pred = _bare_predictor(persons="all", **knobs)
+    outs = [_canned(pred.reba, pred.rula, n, s) for n, s in ((12, 1), (9, 2), (5, 3))]
+    slices = [{"reba": [REBA._angle_log(p) for p in o["result"]], "rula": [RULA._angle_log(p) for p in o["result"]]} for o in outs]
+    people = {"people": outs, "ids": [8, 3, "left"], "frames_total": 20, "pose_logs": slices}
+    # the scorers' own logs hold every person's rows, the target's first: what one pass over everybody leaves behind
+    pred.reba.log = [row for s in slices for row in s["reba"]]
+    pred.rula.log = [row for s in slices for row in s["rula"]]
+    monkeypatch.setattr(base.Predictor, "score_people", lambda self, *a, **k: people)
+    monkeypatch.setattr(base.Predictor, "score_frames", lambda self, *a, **k: pytest.fail("the model must run once"))
+    frames = np.zeros((20, 8, 8, 3), np.uint8)
+    pred(None, None, str(tmp_path / "all"), frames=frames, tracking_results={1: None})
+    per_person = ["REBA_score.png", "RULA_score.png", "reba_result.txt", "rula_result.txt"]
+    csvs = ["REBA_eval_pose_log.csv", "REBA_score_log.csv", "RULA_eval_pose_log.csv", "RULA_score_log.csv", "pose_log.csv"]
+    assert _files(tmp_path / "all") == sorted(per_person + ["people.json"] + [f"debug/{f}" for f in csvs] +
+                                              [f"person_{i}/{f}" for i in (8, 3, "left") for f in per_person + csvs])
+    # the target's folder holds what a 'target' run on the same canned target writes under debug/
+    one = _bare_predictor(**knobs)
+    one.reba.log, one.rula.log = list(slices[0]["reba"]), list(slices[0]["rula"])
+    monkeypatch.setattr(base.Predictor, "score_frames", lambda self, *a, **k: dict(outs[0]))
+    one(None, None, str(tmp_path / "one"), frames=frames, tracking_results={1: None})
+    assert _files(tmp_path / "one") == sorted(per_person + [f"debug/{f}" for f in csvs])
+    for f in ("REBA_score_log.csv", "REBA_eval_pose_log.csv", "pose_log.csv"):
+        assert (tmp_path / "all" / "person_8" / f).read_bytes() == (tmp_path / "one" / "debug" / f).read_bytes(), f
+    # another person's pose-evaluation log is its own slice: frames 2 .. 10 of 20, one row each, its own angles
+    import csv
+    rows = list(csv.reader(open(tmp_path / "all" / "person_3" / "REBA_eval_pose_log.csv", newline="")))
+    names = list(slices[1]["reba"][0])
+    assert rows[0] == ["Frame", ""] + names and len(rows) == 1 + 20
+    for i in range(20):
+        want = [str(i)] + ([""] + [str(slices[1]["reba"][i - 2][n]) for n in names] if 2 <= i < 11 else [])
+        assert rows[1 + i] == want, i
+    assert slices[1]["reba"][0] != slices[0]["reba"][0]
+    assert rows[3][2:] != [str(slices[0]["reba"][0][n]) for n in names]
+
+
 def test_persons_knob_values():
     args = types.SimpleNamespace(persons="everyone")
     assert base._knob(args, "persons", "persons", "target") == "everyone"

@@ -1,4 +1,4 @@
-"""GPU: the people compositor (csrc/compose_people.hip, pr_compose_people) against pr_compose_video (the reduction property) and
+"""GPU: the people compositor (csrc/compose.hip, pr_compose_people) against pr_compose_video (the reduction property) and
 against the numpy restatement of its contract (tests/video_people_ref.py), every byte; its tensors between guard bands; and
 Predictor.score_people / Predictor.__call__ with persons='all' against score_frames and a persons='target' run."""
 import ctypes as C
@@ -13,6 +13,7 @@ import torch
 
 import guard_band as gb
 import people_cases as pc
+import video_ref as vr
 from poserisk_release_amd import _lib, synth, video
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,11 @@ def test_one_box_and_no_tags_is_pr_compose_video_byte_for_byte(gpu_device, size)
     assert got.shape == (3, size[3], size[2] + size[4], 3)
     assert np.array_equal(got, want.cpu().numpy()) and np.array_equal(st, want_st.cpu().numpy()) and st.tolist() == [0, 0, 0]
     assert got[:, :, :size[2]].any() and got[:, :, size[2]:].any()
+    # one kernel serves both entry points, so both are also held against the numpy restatement of pr_compose_video's contract
+    a = c["atlas"]
+    ref, ref_st = vr.compose(c["frames"], c["src_idx"], c["box"][:, 0], c["lines"], c["text"], np.asarray(a.cov), a.adv, a.ascent,
+                             c["dst_h"], c["dst_w"], c["panel_w"], c["box_rgb"][0, 0, :3])
+    assert np.array_equal(got, ref) and np.array_equal(want.cpu().numpy(), ref) and ref_st.tolist() == [0, 0, 0]
 
 
 # ---- the contract, every byte ---------------------------------------------------------------------------------------------------
@@ -158,7 +164,7 @@ def clip():
     return frames, tr
 
 
-def _predictor(gpu_device, score_type="REBA,RULA", **knobs):
+def _predictor(gpu_device, score_type="REBA,RULA", debug=False, **knobs):
     from poserisk_release_amd import dropin
     dropin.install()
     from core import base
@@ -167,7 +173,7 @@ def _predictor(gpu_device, score_type="REBA,RULA", **knobs):
     model = hmr()
     model.load_state_dict(synth.hmr_state_dict(seed=1), strict=False)
     smpl = SMPL(models={"neutral": synth.smpl_model(V=6890, seed=2)}, device=gpu_device)
-    args = types.SimpleNamespace(gpu="0", type=score_type, debug=False, debug_joints="", debug_frame=-1, **knobs)
+    args = types.SimpleNamespace(gpu="0", type=score_type, debug=debug, debug_joints="", debug_frame=-1, **knobs)
     return base.Predictor(args, spin_model=model, smpl_model=smpl, batch_size=16)
 
 
@@ -206,6 +212,19 @@ def test_people_share_batches_and_keep_their_bits(gpu_device, clip, monkeypatch)
     monkeypatch.setattr(pl, "world_and_rank", lambda: (2, 0))
     with pytest.raises(NotImplementedError, match="world_size"):
         pred.score_people(frames, tr, synth.EXAMPLE_INFO)
+
+
+def test_with_debug_every_person_gets_its_own_rows_of_the_angle_logs(gpu_device, clip):
+    frames, tr = clip
+    people = _predictor(gpu_device, debug=True).score_people(frames, tr, synth.EXAMPLE_INFO)
+    assert list(people) == ["people", "ids", "frames_total", "pose_logs"] and len(people["pose_logs"]) == 3
+    for p, pid in enumerate(people["ids"]):
+        alone = _predictor(gpu_device, debug=True)                      # fresh: its scorers' logs start empty
+        alone.score_frames(frames, {pid: tr[pid]}, synth.EXAMPLE_INFO)
+        assert list(people["pose_logs"][p]) == ["reba", "rula"]
+        for key, scorer in (("reba", alone.reba), ("rula", alone.rula)):
+            assert len(scorer.log) == len(tr[pid]['frames']) and people["pose_logs"][p][key] == scorer.log, (pid, key)
+    assert people["pose_logs"][1]["reba"][0] != people["pose_logs"][0]["reba"][0]
 
 
 def test_persons_all_end_to_end(gpu_device, clip, tmp_path, monkeypatch):

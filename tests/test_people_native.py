@@ -1,7 +1,7 @@
 """The people compositor's kernel source and its argument validation on the CPU, under AddressSanitizer +
 UndefinedBehaviorSanitizer.
 
-`poserisk_release_amd/csrc/compose_people.hip` is compiled unchanged for the host against `tests/native/compose_host_shim.h`
+`poserisk_release_amd/csrc/compose.hip` (the one kernel behind both entry points) is compiled unchanged for the host against `tests/native/compose_host_shim.h`
 (tests/test_video_native.py's shim: a workgroup = 256 threads and a barrier, workgroups one after the other) into a stand-alone
 program, `tests/native/compose_people_host.cc`, and run on exact-size heap buffers: the box table, the two line groups, the
 u32 sums and every address the kernel forms are checked against the numpy restatement of the contract
@@ -30,10 +30,10 @@ def _clean(r):
 @pytest.fixture(scope="module")
 def people_host(tmp_path_factory):
     gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/compose_people.hip"
+    assert gxx is not None, "g++ is needed to build the host form of csrc/compose.hip"
     d = tmp_path_factory.mktemp("compose_people_host")
-    shutil.copy(os.path.join(CSRC, "compose_people.hip"), d / "compose_people.hip")
-    shutil.copy(os.path.join(NATIVE, "compose_host_shim.h"), d / "common.h")       # what compose_people.hip includes
+    shutil.copy(os.path.join(CSRC, "compose.hip"), d / "compose.hip")
+    shutil.copy(os.path.join(NATIVE, "compose_host_shim.h"), d / "common.h")       # what compose.hip includes
     shutil.copy(os.path.join(NATIVE, "compose_people_host.cc"), d / "compose_people_host.cc")
     exe = str(d / "compose_people_host")
     cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",

@@ -133,6 +133,36 @@ def test_compose_matches_reference_bit_for_bit(gpu_device, H, W, N, font):
     assert drawn == len(check) and boxed > 0
 
 
+@pytest.mark.parametrize("boxed", [True, False], ids=["box", "no_box"])
+def test_sixteen_lines_on_a_ragged_upsampled_canvas(gpu_device, boxed):
+    """37 x 53 frames to 40 x 31: 3 W = 111 is no multiple of 16, dst_h no multiple of the band's 8 rows, two taps per column;
+    PR_VIDEO_MAX_LINES lines, with a box and with box=None."""
+    H, W, N, L = 53, 37, 7, 16
+    case = dict(_case(H, W, N, _random_atlas(), seed=3, L=L), dst_h=31, dst_w=40, panel_w=23)
+    case["lines"], case["text"] = _lines(N, L, 12, case["atlas"], 31, 40, 23, np.random.default_rng(4))
+    if not boxed:
+        case["box"] = np.tile(np.array(video.NO_BOX, np.int32), (N, 1))
+    fr = torch.from_numpy(case["frames"]).to(gpu_device)
+    out, st = video.compose(fr, case["src_idx"], case["box"] if boxed else None, case["lines"], case["text"], case["atlas"], 31, 40, 23,
+                            box_rgb=BOX_RGB, return_status=True)
+    want, want_st = _reference(case, list(range(N)))
+    assert out.shape == (N, 31, 63, 3) and np.array_equal(st.cpu().numpy(), want_st) and st.tolist().count(1) == 2
+    bad = np.argwhere(out.cpu().numpy() != want)
+    assert bad.size == 0, f"{len(bad)} bytes differ, first (canvas, row, col, channel) {bad[0].tolist()}"
+    assert want[:, :, 40:].any() and want[:, :, :40].any()
+    plain = np.stack([vr.area_resample(case["frames"][f], 31, 40) if 0 <= f < N_FRAMES else np.zeros((31, 40, 3), np.uint8)
+                      for f in case["src_idx"]])
+    assert (want[:, :, :40] != plain).any() == boxed                     # the box, in BOX_RGB, is what changes the image
+
+
+def test_seventeen_lines_are_refused_by_name(gpu_device):
+    case = _case(53, 37, 2, _random_atlas(), seed=3, L=17)
+    fr = torch.from_numpy(case["frames"]).to(gpu_device)
+    with pytest.raises(_lib.PoseRiskHipError, match=r"\(status -1\): pr_compose_video: L = 17 lines outside 0\.\.16$") as e:
+        video.compose(fr, case["src_idx"], case["box"], case["lines"], case["text"], case["atlas"], 31, 40, 23)
+    assert "pr_compose_people" not in str(e.value)
+
+
 def test_panel_free_and_index_free_forms(gpu_device):
     """No lines (an empty panel), no box, no src_idx (canvas n shows frame n), panel_w = 0."""
     H, W = 37, 53
