@@ -2,7 +2,7 @@
 // descriptors pr_jpeg_decode's kernels read.  Nothing is decoded here.  Behind it, the encoder's host half (section j2):
 // pr_jpeg_encode_plan derives the tables and the header bytes pr_jpeg_encode's kernels read, pr_jpeg_encode_bound the size no
 // file exceeds.  Device-free: compiled into libposerisk_hip.so by
-// hipcc as plain C++ and, for tests/native/jpeg_parse_check.cc, by g++ with -fsanitize=address,undefined.  No HIP header may be
+// hipcc as plain C++ and, for the tests/native/jpeg*_native.cc drivers, by g++ with -fsanitize=address,undefined.  No HIP header may be
 // included here.  Every read goes through Reader, which knows the file's end: a stream cut or corrupted anywhere ends in a
 // refusal or in descriptors whose ranges lie inside the file.
 #include <algorithm>

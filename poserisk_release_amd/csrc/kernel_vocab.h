@@ -1,6 +1,6 @@
 // The device-side vocabulary the kernels share: vector types, the buffer-descriptor word, the LDS-DMA swizzle, the bf16 pack
 // helpers, the XCD block remap and the bf16 MFMA steps.  Included by the kernel files themselves, never by common.h:
-// compose.hip and jpeg.hip also compile for the host against tests/native/*_shim.h, which stand in for common.h alone.
+// compose.hip and jpeg.hip also compile for the host against tests/native/host_shim.h, which stands in for common.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 

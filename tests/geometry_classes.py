@@ -3,10 +3,8 @@ up to 256 frames, and the CPU program that derives those classes from the launch
 (tests/native/launch_geometry.cc over csrc/host_plan.h).  Shared by tests/test_launch_geometry.py, which holds the list to
 the rules, and tests/test_encoder_batch_sweep.py, which taps every encoder block at these sizes on the GPU."""
 import os
-import shutil
-import subprocess
 
-from conftest import REPO
+import host_build
 
 ANCHORED = (1, 64)      # checked against fp64 block by block (tests/test_encoder_blocks.py)
 # A greedy cover of the classes of the three configurations below over B = 1 .. 256, plus 37 (a "whole rounds + quarter tail +
@@ -21,13 +19,10 @@ CONFIGS = {"fp32_default": (0, -1, "default"), "fp32_direct": (0, 0, "direct"), 
 def build(tmp_dir):
     """-> (program, blob file) or None where there is no g++."""
     from poserisk_release_amd import synth, weights
-    gxx = shutil.which("g++")
-    if gxx is None:
+    exe = host_build.build(tmp_dir, "launch_geometry", "launch_geometry.cc", sources=("host_plan.cc",), strict=True, sanitize=False,
+                           without_compiler="none")
+    if exe is None:
         return None
-    exe = os.path.join(str(tmp_dir), "launch_geometry")
-    r = subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", exe, os.path.join(REPO, "tests", "native", "launch_geometry.cc"),
-                        os.path.join(REPO, "poserisk_release_amd", "csrc", "host_plan.cc")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
     blob = os.path.join(str(tmp_dir), "blob.f32")
     weights.flatten_state_dict(synth.hmr_state_dict(seed=1)).tofile(blob)
     return exe, blob
@@ -37,10 +32,7 @@ def classes(prog, config, b_first, b_last, max_batch=256, streams=1, concurrency
     """-> {B: set of "<layer family> | <geometry class>" strings} in a clean environment (no POSERISK_* switch)."""
     exe, blob = prog
     precision, form, _ = CONFIGS[config]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("POSERISK_")}
-    r = subprocess.run([exe, blob, str(precision), str(form), str(max_batch), str(streams), str(concurrency), str(b_first), str(b_last)],
-                       capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, r.stderr[-2000:]
+    r = exe.run(blob, precision, form, max_batch, streams, concurrency, b_first, b_last)
     out = {}
     for line in r.stdout.splitlines():
         head, rest = line.split(" | ", 1)

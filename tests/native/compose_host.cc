@@ -1,23 +1,12 @@
-// csrc/compose.hip on the host (see compose_host_shim.h): reads a case file, runs pr_compose_video, writes the canvases.
+// csrc/compose.hip on the host (see host_shim.h): reads a case file, runs pr_compose_video, writes the canvases.
 //   case file: int32 header[24] = N n_frames H W dst_h dst_w panel_w L C S CH CW adv[4] ascent[4] box_rgb[3] has_src_idx,
 //   then frames, src_idx, box, lines, text, atlas as raw bytes.   usage: compose_host <case> <out> [output misalignment]
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-
+#define HOST_SHIM_THREADS      // compose.hip meets at barriers ...
+#define HOST_SHIM_SHARED       // ... and declares its LDS block extern: it is the array below
 #include "common.h"
+#include "native_common.h"
 
 unsigned pr_compose_lds[kLdsBytes / 4] __attribute__((aligned(16)));
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
-
 #include "compose.hip"
 
 int main(int argc, char** argv) {

@@ -1,25 +1,16 @@
-// csrc/compose.hip on the host (see compose_host_shim.h): reads a case file, runs pr_compose_people, writes the canvases.
+// csrc/compose.hip on the host (see host_shim.h): reads a case file, runs pr_compose_people, writes the canvases.
 //   case file: int32 header[24] = N n_frames H W dst_h dst_w panel_w K L L_img C S CH CW adv[4] ascent[4] has_src_idx has_box,
 //   then frames, src_idx, box, box_rgb, lines, text, atlas as raw bytes.
 //   usage: compose_people_host <case> <out> [output misalignment]
 //          compose_people_host --validate      every argument error: PR_ERR_INVALID, `out` untouched, no launch
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-
+#define HOST_SHIM_THREADS      // compose.hip meets at barriers ...
+#define HOST_SHIM_SHARED       // ... and declares its LDS block extern: it is the array below
+#define NATIVE_QUIET_ERRORS    // --validate provokes every refusal and reads its message
 #include "common.h"
+#include "native_common.h"
 
 unsigned pr_compose_lds[kLdsBytes / 4] __attribute__((aligned(16)));
-static char g_error[512];
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-}
-}  // namespace pr
-
+using pr::g_error;
 #include "compose.hip"
 
 static int validate() {

@@ -1,43 +1,18 @@
 // The device-free half of the person detector (csrc/det_host.cc) as a stand-alone program, for a build under
-// -fsanitize=address,undefined (tests/test_detector_native.py): the topology table, fold + pack of a TRUNCATED table into an
+// ASan + UBSan (tests/test_detector_native.py): the topology table, fold + pack of a TRUNCATED table into an
 // exact-size heap block, the refusals, and the activation-buffer plan checked structurally at several input sizes.
 //   det_host_check <n_layers> <weights.f32> <bn_eps> <packed_out.f32>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <string>
-#include <vector>
 
-#include "../../poserisk_release_amd/csrc/det_host.h"
-
-namespace pr {
-static std::string g_err;
-void set_error(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-}  // namespace pr
-
-static int failures = 0;
-#define CHECK(cond, ...)                          \
-  do {                                            \
-    if (!(cond)) {                                \
-      ++failures;                                 \
-      fprintf(stderr, "CHECK FAILED %s:%d: ", __FILE__, __LINE__); \
-      fprintf(stderr, __VA_ARGS__);               \
-      fprintf(stderr, "\n");                      \
-    }                                             \
-  } while (0)
+#define NATIVE_QUIET_ERRORS    // the refusals are provoked on purpose and their messages read
+#include "native_common.h"
+#include "det_host.h"
 
 // Walks the plan as det.hip does and checks that no step writes a buffer it reads, and that every buffer a step reads still
 // holds the tensor it wants (symbolic: content[slot] = the layer whose output is there).
 static void check_plan(int S_h, int S_w) {
   pr::DetPlan P;
-  CHECK(pr::det_plan(S_h, S_w, &P) == PR_OK, "det_plan(%d, %d): %s", S_h, S_w, pr::g_err.c_str());
+  CHECK(pr::det_plan(S_h, S_w, &P) == PR_OK, "det_plan(%d, %d): %s", S_h, S_w, pr::g_error);
   const auto& L = P.layers;
   const int n = (int)L.size();
   std::vector<int> content(P.slot_floats.size(), -1);
@@ -102,7 +77,7 @@ int main(int argc, char** argv) {
   FILE* f = fopen(argv[2], "rb");
   if (!f || fread(w.data(), sizeof(float), nw, f) != nw) return 3;
   fclose(f);
-  CHECK(pr_det_fold_pack(n_layers, w.data(), nw, eps, packed.data(), np_) == PR_OK, "fold_pack: %s", pr::g_err.c_str());
+  CHECK(pr_det_fold_pack(n_layers, w.data(), nw, eps, packed.data(), np_) == PR_OK, "fold_pack: %s", pr::g_error);
   CHECK(pr_det_fold_pack(n_layers, w.data(), nw - 1, eps, packed.data(), np_) == PR_ERR_INVALID, "a short body refused");
   CHECK(pr_det_fold_pack(n_layers, w.data(), nw, eps, packed.data(), np_ + 1) == PR_ERR_INVALID, "a wrong capacity refused");
   CHECK(pr_det_fold_pack(n_layers, w.data(), nw, 0.0, packed.data(), np_) == PR_ERR_INVALID, "bn_eps = 0 refused");
@@ -115,6 +90,6 @@ int main(int argc, char** argv) {
   for (const auto& s : sizes) check_plan(s[0], s[1]);
   pr::DetPlan P;
   CHECK(pr::det_plan(48, 64, &P) == PR_ERR_INVALID && pr::det_plan(0, 64, &P) == PR_ERR_INVALID, "bad sizes refused");
-  printf("det_host_check: %zu floats packed to %zu, %d failures\n", nw, np_, failures);
-  return failures ? 1 : 0;
+  printf("det_host_check: %zu floats packed to %zu, %d failures\n", nw, np_, g_fail);
+  return g_fail ? 1 : 0;
 }

@@ -1,47 +1,22 @@
 // The bf16 fold + pack of the person detector (csrc/det_host.cc, pr_det_fold_pack_bf16) as a stand-alone program, for a build
-// under -fsanitize=address,undefined (tests/test_detector_bf16_native.py): the fold of a (truncated) table into an exact-size
+// under ASan + UBSan (tests/test_detector_bf16_native.py): the fold of a (truncated) table into an exact-size
 // heap block that is NOT aligned beyond a byte, the refusals by name, the rounding rule on its edge cases, and the bf16 plan's
 // buffers checked against every tensor's size in bytes.
 //   det_pack_bf16_check <n_layers> <weights.f32> <bn_eps> <packed_out.bin>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <limits>
 #include <string>
-#include <vector>
 
-#include "../../poserisk_release_amd/csrc/det_host.h"
-
-namespace pr {
-static std::string g_err;
-void set_error(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-}  // namespace pr
-
-static int failures = 0;
-#define CHECK(cond, ...)                          \
-  do {                                            \
-    if (!(cond)) {                                \
-      ++failures;                                 \
-      fprintf(stderr, "CHECK FAILED %s:%d: ", __FILE__, __LINE__); \
-      fprintf(stderr, __VA_ARGS__);               \
-      fprintf(stderr, "\n");                      \
-    }                                             \
-  } while (0)
+#define NATIVE_QUIET_ERRORS    // the refusals are provoked on purpose and their messages read
+#include "native_common.h"
+#include "det_host.h"
 
 static float from_bits(uint32_t u) {
   float f;
   memcpy(&f, &u, 4);
   return f;
 }
-static bool refused(int status, const char* name) { return status == PR_ERR_INVALID && pr::g_err.find(name) != std::string::npos; }
+static bool refused(int status, const char* name) { return status == PR_ERR_INVALID && strstr(pr::g_error, name) != nullptr; }
 
 int main(int argc, char** argv) {
   if (argc != 5) return 2;
@@ -66,19 +41,19 @@ int main(int argc, char** argv) {
   // exact size, one byte into a heap block: a write one byte off either end, or an aligned wide store, is the sanitizer's
   std::vector<unsigned char> block(nb + 1);
   unsigned char* packed = block.data() + 1;
-  CHECK(pr_det_fold_pack_bf16(n_layers, w.data(), nw, eps, packed, nb) == PR_OK, "fold_pack_bf16: %s", pr::g_err.c_str());
+  CHECK(pr_det_fold_pack_bf16(n_layers, w.data(), nw, eps, packed, nb) == PR_OK, "fold_pack_bf16: %s", pr::g_error);
   f = fopen(argv[4], "wb");
   if (!f || fwrite(packed, 1, nb, f) != nb) return 4;
   fclose(f);
-  CHECK(refused(pr_det_fold_pack_bf16(0, w.data(), nw, eps, packed, nb), "n_layers = 0"), "n_layers = 0: %s", pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(108, w.data(), nw, eps, packed, nb), "n_layers = 108"), "n_layers = 108: %s", pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(n_layers, nullptr, nw, eps, packed, nb), "null weights_host"), "null weights: %s", pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, eps, nullptr, nb), "null packed_host"), "null packed: %s", pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw - 1, eps, packed, nb), "n_floats ="), "a short body: %s", pr::g_err.c_str());
+  CHECK(refused(pr_det_fold_pack_bf16(0, w.data(), nw, eps, packed, nb), "n_layers = 0"), "n_layers = 0: %s", pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(108, w.data(), nw, eps, packed, nb), "n_layers = 108"), "n_layers = 108: %s", pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(n_layers, nullptr, nw, eps, packed, nb), "null weights_host"), "null weights: %s", pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, eps, nullptr, nb), "null packed_host"), "null packed: %s", pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw - 1, eps, packed, nb), "n_floats ="), "a short body: %s", pr::g_error);
   CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, eps, packed, nb + 2), "packed_bytes ="), "a wrong capacity: %s",
-        pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, 0.0, packed, nb), "bn_eps = 0"), "bn_eps = 0: %s", pr::g_err.c_str());
-  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, 1.0, packed, nb), "bn_eps = 1"), "bn_eps = 1: %s", pr::g_err.c_str());
+        pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, 0.0, packed, nb), "bn_eps = 0"), "bn_eps = 0: %s", pr::g_error);
+  CHECK(refused(pr_det_fold_pack_bf16(n_layers, w.data(), nw, 1.0, packed, nb), "bn_eps = 1"), "bn_eps = 1: %s", pr::g_error);
 
   // byte offsets: consecutive, 16-byte aligned, ending on the blob's size
   std::vector<int64_t> off;
@@ -101,7 +76,7 @@ int main(int argc, char** argv) {
   const int sizes[][2] = {{32, 32}, {32, 64}, {64, 96}, {256, 416}, {416, 416}};
   for (const auto& s : sizes) {
     pr::DetPlan P32, P16;
-    CHECK(pr::det_plan(s[0], s[1], &P32) == PR_OK && pr::det_plan(s[0], s[1], &P16, 1) == PR_OK, "det_plan: %s", pr::g_err.c_str());
+    CHECK(pr::det_plan(s[0], s[1], &P32) == PR_OK && pr::det_plan(s[0], s[1], &P16, 1) == PR_OK, "det_plan: %s", pr::g_error);
     CHECK(P32.slot == P16.slot && P32.slot_floats == P16.slot_floats, "%dx%d: the two plans place their tensors differently", s[0], s[1]);
     for (int l = 0; l < PR_DET_NUM_LAYERS; ++l) {
       const bool head = l == 81 || l == 82 || l == 93 || l == 94 || l == 105 || l == 106;
@@ -114,7 +89,7 @@ int main(int argc, char** argv) {
       CHECK(P32.slot_frame_bytes[b] == 4 * P32.slot_floats[b] && P16.slot_frame_bytes[b] <= P32.slot_frame_bytes[b], "buffer %zu", b);
   }
   pr::DetPlan P;
-  CHECK(refused(pr::det_plan(64, 96, &P, 2), "precision = 2"), "precision 2: %s", pr::g_err.c_str());
-  printf("det_pack_bf16_check: %zu floats packed to %zu bytes, %d failures\n", nw, nb, failures);
-  return failures ? 1 : 0;
+  CHECK(refused(pr::det_plan(64, 96, &P, 2), "precision = 2"), "precision 2: %s", pr::g_error);
+  printf("det_pack_bf16_check: %zu floats packed to %zu bytes, %d failures\n", nw, nb, g_fail);
+  return g_fail ? 1 : 0;
 }

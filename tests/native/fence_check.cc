@@ -1,6 +1,6 @@
 // CPU-only check of the internal fence's device-free part (csrc/host_common.h: fence_guard_bytes, fence_tail_offset,
 // fence_scan; csrc/host_plan.h: the byte sizes hmr.hip places every tensor by), built by tests/test_internal_fence_cpu.py with
-// g++ -fsanitize=address,undefined -fno-sanitize-recover=all.
+// g++ under ASan + UBSan.
 //
 //   fence_check <blob.f32>
 //
@@ -12,38 +12,14 @@
 //     buffer (the stem's input, residuals, the second source of a dual-source conv3, the whole-block alternates of layer3,
 //     the average pool, the taps of pr_hmr_encode_until, V / M of the Winograd layers, the split-K slab);
 //   * fence_scan on host copies of a guard with no byte, one byte, the first byte, the last byte and a run of bytes changed.
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "../../poserisk_release_amd/csrc/host_plan.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
+#include "host_plan.h"
 
 using namespace pr;
 
-static int g_fail = 0;
 static long g_checked = 0;
-#define CHECK(cond, ...)                                            \
-  do {                                                              \
-    if (!(cond)) {                                                  \
-      fprintf(stderr, "CHECK FAILED %s:%d: ", __FILE__, __LINE__);  \
-      fprintf(stderr, __VA_ARGS__);                                 \
-      fprintf(stderr, "\n");                                        \
-      ++g_fail;                                                     \
-    }                                                               \
-  } while (0)
 
 struct HostSink : PlanSink {
   std::vector<void*> blocks;

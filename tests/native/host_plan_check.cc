@@ -1,5 +1,5 @@
 // CPU-only check of the device-free half of pr_hmr_create (poserisk_release_amd/csrc/host_plan.cc), built by
-// tests/test_host_plan_native.py with  g++ -fsanitize=address,undefined -fno-sanitize-recover=all.
+// tests/test_host_plan_native.py with g++ under ASan + UBSan.
 // ("sanitizer build of the host C++"; the code under test only ever runs behind pr_hmr_create, which
 // needs a GPU, so nothing else exercises its index arithmetic off-device.)
 //
@@ -20,40 +20,15 @@
 // conv_pack_side_by_side for layer2.0's conv3 + downsample must give, byte for byte, what the plan uploaded.
 #include <cinttypes>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <set>
 #include <string>
-#include <vector>
 
-#include "../../poserisk_release_amd/csrc/host_plan.h"
-
-namespace pr {
-static std::string g_err;
-void set_error(const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-}
-}  // namespace pr
+#define NATIVE_QUIET_ERRORS    // the refusals are provoked on purpose and their messages read
+#include "native_common.h"
+#include "host_plan.h"
 
 using namespace pr;
-
-static int g_fail = 0;
-#define CHECK(cond, ...)                                   \
-  do {                                                     \
-    if (!(cond)) {                                         \
-      fprintf(stderr, "CHECK FAILED %s:%d: ", __FILE__, __LINE__); \
-      fprintf(stderr, __VA_ARGS__);                        \
-      fprintf(stderr, "\n");                               \
-      ++g_fail;                                            \
-    }                                                      \
-  } while (0)
 
 struct Upload {
   size_t bytes;
@@ -290,7 +265,7 @@ struct Built {
 static bool build(Built& b, const std::vector<float>& blob, int precision, int form, int max_batch, const char* tag) {
   hmr_plan_configure(&b.plan, precision, form, max_batch);
   const int st = hmr_plan_build(&b.plan, blob.data(), blob.size(), b.sink);
-  CHECK(st == PR_OK, "%s: hmr_plan_build failed: %s", tag, g_err.c_str());
+  CHECK(st == PR_OK, "%s: hmr_plan_build failed: %s", tag, g_error);
   return st == PR_OK;
 }
 
@@ -353,7 +328,7 @@ static void check_block(const Built& b, const ConvSpec* spec, const std::vector<
   const ConvFilter down = f.down.filter();
   BottleneckWeights bw;
   const int st = bottleneck_pack_bf16(kPlanes[L], f.c1.filter(), f.c2.filter(), f.c3.filter(), blk == 0 ? &down : nullptr, &bw);
-  CHECK(st == PR_OK, "%s: bottleneck_pack_bf16 failed: %s", tag, g_err.c_str());
+  CHECK(st == PR_OK, "%s: bottleneck_pack_bf16 failed: %s", tag, g_error);
   if (st != PR_OK) return;
   check_upload(b.sink, spec->w, bw.w1, tag, "w1");
   check_upload(b.sink, spec->w2b, bw.w2, tag, "w2");
@@ -413,7 +388,7 @@ int main(int argc, char** argv) {
   {
     Built b;
     hmr_plan_configure(&b.plan, 0, PR_CONV_FORM_DEFAULT, 64);
-    CHECK(hmr_plan_build(&b.plan, blob.data(), blob.size() - 1, b.sink) == PR_ERR_INVALID && g_err.find("floats") != std::string::npos, "a short blob is refused by size");
+    CHECK(hmr_plan_build(&b.plan, blob.data(), blob.size() - 1, b.sink) == PR_ERR_INVALID && strstr(g_error, "floats") != nullptr, "a short blob is refused by size");
     hmr_plan_configure(&b.plan, 0, PR_CONV_FORM_DEFAULT, 0);
     CHECK(hmr_plan_build(&b.plan, blob.data(), blob.size(), b.sink) == PR_ERR_INVALID, "max_batch 0 is refused");
     CHECK(hmr_conv_form_valid(-1) && hmr_conv_form_valid(0) && hmr_conv_form_valid(5) && hmr_conv_form_valid(244) && hmr_conv_form_valid(505) &&

@@ -1,5 +1,5 @@
-// csrc/jpeg_host.cc and csrc/jpeg_enc.hip on the host (see jpeg_host_shim.h), built by tests/test_jpeg_encode_native.py with
-// g++ -fsanitize=address,undefined.
+// csrc/jpeg_host.cc and csrc/jpeg_enc.hip on the host (see host_shim.h), built by tests/test_jpeg_encode_native.py with
+// g++ under ASan + UBSan.
 //   jpeg_enc_native encode <in> <out>   F frames through pr_jpeg_encode_plan and pr_jpeg_encode, once per capacity, every buffer
 //       an exact-size heap block.  in: int32 F, H, W, hs, vs, restart_interval, quality, bgr, ncap; int64 capacity[ncap] (-1 = the
 //       bound); u8 frames[F,H,W,3].   out, per capacity: int64 capacity used, int32 nbytes[F], int32 status[F], u8 out[F,capacity]
@@ -7,30 +7,11 @@
 //   jpeg_enc_native quant   the reciprocal quantiser against the division for every magnitude 0..16384, both signs, and every
 //       divisor 8..2040.
 //   jpeg_enc_native fdct <in> <out>   in: int32 n, int32 samples[n][64] (0..255).  out: int32 coefficients[n][64] of the 32-bit FDCT.
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
 
 #include "jpeg_host.cc"
 #include "jpeg_enc.hip"
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
 
 static int run_encode(const char* in, const char* outp) {
   std::ifstream f(in, std::ios::binary);

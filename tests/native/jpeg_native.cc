@@ -1,49 +1,24 @@
-// csrc/jpeg_host.cc and csrc/jpeg.hip on the host (see jpeg_host_shim.h), built by tests/test_jpeg_native.py with
-// g++ -fsanitize=address,undefined.
+// csrc/jpeg_host.cc and csrc/jpeg.hip on the host (see host_shim.h), built by tests/test_jpeg_native.py with
+// g++ under ASan + UBSan.
 //   jpeg_native each <pack> <out> [bgr]   every stream of the pack on its own: copied to an exact-size heap block, parsed
 //       (F = 1), its segment ranges checked against the block, decoded into exact-size buffers.
 //       pack: int64 F, int64 offsets[F+1], bytes.   out, per stream: int32 parse_status, counts[4], decode_status (-1 when not
 //       decoded), then for an accepted stream pr_jpeg_frame, its segments, its pr_jpeg_huff, the pixels u8[H,W,3].
 //   jpeg_native idct <in> <out>   the IDCT kernel alone on four hand-made blocks of a 16x16 one-component frame.
 //       in: int16 coef[4][64] (natural order), uint16 quant[64].   out: u8 plane[16][16], int32 status.
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
 
 #include "jpeg_host.cc"
 #include "jpeg.hip"
 
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
-
 static int run_each(const char* in, const char* outp, int bgr) {
-  std::ifstream f(in, std::ios::binary);
-  int64_t F = 0;
-  f.read((char*)&F, 8);
-  std::vector<int64_t> off((size_t)F + 1);
-  f.read((char*)off.data(), (std::streamsize)(8 * (F + 1)));
-  std::vector<uint8_t> all((size_t)off[F]);
-  f.read((char*)all.data(), (std::streamsize)all.size());
+  const Pack k = read_pack(in);
+  const int64_t F = k.F;
   std::ofstream o(outp, std::ios::binary);
   for (int64_t i = 0; i < F; ++i) {
-    const int64_t n = off[i + 1] - off[i];
-    auto data = exact<uint8_t>((size_t)n);
-    memcpy(data.get(), all.data() + off[i], (size_t)n);
+    const int64_t n = k.size(i);
+    auto data = k.copy(i);
     const int64_t offsets[2] = {0, n};
     pr_jpeg_frame fr;
     int32_t st = -1, counts[4] = {0, 0, 0, 0}, dst = -1;

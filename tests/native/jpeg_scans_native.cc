@@ -1,48 +1,23 @@
 // csrc/jpeg_scans_host.cc and csrc/jpeg_scans.hip (with csrc/jpeg_host.cc and csrc/jpeg.hip behind them) on the host, built by
-// tests/test_jpeg_scans_native.py with g++ -fsanitize=address,undefined, each source its own translation unit.
+// tests/test_jpeg_scans_native.py with g++ under ASan + UBSan, each source its own translation unit.
 //   jpeg_scans_native each <pack> <out> [bgr]   every stream of the pack on its own: copied to an exact-size heap block, parsed
 //       by pr_jpeg_parse_scans (F = 1; once for the counts, once into arrays of exactly that size), its segment ranges checked
 //       against the block, decoded by pr_jpeg_decode_scans into exact-size buffers.
 //       pack: int64 F, int64 offsets[F+1], bytes.   out, per stream: int32 parse_status, counts[8], decode_status (-1 when not
 //       decoded), then for an accepted stream pr_jpeg_frame, its segments, their scan indices, its scans, its table sets, the
 //       pixels u8[H,W,3].
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
+#include "native_common.h"
 
 int main(int argc, char** argv) {
   if (argc < 4 || strcmp(argv[1], "each")) return 2;
   const int bgr = argc > 4 ? atoi(argv[4]) : 0;
-  std::ifstream f(argv[2], std::ios::binary);
-  int64_t F = 0;
-  f.read((char*)&F, 8);
-  std::vector<int64_t> off((size_t)F + 1);
-  f.read((char*)off.data(), (std::streamsize)(8 * (F + 1)));
-  std::vector<uint8_t> all((size_t)off[F]);
-  f.read((char*)all.data(), (std::streamsize)all.size());
+  const Pack k = read_pack(argv[2]);
+  const int64_t F = k.F;
   std::ofstream o(argv[3], std::ios::binary);
   for (int64_t i = 0; i < F; ++i) {
-    const int64_t n = off[i + 1] - off[i];
-    auto data = exact<uint8_t>((size_t)n);
-    memcpy(data.get(), all.data() + off[i], (size_t)n);
+    const int64_t n = k.size(i);
+    auto data = k.copy(i);
     const int64_t offsets[2] = {0, n};
     pr_jpeg_frame fr;
     int32_t st = -1, counts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dst = -1;

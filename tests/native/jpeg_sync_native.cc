@@ -1,65 +1,17 @@
-// csrc/jpeg_host.cc, csrc/jpeg.hip and csrc/jpeg_sync.hip on the host (see jpeg_host_shim.h), built by
-// tests/test_jpeg_sync_native.py with g++ -fsanitize=address,undefined.
+// csrc/jpeg_host.cc, csrc/jpeg.hip and csrc/jpeg_sync.hip on the host (see host_shim.h), built by
+// tests/test_jpeg_sync_native.py with g++ under ASan + UBSan.
 //   jpeg_sync_native each <pack> <out> <S> <R> [bgr]   every stream of the pack on its own: copied to an exact-size heap block,
 //       parsed (F = 1), decoded by pr_jpeg_decode and by pr_jpeg_decode_sync (S, R: 0 = the default) into exact-size buffers.
 //       pack: int64 F, int64 offsets[F+1], bytes.   out, per stream: int32 parse_status, counts[4], serial status, sync status
 //       (-1 when not decoded), stats[4], then for an accepted stream the serial pixels and the sync pixels, u8[H,W,3] each.
 //   jpeg_sync_native args <pack>   the first stream of the pack through every argument error of pr_jpeg_decode_sync: each
 //       must return PR_ERR_INVALID and leave pixels, status, stats and workspace as they were.
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
-
-inline int atomicAdd(int* p, int v) {
-  const int old = *p;
-  *p = old + v;
-  return old;
-}
-
-inline int atomicMax(int* p, int v) {
-  const int old = *p;
-  *p = old > v ? old : v;
-  return old;
-}
+#include "native_common.h"
 
 #include "jpeg_host.cc"
 #include "jpeg.hip"
 #include "jpeg_sync.hip"
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
-
-struct Pack {
-  int64_t F = 0;
-  std::vector<int64_t> off;
-  std::vector<uint8_t> all;
-};
-
-static Pack read_pack(const char* in) {
-  Pack k;
-  std::ifstream f(in, std::ios::binary);
-  f.read((char*)&k.F, 8);
-  k.off.resize((size_t)k.F + 1);
-  f.read((char*)k.off.data(), (std::streamsize)(8 * (k.F + 1)));
-  k.all.resize((size_t)k.off[k.F]);
-  f.read((char*)k.all.data(), (std::streamsize)k.all.size());
-  return k;
-}
 
 struct Parsed {
   std::unique_ptr<uint8_t[]> data;
@@ -72,9 +24,8 @@ struct Parsed {
 };
 
 static void parse_one(const Pack& k, int64_t i, Parsed& q) {
-  q.n = k.off[i + 1] - k.off[i];
-  q.data = exact<uint8_t>((size_t)q.n);
-  memcpy(q.data.get(), k.all.data() + k.off[i], (size_t)q.n);
+  q.n = k.size(i);
+  q.data = k.copy(i);
   const int64_t offsets[2] = {0, q.n};
   int rc = pr_jpeg_parse(q.data.get(), offsets, 1, 0, 0, &q.fr, nullptr, 0, nullptr, 0, &q.st, q.counts);
   if (rc != PR_OK && rc != PR_ERR_CAPACITY) {

@@ -24,24 +24,11 @@
 //   bf16: the tile index and its ragged last block; whether layer3's plain blocks take the frame-per-workgroup kernel; balanced
 //     (conv_bal_bf16.hip): channel blocks of 256 or 128, pixel runs capped by the CUs or by the pixel tiles, last 32-row tile
 //     ragged or not.  The whole-Bottleneck and expansion kernels size their grids in their own launchers: not modelled
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <set>
 #include <string>
-#include <vector>
 
-#include "../../poserisk_release_amd/csrc/host_plan.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
+#include "host_plan.h"
 
 using namespace pr;
 

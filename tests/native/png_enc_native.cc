@@ -1,6 +1,6 @@
 // Stand-alone host driver of the PNG encoder for tests/test_png_encode_native.py: csrc/png_enc_host.cc (plan, bound, workspace)
 // and the one-lane instantiation of csrc/png_enc_device.h (filters, adaptive choice, tokens, code construction, bits, stored
-// fallback, checksum algebra), built by g++ with -fsanitize=address,undefined.  Every frame is handled on its own and every
+// fallback, checksum algebra), built by g++ under ASan + UBSan.  Every frame is handled on its own and every
 // buffer -- the pixels, the row filters, each segment's staging area (5 + n bytes: the contract's bound), the file (exactly
 // pr_png_encode_bound) -- is a heap block of EXACTLY its size, so that one byte read or written outside shows.
 //
@@ -8,25 +8,10 @@
 // pack.bin: int32 n, then per frame int32 H, W, filter, mode, bgr and H * W * 3 pixels.  out.bin, per frame: int32 size, the file.
 //   png_enc_native errors
 // prints "ok" when every bad argument of the plan, bound and workspace functions is refused.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
-#include "host_common.h"
-
-static char g_error[512];
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof g_error, fmt, ap);
-  va_end(ap);
-}
-}  // namespace pr
-
+#define NATIVE_QUIET_ERRORS    // `errors` provokes every refusal and reads its message
+#include "native_common.h"
 #include "png_enc_host.cc"
+using pr::g_error;
 
 using namespace pr::pngenc;
 

@@ -1,34 +1,18 @@
 // Stand-alone host driver of the PNG decoder for tests/test_png_native.py: csrc/png_host.cc (the chunk walk) and the one-lane
 // instantiation of csrc/png_device.h (bit reader, tables, symbol decode, every validation decision, Adler-32, unfilter), built by
-// g++ with -fsanitize=address,undefined.  Every file is handled on its own and every buffer -- the file, the gathered stream,
+// g++ under ASan + UBSan.  Every file is handled on its own and every buffer -- the file, the gathered stream,
 // the inflated scanlines, the pixels -- is a heap block of EXACTLY its size, so that one byte read or written outside shows.
 //
 //   png_native each <pack.bin> <out.bin> <bgr>
 // pack.bin: int64 n, int64 offsets[n + 1], the files back to back.  out.bin, per file: int32 head[8] = parse_status, IDAT
 // ranges, palettes, H, W, status, 0, 0; for an accepted file then its pr_png_frame, its ranges (relative to the file) and
 // H * W * 3 pixels.
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
-#include "host_common.h"
+#define NATIVE_QUIET_ERRORS    // thousands of damaged streams: the refusals' words are not what is checked
+#include "native_common.h"
 #include "png_device.h"
-
-namespace pr {
-void set_error(const char*, ...) {}
-}  // namespace pr
-
 #include "png_host.cc"
 
 using namespace pr::png;
-
-static std::vector<uint8_t> read_all(const char* path) {
-  std::ifstream f(path, std::ios::binary);
-  return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
 
 // What pr_png_decode's three kernels do for one frame, on the host: -> status, pixels (H * W * 3)
 static int decode_one(const uint8_t* file, int64_t n, const pr_png_frame& fr, const pr_png_idat* idat, const uint8_t* palettes, int bgr,
@@ -81,18 +65,12 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: png_native each <pack.bin> <out.bin> <bgr>\n");
     return 2;
   }
-  const std::vector<uint8_t> pack = read_all(argv[2]);
+  const Pack pack = read_pack(argv[2]);
   const int bgr = atoi(argv[4]);
-  int64_t n = 0;
-  memcpy(&n, pack.data(), 8);
-  std::vector<int64_t> off((size_t)n + 1);
-  memcpy(off.data(), pack.data() + 8, (size_t)(n + 1) * 8);
-  const uint8_t* blobs = pack.data() + 8 * (n + 2);
   std::ofstream out(argv[3], std::ios::binary);
-  for (int64_t s = 0; s < n; ++s) {
-    const int64_t len = off[s + 1] - off[s];
-    std::unique_ptr<uint8_t[]> file(new uint8_t[(size_t)(len ? len : 1)]);   // exact size: ASan sees the first byte outside
-    memcpy(file.get(), blobs + off[s], (size_t)len);
+  for (int64_t s = 0; s < pack.F; ++s) {
+    const int64_t len = pack.size(s);
+    auto file = pack.copy(s);   // exact size: ASan sees the first byte outside
     const int64_t offsets[2] = {0, len};
     pr_png_frame fr;
     int32_t pst = 0, counts[4] = {0, 0, 0, 0};

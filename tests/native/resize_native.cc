@@ -1,34 +1,15 @@
-// csrc/resize_host.cc and csrc/resize.hip on the host (see jpeg_host_shim.h), built by tests/test_frontend_native.py with
-// g++ -fsanitize=address,undefined.
+// csrc/resize_host.cc and csrc/resize.hip on the host (see host_shim.h), built by tests/test_frontend_native.py with
+// g++ under ASan + UBSan.
 //   resize_native resize <in> <out>   F frames through pr_resize_plan and pr_resize_frames, every buffer an exact-size heap
 //       block, once per alignment 0..3 of the output's first byte (the block is then that much larger and the bytes in front of
 //       the output must keep their fill; behind it the block ends).  in: int32 F, H, W, h, w; u8 frames[F,H,W,3].   out: int32 mode, int32 xofs[w],
 //       int16 xcoef[2w], int32 yofs[h], int16 ycoef[2h], then four times u8 dst[F,h,w,3].
 //   resize_native refusals   every argument error of the two entries returns PR_ERR_INVALID (the words go to stderr).
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
 
 #include "resize_host.cc"
 #include "resize.hip"
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
 
 static int run_resize(const char* in, const char* outp) {
   std::ifstream f(in, std::ios::binary);

@@ -4,23 +4,8 @@
 //   wino_layer1_plan <blob.f32> <conv_form>
 //
 // prints one line per plan entry of stage 0 with a 3x3 kernel:  "<layer> <routed 0|1> <N3> <mfma_macs_per_frame>"
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
-
-#include "../../poserisk_release_amd/csrc/host_plan.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
+#include "host_plan.h"
 
 using namespace pr;
 

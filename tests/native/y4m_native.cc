@@ -1,5 +1,5 @@
-// csrc/y4m_host.cc and csrc/yuv.hip on the host (see jpeg_host_shim.h), built by tests/test_y4m_native.py with
-// g++ -fsanitize=address,undefined.
+// csrc/y4m_host.cc and csrc/yuv.hip on the host (see host_shim.h), built by tests/test_y4m_native.py with
+// g++ under ASan + UBSan.
 //   y4m_native frames <in> <out>   a whole YUV4MPEG2 stream through pr_y4m_parse_header, pr_y4m_index, pr_yuv_plan and
 //       pr_yuv_frames (with h, w > 0 also pr_resize_plan: the fused downscale), every buffer an exact-size heap block, once per
 //       alignment 0..3 of the output's first byte (the block is then that much larger and the bytes in front of the output must
@@ -7,31 +7,12 @@
 //       out: int32 F, H, W, chroma, full_range of the header, fps_num, fps_den, header_bytes, h, w, mode, the six plan integers,
 //       int64 offsets[F] (in the stream), then four times u8 dst[F,h,w,3].
 //   y4m_native refusals   every argument error of the entries returns PR_ERR_INVALID (the words go to stderr).
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
 
 #include "resize_host.cc"
 #include "y4m_host.cc"
 #include "yuv.hip"
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
 
 static int run_frames(const char* in, const char* outp) {
   std::ifstream f(in, std::ios::binary);

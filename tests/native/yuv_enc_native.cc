@@ -1,5 +1,5 @@
-// csrc/y4m_host.cc and csrc/yuv_enc.hip on the host (see jpeg_host_shim.h), built by tests/test_y4m_write_native.py with
-// g++ -fsanitize=address,undefined.
+// csrc/y4m_host.cc and csrc/yuv_enc.hip on the host (see host_shim.h), built by tests/test_y4m_write_native.py with
+// g++ under ASan + UBSan.
 //   yuv_enc_native encode <in> <out>   a list of calls through pr_yuv_enc_plan and pr_yuv_encode, every buffer an exact-size heap
 //       block: src ends where its block ends and begins 0..3 bytes into it, dst likewise (the bytes in front of dst must keep
 //       their fill).  All sixteen pairs of alignments run and must give the same bytes; the stream is then read back by
@@ -7,30 +7,11 @@
 //       u8 src[F,H,W,3].  out: per call int32 total, the nine plan integers, then four times u8 dst[total] (dst at alignment
 //       0, 1, 2, 3).
 //   yuv_enc_native refusals   every argument error of the two entries returns PR_ERR_INVALID (the words go to stderr).
-#include <cstdlib>
-#include <fstream>
-#include <memory>
-#include <vector>
-
 #include "common.h"
-
-namespace pr {
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vfprintf(stderr, fmt, ap);
-  va_end(ap);
-  fputc('\n', stderr);
-}
-}  // namespace pr
+#include "native_common.h"
 
 #include "y4m_host.cc"
 #include "yuv_enc.hip"
-
-template <class T>
-static std::unique_ptr<T[]> exact(size_t n) {   // a heap block of exactly n elements (at least one: new T[0] may not be read)
-  return std::unique_ptr<T[]>(new T[n ? n : 1]());
-}
 
 static int run_encode(const char* in, const char* outp) {
   std::ifstream f(in, std::ios::binary);

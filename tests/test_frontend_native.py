@@ -1,42 +1,23 @@
-"""The frame downscale's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The frame downscale's two halves on the CPU, under ASan + UBSan.
 
 `csrc/resize_host.cc` (pr_resize_plan) and `csrc/resize.hip` (the kernel, compiled unchanged for the host against
-tests/native/jpeg_host_shim.h: a launch = nested loops over workgroups and threads) are built by g++ into one stand-alone driver,
+tests/native/host_shim.h: a launch = nested loops over workgroups and threads) are built by g++ into one stand-alone driver,
 tests/native/resize_native.cc, which runs every call in exact-size heap blocks.  Checked here, without a GPU: tables, mode and
 every output byte against tests/resize_ref.py at every size pair, three frames a call, the output starting at every alignment."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import resize_ref as rr
-from conftest import REPO
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/resize_host.cc and csrc/resize.hip"
     d = tmp_path_factory.mktemp("resize_native")
-    for src, dst in ((os.path.join(CSRC, "resize.hip"), "resize.hip"), (os.path.join(CSRC, "resize_host.cc"), "resize_host.cc"),
-                     (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"),
-                     (os.path.join(NATIVE, "resize_native.cc"), "resize_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "resize_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "resize_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "resize_native", "resize_native.cc", stage=("resize.hip", "resize_host.cc"), shim=True)
 
     def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-6000:])
+        r = exe.run(*args)
         return r.stdout, r.stderr
 
     def resize(frames, h, w):
@@ -46,17 +27,11 @@ def native(tmp_path_factory):
         with open(d / "in.bin", "wb") as f:
             f.write(np.array([F, H, W, h, w], np.int32).tobytes() + frames.tobytes())
         run("resize", d / "in.bin", d / "out.bin")
-        raw, pos = np.fromfile(d / "out.bin", np.uint8), 0
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        take = host_build.taker(d / "out.bin")
         mode = int(take(np.int32, 1)[0])
         tables = take(np.int32, w), take(np.int16, 2 * w), take(np.int32, h), take(np.int16, 2 * h)
         outs = [take(np.uint8, F * h * w * 3).reshape(F, h, w, 3) for _ in range(4)]
-        assert pos == raw.size
+        take.done()
         return (mode, *tables, outs)
     return run, resize
 

@@ -1,4 +1,4 @@
-"""The device-free half of pr_hmr_create under AddressSanitizer + UndefinedBehaviorSanitizer, on the CPU.
+"""The device-free half of pr_hmr_create under ASan + UBSan, on the CPU.
 
 `poserisk_release_amd/csrc/host_plan.cc` (blob layout, BatchNorm folding, every kernel family's weight packing, the Winograd
 G-transform, the 53-convolution launch plan, workspace sizes) only ever runs behind `pr_hmr_create`, which needs a GPU -- so
@@ -7,50 +7,31 @@ its index arithmetic had never run under a sanitizer (SURVEY.md section 5 asks f
 B in {1, 7, 64, 230, 256, 460}, both precisions, every conv form and every plan-shaping switch, against exact-size heap
 blocks, and checks the plans structurally (symbolic dataflow over the buffer rotation, routing, 4 087 136 256 MAC per frame,
 launch counts, workspace sizes), and holds the two default plans against the packers as the stand-alone test entries call them
-(bottleneck_pack_bf16 / conv_pack_side_by_side on filters folded beforehand: byte-equal to the plan's uploads).  Here: it is compiled with g++ -fsanitize=address,undefined, run, and the packed weights it
+(bottleneck_pack_bf16 / conv_pack_side_by_side on filters folded beforehand: byte-equal to the plan's uploads).  Here: it is compiled with g++ under ASan + UBSan, run, and the packed weights it
 produced are compared with a numpy restatement from the same state dict (weights.py's blob order = lib/core/base.py:83-84's
 checkpoint['model'])."""
 import json
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import host_build
 from poserisk_release_amd import synth, weights
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def native_run(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
     d = tmp_path_factory.mktemp("host_plan")
-    exe = str(d / "host_plan_check")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wall", "-Werror", "-o", exe, os.path.join(REPO, "tests", "native", "host_plan_check.cc"), os.path.join(CSRC, "host_plan.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = host_build.build(d, "host_plan_check", "host_plan_check.cc", sources=("host_plan.cc",), strict=True, without_compiler="skip")
     sd = synth.hmr_state_dict(seed=1)
     blob = weights.flatten_state_dict(sd)
     blob.tofile(str(d / "blob.f32"))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    for k in list(env):
-        if k.startswith("POSERISK_"):
-            del env[k]                      # the binary sets the plan's switches itself, one at a time
-    r = subprocess.run([exe, str(d / "blob.f32"), str(d / "manifest.json"), str(d / "dump.bin")], capture_output=True, text=True,
-                       timeout=900, env=env)
-    return r, sd, json.load(open(d / "manifest.json")) if os.path.exists(d / "manifest.json") else None, str(d / "dump.bin")
+    r = exe.run(d / "blob.f32", d / "manifest.json", d / "dump.bin")          # checked: every test stands on a clean run
+    return r, sd, json.load(open(d / "manifest.json")), str(d / "dump.bin")
 
 
 def test_host_plan_is_clean_under_asan_and_ubsan(native_run):
     r, _, manifest, _ = native_run
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-6000:])
-    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "CHECK FAILED" not in r.stderr, r.stderr[-6000:]
     last = r.stdout.strip().splitlines()[-1]
     assert last.startswith("host_plan_check: ") and last.endswith(" 0 failures"), last
     assert int(last.split()[1]) >= 35                      # plans built: 8 forms + 12 batch sizes x precisions + 15 switches
@@ -100,8 +81,7 @@ def _dumped(manifest_entry, dump, i, dtype):
 
 
 def test_packed_weights_equal_a_numpy_restatement(native_run):
-    r, sd, manifest, dump = native_run
-    assert r.returncode == 0 and manifest is not None
+    _, sd, manifest, dump = native_run
     f32, b16 = manifest
     ups = f32["uploads"]
     assert [u["bytes"] for u in ups[-5:]] == [64 * 2048 * 4, 64 * 1024 * 4, 64 * 1024 * 4, 64 * 1024 * 4, 64 * 192 * 4]   # regressor workspaces at B=64

@@ -1,46 +1,27 @@
-"""The JPEG encoder's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The JPEG encoder's two halves on the CPU, under ASan + UBSan.
 
 `csrc/jpeg_host.cc` (pr_jpeg_encode_plan, pr_jpeg_encode_bound) and `csrc/jpeg_enc.hip` (the kernels, compiled unchanged for the
-host against tests/native/jpeg_host_shim.h: a launch = nested loops over workgroups and threads, atomicOr = `|=`) are built by g++
+host against tests/native/host_shim.h: a launch = nested loops over workgroups and threads) are built by g++
 into one stand-alone driver, tests/native/jpeg_enc_native.cc, which runs every call in exact-size heap blocks.  Checked here,
 without a GPU: every golden case byte for byte against Pillow's file, the reciprocal quantiser against the division over its whole
 range, the 32-bit FDCT at the extremes of 8-bit input against an int64 evaluation, and the capacity rule at its edges."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import jpeg_enc_cases as ec
 import jpeg_enc_ref as er
-from conftest import REPO
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 PLAN_BYTES = 32 + 256 + 512 + 64 + 1024 + 32 + 512 + 640
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/jpeg_host.cc and csrc/jpeg_enc.hip"
     d = tmp_path_factory.mktemp("jpeg_enc_native")
-    for src, dst in ((os.path.join(CSRC, "jpeg_enc.hip"), "jpeg_enc.hip"), (os.path.join(CSRC, "jpeg_host.cc"), "jpeg_host.cc"),
-                     (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"),
-                     (os.path.join(NATIVE, "jpeg_enc_native.cc"), "jpeg_enc_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "jpeg_enc_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "jpeg_enc_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "jpeg_enc_native", "jpeg_enc_native.cc", stage=("jpeg_enc.hip", "jpeg_host.cc"), shim=True)
 
     def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
-        return r.stdout
+        return exe.run(*args).stdout
 
     def encode(frames, quality, subsampling, restart_interval, bgr=0, capacities=(-1,)):
         """-> ([(capacity, nbytes int32[F], status int32[F], out u8[F, capacity])], plan bytes, bound)"""
@@ -51,18 +32,12 @@ def native(tmp_path_factory):
             f.write(np.array([F, H, W, hs, vs, restart_interval, quality, bgr, len(capacities)], np.int32).tobytes())
             f.write(np.array(capacities, np.int64).tobytes() + frames.tobytes())
         run("encode", d / "enc.bin", d / "enc_out.bin")
-        raw, pos, out = np.fromfile(d / "enc_out.bin", np.uint8), 0, []
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        take, out = host_build.taker(d / "enc_out.bin"), []
         for _ in capacities:
             cap = int(take(np.int64, 1)[0])
             out.append((cap, take(np.int32, F).copy(), take(np.int32, F).copy(), take(np.uint8, F * cap).reshape(F, cap)))
         plan, bound = take(np.uint8, PLAN_BYTES), int(take(np.int64, 1)[0])
-        assert pos == raw.size
+        take.done()
         return out, plan, bound
 
     def fdct(samples):

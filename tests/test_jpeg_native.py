@@ -1,60 +1,30 @@
-"""The JPEG decoder's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The JPEG decoder's two halves on the CPU, under ASan + UBSan.
 
 `csrc/jpeg_host.cc` (the marker parser) and `csrc/jpeg.hip` (the kernels, compiled unchanged for the host against
-`tests/native/jpeg_host_shim.h`: a launch = nested loops over workgroups and threads) are built by g++ into one driver,
+`tests/native/host_shim.h`: a launch = nested loops over workgroups and threads) are built by g++ into one driver,
 tests/native/jpeg_native.cc, which handles every stream on its own in exact-size heap blocks.  Checked here, without a GPU:
 the parser's descriptors against tests/jpeg_ref.py, every golden case byte for byte against libjpeg's pixels, one stream cut at
 every byte offset and corrupted 2000 times (no sanitizer report; refused, or ranges inside the buffer; a stream that cannot be
 decoded ends with a non-zero status, one that can equals the reference), and the 32-bit IDCT at its stated bound against the
 64-bit reference.  Robustness against bad streams is proven HERE; tests/test_jpeg_gpu.py runs six of these streams once."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import jpeg_cases as jc
 import jpeg_ref as jr
-from conftest import REPO
 from poserisk_release_amd import jpeg
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/jpeg_host.cc and csrc/jpeg.hip"
     d = tmp_path_factory.mktemp("jpeg_native")
-    for src, dst in ((os.path.join(CSRC, "jpeg.hip"), "jpeg.hip"), (os.path.join(CSRC, "jpeg_host.cc"), "jpeg_host.cc"),
-                     (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"), (os.path.join(NATIVE, "jpeg_native.cc"), "jpeg_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "jpeg_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "jpeg_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-    def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
+    exe = host_build.build(d, "jpeg_native", "jpeg_native.cc", stage=("jpeg.hip", "jpeg_host.cc"), shim=True)
 
     def each(streams, bgr=0):
         """-> per stream dict(parse_status, counts, status, and for an accepted one frame, segments, huff, pixels)"""
-        off = np.cumsum([0] + [len(s) for s in streams]).astype(np.int64)
-        with open(d / "pack.bin", "wb") as f:
-            f.write(np.int64(len(streams)).tobytes() + off.tobytes() + b"".join(streams))
-        run("each", d / "pack.bin", d / "out.bin", bgr)
-        raw, pos, out = np.fromfile(d / "out.bin", np.uint8), 0, []
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        exe.run("each", host_build.pack_streams(d / "pack.bin", streams), d / "out.bin", bgr)
+        take, out = host_build.taker(d / "out.bin"), []
         for _ in streams:
             head = take(np.int32, 6)
             rec = dict(parse_status=int(head[0]), counts=head[1:5].copy(), status=int(head[5]))
@@ -64,13 +34,13 @@ def native(tmp_path_factory):
                 rec["huff"] = take(jpeg.HUFF_DTYPE, 1)[0]
                 rec["pixels"] = take(np.uint8, int(head[3]) * int(head[4]) * 3).reshape(int(head[3]), int(head[4]), 3)
             out.append(rec)
-        assert pos == raw.size
+        take.done()
         return out
 
     def idct(coef, quant):
         with open(d / "idct.bin", "wb") as f:
             f.write(np.asarray(coef, np.int16).tobytes() + np.asarray(quant, np.uint16).tobytes())
-        run("idct", d / "idct.bin", d / "idct_out.bin")
+        exe.run("idct", d / "idct.bin", d / "idct_out.bin")
         raw = np.fromfile(d / "idct_out.bin", np.uint8)
         return raw[:256].reshape(16, 16), int(raw[256:].view(np.int32)[0])
     return each, idct

@@ -1,61 +1,33 @@
-"""The multi-scan JPEG decoder's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The multi-scan JPEG decoder's two halves on the CPU, under ASan + UBSan.
 
 `csrc/jpeg_scans_host.cc` (the scan-aware parser) and `csrc/jpeg_scans.hip` (the per-level entropy kernel, compiled unchanged
-for the host against `tests/native/jpeg_scans_host_shim.h`), with `csrc/jpeg_host.cc` and `csrc/jpeg.hip` behind them, are built
+for the host against `tests/native/host_shim.h`), with `csrc/jpeg_host.cc` and `csrc/jpeg.hip` behind them, are built
 by g++ into one stand-alone driver, tests/native/jpeg_scans_native.cc, which handles every stream on its own in exact-size heap
 blocks.  Checked here, without a GPU: every fixture and every transcoded stream byte for byte against libjpeg's pixels, RGB and
 BGR; one progressive stream cut at every byte offset and corrupted 2000 times (no sanitizer report; refused, or ranges inside
 the buffer; a stream the reference cannot decode ends with a non-zero status, one it can equals the reference).  Robustness
 against bad streams is proven HERE; tests/test_jpeg_scans_gpu.py runs six of these streams once."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import jpeg_cases as jc
 import jpeg_scans_cases as sc
 import jpeg_scans_ref as sr
-from conftest import REPO
 from poserisk_release_amd import jpeg
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 SOURCES = ("jpeg_scans_native.cc", "jpeg_host.cc", "jpeg_scans_host.cc", "jpeg.hip", "jpeg_scans.hip")
 
 
 @pytest.fixture(scope="module")
 def each(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/jpeg_scans_host.cc and csrc/jpeg_scans.hip"
     d = tmp_path_factory.mktemp("jpeg_scans_native")
-    for src, dst in [(os.path.join(CSRC, n), n) for n in SOURCES[1:]] + [(os.path.join(NATIVE, "jpeg_scans_host_shim.h"), "common.h"),
-                                                                         (os.path.join(NATIVE, "jpeg_host_shim.h"), "jpeg_host_shim.h"),
-                                                                         (os.path.join(NATIVE, SOURCES[0]), SOURCES[0])]:
-        shutil.copy(src, d / dst)
-    exe = str(d / "jpeg_scans_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe] + [str(d / n) for n in SOURCES]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "jpeg_scans_native", SOURCES[0], sources=SOURCES[1:], stage=SOURCES[1:], shim=True)
 
     def run(streams, bgr=0):
         """-> per stream dict(parse_status, counts, status, and for an accepted one frame, segments, segment_scan, scans, pixels)"""
-        off = np.cumsum([0] + [len(s) for s in streams]).astype(np.int64)
-        with open(d / "pack.bin", "wb") as f:
-            f.write(np.int64(len(streams)).tobytes() + off.tobytes() + b"".join(streams))
-        r = subprocess.run([exe, "each", str(d / "pack.bin"), str(d / "out.bin"), str(bgr)], capture_output=True, text=True,
-                           timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
-        raw, pos, out = np.fromfile(d / "out.bin", np.uint8), 0, []
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        exe.run("each", host_build.pack_streams(d / "pack.bin", streams), d / "out.bin", bgr)
+        take, out = host_build.taker(d / "out.bin"), []
         for _ in streams:
             head = take(np.int32, 10)
             rec = dict(parse_status=int(head[0]), counts=head[1:9].copy(), status=int(head[9]))
@@ -67,7 +39,7 @@ def each(tmp_path_factory):
                 take(jpeg.HUFF_DTYPE, int(head[2]))
                 rec["pixels"] = take(np.uint8, int(head[3]) * int(head[4]) * 3).reshape(int(head[3]), int(head[4]), 3)
             out.append(rec)
-        assert pos == raw.size
+        take.done()
         return out
     return run
 

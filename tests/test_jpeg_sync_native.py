@@ -1,7 +1,7 @@
 """pr_jpeg_decode_sync -- entropy decoding by self-synchronising sub-sequences, csrc/jpeg_sync.hip -- on the CPU, under
-AddressSanitizer + UndefinedBehaviorSanitizer.
+ASan + UBSan.
 
-The kernels index by thread only, so tests/native/jpeg_host_shim.h turns a launch into nested loops and g++ builds
+The kernels index by thread only, so tests/native/host_shim.h turns a launch into nested loops and g++ builds
 csrc/jpeg_host.cc, csrc/jpeg.hip and csrc/jpeg_sync.hip into one stand-alone driver, tests/native/jpeg_sync_native.cc, which
 decodes every stream on its own, in exact-size heap blocks, by pr_jpeg_decode AND by pr_jpeg_decode_sync.  Checked here, without
 a GPU: every golden case byte for byte at four (sub-sequence bytes, rounds) settings with its statistics, that the defaults
@@ -9,58 +9,29 @@ synchronise everything but saturating noise, that the iteration, blocks spanning
 FF 00 pair are really exercised, the header's contract against pr_jpeg_decode and the numpy reference on one stream cut at
 every byte and corrupted 2000 times, and every argument error."""
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import jpeg_cases as jc
 import jpeg_ref as jr
-from conftest import REPO
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 DEFAULT_S, DEFAULT_R = 128, 16        # include/poserisk_hip.h: the build's defaults
 SETTINGS = [(0, 0), (16, 64), (64, 8), (128, 1)]
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/jpeg.hip and csrc/jpeg_sync.hip"
     d = tmp_path_factory.mktemp("jpeg_sync_native")
-    for src, dst in ((os.path.join(CSRC, "jpeg.hip"), "jpeg.hip"), (os.path.join(CSRC, "jpeg_sync.hip"), "jpeg_sync.hip"),
-                     (os.path.join(CSRC, "jpeg_host.cc"), "jpeg_host.cc"), (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"),
-                     (os.path.join(NATIVE, "jpeg_sync_native.cc"), "jpeg_sync_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "jpeg_sync_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "jpeg_sync_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-    def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, \
-            (r.returncode, r.stdout[-500:], r.stderr[-6000:])
-        return r.stdout
-
-    def pack(streams, name):
-        off = np.cumsum([0] + [len(s) for s in streams]).astype(np.int64)
-        with open(d / name, "wb") as f:
-            f.write(np.int64(len(streams)).tobytes() + off.tobytes() + b"".join(streams))
-        return d / name
-
+    exe = host_build.build(d, "jpeg_sync_native", "jpeg_sync_native.cc", stage=("jpeg.hip", "jpeg_sync.hip", "jpeg_host.cc"), shim=True)
     cache = {}
 
     def each(key, streams, S, R, bgr=0):
         """-> per stream dict(parse_status, serial, sync, stats = (n_subseq, rounds, fell_back), serial_px, sync_px)"""
         if (key, S, R, bgr) in cache:
             return cache[key, S, R, bgr]
-        run("each", pack(streams, "pack.bin"), d / "out.bin", S, R, bgr)
+        exe.run("each", host_build.pack_streams(d / "pack.bin", streams), d / "out.bin", S, R, bgr)
         raw, pos, out = np.fromfile(d / "out.bin", np.uint8), 0, []
         for _ in streams:
             head = raw[pos:pos + 44].view(np.int32)
@@ -77,7 +48,7 @@ def native(tmp_path_factory):
         return out
 
     def args(stream):
-        return run("args", pack([stream], "args.bin"))
+        return exe.run("args", host_build.pack_streams(d / "args.bin", [stream])).stdout
     return each, args
 
 

@@ -1,45 +1,24 @@
-"""The people compositor's kernel source and its argument validation on the CPU, under AddressSanitizer +
-UndefinedBehaviorSanitizer.
+"""The people compositor's kernel source and its argument validation on the CPU, under ASan +
+UBSan.
 
-`poserisk_release_amd/csrc/compose.hip` (the one kernel behind both entry points) is compiled unchanged for the host against `tests/native/compose_host_shim.h`
-(tests/test_video_native.py's shim: a workgroup = 256 threads and a barrier, workgroups one after the other) into a stand-alone
+`poserisk_release_amd/csrc/compose.hip` (the one kernel behind both entry points) is compiled unchanged for the host against `tests/native/host_shim.h`
+(as tests/test_video_native.py has it: a workgroup = 256 threads and a barrier, workgroups one after the other) into a stand-alone
 program, `tests/native/compose_people_host.cc`, and run on exact-size heap buffers: the box table, the two line groups, the
 u32 sums and every address the kernel forms are checked against the numpy restatement of the contract
 (tests/video_people_ref.py), byte for byte, without a GPU -- and `--validate` gives pr_compose_people every argument error in
 turn.  Nothing here is loaded into Python.  What this cannot show is anything about the GPU build itself --
 tests/test_people_gpu.py does that."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import people_cases as pc
-from conftest import REPO
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-
-
-def _clean(r):
-    assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout + r.stderr)[-6000:]
 
 
 @pytest.fixture(scope="module")
 def people_host(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/compose.hip"
     d = tmp_path_factory.mktemp("compose_people_host")
-    shutil.copy(os.path.join(CSRC, "compose.hip"), d / "compose.hip")
-    shutil.copy(os.path.join(NATIVE, "compose_host_shim.h"), d / "common.h")       # what compose.hip includes
-    shutil.copy(os.path.join(NATIVE, "compose_people_host.cc"), d / "compose_people_host.cc")
-    exe = str(d / "compose_people_host")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-pthread", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "compose_people_host.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = host_build.build(d, "compose_people_host", "compose_people_host.cc", stage=("compose.hip",), shim=True, threads=True)
 
     def run(c, shift=0, with_box=True):
         a = c["atlas"]
@@ -53,9 +32,7 @@ def people_host(tmp_path_factory):
         with open(d / "case.bin", "wb") as f:
             for arr in (h, c["frames"], c["src_idx"], c["box"], c["box_rgb"], c["lines"], c["text"], cov):
                 f.write(np.ascontiguousarray(arr).tobytes())
-        r = subprocess.run([exe, str(d / "case.bin"), str(d / "out.bin"), str(shift)], capture_output=True, text=True, timeout=600,
-                           env=ENV)
-        _clean(r)
+        exe.run(d / "case.bin", d / "out.bin", shift)
         shape = (N, c["dst_h"], c["dst_w"] + c["panel_w"], 3)
         raw = np.fromfile(d / "out.bin", np.uint8)
         n = int(np.prod(shape))
@@ -65,9 +42,7 @@ def people_host(tmp_path_factory):
 
 
 def test_every_argument_error_is_refused_before_any_work(people_host):
-    r = subprocess.run([people_host.exe, "--validate"], capture_output=True, text=True, timeout=600, env=ENV)
-    _clean(r)
-    assert "0 failures" in r.stdout
+    assert "0 failures" in people_host.exe.run("--validate").stdout
 
 
 @pytest.mark.parametrize("shape", pc.SHAPES, ids=lambda s: "K%d_L%d_Limg%d" % s)

@@ -1,4 +1,4 @@
-"""The PNG encoder's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The PNG encoder's two halves on the CPU, under ASan + UBSan.
 
 `csrc/png_enc_host.cc` (plan, bound, workspace size) and the ONE-LANE instantiation of `csrc/png_enc_device.h` (filters, adaptive
 choice, tokens, code construction, bit layout, stored fallback, checksum algebra) are built by g++ into one stand-alone program
@@ -8,36 +8,20 @@ byte equal to tests/png_enc_ref.py, RGB and BGR, with no sanitizer report; the a
 
 NOT covered by this program: what only the 64-lane form does -- the cross-lane sums, the words several lanes combine into, the
 assemble and place kernels.  tests/test_png_encode_gpu.py (byte-exact cases, guard bands) covers that code."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import png_enc_cases as ec
-from conftest import REPO
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/png_enc_host.cc and csrc/png_enc_device.h"
     d = tmp_path_factory.mktemp("png_enc_native")
-    exe = str(d / "png_enc_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-I", CSRC, "-o", exe, os.path.join(NATIVE, "png_enc_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "png_enc_native", "png_enc_native.cc")
 
     def run(*args):
-        r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
-        return r.stdout
+        return exe.run(*args).stdout
 
     def each(frames):
         """[(px RGB or BGR, filter, mode, bgr)] -> the files"""

@@ -1,4 +1,4 @@
-"""The PNG decoder's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The PNG decoder's two halves on the CPU, under ASan + UBSan.
 
 `csrc/png_host.cc` (the chunk walk) and the ONE-LANE instantiation of `csrc/png_device.h` (bit reader, table construction, symbol
 decode, every validation decision, Adler-32, unfilter, colour) are built by g++ into one stand-alone program with its own
@@ -10,49 +10,24 @@ the outcome agrees with zlib).  Robustness against bad streams is proven HERE; t
 NOT covered by this program: what only the 64-lane form does -- the 64-wide literal and match stores, the ballot ranks of the
 table construction, the lane exchange of the unfilter, the gather kernel's copies.  The GPU tests (byte-exact cases, guard bands
 around data, descriptors, workspace and output) cover that code."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import png_cases as pc
 import png_ref as ref
-from conftest import REPO
 from poserisk_release_amd import png
-
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 
 
 @pytest.fixture(scope="module")
 def each(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/png_host.cc and csrc/png_device.h"
     d = tmp_path_factory.mktemp("png_native")
-    exe = str(d / "png_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-I", CSRC, "-o", exe, os.path.join(NATIVE, "png_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "png_native", "png_native.cc")
 
     def run(files, bgr=0):
         """-> per file dict(parse_status, status, and for an accepted one frame, idat, pixels)"""
-        off = np.cumsum([0] + [len(s) for s in files]).astype(np.int64)
-        with open(d / "pack.bin", "wb") as f:
-            f.write(np.int64(len(files)).tobytes() + off.tobytes() + b"".join(files))
-        r = subprocess.run([exe, "each", str(d / "pack.bin"), str(d / "out.bin"), str(bgr)], capture_output=True, text=True,
-                           timeout=1200, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
-        raw, pos, out = np.fromfile(d / "out.bin", np.uint8), 0, []
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        exe.run("each", host_build.pack_streams(d / "pack.bin", files), d / "out.bin", bgr)
+        take, out = host_build.taker(d / "out.bin"), []
         for _ in files:
             head = take(np.int32, 8)
             rec = dict(parse_status=int(head[0]), status=int(head[5]))
@@ -61,7 +36,7 @@ def each(tmp_path_factory):
                 rec["idat"] = take(png.IDAT_DTYPE, int(head[1]))
                 rec["pixels"] = take(np.uint8, int(head[3]) * int(head[4]) * 3).reshape(int(head[3]), int(head[4]), 3)
             out.append(rec)
-        assert pos == raw.size
+        take.done()
         return out
     return run
 

@@ -1,6 +1,6 @@
-"""The compositor's kernel source on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The compositor's kernel source on the CPU, under ASan + UBSan.
 
-`poserisk_release_amd/csrc/compose.hip` is compiled unchanged for the host against `tests/native/compose_host_shim.h` (a
+`poserisk_release_amd/csrc/compose.hip` is compiled unchanged for the host against `tests/native/host_shim.h` (a
 workgroup = 256 threads and a barrier, workgroups one after the other) and run on exact-size heap buffers: its index
 arithmetic, its u32 sums, the rounded division and every address it forms are checked against the numpy restatement of the
 contract (tests/video_ref.py), byte for byte, without a GPU.  It is a permanent part of the CPU suite, like
@@ -8,35 +8,20 @@ tests/test_host_plan_native.py: the machines that run `-m "not gpu"` have no oth
 no GPU run checks addresses against exact-size buffers.  The price is that compose.hip keeps to what the shim defines
 (threadIdx / blockIdx, __syncthreads, atomicOr, __uint2float_rn, uint4, one dynamic LDS block); a new intrinsic there needs a
 line in the shim.  What this cannot show is anything about the GPU build itself -- tests/test_video_gpu.py does that."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import video_ref as vr
-from conftest import REPO
 from poserisk_release_amd import video
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 BOX_RGB = (17, 250, 99)
 
 
 @pytest.fixture(scope="module")
 def compose_host(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/compose.hip"
     d = tmp_path_factory.mktemp("compose_host")
-    shutil.copy(os.path.join(CSRC, "compose.hip"), d / "compose.hip")
-    shutil.copy(os.path.join(NATIVE, "compose_host_shim.h"), d / "common.h")       # what compose.hip includes
-    shutil.copy(os.path.join(NATIVE, "compose_host.cc"), d / "compose_host.cc")
-    exe = str(d / "compose_host")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-pthread", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "compose_host.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = host_build.build(d, "compose_host", "compose_host.cc", stage=("compose.hip",), shim=True, threads=True)
 
     def run(case, shift):
         a = case["atlas"]
@@ -50,10 +35,7 @@ def compose_host(tmp_path_factory):
         with open(d / "case.bin", "wb") as f:
             for arr in (h, case["frames"], case["src_idx"], case["box"], case["lines"], case["text"], cov):
                 f.write(np.ascontiguousarray(arr).tobytes())
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-        r = subprocess.run([exe, str(d / "case.bin"), str(d / "out.bin"), str(shift)], capture_output=True, text=True, timeout=600,
-                           env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-6000:]
+        exe.run(d / "case.bin", d / "out.bin", shift)
         shape = (N, case["dst_h"], case["dst_w"] + case["panel_w"], 3)
         raw = np.fromfile(d / "out.bin", np.uint8)
         n = int(np.prod(shape))

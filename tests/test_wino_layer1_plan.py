@@ -5,13 +5,9 @@ Pinned: a routed conv2 at 56x56 executes 14 tile rows x 16 B columns (14 tiles +
 64 x 64 multiply-adds per frame (+ conv3's 56 x 56 x 256 x 64 where it rides behind); an unrouted one its direct count
 56 x 56 x 64 x 576.  POSERISK_WINO_LAYER1 routes by BLOCK (1 = layer1.0 only, also when conv3 is not fused), never by what
 happens to be a launch of its own."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import REPO
+import host_build
 from poserisk_release_amd import synth, weights
 
 WINO = 224 * 36 * 64 * 64
@@ -21,24 +17,16 @@ CONV3 = 56 * 56 * 256 * 64
 
 @pytest.fixture(scope="module")
 def plan_exe(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("no g++")
     d = tmp_path_factory.mktemp("wino_layer1_plan")
-    exe = str(d / "wino_layer1_plan")
-    r = subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-o", exe, os.path.join(REPO, "tests", "native", "wino_layer1_plan.cc"),
-                        os.path.join(REPO, "poserisk_release_amd", "csrc", "host_plan.cc")], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
+    exe = host_build.build(d, "wino_layer1_plan", "wino_layer1_plan.cc", sources=("host_plan.cc",), strict=True, sanitize=False,
+                           without_compiler="skip")
     weights.flatten_state_dict(synth.hmr_state_dict(seed=1)).tofile(str(d / "blob.f32"))
     return exe, str(d / "blob.f32")
 
 
 def _plan(plan_exe, form=-1, **env):
     exe, blob = plan_exe
-    e = {k: v for k, v in os.environ.items() if not k.startswith("POSERISK_")}
-    e.update(env)
-    r = subprocess.run([exe, blob, str(form)], capture_output=True, text=True, timeout=300, env=e)
-    assert r.returncode == 0, r.stderr[-2000:]
+    r = exe.run(blob, form, env=env)          # the child's only POSERISK_* switches are the ones given here
     lines = r.stdout.strip().splitlines()
     convs = [tuple(int(v) for v in l.split()) for l in lines[:-1]]      # (layer, routed, N3, executed MACs)
     return convs, tuple(int(v) for v in lines[-1].split()[1:])

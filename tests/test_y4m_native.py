@@ -1,46 +1,28 @@
-"""The YUV4MPEG2 reader's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The YUV4MPEG2 reader's two halves on the CPU, under ASan + UBSan.
 
 `csrc/y4m_host.cc` (header, FRAME index, matrix integers) and `csrc/yuv.hip` (the kernel, compiled unchanged for the host
-against tests/native/jpeg_host_shim.h: a launch = nested loops over workgroups and threads) are built by g++ into one stand-alone
+against tests/native/host_shim.h: a launch = nested loops over workgroups and threads) are built by g++ into one stand-alone
 driver, tests/native/y4m_native.cc, which runs every call in exact-size heap blocks.  Checked here, without a GPU: every output
 byte against tests/yuv_ref.py (and tests/resize_ref.py for the fused downscale) for every chroma layout, both matrices and
 ranges, bgr, seven sizes, frame payloads at all four byte alignments and the output starting at every alignment."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import resize_ref as rr
 import y4m_cases as yc
 import yuv_ref
-from conftest import REPO
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 MATRIX = {"601": 0, "709": 1}
 
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/y4m_host.cc and csrc/yuv.hip"
     d = tmp_path_factory.mktemp("y4m_native")
-    for src, dst in ((os.path.join(CSRC, "yuv.hip"), "yuv.hip"), (os.path.join(CSRC, "y4m_host.cc"), "y4m_host.cc"),
-                     (os.path.join(CSRC, "resize_host.cc"), "resize_host.cc"), (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"),
-                     (os.path.join(NATIVE, "y4m_native.cc"), "y4m_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "y4m_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "y4m_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "y4m_native", "y4m_native.cc", stage=("yuv.hip", "y4m_host.cc", "resize_host.cc"), shim=True)
 
     def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-6000:])
+        r = exe.run(*args)
         return r.stdout, r.stderr
 
     def frames(data, matrix="601", full_range=None, bgr=False, size=None):
@@ -50,19 +32,13 @@ def native(tmp_path_factory):
             f.write(np.array([MATRIX[matrix], -1 if full_range is None else int(full_range), int(bgr), h, w, len(data)], np.int32).tobytes()
                     + data)
         run("frames", d / "in.bin", d / "out.bin")
-        raw, pos = np.fromfile(d / "out.bin", np.uint8), 0
-
-        def take(dtype, n):
-            nonlocal pos
-            a = raw[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-            pos += a.nbytes
-            return a
+        take = host_build.taker(d / "out.bin")
         names = ("F", "H", "W", "chroma", "full_range", "fps_num", "fps_den", "header_bytes", "h", "w", "mode")
         head = dict(zip(names, take(np.int32, 11).tolist()))
         plan = tuple(take(np.int32, 6).tolist())
         offsets = take(np.int64, head["F"]).tolist()
         outs = [take(np.uint8, head["F"] * head["h"] * head["w"] * 3).reshape(head["F"], head["h"], head["w"], 3) for _ in range(4)]
-        assert pos == raw.size
+        take.done()
         return head, plan, offsets, outs
     return run, frames
 

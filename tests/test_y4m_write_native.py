@@ -1,23 +1,17 @@
-"""The YUV4MPEG2 writer's two halves on the CPU, under AddressSanitizer + UndefinedBehaviorSanitizer.
+"""The YUV4MPEG2 writer's two halves on the CPU, under ASan + UBSan.
 
 `csrc/y4m_host.cc` (the forward matrix's integers, and the FRAME index that reads the result back) and `csrc/yuv_enc.hip` (the
-kernel, compiled unchanged for the host against tests/native/jpeg_host_shim.h: a launch = nested loops over workgroups and
+kernel, compiled unchanged for the host against tests/native/host_shim.h: a launch = nested loops over workgroups and
 threads) are built by g++ into one stand-alone driver, tests/native/yuv_enc_native.cc, which runs every call in exact-size heap
 blocks.  Checked here, without a GPU: every output byte against tests/yuv_enc_ref.py for every chroma layout, six sizes, three
 frames a call (so frames begin at different alignments), both matrices and ranges, bgr, padding 0 and 1 on each axis, and src and
 dst starting at each of the four byte alignments."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import yuv_enc_ref as er
-from conftest import REPO
 
-CSRC = os.path.join(REPO, "poserisk_release_amd", "csrc")
-NATIVE = os.path.join(REPO, "tests", "native")
 MATRIX = {"601": 0, "709": 1}
 SIZES = ((1, 1), (2, 2), (3, 3), (7, 5), (17, 13), (64, 2))            # (W, H)
 F = 3
@@ -25,23 +19,11 @@ F = 3
 
 @pytest.fixture(scope="module")
 def native(tmp_path_factory):
-    gxx = shutil.which("g++")
-    assert gxx is not None, "g++ is needed to build the host form of csrc/y4m_host.cc and csrc/yuv_enc.hip"
     d = tmp_path_factory.mktemp("yuv_enc_native")
-    for src, dst in ((os.path.join(CSRC, "yuv_enc.hip"), "yuv_enc.hip"), (os.path.join(CSRC, "y4m_host.cc"), "y4m_host.cc"),
-                     (os.path.join(NATIVE, "jpeg_host_shim.h"), "common.h"),
-                     (os.path.join(NATIVE, "yuv_enc_native.cc"), "yuv_enc_native.cc")):
-        shutil.copy(src, d / dst)
-    exe = str(d / "yuv_enc_native")
-    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           "-Wno-unknown-pragmas", "-x", "c++", "-I", str(d), "-I", CSRC, "-o", exe, str(d / "yuv_enc_native.cc")]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-4000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = host_build.build(d, "yuv_enc_native", "yuv_enc_native.cc", stage=("yuv_enc.hip", "y4m_host.cc"), shim=True)
 
     def run(*args):
-        r = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0 and "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-6000:])
+        r = exe.run(*args)
         return r.stdout, r.stderr
 
     def encode(calls):
