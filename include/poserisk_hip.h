@@ -301,9 +301,19 @@ int pr_stem_pool_nhwc(int device, const void* x_dev, const float* w_host, const 
  * like demo_dataset.py:59), bboxes_dev f32[N,4] (cx,cy,w,h) one per crop, frame_idx_dev int32[N] or NULL
  * (crop n comes from frame n), scale = cfg.DATASET.bbox_scale (1.2) -> crops_dev f32[N,3,224,224] in [0,1].
  * OpenCV's fixed-point bilinear warp is reproduced (integer weights, round-half-even), so crops are bit-exact
- * against the restated algorithm.  A frame index outside [0, F) never becomes an out-of-range read: that crop
- * is zero-filled and status_dev[n] (int32[N], may be NULL) is set to 1 (0 otherwise); the reference would raise
- * from cv2.imread on the missing file. */
+ * against the restated algorithm (oracle/crop_ref.py): every double operation of the affine arithmetic -- control points,
+ * forward and inverse matrix, adelta / bdelta, the per-row X0 / Y0 -- is rounded on its own, never contracted into a fused
+ * multiply-add.  `scale` is read as the shortest decimal that rounds to the float given (1.2f means the reference's double 1.2).
+ * status_dev[n] (int32[N], may be NULL) is 0 for a crop that was cut, else a set of bits; a crop with a bit set is
+ * zero-filled, with or without a status pointer:
+ *   bit 0 (1)  the frame index lies outside [0, F): never an out-of-range read (the reference would raise from cv2.imread
+ *              on the missing file)
+ *   bit 1 (2)  the box has no defined crop.  With the float32 control values the reference forms, sx0 = cx, sy0 = cy,
+ *              sx2 = f32(cx + f32(w scale / 2)), sy1 = f32(cy + f32(h scale / 2)): one of them is not finite (a NaN or
+ *              infinite field), or exceeds 2^18 in magnitude, or sx2 == sx0 or sy1 == sy0 (w or h zero, or so small that
+ *              the half-extent is lost in the centre's rounding: the forward matrix would divide by zero).
+ * Inside that domain every fixed-point integer of the warp fits in int32, so the int64 arithmetic here is OpenCV's
+ * saturate_cast<int> arithmetic; a negative w or h is inside it and gives the mirrored crop. */
 int pr_crop_frames(const uint8_t* frames_dev, int F, int H, int W, int bgr, const int32_t* frame_idx_dev,
                    const float* bboxes_dev, int N, float scale, float* crops_dev, int32_t* status_dev,
                    void* stream);

@@ -68,12 +68,9 @@ def bilinear_table():
 _TABLE = None
 
 
-def warp_affine_u8(img, M_fwd, out_hw=(224, 224)):
-    """cv2.warpAffine(img u8[H,W,C], M, (W',H'), INTER_LINEAR, BORDER_CONSTANT=0) restated."""
-    global _TABLE
-    if _TABLE is None:
-        _TABLE = bilinear_table().astype(np.int64)
-    H, W, C = img.shape
+def warp_integers(M_fwd, out_hw=(224, 224)):
+    """The fixed-point integers warpAffine forms before it touches a pixel: (X0[oh], Y0[oh], adelta[ow], bdelta[ow]),
+    int64, X0 / Y0 with the rounding offset AB_SCALE / TAB / 2 already in them."""
     Mi = invert_affine(M_fwd).reshape(-1)
     oh, ow = out_hw
     xs = np.arange(ow, dtype=np.float64)
@@ -83,6 +80,16 @@ def warp_affine_u8(img, M_fwd, out_hw=(224, 224)):
     rd = AB_SCALE // TAB // 2
     X0 = np.rint((Mi[1] * ys + Mi[2]) * AB_SCALE).astype(np.int64) + rd
     Y0 = np.rint((Mi[4] * ys + Mi[5]) * AB_SCALE).astype(np.int64) + rd
+    return X0, Y0, adelta, bdelta
+
+
+def warp_from_integers(img, X0, Y0, adelta, bdelta):
+    """The pixel half of warpAffine: img u8[H,W,C] sampled at the fixed-point positions of `warp_integers`."""
+    global _TABLE
+    if _TABLE is None:
+        _TABLE = bilinear_table().astype(np.int64)
+    H, W, C = img.shape
+    X0, Y0, adelta, bdelta = (np.asarray(v, np.int64) for v in (X0, Y0, adelta, bdelta))
     X = (X0[:, None] + adelta[None, :]) >> (AB_BITS - INTER_BITS)
     Y = (Y0[:, None] + bdelta[None, :]) >> (AB_BITS - INTER_BITS)
     sx = np.clip(X >> INTER_BITS, -32768, 32767)
@@ -101,7 +108,43 @@ def warp_affine_u8(img, M_fwd, out_hw=(224, 224)):
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
-def crop_to_tensor(img_rgb_u8, bbox, scale=1.2, crop=224):
-    """get_single_image_crop_demo + ToTensor: u8[H,W,3] RGB, bbox (cx,cy,w,h) -> f32[3,crop,crop] in [0,1]."""
-    patch = warp_affine_u8(img_rgb_u8, affine_from_bbox(bbox, scale, crop), (crop, crop))
+def warp_affine_u8(img, M_fwd, out_hw=(224, 224)):
+    """cv2.warpAffine(img u8[H,W,C], M, (W',H'), INTER_LINEAR, BORDER_CONSTANT=0) restated."""
+    return warp_from_integers(img, *warp_integers(M_fwd, out_hw))
+
+
+def to_tensor(patch):
+    """ToTensor (_img_utils.py:259-266): u8[H,W,3] -> f32[3,H,W] in [0,1]."""
     return (patch.astype(np.float32) / np.float32(255)).transpose(2, 0, 1).copy()
+
+
+BOX_LIMIT = float(1 << 18)
+
+
+def control_points(bbox, scale=1.2):
+    """(sx0, sy0, sx2, sy1): the float32 control values of `affine_from_bbox`, as Python floats."""
+    cx, cy, w, h = [float(v) for v in bbox]
+    f32 = np.float32
+    with np.errstate(over="ignore", invalid="ignore"):
+        down = f32((h * scale) * 0.5)
+        right = f32((w * scale) * 0.5)
+        return float(f32(cx)), float(f32(cy)), float(f32(cx + float(right))), float(f32(cy + float(down)))
+
+
+def box_status(bbox, scale=1.2):
+    """The crop's status bits that depend on the box alone: 2 when the box has no defined crop, else 0.  A box is refused
+    when a control value is non-finite or larger than 2^18 in magnitude, or when the half-extent is absorbed by the centre's
+    rounding (sx2 == sx0 or sy1 == sy0: the forward matrix would divide by zero).  Inside that domain every fixed-point
+    integer of the warp fits in int32, so the int64 arithmetic here is OpenCV's `saturate_cast<int>` arithmetic."""
+    sx0, sy0, sx2, sy1 = control_points(bbox, scale)
+    ok = all(np.isfinite(v) and abs(v) <= BOX_LIMIT for v in (sx0, sy0, sx2, sy1)) and sx2 != sx0 and sy1 != sy0
+    return 0 if ok else 2
+
+
+def crop_to_tensor(img_rgb_u8, bbox, scale=1.2, crop=224):
+    """get_single_image_crop_demo + ToTensor: u8[H,W,3] RGB, bbox (cx,cy,w,h) -> f32[3,crop,crop] in [0,1]; zeros for a
+    box that `box_status` refuses."""
+    if box_status(bbox, scale):
+        return np.zeros((3, crop, crop), np.float32)
+    patch = warp_affine_u8(img_rgb_u8, affine_from_bbox(bbox, scale, crop), (crop, crop))
+    return to_tensor(patch)

@@ -6,6 +6,8 @@
 
 #include <cfloat>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 namespace pr {
 namespace {
@@ -236,7 +238,12 @@ __global__ void bf16_to_f32_kernel(const unsigned short* __restrict__ x, float* 
 constexpr int kCropRows = 8;
 __global__ void crop_frames_kernel(const unsigned char* __restrict__ frames, int F, int H, int W, int bgr,
                                    const int* __restrict__ frame_idx, const float* __restrict__ bboxes, int N,
-                                   float scale, float* __restrict__ crops, int* __restrict__ status) {
+                                   double scale, float* __restrict__ crops, int* __restrict__ status) {
+  // OpenCV (and oracle/crop_ref.py) round every double operation of the affine arithmetic on its own; contracted into fused
+  // multiply-adds, `112 - a sx0`, `112 - d sy0` and `M4 y + M5` differ by an ulp, which moves a crop (or its centre row) by 1/32
+  // pixel wherever rint(v * 1024) + 16 sits next to a multiple of 32 (crop front-end).  The pixel arithmetic below
+  // is integer.
+#pragma clang fp contract(off)
   constexpr int S = 224, kPer = S * S / kCropRows;
   static_assert(S % kCropRows == 0, "rows per thread");
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -247,21 +254,27 @@ __global__ void crop_frames_kernel(const unsigned char* __restrict__ frames, int
   // out-of-range read: the crop is zero-filled and flagged.
   const int fi = frame_idx ? frame_idx[n] : n;
   const bool bad_frame = (unsigned)fi >= (unsigned)F;
-  if (status && q == 0) status[n] = bad_frame ? 1 : 0;
-  if (bad_frame) {
+  const float* bb = bboxes + (long)n * 4;
+  // gen_trans_from_patch_cv (rot = 0): control points are stored as float32
+  const double cx = (double)bb[0], cy = (double)bb[1];
+  const float down = (float)(((double)bb[3] * scale) * 0.5);
+  const float right = (float)(((double)bb[2] * scale) * 0.5);
+  const double sx0 = (double)(float)cx, sy0 = (double)(float)cy;
+  const double sy1 = (double)(float)(cy + (double)down), sx2 = (double)(float)(cx + (double)right);
+  // A box without a defined crop (a tracking sidecar can hold anything): a control value that is not finite or lies beyond
+  // 2^18 (inside it every fixed-point integer below fits OpenCV's int32), or a half-extent lost in the centre's rounding (the
+  // forward matrix would divide by zero).  Zero-filled and flagged like a bad frame index; both bits can be set.
+  constexpr double kBoxLimit = 262144.0;
+  const bool bad_box = !(fabs(sx0) <= kBoxLimit && fabs(sy0) <= kBoxLimit && fabs(sx2) <= kBoxLimit && fabs(sy1) <= kBoxLimit) ||
+                       sx2 == sx0 || sy1 == sy0;
+  if (status && q == 0) status[n] = (bad_frame ? 1 : 0) | (bad_box ? 2 : 0);
+  if (bad_frame || bad_box) {
 #pragma unroll
     for (int k = 0; k < kCropRows; ++k)
 #pragma unroll
       for (int c = 0; c < 3; ++c) crops[((long)n * 3 + c) * S * S + (y0 + k * (S / kCropRows)) * S + x] = 0.f;
     return;
   }
-  const float* bb = bboxes + (long)n * 4;
-  // gen_trans_from_patch_cv (rot = 0): control points are stored as float32
-  const double cx = (double)bb[0], cy = (double)bb[1];
-  const float down = (float)(((double)bb[3] * (double)scale) * 0.5);
-  const float right = (float)(((double)bb[2] * (double)scale) * 0.5);
-  const double sx0 = (double)(float)cx, sy0 = (double)(float)cy;
-  const double sy1 = (double)(float)(cy + (double)down), sx2 = (double)(float)(cx + (double)right);
   const double a = 112.0 / (sx2 - sx0), d = 112.0 / (sy1 - sy0);
   double M[6] = {a, 0.0, 112.0 - a * sx0, 0.0, d, 112.0 - d * sy0};
   // cv::warpAffine inverts the forward matrix in place
@@ -936,12 +949,25 @@ int launch_bf16_to_f32(const void* x, float* y, long n, hipStream_t s) {
   hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const unsigned short*)x, y, n);
   return check_launch("bf16_to_f32_kernel");
 }
+// The C entry carries the box scale as a float; the reference multiplies by the Python float of its config (1.2, a double).
+// The float is read as the shortest decimal that rounds to it -- 1.2f is 1.2 again, as is every scale written with up to six
+// significant digits -- because the two widths round the half-extent differently: the last side absorbed by cx = 300 is not
+// the same float32 under 1.2f, and 37 of test_hip_parity.py's 120 seeded boxes get a control point one ulp away.
+static double scale_as_written(float scale) {
+  char text[40];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(text, sizeof text, "%.*e", digits - 1, (double)scale);
+    const double v = strtod(text, nullptr);
+    if ((float)v == scale) return v;
+  }
+  return (double)scale;
+}
 int launch_crop_frames(const unsigned char* frames, int F, int H, int W, int bgr, const int* frame_idx,
                        const float* bboxes, int N, float scale, float* crops, int* status, hipStream_t s) {
   const long n = (long)N * 224 * 224 / kCropRows;       // a thread writes kCropRows pixels of one column
   if (n == 0) return PR_OK;
   hipLaunchKernelGGL(crop_frames_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, frames, F, H, W, bgr,
-                     frame_idx, bboxes, N, scale, crops, status);
+                     frame_idx, bboxes, N, scale_as_written(scale), crops, status);
   return check_launch("crop_frames_kernel");
 }
 int launch_state_init(const float* init157, float* state, int B, hipStream_t s) {

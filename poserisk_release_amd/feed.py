@@ -23,8 +23,10 @@ import torch
 from . import _lib
 from .pipeline import FramePipeline
 
-# status: the reference's two rotation asserts as bits (pr_pose_to_euler); crop_status: 1 = the frame index named no decoded
-# frame (pr_crop_frames zero-fills that crop; the reference would raise from cv2.imread)
+# status: the reference's two rotation asserts as bits (pr_pose_to_euler); crop_status, bits: 1 = the frame index named no
+# decoded frame (the reference would raise from cv2.imread), 2 = the box has no defined crop (a NaN or infinite field, a control
+# value beyond 2^18, w or h zero or lost in the centre's rounding; include/poserisk_hip.h f-1).  pr_crop_frames zero-fills a
+# crop with either bit set, and the row's results are those of a blank crop.
 RESULT_KEYS = ("euler", "joint_cam", "axis_angle", "reba", "rula", "status", "crop_status")
 
 
