@@ -591,6 +591,68 @@ typedef struct pr_compose_people_args {
 int pr_compose_people(const pr_compose_people_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* r4  people mesh overlay: the fitted meshes of every tracked person of a frame drawn   */
+/*     over it, depth-tested against each other, one call a batch.  No counterpart in    */
+/*     the reference, which draws one person; no ABI bump: functions and a struct were   */
+/*     added, no signature changed                                                        */
+/* ------------------------------------------------------------------------------------ */
+/* People raster contract.  Integer-exact, so that tests/raster_people_ref.py (numpy, on tests/raster_ref.py) reproduces
+ * face_id bit for bit.  Projection, fixed point, coverage, shading and blend: r1's, word for word, per mesh.  What differs:
+ *
+ * Canvases.  N meshes, M canvases.  canvas int32[N] names the canvas mesh n is drawn on, src_idx int32[M] the source frame of
+ *   canvas m (NULL: canvas m over frame m, M <= n_frames).  A canvas may hold any number of meshes; one that holds none is a
+ *   copy of its frame.
+ * Depth between meshes.  zf = rint(4096 Z) + 2^20 + z_step[n], z_step int32[N] (NULL: all zero), 0 <= z_step <= 2^24
+ *   (PR_RENDER_Z_STEP_MAX = 4096 m), added AFTER the rounding.  The weights of a covered sample sum to A, so shifting all three
+ *   zf of a face by an integer k shifts (w0 zf_a + w1 zf_b + w2 zf_c) / A = floor(.) by exactly k.  Hence: the same extra shift
+ *   on every mesh of a canvas leaves that canvas byte for byte what it was, and a canvas with one mesh is pr_render_overlay's
+ *   image whatever that mesh's z_step.  (A float offset added before rint would have neither property: ties break half to
+ *   even.)  Bound: |xf|, |yf| < 2^17, so A and every wk are below 2^37; zf < 2^20 + 2^20 + 2^24 < 2^25; the depth numerator
+ *   is at most A max(zf) < 2^62, inside int64, and depth < 2^25 fits the key's upper half.
+ * Visibility.  One key buffer u64[M,H,W].  key = (uint64)depth << 32 | (n F + f), N F < 2^31; the smallest key wins: equal
+ *   depths go to the lower mesh index, then to the lower face.  The bytes of a canvas depend only on its own meshes and their
+ *   relative order, not on what else is in the batch.
+ *
+ * Arguments (device pointers): verts, faces, cam, bboxes, scale, frames, bgr, face_part, part_rgb u8[N,P,3], P, alpha as in
+ *   r1, and canvas, src_idx, z_step as above.
+ *   out u8[M,H,W,3]; face_id int32[M,H,W] or NULL (n F + f of the visible face, -1 where none); vert_fx int32[N,V,4] or NULL
+ *   (zf includes z_step); status int32[N] or NULL:
+ *     bit 0  the mesh's canvas has a source index outside [0, n_frames) (nothing of it is drawn)
+ *     bit 1  an invalid vertex                        bit 2  a face index outside [0, V) (that face is skipped)
+ *     bit 3  canvas[n] outside [0, M)                 bit 4  z_step[n] outside [0, 2^24]
+ *   A mesh with bit 3 or bit 4 set draws nothing: its vert_fx rows are all zero and its bits 0-2 stay clear.
+ *   canvas_status int32[M] or NULL: bit 0  src_idx[m] outside [0, n_frames): that canvas is zero-filled, its face_id -1 (as r1).
+ * workspace: device memory of at least pr_render_people_workspace_bytes(N, M, V, F, H, W) bytes (the key buffer, sized by M;
+ *   projected vertices, face colours and the big-face queue, sized by N), owned by the caller.  Argument errors return
+ *   PR_ERR_INVALID before any device work.  M = 0 returns PR_OK; N = 0 with M > 0 is valid and copies the frames (the mesh
+ *   pointers, V, F and P are then not looked at).  Asynchronous on `stream`, no allocation, no synchronisation.  Launches:
+ *   clear, vertex, face, big face, resolve (N = 0: clear and resolve). */
+#define PR_RENDER_Z_STEP_MAX (1 << 24)
+typedef struct pr_render_people_args {
+  const float* verts;        /* f32[N,V,3] */
+  const int32_t* faces;      /* int32[F,3] */
+  const float* cam;          /* f32[N,3] */
+  const float* bboxes;       /* f32[N,4] */
+  const uint8_t* frames;     /* u8[n_frames,H,W,3] */
+  const int32_t* canvas;     /* int32[N] */
+  const int32_t* src_idx;    /* int32[M] or NULL */
+  const int32_t* z_step;     /* int32[N] or NULL */
+  const int32_t* face_part;  /* int32[F] */
+  const uint8_t* part_rgb;   /* u8[N,P,3] */
+  uint8_t* out;              /* u8[M,H,W,3] */
+  int32_t* face_id;          /* int32[M,H,W] or NULL */
+  int32_t* vert_fx;          /* int32[N,V,4] or NULL */
+  int32_t* status;           /* int32[N] or NULL */
+  int32_t* canvas_status;    /* int32[M] or NULL */
+  int N, M, V, F, P;
+  int n_frames, H, W, bgr;
+  float scale, alpha;
+} pr_render_people_args;
+
+size_t pr_render_people_workspace_bytes(int N, int M, int V, int F, int H, int W);
+int pr_render_people(const pr_render_people_args* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* j1  baseline JPEG frames -> u8[F,H,W,3] on the device, bit-exact with libjpeg         */
 /* replaces: cv2.imread in CropDataset.__getitem__ data/demo_dataset.py:58-59 on the      */
 /*           <output>/tmp/%09d.jpg files the front end writes (lib/core/base.py:47-56)    */

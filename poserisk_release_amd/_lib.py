@@ -38,6 +38,14 @@ class RenderArgs(C.Structure):
                [("scale", C.c_float), ("alpha", C.c_float)]
 
 
+class RenderPeopleArgs(C.Structure):
+    """pr_render_people_args (include/poserisk_hip.h, the people mesh overlay)."""
+    _fields_ = [(n, C.c_void_p) for n in ("verts", "faces", "cam", "bboxes", "frames", "canvas", "src_idx", "z_step", "face_part",
+                                           "part_rgb", "out", "face_id", "vert_fx", "status", "canvas_status")] + \
+               [(n, C.c_int) for n in ("N", "M", "V", "F", "P", "n_frames", "H", "W", "bgr")] + \
+               [("scale", C.c_float), ("alpha", C.c_float)]
+
+
 class ComposeArgs(C.Structure):
     """pr_compose_args (include/poserisk_hip.h, the annotated score video)."""
     _fields_ = [(n, C.c_void_p) for n in ("frames", "src_idx", "box", "lines", "text", "atlas", "out", "status")] + \
@@ -175,6 +183,8 @@ SIGNATURES = {
                                C.POINTER(FramesOut), _P]),
     "pr_render_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "pr_render_overlay": (_I, [C.POINTER(RenderArgs), _P, C.c_size_t, _P]),
+    "pr_render_people_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I]),
+    "pr_render_people": (_I, [C.POINTER(RenderPeopleArgs), _P, C.c_size_t, _P]),
     "pr_compose_video": (_I, [C.POINTER(ComposeArgs), _P]),
     "pr_compose_people": (_I, [C.POINTER(ComposePeopleArgs), _P]),
     "pr_jpeg_parse": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P, _P]),

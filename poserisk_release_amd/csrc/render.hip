@@ -10,6 +10,9 @@
 //   big face  a grid-stride loop of workgroups over the queue, threads over the face's box
 //   resolve   one thread per output pixel: key -> face colour, blend with the frame, write out (and face_id)
 // The smallest key wins whatever the order of the atomics, so the result is bit-for-bit deterministic.
+//
+// pr_render_people (header section r4) draws N meshes on M canvases with one key buffer u64[M,H,W], so that the people of a
+// frame are depth-tested against each other; its kernels, below the ones above, share every device function with them.
 #include "common.h"
 
 namespace pr {
@@ -99,21 +102,8 @@ __device__ __forceinline__ unsigned long long sample_key(const Setup& s, int j, 
   return ((unsigned long long)depth << 32) | f;
 }
 
-__global__ void render_clear_kernel(unsigned long long* __restrict__ zbuf, long n_keys, unsigned* __restrict__ queue_count,
-                                    int32_t* __restrict__ status, Geo g) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_keys) zbuf[i] = ~0ull;
-  if (i == 0) *queue_count = 0u;
-  if (status && i < g.N) {
-    int fi;
-    status[i] = crop_frame(g, (int)i, &fi) ? 0 : 1;
-  }
-}
-
-__global__ void render_vertex_kernel(Geo g, int4* __restrict__ vfx, int32_t* __restrict__ status) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)g.N * g.V) return;
-  const int n = (int)(i / g.V);
+// Vertex i = n V + v of mesh n in fixed point (xf, yf, zf + z_step, 1); all zero when it is invalid.
+__device__ __forceinline__ int4 project_vertex(const Geo& g, long i, int n, int z_step) {
   const float* p = g.verts + i * 3;
   const float* cm = g.cam + (long)n * 3;
   const float* bb = g.bboxes + (long)n * 4;
@@ -123,28 +113,14 @@ __global__ void render_vertex_kernel(Geo g, int4* __restrict__ vfx, int32_t* __r
   const double y = (double)bb[1] + s * (Y + ty) * (double)bb[3] * (double)g.scale * 0.5;
   const bool valid = isfinite(x) && isfinite(y) && isfinite(Z) && x > -kGuard && x < (g.W - 1) + kGuard && y > -kGuard &&
                      y < (g.H - 1) + kGuard && fabs(Z) < kZMax;
-  int4 o = make_int4(0, 0, 0, 0);
-  if (valid) o = make_int4(__double2int_rn(kFix * x), __double2int_rn(kFix * y), __double2int_rn(kZFix * Z) + kZBias, 1);
-  else if (status) atomicOr(status + n, 2);
-  vfx[i] = o;
+  if (!valid) return make_int4(0, 0, 0, 0);
+  return make_int4(__double2int_rn(kFix * x), __double2int_rn(kFix * y), __double2int_rn(kZFix * Z) + kZBias + z_step, 1);
 }
 
-__global__ void render_face_kernel(Geo g, const int4* __restrict__ vfx, const int32_t* __restrict__ face_part,
-                                   const uint8_t* __restrict__ part_rgb, int P, int bgr, unsigned* __restrict__ colour,
-                                   unsigned long long* __restrict__ zbuf, unsigned* __restrict__ queue_count,
-                                   unsigned* __restrict__ queue, int32_t* __restrict__ status) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)g.N * g.F) return;
-  const int n = (int)(i / g.F), f = (int)(i - (long)n * g.F);
-  int fi;
-  if (!crop_frame(g, n, &fi)) return;   // zero-filled by the resolve pass
-  Setup s;
-  bool bad_index;
-  if (!face_setup(g, vfx, n, f, s, &bad_index)) {
-    if (bad_index && status) atomicOr(status + n, 4);
-    return;
-  }
-  // flat shading from the float vertices in the face's own order; the light is along the view axis, two-sided
+// Flat shading of face f of mesh n from the float vertices in the face's own order; the light is along the view axis,
+// two-sided.  Returns the colour packed in quarter steps, 10 bits a channel.
+__device__ __forceinline__ unsigned face_colour(const Geo& g, int n, int f, const int32_t* __restrict__ face_part,
+                                                const uint8_t* __restrict__ part_rgb, int P, int bgr) {
   const long base = (long)n * g.V;
   const float* va = g.verts + (base + g.faces[3 * f]) * 3;
   const float* vb = g.verts + (base + g.faces[3 * f + 1]) * 3;
@@ -164,7 +140,55 @@ __global__ void render_face_kernel(Geo g, const int4* __restrict__ vfx, const in
     const unsigned q = (unsigned)min(__float2int_rn(4.f * c), 1020);
     packed |= q << (10 * k);
   }
-  colour[i] = packed;
+  return packed;
+}
+
+// out = rint((1 - alpha) frame + alpha colour), clamped, for one pixel
+__device__ __forceinline__ void blend_pixel(const uint8_t* __restrict__ src, unsigned packed, float alpha, uint8_t* __restrict__ o) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float c = 0.25f * (float)((packed >> (10 * k)) & 1023u);
+    const int v = __float2int_rn((1.f - alpha) * (float)src[k] + alpha * c);
+    o[k] = (uint8_t)min(max(v, 0), 255);
+  }
+}
+
+__global__ void render_clear_kernel(unsigned long long* __restrict__ zbuf, long n_keys, unsigned* __restrict__ queue_count,
+                                    int32_t* __restrict__ status, Geo g) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_keys) zbuf[i] = ~0ull;
+  if (i == 0) *queue_count = 0u;
+  if (status && i < g.N) {
+    int fi;
+    status[i] = crop_frame(g, (int)i, &fi) ? 0 : 1;
+  }
+}
+
+__global__ void render_vertex_kernel(Geo g, int4* __restrict__ vfx, int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)g.N * g.V) return;
+  const int n = (int)(i / g.V);
+  const int4 o = project_vertex(g, i, n, 0);
+  if (!o.w && status) atomicOr(status + n, 2);
+  vfx[i] = o;
+}
+
+__global__ void render_face_kernel(Geo g, const int4* __restrict__ vfx, const int32_t* __restrict__ face_part,
+                                   const uint8_t* __restrict__ part_rgb, int P, int bgr, unsigned* __restrict__ colour,
+                                   unsigned long long* __restrict__ zbuf, unsigned* __restrict__ queue_count,
+                                   unsigned* __restrict__ queue, int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)g.N * g.F) return;
+  const int n = (int)(i / g.F), f = (int)(i - (long)n * g.F);
+  int fi;
+  if (!crop_frame(g, n, &fi)) return;   // zero-filled by the resolve pass
+  Setup s;
+  bool bad_index;
+  if (!face_setup(g, vfx, n, f, s, &bad_index)) {
+    if (bad_index && status) atomicOr(status + n, 4);
+    return;
+  }
+  colour[i] = face_colour(g, n, f, face_part, part_rgb, P, bgr);
   if ((s.x1 - s.x0 + 1) * (s.y1 - s.y0 + 1) > kSmallBox) {
     queue[atomicAdd(queue_count, 1u)] = (unsigned)i;
     return;
@@ -221,14 +245,144 @@ __global__ void render_resolve_kernel(Geo g, const unsigned long long* __restric
     return;
   }
   const unsigned f = (unsigned)(key & 0xffffffffull);
-  const unsigned packed = colour[(long)n * g.F + f];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float c = 0.25f * (float)((packed >> (10 * k)) & 1023u);
-    const int v = __float2int_rn((1.f - alpha) * (float)src[k] + alpha * c);
-    o[k] = (uint8_t)min(max(v, 0), 255);
-  }
+  blend_pixel(src, colour[(long)n * g.F + f], alpha, o);
   if (face_id) face_id[i] = (int32_t)f;
+}
+
+// ---- r4: the meshes of every person of a frame on one canvas (pr_render_people) ------------------------------------------------
+// The same five passes over N meshes and M canvases.  The key buffer is u64[M,H,W]; a key's low half is n F + f, which is also
+// the face's slot in the colour table and in the big-face queue.  Setup, coverage, depth, shading and blend are the device
+// functions above; Geo's frame_idx is not used (the frame of a mesh is src_idx[canvas[n]]).
+struct People {
+  const int32_t* canvas;
+  const int32_t* src_idx;
+  const int32_t* z_step;
+  int M;
+};
+
+constexpr int kZStepMax = PR_RENDER_Z_STEP_MAX;
+
+__device__ __forceinline__ bool canvas_frame(const Geo& g, const People& p, int m, int* fi) {
+  const int f = p.src_idx ? p.src_idx[m] : m;
+  *fi = f;
+  return (unsigned)f < (unsigned)g.n_frames;
+}
+
+// status bits 0, 3 and 4 of mesh n (0: it is drawn); *m is its canvas when bit 3 is clear, *z its depth step when bit 4 is
+__device__ __forceinline__ int mesh_state(const Geo& g, const People& p, int n, int* m, int* z) {
+  *m = p.canvas[n];
+  *z = p.z_step ? p.z_step[n] : 0;
+  int bits = 0;
+  if ((unsigned)*m >= (unsigned)p.M) bits |= 8;
+  if (*z < 0 || *z > kZStepMax) bits |= 16;
+  int fi;
+  if (!bits && !canvas_frame(g, p, *m, &fi)) bits = 1;
+  return bits;
+}
+
+__global__ void people_clear_kernel(unsigned long long* __restrict__ zbuf, long n_keys, unsigned* __restrict__ queue_count,
+                                    int32_t* __restrict__ status, int32_t* __restrict__ canvas_status, Geo g, People p) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_keys) zbuf[i] = ~0ull;
+  if (i == 0) *queue_count = 0u;
+  if (status && i < g.N) {
+    int m, z;
+    status[i] = mesh_state(g, p, (int)i, &m, &z);
+  }
+  if (canvas_status && i < p.M) {
+    int fi;
+    canvas_status[i] = canvas_frame(g, p, (int)i, &fi) ? 0 : 1;
+  }
+}
+
+__global__ void people_vertex_kernel(Geo g, People p, int4* __restrict__ vfx, int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)g.N * g.V) return;
+  const int n = (int)(i / g.V);
+  int m, zs;
+  if (mesh_state(g, p, n, &m, &zs) & (8 | 16)) {   // draws nothing: no vertex of it is looked at
+    vfx[i] = make_int4(0, 0, 0, 0);
+    return;
+  }
+  const int4 o = project_vertex(g, i, n, zs);
+  if (!o.w && status) atomicOr(status + n, 2);
+  vfx[i] = o;
+}
+
+__global__ void people_face_kernel(Geo g, People p, const int4* __restrict__ vfx, const int32_t* __restrict__ face_part,
+                                   const uint8_t* __restrict__ part_rgb, int P, int bgr, unsigned* __restrict__ colour,
+                                   unsigned long long* __restrict__ zbuf, unsigned* __restrict__ queue_count,
+                                   unsigned* __restrict__ queue, int32_t* __restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)g.N * g.F) return;
+  const int n = (int)(i / g.F), f = (int)(i - (long)n * g.F);
+  int m, zs;
+  if (mesh_state(g, p, n, &m, &zs)) return;   // no canvas, no depth, or a canvas the resolve pass zero-fills
+  Setup s;
+  bool bad_index;
+  if (!face_setup(g, vfx, n, f, s, &bad_index)) {
+    if (bad_index && status) atomicOr(status + n, 4);
+    return;
+  }
+  colour[i] = face_colour(g, n, f, face_part, part_rgb, P, bgr);
+  if ((s.x1 - s.x0 + 1) * (s.y1 - s.y0 + 1) > kSmallBox) {
+    queue[atomicAdd(queue_count, 1u)] = (unsigned)i;
+    return;
+  }
+  unsigned long long* zb = zbuf + (long)m * g.H * g.W;
+  for (int y = s.y0; y <= s.y1; ++y)
+    for (int x = s.x0; x <= s.x1; ++x) {
+      const unsigned long long key = sample_key(s, x, y, (unsigned)i);
+      if (key != ~0ull) atomicMin(zb + (long)y * g.W + x, key);
+    }
+}
+
+__global__ void __launch_bounds__(kBigThreads) people_bigface_kernel(Geo g, People p, const int4* __restrict__ vfx,
+                                                                     unsigned long long* __restrict__ zbuf,
+                                                                     const unsigned* __restrict__ queue_count,
+                                                                     const unsigned* __restrict__ queue) {
+  const unsigned count = *queue_count;
+  for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
+    const unsigned i = queue[q];
+    const int n = (int)(i / (unsigned)g.F), f = (int)(i - (unsigned)n * (unsigned)g.F);
+    Setup s;
+    bool bad_index;
+    if (!face_setup(g, vfx, n, f, s, &bad_index)) continue;   // never: the face pass queued it after the same setup
+    const int bw = s.x1 - s.x0 + 1, bh = s.y1 - s.y0 + 1;
+    unsigned long long* zb = zbuf + (long)p.canvas[n] * g.H * g.W;   // in [0, M): the face pass checked it
+    for (int k = threadIdx.x; k < bw * bh; k += kBigThreads) {
+      const int y = s.y0 + k / bw, x = s.x0 + k % bw;
+      const unsigned long long key = sample_key(s, x, y, i);
+      if (key != ~0ull) atomicMin(zb + (long)y * g.W + x, key);
+    }
+  }
+}
+
+__global__ void people_resolve_kernel(Geo g, People p, const unsigned long long* __restrict__ zbuf,
+                                      const unsigned* __restrict__ colour, const uint8_t* __restrict__ frames, float alpha,
+                                      uint8_t* __restrict__ out, int32_t* __restrict__ face_id) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long hw = (long)g.H * g.W;
+  if (i >= (long)p.M * hw) return;
+  const int m = (int)(i / hw);
+  const long pix = i - (long)m * hw;
+  uint8_t* o = out + i * 3;
+  int fi;
+  if (!canvas_frame(g, p, m, &fi)) {
+    o[0] = 0; o[1] = 0; o[2] = 0;
+    if (face_id) face_id[i] = -1;
+    return;
+  }
+  const uint8_t* src = frames + ((long)fi * hw + pix) * 3;
+  const unsigned long long key = zbuf[i];
+  if (key == ~0ull) {
+    o[0] = src[0]; o[1] = src[1]; o[2] = src[2];
+    if (face_id) face_id[i] = -1;
+    return;
+  }
+  const unsigned id = (unsigned)(key & 0xffffffffull);   // n F + f
+  blend_pixel(src, colour[id], alpha, o);
+  if (face_id) face_id[i] = (int32_t)id;
 }
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -237,10 +391,11 @@ struct Layout {
   size_t zbuf, vfx, colour, queue, total;
 };
 
-inline Layout layout(int N, int V, int F, int H, int W) {
+// n_canvases key planes (pr_render_overlay: one per crop), the rest sized by the N meshes
+inline Layout layout(int N, int n_canvases, int V, int F, int H, int W) {
   Layout l;
   l.zbuf = 0;
-  l.vfx = l.zbuf + align256((size_t)N * H * W * 8);
+  l.vfx = l.zbuf + align256((size_t)n_canvases * H * W * 8);
   l.colour = l.vfx + align256((size_t)N * V * 16);
   l.queue = l.colour + align256((size_t)N * F * 4);
   l.total = l.queue + align256(16 + (size_t)N * F * 4);   // counter, then at most N * F entries
@@ -256,7 +411,7 @@ extern "C" {
 
 size_t pr_render_workspace_bytes(int N, int V, int F, int H, int W) {
   if (N <= 0 || V <= 0 || F <= 0 || H <= 0 || W <= 0) return 0;
-  return pr::layout(N, V, F, H, W).total;
+  return pr::layout(N, N, V, F, H, W).total;
 }
 
 int pr_render_overlay(const pr_render_args* a, void* workspace, size_t workspace_bytes, void* stream) {
@@ -277,7 +432,7 @@ int pr_render_overlay(const pr_render_args* a, void* workspace, size_t workspace
   PR_REQUIRE(a->alpha >= 0.f && a->alpha <= 1.f, "pr_render_overlay: alpha %g outside [0, 1]", (double)a->alpha);
   PR_REQUIRE(a->frame_idx || a->N <= a->n_frames, "pr_render_overlay: %d crops for %d frames without a frame index", a->N,
              a->n_frames);
-  const Layout l = layout(a->N, a->V, a->F, a->H, a->W);
+  const Layout l = layout(a->N, a->N, a->V, a->F, a->H, a->W);
   PR_REQUIRE(workspace_bytes >= l.total, "pr_render_overlay: workspace of %zu bytes, %zu needed (pr_render_workspace_bytes)",
              workspace_bytes, l.total);
   hipStream_t s = (hipStream_t)stream;
@@ -303,6 +458,65 @@ int pr_render_overlay(const pr_render_args* a, void* workspace, size_t workspace
   hipLaunchKernelGGL(render_resolve_kernel, dim3(blocks_for(n_keys, 256)), dim3(256), 0, s, g, (const unsigned long long*)zbuf,
                      (const unsigned*)colour, a->frames, a->alpha, a->out, a->face_id);
   return check_launch("render_resolve_kernel");
+}
+
+size_t pr_render_people_workspace_bytes(int N, int M, int V, int F, int H, int W) {
+  if (N < 0 || M <= 0 || H <= 0 || W <= 0 || (N > 0 && (V <= 0 || F <= 0))) return 0;
+  return N ? pr::layout(N, M, V, F, H, W).total : pr::layout(0, M, 0, 0, H, W).total;
+}
+
+int pr_render_people(const pr_render_people_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace pr;
+  PR_REQUIRE(a, "pr_render_people: null argument struct");
+  PR_REQUIRE(a->N >= 0 && a->M >= 0, "pr_render_people: N = %d, M = %d", a->N, a->M);
+  if (a->M == 0) return PR_OK;
+  PR_REQUIRE(a->frames && a->out, "pr_render_people: null required pointer (frames, out)");
+  PR_REQUIRE(workspace, "pr_render_people: null workspace");
+  PR_REQUIRE(a->n_frames >= 1, "pr_render_people: n_frames = %d", a->n_frames);
+  PR_REQUIRE(a->H >= 1 && a->W >= 1 && a->H <= 4096 && a->W <= 4096, "pr_render_people: frame %d x %d outside 1..4096", a->H,
+             a->W);
+  PR_REQUIRE((long)a->M * a->H * a->W < (1l << 40), "pr_render_people: batch too large (M=%d)", a->M);
+  PR_REQUIRE(a->alpha >= 0.f && a->alpha <= 1.f, "pr_render_people: alpha %g outside [0, 1]", (double)a->alpha);
+  PR_REQUIRE(a->src_idx || a->M <= a->n_frames, "pr_render_people: %d canvases for %d frames without src_idx", a->M,
+             a->n_frames);
+  if (a->N > 0) {
+    PR_REQUIRE(a->verts && a->faces && a->cam && a->bboxes && a->canvas && a->face_part && a->part_rgb,
+               "pr_render_people: null required pointer (verts, faces, cam, bboxes, canvas, face_part, part_rgb)");
+    PR_REQUIRE(a->V >= 3 && a->F >= 1 && a->P >= 1, "pr_render_people: bad sizes V=%d F=%d P=%d", a->V, a->F, a->P);
+    PR_REQUIRE((long)a->N * a->V < (1l << 31) && (long)a->N * a->F < (1l << 31),
+               "pr_render_people: batch too large (N=%d V=%d F=%d)", a->N, a->V, a->F);
+    PR_REQUIRE(a->scale > 0.f && a->scale < 1e6f, "pr_render_people: bbox scale %g", (double)a->scale);
+  }
+  const int V = a->N ? a->V : 0, F = a->N ? a->F : 0;
+  const Layout l = layout(a->N, a->M, V, F, a->H, a->W);
+  PR_REQUIRE(workspace_bytes >= l.total,
+             "pr_render_people: workspace of %zu bytes, %zu needed (pr_render_people_workspace_bytes)", workspace_bytes, l.total);
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  auto* zbuf = (unsigned long long*)(ws + l.zbuf);
+  auto* vfx = a->vert_fx ? (int4*)a->vert_fx : (int4*)(ws + l.vfx);
+  auto* colour = (unsigned*)(ws + l.colour);
+  auto* qcount = (unsigned*)(ws + l.queue);
+  auto* queue = qcount + 4;
+  Geo g{a->verts, a->faces, a->cam, a->bboxes, nullptr, a->N, V, F, a->H, a->W, a->n_frames, a->scale};
+  People p{a->canvas, a->src_idx, a->z_step, a->M};
+  const long n_keys = (long)a->M * a->H * a->W;
+  hipLaunchKernelGGL(people_clear_kernel, dim3(blocks_for(std::max(n_keys, (long)a->N), 256)), dim3(256), 0, s, zbuf, n_keys,
+                     qcount, a->status, a->canvas_status, g, p);
+  PR_TRY(check_launch("people_clear_kernel"));
+  if (a->N > 0) {
+    hipLaunchKernelGGL(people_vertex_kernel, dim3(blocks_for((long)a->N * V, 256)), dim3(256), 0, s, g, p, vfx, a->status);
+    PR_TRY(check_launch("people_vertex_kernel"));
+    hipLaunchKernelGGL(people_face_kernel, dim3(blocks_for((long)a->N * F, 256)), dim3(256), 0, s, g, p, (const int4*)vfx,
+                       a->face_part, a->part_rgb, a->P, a->bgr, colour, zbuf, qcount, queue, a->status);
+    PR_TRY(check_launch("people_face_kernel"));
+    hipLaunchKernelGGL(people_bigface_kernel, dim3(kBigBlocks), dim3(kBigThreads), 0, s, g, p, (const int4*)vfx, zbuf,
+                       (const unsigned*)qcount, (const unsigned*)queue);
+    PR_TRY(check_launch("people_bigface_kernel"));
+  }
+  hipLaunchKernelGGL(people_resolve_kernel, dim3(blocks_for(n_keys, 256)), dim3(256), 0, s, g, p,
+                     (const unsigned long long*)zbuf, (const unsigned*)colour, a->frames, a->alpha, a->out, a->face_id);
+  return check_launch("people_resolve_kernel");
 }
 
 }  // extern "C"

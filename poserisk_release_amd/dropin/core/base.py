@@ -171,6 +171,12 @@ class Predictor:
         self.persons = str(_knob(args, 'persons', 'persons', 'target'))
         if self.persons not in ('target', 'all'):
             raise ValueError(f"persons {self.persons!r} is not known: 'target' or 'all' (cfg.DATASET.persons / args.persons)")
+        # the mesh of EVERY scored person over every frame, depth-tested against each other (render_people, pr_render_people):
+        # args.people_mesh, else cfg.DATASET.people_mesh (False).  A knob of its own: render_mesh stays the target's overlay
+        self.people_mesh = bool(_knob(args, 'people_mesh', 'people_mesh', False))
+        if self.people_mesh and self.persons != 'all':
+            raise ValueError(f"people_mesh draws the people that persons 'all' scores, but persons is {self.persons!r} "
+                             "(cfg.DATASET.people_mesh / args.people_mesh, cfg.DATASET.persons / args.persons)")
         # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
         # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
         # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
@@ -422,13 +428,15 @@ class Predictor:
         return self._score_tracks(frames, [target], add_info, bgr, bbox_scale, shard,
                                   self.render_mesh if with_smpl_params is None else with_smpl_params)[0][0]
 
-    def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None):
+    def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None):
         """Decoded frames + tracker output -> the scores of EVERY person tracks.people_tracks keeps, in one pass over the model:
         {'people': [out_0, out_1, ...], 'ids': [...], 'frames_total': F}, in people_tracks order (element 0 is the person
         score_frames scores).  Each out_p holds what score_frames returns for that person alone -- result, joint_cam,
         debug_result, reba, rula, frames, bboxes -- bit for bit: a frame's bits do not depend on its batch
         (tests/test_encoder_batch_sweep.py), so the people share batches (_score_tracks).  With args.debug the dict also holds
-        'pose_logs', each person's rows of the scorers' angle logs.
+        'pose_logs', each person's rows of the scorers' angle logs.  `with_smpl_params` (default: the people_mesh knob): every
+        out_p also holds rotmat, betas, cam, add_info and bbox_scale, as score_frames(with_smpl_params=True) returns them for
+        that person alone; render_people draws from them.
 
         Not supported, by name: several ranks (hip_world_size / args.world_size > 1) and the render_mesh knob
         (pr_render_overlay draws one mesh per canvas)."""
@@ -442,7 +450,9 @@ class Predictor:
                                       "canvas (cfg.DATASET.render_mesh / args.render_mesh)")
         n_frames = len(frames)
         people = tracks.people_tracks(tracking_results, n_frames, cfg.DATASET.min_frame_ratio)
-        outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale)
+        if with_smpl_params is None:
+            with_smpl_params = getattr(self, 'people_mesh', False)
+        outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale, with_smpl_params=bool(with_smpl_params))
         people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': n_frames}
         return dict(people_out, pose_logs=pose_logs) if self.debugging else people_out
 
@@ -470,19 +480,66 @@ class Predictor:
         info = out.get('add_info') or default_information()
         for i in range(0, n, self.batch_size):
             j = min(i + self.batch_size, n)
-            rotmat = torch.as_tensor(out['rotmat'][i:j], device=dev)
-            aa, eul, _ = ops.pose_to_euler(rotmat)
-            betas = torch.as_tensor(out['betas'][i:j], device=dev)
-            verts, _ = layer(aa.reshape(j - i, 72), betas)
-            if scheme is None:
-                rgb = render.part_colours(np.zeros((j - i, 1)), None)
-            else:
-                packed = (ops.reba if scheme == 'REBA' else ops.rula)(eul, info[scheme]).cpu().numpy()
-                rgb = render.part_colours(packed, scheme)
+            verts, rgb = self._posed_meshes(out['rotmat'][i:j], out['betas'][i:j], info, scheme, dev)
             img = render.overlay(frames, verts, faces_dev, out['cam'][i:j], out['bboxes'][i:j],
                                  scale=out.get('bbox_scale', cfg.DATASET.bbox_scale), frame_idx=fidx[i:j].astype(np.int32),
                                  face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
             yield fidx[i:j], img
+
+    def _posed_meshes(self, rotmat, betas, info, scheme, dev):
+        """rotmat f32[n,24,3,3] + betas f32[n,10] (n <= batch_size) -> (vertices f32[n,V,3] on `dev`, part_rgb u8[n,P,3]): the
+        meshes render_overlay and render_people draw and their parts' colours by the scheme's risk levels of each row."""
+        from poserisk_release_amd import ops, render
+        n = len(rotmat)
+        aa, eul, _ = ops.pose_to_euler(torch.as_tensor(rotmat, device=dev))
+        verts, _ = self.smpl_model.layer['neutral'](aa.reshape(n, 72), torch.as_tensor(betas, device=dev))
+        if scheme is None:
+            return verts, render.part_colours(np.zeros((n, 1)), None)
+        packed = (ops.reba if scheme == 'REBA' else ops.rula)(eul, info[scheme]).cpu().numpy()
+        return verts, render.part_colours(packed, scheme)
+
+    def render_people(self, people_out, frames, title='REBA', bgr=False, alpha=0.6):
+        """Yield (video frame numbers int[b], frames u8[b,H,W,3] CUDA) over ALL frames of the video, batch_size frames at a
+        time: the fitted mesh of every scored person who is in the frame drawn over it, the people depth-tested against each
+        other (poserisk_release_amd.render.overlay_people, pr_render_people); a frame nobody is in comes back as it is.
+        `people_out` is what score_people returned with the SMPL parameters.  Meshes as in render_overlay, each person's parts
+        coloured by that person's own risk levels of that frame; the meshes of a frame are ordered as tracks.people_tracks
+        orders the people, and their depth steps come from render.people_z_step, the cameras' size on the screen."""
+        from poserisk_release_amd import render
+        outs = people_out['people']
+        if any('rotmat' not in o for o in outs):
+            raise ValueError("render_people needs score_people(..., with_smpl_params=True) (or the people_mesh knob)")
+        layer = self.smpl_model.layer['neutral']
+        faces = np.asarray(self.smpl_model.face)
+        if faces.ndim != 2 or faces.shape[0] == 0:
+            raise ValueError("the SMPL model has no faces to draw")
+        scheme = None if title is None else str(title).upper()
+        face_part = render.face_parts(layer.th_weights.numpy(), faces, scheme)
+        frames = self._on_device(frames)
+        dev = frames.device
+        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        faces_dev = torch.as_tensor(faces.astype(np.int32), device=dev)
+        if not outs:
+            raise ValueError("render_people: nobody was scored")
+        scale = outs[0].get('bbox_scale', cfg.DATASET.bbox_scale)
+        info = outs[0].get('add_info') or default_information()
+        # every (person, track frame) row is a mesh, person after person: a selection of rows keeps the people's order
+        cat = lambda key: np.concatenate([np.asarray(o[key]) for o in outs])
+        fidx, cam, bboxes, rotmat, betas = cat('frames'), cat('cam'), cat('bboxes'), cat('rotmat'), cat('betas')
+        z_step = render.people_z_step(cam, bboxes, scale, H, W)
+        for lo in range(0, n_frames, self.batch_size):
+            hi = min(lo + self.batch_size, n_frames)
+            sel = np.nonzero((fidx >= lo) & (fidx < hi))[0]
+            verts, rgb = [], []
+            for i in range(0, len(sel), self.batch_size):               # the SMPL layer takes batch_size rows a call
+                v, c = self._posed_meshes(rotmat[sel[i:i + self.batch_size]], betas[sel[i:i + self.batch_size]], info, scheme, dev)
+                verts.append(v)
+                rgb.append(c)
+            verts = torch.cat(verts) if verts else torch.zeros((0, int(faces.max()) + 1, 3), device=dev)
+            img = render.overlay_people(frames, verts, faces_dev, cam[sel], bboxes[sel], (fidx[sel] - lo).astype(np.int32),
+                                        np.arange(lo, hi, dtype=np.int32), z_step[sel], scale=scale, face_part=face_part,
+                                        part_rgb=np.concatenate(rgb) if rgb else None, alpha=alpha, bgr=bgr)
+            yield np.arange(lo, hi), img
 
     def _open_sink(self, output_path, name, frame_size, fps, bgr):
         """<output>/<name>: the sink of the gpu_video_codec knob (poserisk_release_amd/sinks.py) for frames of (height, width) =
@@ -545,11 +602,14 @@ class Predictor:
                                     title + '_video', bgr, fps)
 
     # ---- the persons='all' outputs (no counterpart in the reference, which describes one person) -----------------------------
-    def write_people_video(self, people_out, frames, output_path, title, bgr=False, fps=30.0):
+    def write_people_video(self, people_out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
         """`<TITLE>_people`: every frame of the video at 720 px wide with every scored person's box and `#<id> <score>` tag in
         the colour of that frame's action level, beside a panel that lists the people of the frame
         (poserisk_release_amd.video.people_draw_list, pr_compose_people), from what score_people returned.  Written through
-        the sink of the gpu_video_codec knob, as write_gpu_video's.  Returns the path written."""
+        the sink of the gpu_video_codec knob, as write_gpu_video's.  With the people_mesh knob the image region is
+        render_people's frame, boxes and tags over the meshes (`people_out` must then hold the SMPL parameters), and
+        `mesh_sink(frame numbers, images)` receives every rendered batch, so that <TITLE>_people_mesh is written from the same
+        rendering.  Returns the path written."""
         from poserisk_release_amd import video
         frames = self._on_device(frames)
         n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
@@ -562,8 +622,19 @@ class Predictor:
                                names=[a[1] for a in acts]))
         canvas_h, resize_w, _ = video.canvas_size(H, W)
         draw = video.people_draw_list(title, n_frames, people, canvas_h, resize_w, H, W, bgr=bgr)
-        return self._write_canvases(video.people_frames(frames, draw, self.batch_size), frames, output_path, title + '_people',
-                                    bgr, fps)
+        overlay = None
+        if getattr(self, 'people_mesh', False):
+            meshed = self.render_people(people_out, frames, title, bgr)       # batch_size frames a step, as people_frames asks
+
+            def overlay(lo, hi):
+                numbers, images = next(meshed)
+                if numbers[0] != lo or numbers[-1] != hi - 1:
+                    raise RuntimeError(f"render_people yielded frames {numbers[0]}..{numbers[-1]} where {lo}..{hi - 1} are composed")
+                if mesh_sink is not None:
+                    mesh_sink(numbers, images)
+                return numbers, images
+        return self._write_canvases(video.people_frames(frames, draw, self.batch_size, overlay=overlay), frames, output_path,
+                                    title + '_people', bgr, fps)
 
     def _write_reports(self, out, folder, debug_folder, n_frames, pose_logs, after_plot=lambda title: None, after_txt=lambda title: None):
         """One scored person's files.  Into `folder`, per title scored: <TITLE>_score.png, then <title>_result.txt.  With args.debug
@@ -961,10 +1032,23 @@ class Predictor:
         self._write_reports(out, output_path, debug_path, timestamp[2], {'reba': self.reba.log, 'rula': self.rula.log}, videos, mesh_alone)
         if people_out is not None:
             self.write_people_reports(people_out, output_path)
+            people_mesh = getattr(self, 'people_mesh', False)
             if on_gpu:
                 for title in ('REBA', 'RULA'):
-                    if title.lower() in out:
+                    if title.lower() not in out:
+                        continue
+                    if people_mesh:                     # one rendering of the meshes feeds both outputs, as in videos()
+                        mesh = self._open_sink(output_path, title + '_people_mesh', frames.shape[1:3], fps, bgr)
+                        try:
+                            self.write_people_video(people_out, frames, output_path, title, bgr, fps, mesh_sink=mesh.put)
+                        except BaseException:
+                            mesh.abort()
+                            raise
+                        mesh.close()
+                    else:
                         self.write_people_video(people_out, frames, output_path, title, bgr, fps)
             elif show:
                 print("The people video (<TITLE>_people) is composed on the GPU only: it needs the gpu_video knob and is skipped")
+                if people_mesh:
+                    print("The people mesh (<TITLE>_people_mesh) is drawn beside it: it needs the gpu_video knob too and is skipped")
         return out

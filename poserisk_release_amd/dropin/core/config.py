@@ -57,6 +57,10 @@ absent from the reference and all optional:
                               track tracks.people_tracks keeps in one pass (Predictor.score_people) and adds <output>/person_<id>/,
                               <output>/people.json and, with gpu_video, <TITLE>_people (pr_compose_people); every other output
                               stays what 'target' writes (args.persons overrides it)
+    cfg.DATASET.people_mesh   False | True, with persons 'all' only (anything else raises): Predictor.score_people also returns every
+                              person's SMPL parameters, and with gpu_video the image region of <TITLE>_people is the frame with
+                              everybody's fitted mesh over it, the people depth-tested against each other (pr_render_people), also
+                              written on its own as <TITLE>_people_mesh (args.people_mesh overrides it)
     cfg.TRACKER               the built-in person detector and tracker (poserisk_release_amd.detector: YOLOv3 on the GPU,
                               poserisk_release_amd.sort: SORT on the host).  All of it is inert while `weights` is '':
                               weights '' | the path of a darknet yolov3.weights file; img_size (416, 416) = (rows, columns) of the
@@ -128,7 +132,7 @@ def _defaults(root):
                     'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
                     'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True,
                     'yuv_matrix': '601', 'video_decoder': '', 'video_encoder': '', 'video_encoder_ext': '.mp4',
-                    'video_chroma': '420mpeg2', 'persons': 'target'},
+                    'video_chroma': '420mpeg2', 'persons': 'target', 'people_mesh': False},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),

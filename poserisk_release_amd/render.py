@@ -3,7 +3,11 @@ level (include/poserisk_hip.h, pr_render_overlay; the kernels are csrc/render.hi
 
 `overlay` is the torch wrapper of the kernel.  `face_parts` and `part_colours` turn SMPL's skinning weights and the REBA /
 RULA logs into the kernel's face_part and part_rgb tables.  The Predictor's `render_overlay` (dropin/core/base.py) chains
-them on the arrays `score_frames` returns."""
+them on the arrays `score_frames` returns.
+
+`overlay_people` is the wrapper of pr_render_people (header section r4): the meshes of everybody in a frame on one canvas,
+depth-tested against each other; `people_z_step` is the host rule that orders them in depth.  The Predictor's `render_people`
+chains them on what `score_people` returns."""
 import numpy as np
 import torch
 
@@ -122,4 +126,110 @@ def overlay(frames, verts, faces, cam, bboxes, scale=1.2, frame_idx=None, face_p
     _lib.check(lib.pr_render_overlay(args, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
                "pr_render_overlay")
     extra = [t for t, want in ((fid, return_face_id), (vfx, return_vert_fx), (st, return_status)) if want]
+    return (out, *extra) if extra else out
+
+
+# ---- the people mesh overlay (pr_render_people): everybody of a frame on one canvas, depth-tested against each other ----------
+Z_STEP_MAX = 1 << 24        # PR_RENDER_Z_STEP_MAX, 4096 m in depth steps
+Z_FIX = 4096.0              # depth steps per metre
+
+
+def people_z_step(cam, bboxes, scale, H, W):
+    """The one host rule that orders the people of a frame in depth from their weak-perspective cameras: cam [N,3] (s, tx, ty),
+    bboxes [N,4] (cx, cy, w, h), scale = cfg.DATASET.bbox_scale, the frame's H and W -> z_step int32[N] for overlay_people.
+
+    A metre of the body spans ppm = s scale (w + h) / 4 pixels (the projection's s w scale / 2 and s h scale / 2, averaged),
+    evaluated in float64.  Under a pinhole camera of focal length hypot(H, W) px that is a depth of d = hypot(H, W) / ppm
+    metres; z_step = min(rint(4096 d), 2^24), and 0 where s or ppm is not finite or not positive.  The order of the people
+    depends on ppm alone: who is drawn larger is nearer.  The focal length -- an ASSUMPTION, a 53 degree diagonal field of
+    view -- only sets how far apart they stand compared with a body's own +-0.5 m of depth.  The rule has not been checked
+    against true occlusion on real video."""
+    c = np.asarray(cam, np.float64).reshape(-1, 3)
+    b = np.asarray(bboxes, np.float64).reshape(-1, 4)
+    if c.shape[0] != b.shape[0]:
+        raise ValueError(f"{c.shape[0]} cameras for {b.shape[0]} boxes")
+    s = c[:, 0]
+    with np.errstate(all="ignore"):
+        ppm = s * float(scale) * (b[:, 2] + b[:, 3]) / 4.0
+        ok = np.isfinite(s) & (s > 0) & np.isfinite(ppm) & (ppm > 0)
+        d = float(np.hypot(float(H), float(W))) / np.where(ok, ppm, 1.0)
+        z = np.minimum(np.rint(Z_FIX * d), float(Z_STEP_MAX))
+    return np.where(ok, z, 0.0).astype(np.int32)
+
+
+def _host_ints(x, n, what):
+    a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if a.shape != (n,) or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be int[{n}], got {a.dtype}{list(a.shape)}")
+    return a.astype(np.int32)
+
+
+def overlay_people(frames, verts, faces, cam, bboxes, canvas, src_idx, z_step=None, scale=1.2, face_part=None, part_rgb=None,
+                   alpha=0.6, bgr=False, out=None, return_face_id=False, return_vert_fx=False, return_status=False,
+                   return_canvas_status=False):
+    """Draw N meshes on M canvases on the GPU, the meshes of a canvas depth-tested against each other (pr_render_people; the
+    contract is section r4 of include/poserisk_hip.h).
+
+    As `overlay`, with canvas int[N] (the canvas of each mesh), src_idx int[M] (the source frame of each canvas) and z_step
+    int[N] or None (all zero; people_z_step makes it from the cameras) in place of frame_idx.  Returns out u8[M,H,W,3],
+    followed by face_id int32[M,H,W] (n F + f), vert_fx int32[N,V,4], status int32[N] and canvas_status int32[M] as asked
+    for.  Shapes and face indices are checked here, once, on the host, before anything goes to the device; indices in
+    canvas, src_idx and z_step outside their ranges are the kernel's to flag (status bits 3, 4, and canvas_status)."""
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError("frames must be a uint8 tensor [n_frames,H,W,3]")
+    n_frames, H, W, _ = frames.shape
+    vshape = tuple(verts.shape) if hasattr(verts, "shape") else np.shape(verts)
+    if len(vshape) != 3 or vshape[2] != 3:
+        raise ValueError(f"verts must have shape (N, V, 3), got {tuple(vshape)}")
+    N, V = int(vshape[0]), int(vshape[1])
+    faces_host = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if faces_host.ndim != 2 or faces_host.shape[1] != 3 or faces_host.shape[0] == 0:
+        raise ValueError(f"faces must be int [F,3], got shape {faces_host.shape}")
+    if int(faces_host.min()) < 0 or int(faces_host.max()) >= V:
+        raise ValueError(f"face indices {int(faces_host.min())}..{int(faces_host.max())} outside [0, {V})")
+    F = faces_host.shape[0]
+    cv = _host_ints(canvas, N, "canvas")
+    M = int(np.shape(src_idx)[0]) if np.ndim(src_idx) == 1 else -1
+    if M < 0:
+        raise ValueError(f"src_idx must be int[M], got shape {tuple(np.shape(src_idx))}")
+    si = _host_ints(src_idx, M, "src_idx")
+    zs = None if z_step is None else _host_ints(z_step, N, "z_step")
+    if N * F >= 1 << 31:
+        raise ValueError(f"N F = {N * F} does not fit the key's low half (2^31)")
+    if frames.device.type != "cuda":
+        raise _lib.PoseRiskHipError("overlay_people: frames must be a CUDA tensor (no CPU fallback)")
+    dev = frames.device
+    frames = frames.contiguous()
+    v = _dev_tensor(verts, torch.float32, dev, (N, V, 3), "verts")
+    f = _dev_tensor(faces if isinstance(faces, torch.Tensor) else faces_host, torch.int32, dev)
+    c = _dev_tensor(cam, torch.float32, dev, (N, 3), "cam")
+    bb = _dev_tensor(bboxes, torch.float32, dev, (N, 4), "bboxes")
+    fp = _dev_tensor(np.zeros(F, np.int32) if face_part is None else face_part, torch.int32, dev, (F,), "face_part")
+    rgb = _dev_tensor(NEUTRAL_RGB[None] if part_rgb is None else part_rgb, torch.uint8, dev)
+    if rgb.dim() == 2:
+        rgb = rgb[None].expand(N, -1, -1).contiguous()
+    if rgb.dim() != 3 or rgb.shape[0] != N or rgb.shape[2] != 3 or rgb.shape[1] == 0:
+        raise ValueError(f"part_rgb must be u8[N,P,3] or u8[P,3], got {tuple(rgb.shape)}")
+    P = rgb.shape[1]
+    cv, si = torch.from_numpy(cv).to(dev), torch.from_numpy(si).to(dev)
+    zs = None if zs is None else torch.from_numpy(zs).to(dev)
+    if out is None:
+        out = torch.empty((M, H, W, 3), dtype=torch.uint8, device=dev)
+    elif out.shape != (M, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous uint8 [M,H,W,3] tensor on the frames' device")
+    fid = torch.empty((M, H, W), dtype=torch.int32, device=dev) if return_face_id else None
+    vfx = torch.empty((N, V, 4), dtype=torch.int32, device=dev) if return_vert_fx else None
+    st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    cst = torch.empty((M,), dtype=torch.int32, device=dev) if return_canvas_status else None
+    lib = _lib.load()
+    nbytes = lib.pr_render_people_workspace_bytes(N, M, V, F, H, W)
+    ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    args = _lib.RenderPeopleArgs(v.data_ptr(), f.data_ptr(), c.data_ptr(), bb.data_ptr(), frames.data_ptr(), cv.data_ptr(),
+                                 si.data_ptr(), ptr(zs), fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), ptr(fid), ptr(vfx),
+                                 ptr(st), ptr(cst), N, M, V, F, P, n_frames, H, W, int(bool(bgr)), float(scale), float(alpha))
+    _lib.check(lib.pr_render_people(args, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+               "pr_render_people")
+    extra = [t for t, want in ((fid, return_face_id), (vfx, return_vert_fx), (st, return_status), (cst, return_canvas_status))
+             if want]
     return (out, *extra) if extra else out

@@ -342,9 +342,11 @@ def pack_people(draw, lo, hi, n_tags=None, L=None, C=None):
     return lines, codes, n_tags
 
 
-def people_frames(frames, draw, batch_size=64, atlas=None):
+def people_frames(frames, draw, batch_size=64, atlas=None, overlay=None):
     """Yield the people canvases of the whole video in order, `batch_size` video frames at a time, as CUDA u8[b,dst_h,1000,3]
-    in the frames' channel order.  frames u8[F,H,W,3] CUDA; draw = people_draw_list(..., canvas_size(H, W)[0], RESIZE_W, H, W)."""
+    in the frames' channel order.  frames u8[F,H,W,3] CUDA; draw = people_draw_list(..., canvas_size(H, W)[0], RESIZE_W, H, W).
+    `overlay(lo, hi)`, as annotated_frames': (frame numbers int[m], images u8[m,H,W,3] CUDA) for the frames in [lo, hi) that
+    have a drawn-over version (Predictor.render_people's meshes): those replace the plain frames, under the boxes and tags."""
     if not (isinstance(frames, torch.Tensor) and frames.device.type == "cuda"):
         raise _lib.PoseRiskHipError("people_frames: frames must be a CUDA tensor (no CPU fallback)")
     F, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
@@ -357,5 +359,11 @@ def people_frames(frames, draw, batch_size=64, atlas=None):
     for lo in range(0, F, batch_size):
         hi = min(lo + batch_size, F)
         lines, codes, L_img = pack_people(draw, lo, hi, n_tags, L, C)
-        yield compose_people(frames, np.arange(lo, hi, dtype=np.int32), draw.box[lo:hi], draw.box_rgb[lo:hi], lines, codes, L_img,
-                             atlas, dst_h, dst_w, panel_w)
+        src, idx = frames, np.arange(lo, hi, dtype=np.int32)
+        if overlay is not None:
+            numbers, images = overlay(lo, hi)
+            if len(numbers):
+                src = frames[lo:hi].clone()
+                src[torch.as_tensor(np.asarray(numbers) - lo, device=src.device, dtype=torch.long)] = images
+                idx = None
+        yield compose_people(src, idx, draw.box[lo:hi], draw.box_rgb[lo:hi], lines, codes, L_img, atlas, dst_h, dst_w, panel_w)
