@@ -1671,6 +1671,76 @@ int pr_det_detect(pr_det_t* h, const uint8_t* frames_dev, int B, int H, int W, i
                   int max_det, float* boxes_dev, float* scores_dev, int32_t* count_dev, int32_t* status_dev, void* stream);
 int pr_det_unmap(float* boxes_dev, const int32_t* count_dev, int B, int max_det, int H, int W, int S_h, int S_w, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* s1  temporal smoothing of each track's poses (csrc/smooth.hip; ABI 16: added, nothing changed) */
+/* precedent: the reference's median-then-Gaussian recipe for boxes, lib/utils/smooth_bbox.py:106-121, moved to rotations */
+/* ------------------------------------------------------------------------------------ */
+/* The rows of all tracks lie end to end: rotmat f32[N,24,3,3], optionally betas f32[N,10] and cam f32[N,3], frame_no i32[N]
+ * on the device; track t owns the rows track_start[t] .. track_start[t + 1] - 1 (track_start int[T + 1], a HOST array, read
+ * before the call returns; 0 = s_0 <= s_1 <= ... <= s_T = N or the call is refused).  tests/smooth_ref.py restates all of
+ * this in float64 numpy.
+ *
+ * Parameters: median_radius m in 0..15, sigma >= 0 and finite, g = min(ceil(3 sigma), 15); anything else is refused.  m = 0
+ * skips stage 1, sigma = 0 skips stage 2, with both 0 the outputs hold the inputs' bits.  The unit is frames.
+ *
+ * Groups: one vector per row -- each of the 24 joints (9 floats), cam (3), betas (10); every group is filtered on its own.
+ * Window of row i with radius r: the rows k of the same track with |k - i| <= r and |frame_no[k] - frame_no[i]| <= r (the
+ * difference taken in 64 bits).  It is defined on frame numbers, so a gap in a track shrinks it; it never crosses a track
+ * boundary, holds row i itself, and is well defined and memory-safe for ANY frame_no content: no global address is formed
+ * outside rows i - 15 .. i + 15 clamped to the track.
+ *
+ * Stage 1, medoid, radius m: cost_k = sum over the window's members l, ascending, self term included, of ||x_k - x_l||_2 --
+ * each difference, the sum of squares in element order and the square root in float64, each operation rounded on its own
+ * (never fused) -- and the output is x_k* with the smallest cost; exact ties go to the smaller |frame_no[k] - frame_no[i]|,
+ * then to the smaller k.  The output holds an input row's bits.  (A one-float group's medoid is its median.)
+ *
+ * Stage 2, Gaussian, radius g, on stage 1's outputs y: w_k = exp(-(frame_no[k] - frame_no[i])^2 / (2 sigma^2)) in float64
+ * (1 where the two frame numbers are equal, whatever sigma^2 rounds to).
+ *   a window whose only member is row i itself (an isolated row): the output is y_i's bits, for every group.
+ *   cam, betas: sum(w y) / sum(w) per element in float64, members ascending, rounded to f32 once.
+ *   a joint: A = sum w_k Y_k (not normalised: what follows is invariant to A's scale), c = det(A) / (||A||_F / sqrt 3)^3
+ *     (1 when all members agree).  c >= 0.05: the output is the rotation nearest A in Frobenius norm, the orthogonal polar
+ *     factor of A (U diag(1, 1, det(U V^T)) V^T of its SVD; the kernel iterates the scaled Newton step X <- (mu X + X^-T / mu) / 2,
+ *     mu = |det X|^(-1/3), from A / (||A||_F / sqrt 3) in float64), rounded to f32 once: every entry within 2^-24 of the
+ *     float64 reference.  c >= 0.05 implies s2 + s3 >= 0.196 s1 for A's singular values, so det(A) > 0, the factor is a
+ *     proper rotation and the iteration is well conditioned.
+ *     c < 0.05 (or not a number): the joint's output is y_i, stage 1's output for the row itself, and bit j of status[i] is set.
+ *
+ * status_dev i32[N] or NULL: bits 0..23 as above, else 0.  outputs->replaced i32[N] or NULL: bit j (joints 0..23; 24 = cam,
+ * 25 = betas) is set where stage 1 chose another row than i itself, else 0.
+ * outputs->betas / ->cam are required exactly where inputs->betas / ->cam are given.  No output, status, replaced or the
+ * workspace may be the same pointer as an input or as each other.  workspace_dev: pr_smooth_workspace_bytes(N, has_betas,
+ * has_cam) bytes (stage 1's outputs), needed only when both stages run, else it may be NULL.
+ *
+ * Two launches on `stream` per PR_SMOOTH_TRACKS_PER_LAUNCH tracks (their bounds travel in the kernel's arguments: no copy
+ * to the device): stage 1 into the workspace, stage 2 out of it.  A workgroup takes pr_smooth_tile_rows() consecutive rows
+ * (counted from the first row of its PR_SMOOTH_TRACKS_PER_LAUNCH tracks, i.e. from row 0 for T up to that many) and stages
+ * them with their halo in LDS once.  Asynchronous, no allocation, no copy, no synchronisation (capturable).  Argument errors
+ * return PR_ERR_INVALID by name before any device work; N = 0 (with T >= 0 and all starts 0) returns PR_OK. */
+#define PR_SMOOTH_MAX_RADIUS 15
+#define PR_SMOOTH_TRACKS_PER_LAUNCH 256
+typedef struct pr_smooth_params {
+  int32_t median_radius; /* m */
+  int32_t reserved;      /* 0 */
+  double sigma;
+} pr_smooth_params;
+typedef struct pr_smooth_inputs {
+  const float* rotmat; /* f32[N,24,3,3] */
+  const float* betas;  /* f32[N,10] or NULL */
+  const float* cam;    /* f32[N,3] or NULL */
+} pr_smooth_inputs;
+typedef struct pr_smooth_outputs {
+  float* rotmat;
+  float* betas;
+  float* cam;
+  int32_t* replaced; /* i32[N] or NULL */
+} pr_smooth_outputs;
+int pr_smooth_tile_rows(void);
+size_t pr_smooth_workspace_bytes(int N, int has_betas, int has_cam); /* 0 for N < 0 */
+int pr_smooth_tracks(const pr_smooth_params* params, const pr_smooth_inputs* inputs, const int32_t* frame_no_dev,
+                     const int* track_start_host, int T, int N, const pr_smooth_outputs* outputs, int32_t* status_dev,
+                     void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,21 @@ class DetLayer(C.Structure):
                                           "kpad")] + [("weight_offset", C.c_int64), ("pack_offset", C.c_int64)]
 
 
+class SmoothParams(C.Structure):
+    """pr_smooth_params (include/poserisk_hip.h, section s1)."""
+    _fields_ = [("median_radius", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_double)]
+
+
+class SmoothInputs(C.Structure):
+    """pr_smooth_inputs (include/poserisk_hip.h, section s1)."""
+    _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam")]
+
+
+class SmoothOutputs(C.Structure):
+    """pr_smooth_outputs (include/poserisk_hip.h, section s1)."""
+    _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "replaced")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -240,6 +255,10 @@ SIGNATURES = {
     "pr_det_postprocess": (_I, [_P, _P, _P, _P, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
     "pr_det_detect": (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _P, _P, _P, _P, _P]),
     "pr_det_unmap": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "pr_smooth_tile_rows": (_I, []),
+    "pr_smooth_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "pr_smooth_tracks": (_I, [C.POINTER(SmoothParams), C.POINTER(SmoothInputs), _P, C.POINTER(_I), _I, _I, C.POINTER(SmoothOutputs),
+                              _P, _P, _P]),
 }
 
 _lib = None

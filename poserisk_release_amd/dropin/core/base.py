@@ -177,6 +177,12 @@ class Predictor:
         if self.people_mesh and self.persons != 'all':
             raise ValueError(f"people_mesh draws the people that persons 'all' scores, but persons is {self.persons!r} "
                              "(cfg.DATASET.people_mesh / args.people_mesh, cfg.DATASET.persons / args.persons)")
+        # temporal smoothing of each track's poses before scoring (poserisk_release_amd/smooth.py, pr_smooth_tracks), both in
+        # FRAMES: args.smooth_median_radius, else cfg.DATASET.smooth_median_radius (0); args.smooth_sigma, else
+        # cfg.DATASET.smooth_sigma (0.0).  Both 0 = off: _score_tracks takes the path it always took
+        from poserisk_release_amd.smooth import check_parameters
+        self.smooth_median_radius, self.smooth_sigma = check_parameters(_knob(args, 'smooth_median_radius', 'smooth_median_radius', 0),
+                                                                        _knob(args, 'smooth_sigma', 'smooth_sigma', 0.0))
         # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
         # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
         # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
@@ -357,13 +363,40 @@ class Predictor:
         self._run_scorers(out, add_info)
         return out
 
+    def _smooth_rows(self, smpl, people, fidx, median_radius, sigma):
+        """The smoothing knobs' half of _score_tracks: every person's rows of the network's rotmat, betas and cam (`smpl`, host
+        arrays, person after person) are smoothed along their track in ONE call (smooth.smooth_tracks: windows on the frame
+        numbers `fidx`, never across people), `smpl` is updated with the smoothed arrays, and the back half is run again from
+        the smoothed rotations as get_pose_estimation_results runs it: ops.pose_to_euler, then the SMPL layer's joint_cam,
+        which overwrites the axis-angle root rows with (3.14, 0, 0) -> (result, joint_cam, debug_result, {'status',
+        'replaced'} i32[n])."""
+        from poserisk_release_amd import ops, smooth
+        layer = self.smpl_model.layer['neutral']
+        dev = layer.device
+        track_start = np.cumsum([0] + [len(f) for _, _, f in people]).astype(np.int64)
+        sm = smooth.smooth_tracks(torch.as_tensor(smpl['rotmat'], device=dev), np.asarray(fidx, np.int64), track_start, median_radius,
+                                  sigma, betas=torch.as_tensor(smpl['betas'], device=dev), cam=torch.as_tensor(smpl['cam'], device=dev))
+        aa, eul, st = ops.pose_to_euler(sm['rotmat'])
+        n = aa.shape[0]
+        joint_cam = torch.empty((n, 24, 3), dtype=torch.float32, device=dev)
+        for lo in range(0, n, self.batch_size):                     # the SMPL layer takes batch_size rows a call
+            layer.joint_cam(aa[lo:lo + self.batch_size], out=joint_cam[lo:lo + self.batch_size])
+        status = st.cpu().numpy()
+        if np.any(status != 0):     # as get_pose_estimation_results: the reference aborts on these
+            raise AssertionError(f"invalid rotation after smoothing in rows {np.nonzero(status)[0].tolist()}")
+        smpl.update({k: sm[k].cpu().numpy() for k in ('rotmat', 'betas', 'cam')})
+        flags = {k: sm[k].cpu().numpy() for k in ('status', 'replaced')}
+        return eul.cpu().numpy(), joint_cam.cpu().numpy(), aa.cpu().numpy(), flags
+
     def _score_tracks(self, frames, people, add_info, bgr, bbox_scale, shard=None, with_smpl_params=False):
         """The one scoring pass under score_frames and score_people: people [(id, bboxes f32[n,4], frame indices int[n])] -> (a
         dict per person as score_frames returns it, each person's rows of the scorers' angle logs).  Everybody's (frame index,
         box) rows are concatenated, cut into batches of self.batch_size across person boundaries (sum(n_p) / batch_size launches,
         rounded up once), cropped and run through get_pose_estimation_results once, and split back by offsets; the scorers and
         the aggregation run per person on the host.  `shard(bboxes, fidx)`, a sharding caller's, runs after the range check ->
-        (lo, hi, n_total): the crops cover rows [lo, hi), this rank's, of the n_total the results are gathered to."""
+        (lo, hi, n_total): the crops cover rows [lo, hi), this rank's, of the n_total the results are gathered to.
+        With a smoothing knob positive (smooth_median_radius, smooth_sigma) the rows go through _smooth_rows between the model
+        and the split: each dict then holds the smoothed values and 'smooth'; with both 0 nothing here differs."""
         from poserisk_release_amd import ops
         frames = self._on_device(frames)
         if bbox_scale is None:
@@ -380,15 +413,23 @@ class Predictor:
             for i in range(lo, hi, self.batch_size):
                 j = min(i + self.batch_size, hi)
                 yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
-        smpl = {} if with_smpl_params else None
+        smooth_m, smooth_sigma = getattr(self, 'smooth_median_radius', 0), getattr(self, 'smooth_sigma', 0.0)
+        smoothing = smooth_m > 0 or smooth_sigma > 0
+        smpl = {} if with_smpl_params or smoothing else None
         result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False, n_total=n_total,
                                                                               smpl_params=smpl)
+        if smoothing:
+            # every rank holds all rows after the gather and smooths the same ones: no further collective
+            result, joint_cam, debug_result, smooth_flags = self._smooth_rows(smpl, people, fidx, smooth_m, smooth_sigma)
         outs, pose_logs, at = [], [], 0
         for _, box_p, frames_p in people:
             rows = slice(at, at + len(frames_p))
             out = dict(result=result[rows], joint_cam=joint_cam[rows], debug_result=debug_result[rows])
             if with_smpl_params:
                 out.update({k: v[rows] for k, v in smpl.items()}, add_info=add_info)
+            if smoothing:
+                out['smooth'] = dict(median_radius=smooth_m, sigma=smooth_sigma, status=smooth_flags['status'][rows],
+                                     replaced=smooth_flags['replaced'][rows])
             pose_logs.append(self._run_scorers(out, add_info))
             out['frames'], out['bboxes'] = frames_p, box_p
             if with_smpl_params:
@@ -679,6 +720,23 @@ class Predictor:
         with open(osp.join(output_path, 'people.json'), 'w') as f:
             json.dump({'frames_total': n_frames, 'people': summary}, f, indent=1)
         return summary
+
+    def write_smooth_report(self, out, people_out, output_path):
+        """<output>/smooth.json, written only when a smoothing knob is on: the parameters (in frames) and per scored person
+        (the target alone, id null, without persons 'all') how many (row, joint) items stage 1 replaced by another frame's
+        rotation and how many fell back in stage 2 (pr_smooth_tracks' replaced and status bits).  Returns what it holds."""
+        from poserisk_release_amd import smooth
+        plain = lambda v: v.item() if isinstance(v, np.generic) else v
+        scored = list(zip(people_out['ids'], people_out['people'])) if people_out is not None else [(None, out)]
+        people = []
+        for pid, o in scored:
+            replaced, fallbacks = smooth.counts(o['smooth']['status'], o['smooth']['replaced'])
+            people.append(dict(id=plain(pid), n_frames=int(len(o['smooth']['status'])), replaced=replaced, fallbacks=fallbacks))
+        report = dict(median_radius=int(out['smooth']['median_radius']), sigma=float(out['smooth']['sigma']), unit='frames',
+                      gaussian_radius=smooth.gaussian_radius(float(out['smooth']['sigma'])), people=people)
+        with open(osp.join(output_path, 'smooth.json'), 'w') as f:
+            json.dump(report, f, indent=1)
+        return report
 
     # ---- base.py:273-282 ------------------------------------------------------------------------------------
     def visualize_joint_cam_mesh(self, debug_result, joint_cam, frames, output_path):
@@ -981,6 +1039,8 @@ class Predictor:
             # every rank holds all frames' results after the gather; the reports (result txt, plots, mp4, debug CSVs and
             # OBJ) are ONE set of files in <output>: rank 0 writes them, the others would race it on the same names
             return out
+        if 'smooth' in out:                                        # only with a smoothing knob on
+            self.write_smooth_report(out, people_out, output_path)
         fidx = out['frames']
         timestamp = (0, fidx, int(frames.shape[0]))                # base.py:130 (torch tensor or numpy: both have .shape)
         debug_path = osp.join(output_path, 'debug')

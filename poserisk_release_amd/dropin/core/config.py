@@ -61,6 +61,12 @@ absent from the reference and all optional:
                               person's SMPL parameters, and with gpu_video the image region of <TITLE>_people is the frame with
                               everybody's fitted mesh over it, the people depth-tested against each other (pr_render_people), also
                               written on its own as <TITLE>_people_mesh (args.people_mesh overrides it)
+    cfg.DATASET.smooth_median_radius  0 (off) .. 15, in FRAMES: each track's joint rotations (and cam, betas) are replaced by the
+                              medoid of their window of that many frames on each side before scoring: removes single-frame
+                              outliers (args.smooth_median_radius overrides it)
+    cfg.DATASET.smooth_sigma  0.0 (off) or the standard deviation, in FRAMES, of the Gaussian that then averages each track's
+                              poses over min(ceil(3 sigma), 15) frames on each side: removes jitter.  With both at 0 nothing
+                              changes anywhere (args.smooth_sigma overrides it; pr_smooth_tracks)
     cfg.TRACKER               the built-in person detector and tracker (poserisk_release_amd.detector: YOLOv3 on the GPU,
                               poserisk_release_amd.sort: SORT on the host).  All of it is inert while `weights` is '':
                               weights '' | the path of a darknet yolov3.weights file; img_size (416, 416) = (rows, columns) of the
@@ -132,7 +138,8 @@ def _defaults(root):
                     'render_mesh': False, 'gpu_video': False, 'gpu_video_codec': '', 'gpu_video_quality': 90,
                     'front_max_w': 800, 'front_max_h': 450, 'jpeg_entropy': 'auto', 'jpeg_progressive': True,
                     'yuv_matrix': '601', 'video_decoder': '', 'video_encoder': '', 'video_encoder_ext': '.mp4',
-                    'video_chroma': '420mpeg2', 'persons': 'target', 'people_mesh': False},
+                    'video_chroma': '420mpeg2', 'persons': 'target', 'people_mesh': False,
+                    'smooth_median_radius': 0, 'smooth_sigma': 0.0},
         'MODEL': {'input_shape': (224, 224)},
         'SPIN': {'spin_dir': spin_dir, 'SMPL_MEAN_PARAMS': osp.join(spin_data, 'smpl_mean_params.npz'),
                  'checkpoint': osp.join(spin_data, 'model_checkpoint.pt'),
