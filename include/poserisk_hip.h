@@ -461,7 +461,8 @@ int pr_frames_forward(pr_hmr_t* hmr, pr_smpl_t* smpl, const float* x_dev, int B,
  *     bit 2  a face index outside [0, V) (that face is skipped)
  * workspace: device memory of at least pr_render_workspace_bytes(N, V, F, H, W) bytes (z-buffer, projected vertices, face
  * colours, big-face queue), owned by the caller.  Argument errors return PR_ERR_INVALID before any device work; N = 0 returns
- * PR_OK.  Asynchronous on `stream`, no allocation, no synchronisation. */
+ * PR_OK.  Asynchronous on `stream`, no allocation, no synchronisation.  Launches: r4's five kernels, as the case of one mesh
+ * per canvas (canvas n = crop n over frame frame_idx[n], no depth step); face_id stays the face's own index f. */
 typedef struct pr_render_args {
   const float* verts;
   const int32_t* faces;
@@ -626,7 +627,8 @@ int pr_compose_people(const pr_compose_people_args* args, void* stream);
  *   projected vertices, face colours and the big-face queue, sized by N), owned by the caller.  Argument errors return
  *   PR_ERR_INVALID before any device work.  M = 0 returns PR_OK; N = 0 with M > 0 is valid and copies the frames (the mesh
  *   pointers, V, F and P are then not looked at).  Asynchronous on `stream`, no allocation, no synchronisation.  Launches:
- *   clear, vertex, face, big face, resolve (N = 0: clear and resolve). */
+ *   clear, vertex, face, big face, resolve (N = 0: clear and resolve).  These are the only raster kernels: r1's entry runs
+ *   them too.  canvas is required whenever N > 0 (a null canvas is an argument error, not r1's identity). */
 #define PR_RENDER_Z_STEP_MAX (1 << 24)
 typedef struct pr_render_people_args {
   const float* verts;        /* f32[N,V,3] */

@@ -508,15 +508,7 @@ class Predictor:
         from poserisk_release_amd import ops, render
         if 'rotmat' not in out:
             raise ValueError("render_overlay needs score_frames(..., with_smpl_params=True) (or the render_mesh knob)")
-        layer = self.smpl_model.layer['neutral']
-        faces = np.asarray(self.smpl_model.face)
-        if faces.ndim != 2 or faces.shape[0] == 0:
-            raise ValueError("the SMPL model has no faces to draw")
-        scheme = None if title is None else str(title).upper()
-        face_part = render.face_parts(layer.th_weights.numpy(), faces, scheme)
-        frames = self._on_device(frames)
-        dev = frames.device
-        faces_dev = torch.as_tensor(faces.astype(np.int32), device=dev)
+        scheme, faces, face_part, frames, dev, faces_dev = self._mesh_setup(frames, title)
         fidx, n = np.asarray(out['frames']), len(out['frames'])
         info = out.get('add_info') or default_information()
         for i in range(0, n, self.batch_size):
@@ -526,6 +518,18 @@ class Predictor:
                                  scale=out.get('bbox_scale', cfg.DATASET.bbox_scale), frame_idx=fidx[i:j].astype(np.int32),
                                  face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
             yield fidx[i:j], img
+
+    def _mesh_setup(self, frames, title):
+        """What render_overlay and render_people share before their loops -> (scheme, the model's faces, face_part by the
+        scheme, frames on the device, that device, the faces on it)."""
+        from poserisk_release_amd import render
+        faces = np.asarray(self.smpl_model.face)
+        if faces.ndim != 2 or faces.shape[0] == 0:
+            raise ValueError("the SMPL model has no faces to draw")
+        scheme = None if title is None else str(title).upper()
+        face_part = render.face_parts(self.smpl_model.layer['neutral'].th_weights.numpy(), faces, scheme)
+        frames = self._on_device(frames)
+        return scheme, faces, face_part, frames, frames.device, torch.as_tensor(faces.astype(np.int32), device=frames.device)
 
     def _posed_meshes(self, rotmat, betas, info, scheme, dev):
         """rotmat f32[n,24,3,3] + betas f32[n,10] (n <= batch_size) -> (vertices f32[n,V,3] on `dev`, part_rgb u8[n,P,3]): the
@@ -550,16 +554,8 @@ class Predictor:
         outs = people_out['people']
         if any('rotmat' not in o for o in outs):
             raise ValueError("render_people needs score_people(..., with_smpl_params=True) (or the people_mesh knob)")
-        layer = self.smpl_model.layer['neutral']
-        faces = np.asarray(self.smpl_model.face)
-        if faces.ndim != 2 or faces.shape[0] == 0:
-            raise ValueError("the SMPL model has no faces to draw")
-        scheme = None if title is None else str(title).upper()
-        face_part = render.face_parts(layer.th_weights.numpy(), faces, scheme)
-        frames = self._on_device(frames)
-        dev = frames.device
+        scheme, faces, face_part, frames, dev, faces_dev = self._mesh_setup(frames, title)
         n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        faces_dev = torch.as_tensor(faces.astype(np.int32), device=dev)
         if not outs:
             raise ValueError("render_people: nobody was scored")
         scale = outs[0].get('bbox_scale', cfg.DATASET.bbox_scale)
@@ -1064,16 +1060,19 @@ class Predictor:
         if on_gpu:
             frames = torch.as_tensor(frames).to(self.device)       # one upload for both titles' videos (and the mesh)
 
+        def with_mesh_sink(name, write):                           # one rendering of the meshes feeds the video and <output>/<name>
+            mesh = self._open_sink(output_path, name, frames.shape[1:3], fps, bgr)
+            try:
+                write(mesh.put)
+            except BaseException:
+                mesh.abort()                    # the video's error stands; a mesh encoder child is reaped all the same
+                raise
+            mesh.close()
+
         def videos(title):                                         # base.py:156,173: behind the title's plot
             if on_gpu:
                 if self.render_mesh:                # one rendering of the mesh feeds both outputs
-                    mesh = self._open_sink(output_path, title + '_mesh', frames.shape[1:3], fps, bgr)
-                    try:
-                        self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=mesh.put)
-                    except BaseException:
-                        mesh.abort()                    # the video's error stands; a mesh encoder child is reaped all the same
-                        raise
-                    mesh.close()
+                    with_mesh_sink(title + '_mesh', lambda put: self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=put))
                 else:
                     self.write_gpu_video(out, frames, output_path, title, bgr, fps)
             elif show:                                             # ... (OpenCV only)
@@ -1098,13 +1097,8 @@ class Predictor:
                     if title.lower() not in out:
                         continue
                     if people_mesh:                     # one rendering of the meshes feeds both outputs, as in videos()
-                        mesh = self._open_sink(output_path, title + '_people_mesh', frames.shape[1:3], fps, bgr)
-                        try:
-                            self.write_people_video(people_out, frames, output_path, title, bgr, fps, mesh_sink=mesh.put)
-                        except BaseException:
-                            mesh.abort()
-                            raise
-                        mesh.close()
+                        with_mesh_sink(title + '_people_mesh',
+                                       lambda put: self.write_people_video(people_out, frames, output_path, title, bgr, fps, mesh_sink=put))
                     else:
                         self.write_people_video(people_out, frames, output_path, title, bgr, fps)
             elif show:

@@ -72,6 +72,48 @@ def _dev_tensor(x, dtype, dev, shape=None, what=""):
     return t
 
 
+def _host_faces(faces, V):
+    """faces int[F,3] as a host array, its indices checked against [0, V): once, here, for both wrappers."""
+    faces_host = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if faces_host.ndim != 2 or faces_host.shape[1] != 3 or faces_host.shape[0] == 0:
+        raise ValueError(f"faces must be int [F,3], got shape {faces_host.shape}")
+    if int(faces_host.min()) < 0 or int(faces_host.max()) >= V:
+        raise ValueError(f"face indices {int(faces_host.min())}..{int(faces_host.max())} outside [0, {V})")
+    return faces_host
+
+
+def _mesh_tensors(faces, faces_host, cam, bboxes, face_part, part_rgb, N, dev, min_parts):
+    """What both entries read beside the vertices, on `dev` in the kernel's dtypes: faces, cam [N,3], bboxes [N,4], face_part
+    [F] (None: all part 0) and part_rgb [N,P,3], P >= min_parts ([P,3]: the same for every mesh; None: neutral grey)."""
+    F = faces_host.shape[0]
+    f = _dev_tensor(faces if isinstance(faces, torch.Tensor) else faces_host, torch.int32, dev)
+    c = _dev_tensor(cam, torch.float32, dev, (N, 3), "cam")
+    bb = _dev_tensor(bboxes, torch.float32, dev, (N, 4), "bboxes")
+    fp = _dev_tensor(np.zeros(F, np.int32) if face_part is None else face_part, torch.int32, dev, (F,), "face_part")
+    rgb = _dev_tensor(NEUTRAL_RGB[None] if part_rgb is None else part_rgb, torch.uint8, dev)
+    if rgb.dim() == 2:
+        rgb = rgb[None].expand(N, -1, -1).contiguous()
+    if rgb.dim() != 3 or rgb.shape[0] != N or rgb.shape[2] != 3 or rgb.shape[1] < min_parts:
+        raise ValueError(f"part_rgb must be u8[N,P,3] or u8[P,3], got {tuple(rgb.shape)}")
+    return f, c, bb, fp, rgb
+
+
+def _outputs(out, images, lead, N, V, H, W, dev, return_face_id, return_vert_fx, return_status):
+    """out u8[images,H,W,3] (checked when given; `lead` names its first axis) and the optional face_id, vert_fx and status."""
+    if out is None:
+        out = torch.empty((images, H, W, 3), dtype=torch.uint8, device=dev)
+    elif out.shape != (images, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous uint8 [{lead},H,W,3] tensor on the frames' device")
+    fid = torch.empty((images, H, W), dtype=torch.int32, device=dev) if return_face_id else None
+    vfx = torch.empty((N, V, 4), dtype=torch.int32, device=dev) if return_vert_fx else None
+    st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    return out, fid, vfx, st
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def overlay(frames, verts, faces, cam, bboxes, scale=1.2, frame_idx=None, face_part=None, part_rgb=None, alpha=0.6,
             bgr=False, out=None, return_face_id=False, return_vert_fx=False, return_status=False):
     """Draw the meshes over their frames on the GPU.
@@ -90,42 +132,20 @@ def overlay(frames, verts, faces, cam, bboxes, scale=1.2, frame_idx=None, face_p
     n_frames, H, W, _ = frames.shape
     v = _dev_tensor(verts, torch.float32, dev, (None, None, 3), "verts")
     N, V = v.shape[0], v.shape[1]
-    faces_host = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
-    if faces_host.ndim != 2 or faces_host.shape[1] != 3 or faces_host.shape[0] == 0:
-        raise ValueError(f"faces must be int [F,3], got shape {faces_host.shape}")
-    if int(faces_host.min()) < 0 or int(faces_host.max()) >= V:
-        raise ValueError(f"face indices {int(faces_host.min())}..{int(faces_host.max())} outside [0, {V})")
+    faces_host = _host_faces(faces, V)
     F = faces_host.shape[0]
-    f = _dev_tensor(faces if isinstance(faces, torch.Tensor) else faces_host, torch.int32, dev)
-    c = _dev_tensor(cam, torch.float32, dev, (N, 3), "cam")
-    bb = _dev_tensor(bboxes, torch.float32, dev, (N, 4), "bboxes")
-    fp = _dev_tensor(np.zeros(F, np.int32) if face_part is None else face_part, torch.int32, dev, (F,), "face_part")
-    rgb = _dev_tensor(NEUTRAL_RGB[None] if part_rgb is None else part_rgb, torch.uint8, dev)
-    if rgb.dim() == 2:
-        rgb = rgb[None].expand(N, -1, -1).contiguous()
-    if rgb.dim() != 3 or rgb.shape[0] != N or rgb.shape[2] != 3:
-        raise ValueError(f"part_rgb must be u8[N,P,3] or u8[P,3], got {tuple(rgb.shape)}")
-    P = rgb.shape[1]
-    idx = None
-    if frame_idx is not None:
-        idx = _dev_tensor(frame_idx, torch.int32, dev, (N,), "frame_idx")
-    if out is None:
-        out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=dev)
-    elif out.shape != (N, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous uint8 [N,H,W,3] tensor on the frames' device")
-    fid = torch.empty((N, H, W), dtype=torch.int32, device=dev) if return_face_id else None
-    vfx = torch.empty((N, V, 4), dtype=torch.int32, device=dev) if return_vert_fx else None
-    st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    f, c, bb, fp, rgb = _mesh_tensors(faces, faces_host, cam, bboxes, face_part, part_rgb, N, dev, min_parts=0)
+    idx = None if frame_idx is None else _dev_tensor(frame_idx, torch.int32, dev, (N,), "frame_idx")
+    out, fid, vfx, st = _outputs(out, N, "N", N, V, H, W, dev, return_face_id, return_vert_fx, return_status)
     lib = _lib.load()
     nbytes = lib.pr_render_workspace_bytes(N, V, F, H, W)
     ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    args = _lib.RenderArgs(v.data_ptr(), f.data_ptr(), c.data_ptr(), bb.data_ptr(), frames.data_ptr(), ptr(idx),
-                           fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), ptr(fid), ptr(vfx), ptr(st),
-                           N, V, F, P, n_frames, H, W, int(bool(bgr)), float(scale), float(alpha))
+    args = _lib.RenderArgs(v.data_ptr(), f.data_ptr(), c.data_ptr(), bb.data_ptr(), frames.data_ptr(), _ptr(idx),
+                           fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), _ptr(fid), _ptr(vfx), _ptr(st),
+                           N, V, F, rgb.shape[1], n_frames, H, W, int(bool(bgr)), float(scale), float(alpha))
     _lib.check(lib.pr_render_overlay(args, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
                "pr_render_overlay")
-    extra = [t for t, want in ((fid, return_face_id), (vfx, return_vert_fx), (st, return_status)) if want]
+    extra = [t for t in (fid, vfx, st) if t is not None]
     return (out, *extra) if extra else out
 
 
@@ -182,11 +202,7 @@ def overlay_people(frames, verts, faces, cam, bboxes, canvas, src_idx, z_step=No
     if len(vshape) != 3 or vshape[2] != 3:
         raise ValueError(f"verts must have shape (N, V, 3), got {tuple(vshape)}")
     N, V = int(vshape[0]), int(vshape[1])
-    faces_host = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
-    if faces_host.ndim != 2 or faces_host.shape[1] != 3 or faces_host.shape[0] == 0:
-        raise ValueError(f"faces must be int [F,3], got shape {faces_host.shape}")
-    if int(faces_host.min()) < 0 or int(faces_host.max()) >= V:
-        raise ValueError(f"face indices {int(faces_host.min())}..{int(faces_host.max())} outside [0, {V})")
+    faces_host = _host_faces(faces, V)
     F = faces_host.shape[0]
     cv = _host_ints(canvas, N, "canvas")
     M = int(np.shape(src_idx)[0]) if np.ndim(src_idx) == 1 else -1
@@ -201,35 +217,19 @@ def overlay_people(frames, verts, faces, cam, bboxes, canvas, src_idx, z_step=No
     dev = frames.device
     frames = frames.contiguous()
     v = _dev_tensor(verts, torch.float32, dev, (N, V, 3), "verts")
-    f = _dev_tensor(faces if isinstance(faces, torch.Tensor) else faces_host, torch.int32, dev)
-    c = _dev_tensor(cam, torch.float32, dev, (N, 3), "cam")
-    bb = _dev_tensor(bboxes, torch.float32, dev, (N, 4), "bboxes")
-    fp = _dev_tensor(np.zeros(F, np.int32) if face_part is None else face_part, torch.int32, dev, (F,), "face_part")
-    rgb = _dev_tensor(NEUTRAL_RGB[None] if part_rgb is None else part_rgb, torch.uint8, dev)
-    if rgb.dim() == 2:
-        rgb = rgb[None].expand(N, -1, -1).contiguous()
-    if rgb.dim() != 3 or rgb.shape[0] != N or rgb.shape[2] != 3 or rgb.shape[1] == 0:
-        raise ValueError(f"part_rgb must be u8[N,P,3] or u8[P,3], got {tuple(rgb.shape)}")
-    P = rgb.shape[1]
+    f, c, bb, fp, rgb = _mesh_tensors(faces, faces_host, cam, bboxes, face_part, part_rgb, N, dev, min_parts=1)
     cv, si = torch.from_numpy(cv).to(dev), torch.from_numpy(si).to(dev)
     zs = None if zs is None else torch.from_numpy(zs).to(dev)
-    if out is None:
-        out = torch.empty((M, H, W, 3), dtype=torch.uint8, device=dev)
-    elif out.shape != (M, H, W, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous uint8 [M,H,W,3] tensor on the frames' device")
-    fid = torch.empty((M, H, W), dtype=torch.int32, device=dev) if return_face_id else None
-    vfx = torch.empty((N, V, 4), dtype=torch.int32, device=dev) if return_vert_fx else None
-    st = torch.empty((N,), dtype=torch.int32, device=dev) if return_status else None
+    out, fid, vfx, st = _outputs(out, M, "M", N, V, H, W, dev, return_face_id, return_vert_fx, return_status)
     cst = torch.empty((M,), dtype=torch.int32, device=dev) if return_canvas_status else None
     lib = _lib.load()
     nbytes = lib.pr_render_people_workspace_bytes(N, M, V, F, H, W)
     ws = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     args = _lib.RenderPeopleArgs(v.data_ptr(), f.data_ptr(), c.data_ptr(), bb.data_ptr(), frames.data_ptr(), cv.data_ptr(),
-                                 si.data_ptr(), ptr(zs), fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), ptr(fid), ptr(vfx),
-                                 ptr(st), ptr(cst), N, M, V, F, P, n_frames, H, W, int(bool(bgr)), float(scale), float(alpha))
+                                 si.data_ptr(), _ptr(zs), fp.data_ptr(), rgb.data_ptr(), out.data_ptr(), _ptr(fid), _ptr(vfx),
+                                 _ptr(st), _ptr(cst), N, M, V, F, rgb.shape[1], n_frames, H, W, int(bool(bgr)), float(scale),
+                                 float(alpha))
     _lib.check(lib.pr_render_people(args, ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
                "pr_render_people")
-    extra = [t for t, want in ((fid, return_face_id), (vfx, return_vert_fx), (st, return_status), (cst, return_canvas_status))
-             if want]
+    extra = [t for t in (fid, vfx, st, cst) if t is not None]
     return (out, *extra) if extra else out

@@ -2,7 +2,8 @@
 a closed synthetic body with SMPL's counts (V = 6890, F = 13776) at person size, REBA-like part colours.  Prints ms per
 batch, frames/s, the HBM traffic floor, and the numpy reference's time for one frame (tests/raster_ref.py).
 
-usage: python scripts/bench_render.py [--batch 64] [--iters 50] [--warmup 5] [--out profiles/<name>.json]"""
+usage: python scripts/bench_render.py [--batch 64] [--iters 50] [--rounds 1] [--warmup 5] [--out profiles/<name>.json]
+(--rounds R: ms_per_batch is the median of R timed rounds of --iters calls, each listed in ms_per_round)"""
 import argparse
 import json
 import os
@@ -39,6 +40,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--height", type=int, default=450)
     ap.add_argument("--width", type=int, default=800)
@@ -72,12 +74,15 @@ def main():
         _lib.check(lib.pr_render_overlay(args, ws.data_ptr(), nb, stream), "pr_render_overlay")
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
-        lib.pr_render_overlay(args, ws.data_ptr(), nb, stream)
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / a.iters
+    rounds = []
+    for _ in range(a.rounds):
+        e0.record()
+        for _ in range(a.iters):
+            lib.pr_render_overlay(args, ws.data_ptr(), nb, stream)
+        e1.record()
+        torch.cuda.synchronize()
+        rounds.append(e0.elapsed_time(e1) / a.iters)
+    ms = float(np.median(rounds))
     # the wrapper end to end (host face check, uploads, workspace) for comparison
     t0 = time.perf_counter()
     for _ in range(5):
@@ -94,7 +99,7 @@ def main():
     keys = rr.raster_keys(vfx[0], faces, H, W)
     rr.composite(frames[0].cpu().numpy(), rr.face_id(keys), rr.face_colours(verts[0], faces, fpart, rgb[0]), 0.6)
     numpy_ms = (time.perf_counter() - t0) * 1e3
-    rec = {"batch": B, "height": H, "width": W, "V": V, "F": F, "ms_per_batch": round(ms, 4),
+    rec = {"batch": B, "height": H, "width": W, "V": V, "F": F, "ms_per_batch": round(ms, 4), "ms_per_round": [round(x, 4) for x in rounds],
            "frames_per_s": round(B / ms * 1e3, 1), "wrapper_ms_per_batch": round(wrapper_ms, 3),
            "covered_fraction": round(coverage, 4), "traffic_floor_bytes": floor_bytes,
            "traffic_floor_ms": round(floor_bytes / HBM_BYTES_PER_S * 1e3, 4),

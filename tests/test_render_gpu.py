@@ -1,12 +1,18 @@
 """GPU: the mesh overlay (csrc/render.hip, pr_render_overlay) against the numpy restatement of its contract
 (tests/raster_ref.py) -- face_id bit for bit when the reference is fed the GPU's own vert_fx -- and end to end through
 Predictor.score_frames -> render_overlay."""
+import ctypes as C
+import json
+import os
+import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import guard_band as gb
+import people_mesh_cases as pmc
 import raster_ref as rr
 from poserisk_release_amd import _lib, render, synth
 
@@ -292,3 +298,93 @@ def test_predictor_call_writes_one_image_per_track_frame(gpu_device, tmp_path):
     dbg, _ = _predictor(gpu_device, debug=True, debug_frame=4)
     dbg(str(src), "", str(tmp_path / "dbg"))
     assert (tmp_path / "dbg" / "debug" / "mesh_overlay.png").is_file()
+
+
+# ---- pr_render_overlay's own pins: recorded bytes, argument errors, guard bands ---------------------------------------------------
+def test_bytes_are_those_of_the_recorded_build(gpu_device):
+    """out, face_id, vert_fx and status on scripts/render_overlay_digests.py's scenes hash to what the build recorded in
+    tests/render_overlay_digests.json wrote (the commit before the overlay moved onto the people kernels)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
+    import render_overlay_digests as rod
+    with open(rod.DIGESTS) as f:
+        want = json.load(f)["digests"]
+    got = rod.digests(gpu_device)
+    assert sorted(got) == sorted(want) and len(got) == 6
+    for name in want:
+        assert got[name] == want[name], name
+
+
+def _c_case(gpu_device):
+    """A soup of N = 3 crops at 37 x 53 over two frames with a frame index, as host arrays and as device tensors in the dtypes
+    the C entry reads."""
+    H, W = pmc.SIZES[0]
+    sc = pmc.soup(3, H, W, seed=8)
+    host = dict(verts=sc["verts"], faces=sc["faces"], cam=sc["cam"], bboxes=sc["bboxes"], frames=pmc.frames(2, H, W),
+                frame_idx=np.array([1, 0, 1], np.int32), face_part=np.arange(len(sc["faces"]), dtype=np.int32) % 5,
+                part_rgb=pmc.part_table(3, 5))
+    return host, {k: torch.from_numpy(np.ascontiguousarray(v)).to(gpu_device) for k, v in host.items()}
+
+
+def test_every_argument_error_of_the_c_entry(gpu_device):
+    lib = _lib.load()
+    H, W = pmc.SIZES[0]
+    host, t = _c_case(gpu_device)
+    N, V, F = 3, host["verts"].shape[1], len(host["faces"])
+    out = torch.full((N, H, W, 3), 7, dtype=torch.uint8, device=gpu_device)
+    status = torch.full((N,), -7, dtype=torch.int32, device=gpu_device)
+    nb = lib.pr_render_workspace_bytes(N, V, F, H, W)
+    assert nb >= N * H * W * 8 + N * V * 16 + 2 * N * F * 4
+    ws = torch.empty((nb,), dtype=torch.uint8, device=gpu_device)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(ws_bytes=nb, workspace=ws.data_ptr(), **over):
+        v = dict({k: x.data_ptr() for k, x in t.items()}, out=out.data_ptr(), face_id=None, vert_fx=None, status=status.data_ptr(),
+                 N=N, V=V, F=F, P=5, n_frames=2, H=H, W=W, bgr=0, scale=pmc.SCALE, alpha=0.6)
+        v.update(over)
+        rc = lib.pr_render_overlay(C.byref(_lib.RenderArgs(**v)), workspace, ws_bytes, stream)
+        return rc, lib.pr_last_error().decode()
+    required = ("verts", "faces", "cam", "bboxes", "frames", "face_part", "part_rgb", "out")
+    for over, word in ((dict(N=-1), "N = -1"), *((({name: None}), "null required pointer") for name in required),
+                       (dict(workspace=None), "null workspace"), (dict(ws_bytes=nb - 1), "workspace of"),
+                       (dict(V=2), "V=2"), (dict(F=0), "F=0"), (dict(P=0), "P=0"), (dict(n_frames=0), "frames=0"),
+                       (dict(H=0), "1..4096"), (dict(W=4097), "1..4096"), (dict(scale=0.0), "scale"),
+                       (dict(alpha=1.5), "alpha"), (dict(alpha=-0.1), "alpha"), (dict(frame_idx=None), "without a frame index")):
+        rc, msg = call(**over)
+        assert rc == -1 and word in msg and "pr_render_overlay" in msg, (over, rc, msg)       # PR_ERR_INVALID
+    assert lib.pr_render_overlay(None, ws.data_ptr(), nb, stream) == -1
+    assert "pr_render_overlay" in lib.pr_last_error().decode() and "null argument struct" in lib.pr_last_error().decode()
+    # N = 0: PR_OK before anything is looked at
+    nothing = {k: None for k in (*required, "frame_idx", "status")}
+    assert call(N=0, workspace=None, ws_bytes=0, V=0, F=0, P=0, n_frames=0, H=0, W=0, **nothing)[0] == 0
+    torch.cuda.synchronize()
+    assert (out == 7).all() and (status == -7).all()                                      # no device work happened
+    assert call()[0] == 0                                                                 # and the call these were derived from is valid
+    torch.cuda.synchronize()
+    assert status.cpu().tolist() == [0, 0, 0] and (out.cpu().numpy() != host["frames"][[1, 0, 1]]).any()
+
+
+def test_every_tensor_of_the_c_entry_stays_inside_its_guard_bands(gpu_device):
+    """Outputs between canary guards, inputs between guards of NaN / 255 / 0x7fffffff (tests/guard_band.py); the soup holds
+    faces larger than the frame and faces across every frame edge, and the workspace is exactly pr_render_workspace_bytes
+    long.  (A vertex coordinate may be the int32 canary, -7, in its own right: the comparison with an unguarded run says
+    whether every word was written.)"""
+    H, W = pmc.SIZES[0]
+    host, t = _c_case(gpu_device)
+    N, V, F = 3, host["verts"].shape[1], len(host["faces"])
+    lib = _lib.load()
+    nb = lib.pr_render_workspace_bytes(N, V, F, H, W)
+
+    def call(i, o):
+        ws = torch.empty((nb,), dtype=torch.uint8, device=gpu_device)
+        args = _lib.RenderArgs(i["verts"].data_ptr(), i["faces"].data_ptr(), i["cam"].data_ptr(), i["bboxes"].data_ptr(),
+                               i["frames"].data_ptr(), i["frame_idx"].data_ptr(), i["face_part"].data_ptr(), i["part_rgb"].data_ptr(),
+                               o["out"].data_ptr(), o["face_id"].data_ptr(), o["vert_fx"].data_ptr(), o["status"].data_ptr(),
+                               N, V, F, 5, 2, H, W, 0, pmc.SCALE, 0.6)
+        _lib.check(lib.pr_render_overlay(C.byref(args), ws.data_ptr(), nb, torch.cuda.current_stream().cuda_stream), "pr_render_overlay")
+    got = gb.run_guarded(call, t, {"out": ((N, H, W, 3), torch.uint8), "face_id": ((N, H, W), torch.int32),
+                                   "vert_fx": ((N, V, 4), torch.int32), "status": ((N,), torch.int32)}, may_hold_canary=("out", "vert_fx"))
+    kw = {k: v for k, v in host.items() if k != "frames"}
+    want = render.overlay(t["frames"], scale=pmc.SCALE, alpha=0.6, return_face_id=True, return_vert_fx=True, return_status=True, **kw)
+    for name, w in zip(("out", "face_id", "vert_fx", "status"), want):
+        assert np.array_equal(got[name].cpu().numpy(), w.cpu().numpy()), name
+    assert (want[1] >= 0).any() and not want[3].any()
