@@ -1743,6 +1743,86 @@ int pr_smooth_tracks(const pr_smooth_params* params, const pr_smooth_inputs* inp
                      const int* track_start_host, int T, int N, const pr_smooth_outputs* outputs, int32_t* status_dev,
                      void* workspace_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* t1  REBA's activity score and RULA's muscle use from each track's motion (csrc/activity.hip; ABI 16: added, nothing changed) */
+/* extends: add_info["REBA"]["Activity_Score"] lib/utils/reba.py:69 and add_info["RULA"]["A_Muscle_use_L" / "_R", "B_Muscle_use"] */
+/*          lib/utils/rula.py:75-81, constants of the information file in the reference, which never looks at time */
+/* ------------------------------------------------------------------------------------ */
+/* Rows and tracks as in s1: rotmat f32[N,24,3,3] and frame_no i32[N] on the device, track_start int[T + 1] on the HOST with
+ * s1's rules and refusals.  Every output is an integer and every comparison is made on a float64 value that
+ * tests/activity_ref.py (numpy) reproduces bit for bit: there is no tolerance anywhere.
+ *
+ * Parameters (pr_activity_params): hold_frames H in 1..PR_ACTIVITY_MAX_HOLD, rapid_frames R in 1..H, gap_frames G >= 1,
+ * rep_events E >= 0; dot_static, dot_move, dot_rapid finite and in [-1, 3]: the thresholds 1 + 2 cos(angle), which the caller
+ * computes once (poserisk_release_amd/activity.py::thresholds); no kernel calls a trigonometric function.  Anything else is
+ * refused by name before any device work.
+ *
+ * Scored joints, bit b = 0..11: Torso 3, Neck 12, L_Knee 4, R_Knee 5, L_Thorax 13, L_Shoulder 16, L_Elbow 18, L_Wrist 20,
+ * R_Thorax 14, R_Shoulder 17, R_Elbow 19, R_Wrist 21 (the joints the rules read).  Masks: B = bits 0..3, L = bits 4..7,
+ * R = bits 8..11.
+ *
+ * dot_b(k, i) = sum over e = 0..8, ascending, of (double)R_k[e] * (double)R_i[e], R_k the 9 floats of joint b in row k: the
+ * trace of R_k^T R_i = 1 + 2 cos(theta).  The product of two floats is exact in float64, so a fused multiply-add and a
+ * multiply followed by an add round alike and the library's -ffp-contract setting cannot change a bit of it.
+ *
+ * Window W_i(L): the rows k of row i's track with k <= i, i - k <= L and 0 <= frame_no[i] - frame_no[k] <= L (differences in
+ * 64 bits).  Like s1's it is defined and memory-safe for ANY frame_no content: no address is formed outside rows
+ * i - L .. i + L clamped to the track (a workgroup's addresses lie in the union of these ranges over its rows).
+ *
+ * Stage A, events; sequential by definition, per track and joint.  The anchor starts at the track's first row.  For each
+ * further row k, ascending: if frame_no[k] - frame_no[k - 1] > G or < 0 the anchor becomes k and no event is recorded; else
+ * if dot_b(anchor, k) < dot_move, bit b of moved[k] is set and the anchor becomes k.
+ *
+ * Stage B, per row i and joint b.  p = the first (lowest) row of W_i(H).  covered_i: frame_no[i] - frame_no[p] > H - G and
+ * every two rows that follow each other in W_i(H) differ by 1..G frames.
+ *   held     = covered_i and dot_b(k, i) >= dot_static for every k in W_i(H)
+ *   repeated = covered_i and (the number of k in W_i(H) with bit b of moved[k] set) > E
+ *   rapid    = dot_b(k, i) < dot_rapid for some k in W_i(R)
+ * The comparisons are written exactly so: a NaN makes each of them false.
+ *
+ * Stage C, spread: the final held and repeated bits of row i are the OR of stage B's over the rows e of the same track with
+ * e >= i, e - i <= H and 0 <= frame_no[e] - frame_no[i] <= H: the whole held minute is marked, not only its end.  rapid is
+ * not spread.
+ *
+ * Outputs (device): flags i32[N,4] = the held, repeated, rapid and moved masks; adds i32[N,4] =
+ *   reba_activity = (held != 0) + (repeated != 0) + (rapid != 0),   a_muscle_l = ((held | repeated) & L) != 0,
+ *   a_muscle_r = ((held | repeated) & R) != 0,                      b_muscle = ((held | repeated) & B) != 0.
+ * workspace_dev: pr_activity_workspace_bytes(N) bytes, 4-byte aligned (stage A's and stage B's masks).  No pointer may be
+ * the same as another.
+ *
+ * Three launches on `stream` per PR_ACTIVITY_TRACKS_PER_LAUNCH tracks (their bounds travel in the kernels' arguments).
+ * Stage A: a workgroup per track, twelve lanes walk the twelve chains through chunks staged in LDS.  Stage B: a workgroup
+ * takes pr_activity_tile_rows() consecutive rows (counted from the first row of the launch's tracks) and streams them and the
+ * H rows before them through LDS, newest first, in chunks of pr_activity_chunk_rows() rows; it stops where no output of the
+ * tile can change any more.  Stage C reads the masks only.  Asynchronous, no allocation, no copy, no synchronisation
+ * (capturable).  N = 0 (with T >= 0 and all starts 0) returns PR_OK. */
+#define PR_ACTIVITY_MAX_HOLD 16384
+#define PR_ACTIVITY_TRACKS_PER_LAUNCH 256
+typedef struct pr_activity_params {
+  int32_t hold_frames;  /* H */
+  int32_t rapid_frames; /* R */
+  int32_t gap_frames;   /* G */
+  int32_t rep_events;   /* E */
+  double dot_static;
+  double dot_move;
+  double dot_rapid;
+} pr_activity_params;
+int pr_activity_tile_rows(void);
+int pr_activity_chunk_rows(void);
+size_t pr_activity_workspace_bytes(int N); /* 0 for N < 0 */
+int pr_activity_tracks(const pr_activity_params* params, const float* rotmat_dev, const int32_t* frame_no_dev,
+                       const int* track_start_host, int T, int N, int32_t* flags_dev, int32_t* adds_dev, void* workspace_dev,
+                       void* stream);
+
+/* The scorers of a12-a13 with per-row addends.  activity_rows_dev i32[N] or NULL: row f's value is added to
+ * info->activity where reba.py:69 adds it.  muscle_rows_dev i32[N,3] (a_l, a_r, b) or NULL: row f's values are added to
+ * info->a_muscle_l, ->a_muscle_r and ->b_muscle where rula.py:75-81 add them.  With NULL every output is pr_reba's /
+ * pr_rula's; the rule bodies exist once (pr_reba and pr_rula are these with NULL). */
+int pr_reba_rows(const double* euler_deg_dev, int N, const pr_reba_info* info, const int32_t* activity_rows_dev,
+                 int32_t* out_dev, void* stream);
+int pr_rula_rows(const double* euler_deg_dev, int N, const pr_rula_info* info, const int32_t* muscle_rows_dev,
+                 int32_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,12 @@ class SmoothOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "replaced")]
 
 
+class ActivityParams(C.Structure):
+    """pr_activity_params (include/poserisk_hip.h, section t1)."""
+    _fields_ = [(n, C.c_int32) for n in ("hold_frames", "rapid_frames", "gap_frames", "rep_events")] + \
+               [(n, C.c_double) for n in ("dot_static", "dot_move", "dot_rapid")]
+
+
 class FramesOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("rotmat", "betas", "cam", "axis_angle", "euler_deg", "joint_cam",
                                            "verts", "reba", "rula", "status")]
@@ -259,6 +265,12 @@ SIGNATURES = {
     "pr_smooth_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "pr_smooth_tracks": (_I, [C.POINTER(SmoothParams), C.POINTER(SmoothInputs), _P, C.POINTER(_I), _I, _I, C.POINTER(SmoothOutputs),
                               _P, _P, _P]),
+    "pr_activity_tile_rows": (_I, []),
+    "pr_activity_chunk_rows": (_I, []),
+    "pr_activity_workspace_bytes": (C.c_size_t, [_I]),
+    "pr_activity_tracks": (_I, [C.POINTER(ActivityParams), _P, _P, C.POINTER(_I), _I, _I, _P, _P, _P, _P]),
+    "pr_reba_rows": (_I, [_P, _I, C.POINTER(RebaInfo), _P, _P, _P]),
+    "pr_rula_rows": (_I, [_P, _I, C.POINTER(RulaInfo), _P, _P, _P]),
 }
 
 _lib = None

@@ -98,6 +98,20 @@ int pr_rula(const double* euler_deg_dev, int N, const pr_rula_info* info, int32_
   return pr::launch_rula(euler_deg_dev, N, *info, out_dev, (hipStream_t)stream);
 }
 
+int pr_reba_rows(const double* euler_deg_dev, int N, const pr_reba_info* info, const int32_t* activity_rows_dev, int32_t* out_dev,
+                 void* stream) {
+  PR_REQUIRE(euler_deg_dev && info && out_dev && N >= 0, "pr_reba_rows: bad argument");
+  PR_REQUIRE((const void*)activity_rows_dev != (const void*)out_dev, "pr_reba_rows: activity_rows is the output");
+  return pr::launch_reba(euler_deg_dev, N, *info, out_dev, (hipStream_t)stream, activity_rows_dev);
+}
+
+int pr_rula_rows(const double* euler_deg_dev, int N, const pr_rula_info* info, const int32_t* muscle_rows_dev, int32_t* out_dev,
+                 void* stream) {
+  PR_REQUIRE(euler_deg_dev && info && out_dev && N >= 0, "pr_rula_rows: bad argument");
+  PR_REQUIRE((const void*)muscle_rows_dev != (const void*)out_dev, "pr_rula_rows: muscle_rows is the output");
+  return pr::launch_rula(euler_deg_dev, N, *info, out_dev, (hipStream_t)stream, muscle_rows_dev);
+}
+
 int pr_crop_frames(const uint8_t* frames_dev, int F, int H, int W, int bgr, const int32_t* frame_idx_dev,
                    const float* bboxes_dev, int N, float scale, float* crops_dev, int32_t* status_dev,
                    void* stream) {

@@ -30,7 +30,10 @@ int launch_fc_rows16(const float* x, const float* w, const float* bias, const fl
 int launch_rot6d(const float* pose6d, float* rotmat, long n_joints, hipStream_t s);
 int launch_pose_to_euler(const float* rotmat, int N, float* axis_angle, double* euler, int32_t* status,
                          hipStream_t s);
-int launch_reba(const double* euler, int N, const pr_reba_info& info, int32_t* out, hipStream_t s);
-int launch_rula(const double* euler, int N, const pr_rula_info& info, int32_t* out, hipStream_t s);
+// activity_rows i32[N] / muscle_rows i32[N,3] (a_l, a_r, b): per-row addends to the info's constants, or null
+int launch_reba(const double* euler, int N, const pr_reba_info& info, int32_t* out, hipStream_t s,
+                const int32_t* activity_rows = nullptr);
+int launch_rula(const double* euler, int N, const pr_rula_info& info, int32_t* out, hipStream_t s,
+                const int32_t* muscle_rows = nullptr);
 
 }  // namespace pr

@@ -627,8 +627,9 @@ __device__ inline int reba_open_branch(double a2) {  // reba.py:213-219 / :232-2
   return 1;
 }
 
+// activity_rows (i32[N] or null): row f's addend to info.activity (pr_reba_rows; section t1 derives it from the track's motion)
 __global__ void reba_kernel(const double* __restrict__ euler, int N, pr_reba_info info,
-                            int32_t* __restrict__ out) {
+                            const int32_t* __restrict__ activity_rows, int32_t* __restrict__ out) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= N) return;
   const double* p = euler + (long)f * 72;
@@ -746,16 +747,22 @@ __global__ void reba_kernel(const double* __restrict__ euler, int N, pr_reba_inf
   score_a = clampi(score_a, 1, 12);
   score_b = clampi(score_b, 1, 12);
   int32_t* o = out + (long)f * 10;
-  o[0] = kRebaC[score_a - 1][score_b - 1] + info.activity;
+  o[0] = kRebaC[score_a - 1][score_b - 1] + info.activity + (activity_rows ? activity_rows[f] : 0);
   o[1] = trunk; o[2] = neck; o[3] = leg;
   o[4] = ua_l; o[5] = ua_r; o[6] = la_l; o[7] = la_r; o[8] = wr_l; o[9] = wr_r;
 #undef ANG
 }
 
+// muscle_rows (i32[N,3] or null): row f's addends to info.a_muscle_l, .a_muscle_r and .b_muscle (pr_rula_rows)
 __global__ void rula_kernel(const double* __restrict__ euler, int N, pr_rula_info info,
-                            int32_t* __restrict__ out) {
+                            const int32_t* __restrict__ muscle_rows, int32_t* __restrict__ out) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= N) return;
+  if (muscle_rows) {
+    info.a_muscle_l += muscle_rows[(long)f * 3];
+    info.a_muscle_r += muscle_rows[(long)f * 3 + 1];
+    info.b_muscle += muscle_rows[(long)f * 3 + 2];
+  }
   const double* p = euler + (long)f * 72;
 #define ANG(j, k) p[(j)*3 + (k)]
   const double l2 = ANG(L_SHOULDER, 2), l1 = ANG(L_SHOULDER, 1);
@@ -996,14 +1003,14 @@ int launch_pose_to_euler(const float* rotmat, int N, float* aa, double* euler, i
                      dim3(kEulerFramesPerBlock * 24), 0, s, rotmat, N, aa, euler, status);
   return check_launch("pose_to_euler_kernel");
 }
-int launch_reba(const double* euler, int N, const pr_reba_info& info, int32_t* out, hipStream_t s) {
+int launch_reba(const double* euler, int N, const pr_reba_info& info, int32_t* out, hipStream_t s, const int32_t* activity_rows) {
   if (N == 0) return PR_OK;
-  hipLaunchKernelGGL(reba_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, s, euler, N, info, out);
+  hipLaunchKernelGGL(reba_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, s, euler, N, info, activity_rows, out);
   return check_launch("reba_kernel");
 }
-int launch_rula(const double* euler, int N, const pr_rula_info& info, int32_t* out, hipStream_t s) {
+int launch_rula(const double* euler, int N, const pr_rula_info& info, int32_t* out, hipStream_t s, const int32_t* muscle_rows) {
   if (N == 0) return PR_OK;
-  hipLaunchKernelGGL(rula_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, s, euler, N, info, out);
+  hipLaunchKernelGGL(rula_kernel, dim3(blocks_for(N, 64)), dim3(64), 0, s, euler, N, info, muscle_rows, out);
   return check_launch("rula_kernel");
 }
 

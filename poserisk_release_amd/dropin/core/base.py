@@ -183,6 +183,10 @@ class Predictor:
         from poserisk_release_amd.smooth import check_parameters
         self.smooth_median_radius, self.smooth_sigma = check_parameters(_knob(args, 'smooth_median_radius', 'smooth_median_radius', 0),
                                                                         _knob(args, 'smooth_sigma', 'smooth_sigma', 0.0))
+        # REBA's activity score and RULA's muscle use derived from each track's motion (poserisk_release_amd/activity.py,
+        # pr_activity_tracks): args.derive_activity, else cfg.ACTIVITY.derive (False).  Off = None: _score_tracks takes the path it
+        # always took.  On: cfg.ACTIVITY's other keys, refused by name here where they make no sense at any frame rate
+        self.activity = self._activity_knob(args)
         # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
         # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
         # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
@@ -218,6 +222,22 @@ class Predictor:
                     print("\n\nInvalid Joint name!\n\n")
                     assert 0
             self.debug_joints = dj
+
+    @staticmethod
+    def _activity_knob(args):
+        """None (off), or cfg.ACTIVITY's parameters without `derive`, checked (at 1 fps, the lowest rate at which seconds still
+        round to whole frames: what is refused there is refused at every rate)."""
+        from poserisk_release_amd.activity import DEFAULTS, check_parameters
+        section = cfg.get('ACTIVITY', None) or {}
+        derive = getattr(args, 'derive_activity', None)
+        if not bool(section.get('derive', False) if derive is None else derive):
+            return None
+        parameters = {k: section.get(k, v) for k, v in DEFAULTS.items() if k != 'derive'}
+        unknown = sorted(set(section) - set(DEFAULTS))
+        if unknown:
+            raise ValueError(f"cfg.ACTIVITY holds unknown key(s) {unknown}: {sorted(DEFAULTS)}")
+        check_parameters(1.0, **parameters)
+        return parameters
 
     def _join_world(self, args):
         """One process per GPU.  The world size asked for: `args.world_size` when the namespace has one,
@@ -337,14 +357,21 @@ class Predictor:
         frames = torch.as_tensor(frames)
         return frames if frames.device.type == 'cuda' else frames.to(self.device)
 
-    def _run_scorers(self, out, add_info):
+    def _run_scorers(self, out, add_info, rows=None):
         """REBA / RULA and the aggregation over out['result'], out['joint_cam'] -> out['reba'], out['rula'] = (final, scores,
-        logs, level).  Returns {key: the rows this call added to that scorer's angle log} (none without args.debug)."""
+        logs, level).  Returns {key: the rows this call added to that scorer's angle log} (none without args.debug).
+        `rows`: None, or the derived addends int[n,4] of these rows (activity.ADDS): column 0 goes to REBA's activity score,
+        columns 1..3 to RULA's muscle use, row by row, on top of add_info's constants."""
         added = {}
         for key, run, scorer in (('reba', self.run_reba, self.reba), ('rula', self.run_rula, self.rula)):
             if run:
                 seen = len(scorer.log)
-                final, scores, logs = self.post_processing(scorer(out['result'], out['joint_cam'], add_info))
+                if rows is None:
+                    results = scorer(out['result'], out['joint_cam'], add_info)
+                else:
+                    results = scorer(out['result'], out['joint_cam'], add_info,
+                                     rows=np.ascontiguousarray(rows[:, 0] if key == 'reba' else rows[:, 1:4]))
+                final, scores, logs = self.post_processing(results)
                 out[key] = (final, scores, logs, scorer.action_level(final[4]))
                 added[key] = scorer.log[seen:]
         return added
@@ -388,7 +415,17 @@ class Predictor:
         flags = {k: sm[k].cpu().numpy() for k in ('status', 'replaced')}
         return eul.cpu().numpy(), joint_cam.cpu().numpy(), aa.cpu().numpy(), flags
 
-    def _score_tracks(self, frames, people, add_info, bgr, bbox_scale, shard=None, with_smpl_params=False):
+    def _activity_rows(self, rotmat, people, fidx, fps, parameters):
+        """The activity knob's half of _score_tracks: ONE activity.activity_tracks call over everybody's rows of `rotmat` (host
+        f32[n,24,3,3], person after person; windows on the frame numbers `fidx`, never across people) -> (flags i32[n,4],
+        adds i32[n,4], the parameters in seconds and frames), host arrays."""
+        from poserisk_release_amd import activity
+        dev = self.smpl_model.layer['neutral'].device
+        track_start = np.cumsum([0] + [len(f) for _, _, f in people]).astype(np.int64)
+        act = activity.activity_tracks(torch.as_tensor(rotmat, device=dev), np.asarray(fidx, np.int64), track_start, fps, **parameters)
+        return act['flags'].cpu().numpy(), act['adds'].cpu().numpy(), act['parameters']
+
+    def _score_tracks(self, frames, people, add_info, bgr, bbox_scale, shard=None, with_smpl_params=False, fps=None):
         """The one scoring pass under score_frames and score_people: people [(id, bboxes f32[n,4], frame indices int[n])] -> (a
         dict per person as score_frames returns it, each person's rows of the scorers' angle logs).  Everybody's (frame index,
         box) rows are concatenated, cut into batches of self.batch_size across person boundaries (sum(n_p) / batch_size launches,
@@ -396,8 +433,15 @@ class Predictor:
         the aggregation run per person on the host.  `shard(bboxes, fidx)`, a sharding caller's, runs after the range check ->
         (lo, hi, n_total): the crops cover rows [lo, hi), this rank's, of the n_total the results are gathered to.
         With a smoothing knob positive (smooth_median_radius, smooth_sigma) the rows go through _smooth_rows between the model
-        and the split: each dict then holds the smoothed values and 'smooth'; with both 0 nothing here differs."""
+        and the split: each dict then holds the smoothed values and 'smooth'; with both 0 nothing here differs.
+        With the activity knob on (self.activity) the rotations -- the smoothed ones where smoothing is on -- go through
+        _activity_rows once, each person's derived addends reach the scorers as `rows`, and each dict holds 'activity'
+        (parameters, flags, adds); `fps` is then needed (ValueError without).  Off, nothing here differs."""
         from poserisk_release_amd import ops
+        deriving = getattr(self, 'activity', None)
+        if deriving is not None and fps is None:
+            raise ValueError("the activity knob (cfg.ACTIVITY.derive / args.derive_activity) needs fps to turn its seconds into "
+                             "frames: pass fps= to score_frames / score_people (Predictor.__call__ does)")
         frames = self._on_device(frames)
         if bbox_scale is None:
             bbox_scale = cfg.DATASET.bbox_scale                                   # base.py:121
@@ -415,12 +459,15 @@ class Predictor:
                 yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
         smooth_m, smooth_sigma = getattr(self, 'smooth_median_radius', 0), getattr(self, 'smooth_sigma', 0.0)
         smoothing = smooth_m > 0 or smooth_sigma > 0
-        smpl = {} if with_smpl_params or smoothing else None
+        smpl = {} if with_smpl_params or smoothing or deriving is not None else None
         result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False, n_total=n_total,
                                                                               smpl_params=smpl)
         if smoothing:
             # every rank holds all rows after the gather and smooths the same ones: no further collective
             result, joint_cam, debug_result, smooth_flags = self._smooth_rows(smpl, people, fidx, smooth_m, smooth_sigma)
+        if deriving is not None:
+            # as with smoothing, every rank computes on the gathered rows
+            act_flags, act_adds, act_parameters = self._activity_rows(smpl['rotmat'], people, fidx, fps, deriving)
         outs, pose_logs, at = [], [], 0
         for _, box_p, frames_p in people:
             rows = slice(at, at + len(frames_p))
@@ -430,7 +477,11 @@ class Predictor:
             if smoothing:
                 out['smooth'] = dict(median_radius=smooth_m, sigma=smooth_sigma, status=smooth_flags['status'][rows],
                                      replaced=smooth_flags['replaced'][rows])
-            pose_logs.append(self._run_scorers(out, add_info))
+            if deriving is not None:
+                out['activity'] = dict(parameters=act_parameters, flags=act_flags[rows], adds=act_adds[rows])
+                pose_logs.append(self._run_scorers(out, add_info, rows=act_adds[rows]))
+            else:
+                pose_logs.append(self._run_scorers(out, add_info))
             out['frames'], out['bboxes'] = frames_p, box_p
             if with_smpl_params:
                 out['bbox_scale'] = float(bbox_scale)
@@ -438,10 +489,11 @@ class Predictor:
             at = rows.stop
         return outs, pose_logs
 
-    def score_frames(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None):
+    def score_frames(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None, fps=None):
         """Decoded frames + tracker output -> scores, all on the GPU (BASELINE config 5 without the detector).
         `with_smpl_params` (default: the render_mesh knob): also return the network's rotmat, betas and cam per track frame
-        (and the add_info used), which render_overlay draws from.
+        (and the add_info used), which render_overlay draws from.  `fps`: the video's frame rate, needed (ValueError without)
+        only with the activity knob on.
 
         frames: uint8[F,H,W,3] (torch CUDA tensor or numpy); tracking_results: multi_person_tracker's dict
         {id: {'bbox': [n,4] (cx,cy,w,h), 'frames': [n]}}.  Does what base.py:53-73 (track filter + target
@@ -467,9 +519,9 @@ class Predictor:
                                        "output (Predictor.__call__ does), or pass every rank the same frames and tracking dict")
             return pl.shard_bounds(len(fidx), world, rank) + (len(fidx) if world > 1 else None,)
         return self._score_tracks(frames, [target], add_info, bgr, bbox_scale, shard,
-                                  self.render_mesh if with_smpl_params is None else with_smpl_params)[0][0]
+                                  self.render_mesh if with_smpl_params is None else with_smpl_params, fps=fps)[0][0]
 
-    def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None):
+    def score_people(self, frames, tracking_results, add_info=None, bgr=False, bbox_scale=None, with_smpl_params=None, fps=None):
         """Decoded frames + tracker output -> the scores of EVERY person tracks.people_tracks keeps, in one pass over the model:
         {'people': [out_0, out_1, ...], 'ids': [...], 'frames_total': F}, in people_tracks order (element 0 is the person
         score_frames scores).  Each out_p holds what score_frames returns for that person alone -- result, joint_cam,
@@ -477,7 +529,7 @@ class Predictor:
         (tests/test_encoder_batch_sweep.py), so the people share batches (_score_tracks).  With args.debug the dict also holds
         'pose_logs', each person's rows of the scorers' angle logs.  `with_smpl_params` (default: the people_mesh knob): every
         out_p also holds rotmat, betas, cam, add_info and bbox_scale, as score_frames(with_smpl_params=True) returns them for
-        that person alone; render_people draws from them.
+        that person alone; render_people draws from them.  `fps`: as for score_frames.
 
         Not supported, by name: several ranks (hip_world_size / args.world_size > 1) and the render_mesh knob
         (pr_render_overlay draws one mesh per canvas)."""
@@ -493,7 +545,7 @@ class Predictor:
         people = tracks.people_tracks(tracking_results, n_frames, cfg.DATASET.min_frame_ratio)
         if with_smpl_params is None:
             with_smpl_params = getattr(self, 'people_mesh', False)
-        outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale, with_smpl_params=bool(with_smpl_params))
+        outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale, with_smpl_params=bool(with_smpl_params), fps=fps)
         people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': n_frames}
         return dict(people_out, pose_logs=pose_logs) if self.debugging else people_out
 
@@ -731,6 +783,24 @@ class Predictor:
         report = dict(median_radius=int(out['smooth']['median_radius']), sigma=float(out['smooth']['sigma']), unit='frames',
                       gaussian_radius=smooth.gaussian_radius(float(out['smooth']['sigma'])), people=people)
         with open(osp.join(output_path, 'smooth.json'), 'w') as f:
+            json.dump(report, f, indent=1)
+        return report
+
+    def write_activity_report(self, out, people_out, output_path):
+        """<output>/activity.json, written only with the activity knob on: the parameters in seconds, degrees and frames, and
+        per scored person (the target alone, id null, without persons 'all') the rows flagged per kind -- held, repeated,
+        rapid, moved -- in all and per joint name, and the sum of each derived addend.  Returns what it holds."""
+        from poserisk_release_amd import activity
+        plain = lambda v: v.item() if isinstance(v, np.generic) else v
+        scored = list(zip(people_out['ids'], people_out['people'])) if people_out is not None else [(None, out)]
+        people = []
+        for pid, o in scored:
+            adds = np.asarray(o['activity']['adds']).reshape(-1, 4)
+            people.append(dict(id=plain(pid), n_frames=int(len(adds)), **activity.counts(o['activity']['flags']),
+                               adds={name: int(adds[:, c].sum()) for c, name in enumerate(activity.ADDS)}))
+        report = dict(parameters={k: plain(v) for k, v in out['activity']['parameters'].items()}, joints=list(activity.JOINT_NAMES),
+                      people=people)
+        with open(osp.join(output_path, 'activity.json'), 'w') as f:
             json.dump(report, f, indent=1)
         return report
 
@@ -1025,11 +1095,11 @@ class Predictor:
         people_out = None
         if getattr(self, 'persons', 'target') == 'all':
             # everybody in one pass; the target is element 0, bit for bit what score_frames returns, so the model runs once
-            people_out = self.score_people(frames, tracking_results, add_info, bgr=bgr)
+            people_out = self.score_people(frames, tracking_results, add_info, bgr=bgr, fps=fps)
             out = dict(people_out['people'][0])
             out['people'] = people_out
         else:
-            out = self.score_frames(frames, tracking_results, add_info, bgr=bgr)
+            out = self.score_frames(frames, tracking_results, add_info, bgr=bgr, fps=fps)
         out['fps'] = fps
         if rank != 0:
             # every rank holds all frames' results after the gather; the reports (result txt, plots, mp4, debug CSVs and
@@ -1037,6 +1107,8 @@ class Predictor:
             return out
         if 'smooth' in out:                                        # only with a smoothing knob on
             self.write_smooth_report(out, people_out, output_path)
+        if 'activity' in out:                                      # only with the activity knob on
+            self.write_activity_report(out, people_out, output_path)
         fidx = out['frames']
         timestamp = (0, fidx, int(frames.shape[0]))                # base.py:130 (torch tensor or numpy: both have .shape)
         debug_path = osp.join(output_path, 'debug')

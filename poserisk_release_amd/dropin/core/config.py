@@ -76,6 +76,17 @@ absent from the reference and all optional:
                               its agreement with fp32 on trained weights is unmeasured).
                               With weights set, a video file's tracking comes from it after the tracking given and the sidecar
                               and before multi_person_tracker, and a frame folder without tracking.pkl is accepted
+    cfg.ACTIVITY              REBA's activity score and RULA's muscle use derived from each track's motion instead of taken as 0
+                              (poserisk_release_amd.activity, pr_activity_tracks).  derive False (default:
+                              nothing changes anywhere; args.derive_activity overrides it) | True: every scored person's rows get
+                              +1 REBA activity for a scored joint held within static_deg (10) for longer than hold_seconds (60),
+                              +1 for more than rep_events (8: more than four out-and-back actions) movements of move_deg (15)
+                              within hold_seconds, +1 for a change of rapid_deg (45) within rapid_seconds (1), and +1 RULA muscle
+                              use per group (left arm, right arm, neck-trunk-legs) held or repeated; a step of more than
+                              gap_seconds (0.2) between two frames of a track breaks a window.  The values are ADDED to the
+                              information file's constants (leave those at 0) and <output>/activity.json is written.  The
+                              degrees are this project's choice: the worksheets give none, and nobody has measured the rule on
+                              real footage
 main/run.py has its `--cfg` option commented out (run.py:20-24), so a YAML of overrides named by $POSERISK_CFG is applied
 when this module is imported -- `POSERISK_CFG=bf16.yaml python main/run.py ...` with the one line `SPIN: {precision: bf16}`.
 """
@@ -149,6 +160,8 @@ def _defaults(root):
         'TEST': {},
         'TRACKER': {'weights': '', 'img_size': (416, 416), 'conf_thres': 0.1, 'nms_thres': 0.4, 'max_age': 1, 'min_hits': 3,
                     'iou_thres': 0.3, 'batch': 8, 'precision': 'fp32'},
+        'ACTIVITY': {'derive': False, 'hold_seconds': 60.0, 'static_deg': 10.0, 'move_deg': 15.0, 'rep_events': 8,
+                     'rapid_seconds': 1.0, 'rapid_deg': 45.0, 'gap_seconds': 0.2},
     }
 
 

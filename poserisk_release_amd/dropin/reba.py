@@ -24,9 +24,10 @@ class REBA:
         self.angle_log = {}
         self.log = []          # accumulates across calls, never cleared (Q19)
 
-    def __call__(self, poses, joint_cams, add_info):
+    def __call__(self, poses, joint_cams, add_info, *, rows=None):
         # joint_cams is accepted and ignored, exactly as every rule of the reference does (Q6)
-        packed = ops.reba(to_device_poses(poses), add_info["REBA"]).cpu().numpy()
+        # rows (keyword only; the positional use stays the reference's): int[N] added row by row to Activity_Score (ops.reba)
+        packed = ops.reba(to_device_poses(poses), add_info["REBA"], rows=rows).cpu().numpy()
         if self.debugging:
             P = poses.cpu().numpy() if hasattr(poses, "cpu") else np.asarray(poses)
             self.log.extend(self._angle_log(p) for p in P)

@@ -17,8 +17,9 @@ class RULA:
         self.angle_log = {}
         self.log = []
 
-    def __call__(self, poses, joint_cams, add_info):
-        packed = ops.rula(to_device_poses(poses), add_info["RULA"]).cpu().numpy()
+    def __call__(self, poses, joint_cams, add_info, *, rows=None):
+        # rows (keyword only): int[N,3] added row by row to A_Muscle_use_L, A_Muscle_use_R and B_Muscle_use (ops.rula)
+        packed = ops.rula(to_device_poses(poses), add_info["RULA"], rows=rows).cpu().numpy()
         if self.debugging:
             P = poses.cpu().numpy() if hasattr(poses, "cpu") else np.asarray(poses)
             self.log.extend(self._angle_log(p) for p in P)

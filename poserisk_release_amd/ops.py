@@ -72,25 +72,45 @@ def axis_angle_to_euler(axis_angle, out=None):
     return eul, st
 
 
-def reba(euler_deg, info, out=None):
-    """REBA.__call__ arithmetic (lib/utils/reba.py:50-81).  f64[N,24,3] -> int32[N,10]."""
+def _addend_rows(rows, shape, dev, name):
+    """A scorer's per-row addends (tensor or array of integers) -> a contiguous int32 tensor of `shape` on `dev`."""
+    rows = torch.as_tensor(rows)
+    if rows.dtype not in (torch.int32, torch.int64) or tuple(rows.shape) != tuple(shape):
+        raise ValueError(f"{name}: rows must be integers of shape {tuple(shape)}, got {rows.dtype} {tuple(rows.shape)}")
+    return rows.to(dev, torch.int32).contiguous()
+
+
+def reba(euler_deg, info, out=None, rows=None):
+    """REBA.__call__ arithmetic (lib/utils/reba.py:50-81).  f64[N,24,3] -> int32[N,10].
+    rows: None, or int[N]: row f's value is added to info's Activity_Score (pr_reba_rows; activity.activity_tracks derives it)."""
     _need_cuda(euler_deg, "reba")
     e = euler_deg.contiguous().double()
     N = e.shape[0]
     out = _out(out, (N, 10), torch.int32, e.device)
     s = _lib.reba_info_struct(info)
-    _lib.check(_lib.load().pr_reba(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_reba")
+    if rows is None:
+        _lib.check(_lib.load().pr_reba(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_reba")
+    else:
+        rows = _addend_rows(rows, (N,), e.device, "reba")
+        _lib.check(_lib.load().pr_reba_rows(e.data_ptr(), N, s, rows.data_ptr() if N else None, out.data_ptr(), _stream(e.device)),
+                   "pr_reba_rows")
     return out
 
 
-def rula(euler_deg, info, out=None):
-    """RULA.__call__ arithmetic (lib/utils/rula.py:66-98).  f64[N,24,3] -> int32[N,12]."""
+def rula(euler_deg, info, out=None, rows=None):
+    """RULA.__call__ arithmetic (lib/utils/rula.py:66-98).  f64[N,24,3] -> int32[N,12].
+    rows: None, or int[N,3]: row f's values are added to info's A_Muscle_use_L, A_Muscle_use_R and B_Muscle_use (pr_rula_rows)."""
     _need_cuda(euler_deg, "rula")
     e = euler_deg.contiguous().double()
     N = e.shape[0]
     out = _out(out, (N, 12), torch.int32, e.device)
     s = _lib.rula_info_struct(info)
-    _lib.check(_lib.load().pr_rula(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_rula")
+    if rows is None:
+        _lib.check(_lib.load().pr_rula(e.data_ptr(), N, s, out.data_ptr(), _stream(e.device)), "pr_rula")
+    else:
+        rows = _addend_rows(rows, (N, 3), e.device, "rula")
+        _lib.check(_lib.load().pr_rula_rows(e.data_ptr(), N, s, rows.data_ptr() if N else None, out.data_ptr(), _stream(e.device)),
+                   "pr_rula_rows")
     return out
 
 
