@@ -1708,6 +1708,16 @@ int pr_det_unmap(float* boxes_dev, const int32_t* count_dev, int B, int max_det,
  *     proper rotation and the iteration is well conditioned.
  *     c < 0.05 (or not a number): the joint's output is y_i, stage 1's output for the row itself, and bit j of status[i] is set.
  *
+ * Non-finite values.  Membership is decided on rows and frame numbers alone, and a row that is no member of a window (another
+ * track's, one beyond a gap) is never read into any result of that window: a NaN or an inf stays inside the windows that
+ * hold its row.  Stage 1: a cost that is NaN (any member's group holds a NaN, or the candidate's own holds an inf) is never
+ * smaller than anything, nothing is smaller than it and it equals nothing: with a NaN on either side the member found first
+ * stays; a window whose
+ * every cost is NaN yields its FIRST member in row order (not the nearest frame: no tie is exact).  Stage 2: a NaN or an inf
+ * among a joint's members makes c not a number, so the joint falls back to y_i (itself possibly non-finite) and sets its
+ * status bit; cam and betas have no fallback and propagate it (sum(w y) / sum(w) is NaN, or the inf where no weight is 0).
+ * An isolated row still comes back as y_i's bits, status 0.
+ *
  * status_dev i32[N] or NULL: bits 0..23 as above, else 0.  outputs->replaced i32[N] or NULL: bit j (joints 0..23; 24 = cam,
  * 25 = betas) is set where stage 1 chose another row than i itself, else 0.
  * outputs->betas / ->cam are required exactly where inputs->betas / ->cam are given.  No output, status, replaced or the

@@ -108,7 +108,7 @@ def guarded_input(t, device=None):
     return big, view
 
 
-def run_guarded(fn, inputs, outputs, device=None, mutated=(), may_hold_canary=()):
+def run_guarded(fn, inputs, outputs, device=None, mutated=(), may_hold_canary=(), nan_expected=None):
     """Run `fn` once with every tensor in an arena and check that it stayed inside them.
 
     inputs   {name: tensor}: each is copied into a view whose guards hold NaN / 255 / 0x7fffffff.  Give each in the dtype
@@ -120,7 +120,9 @@ def run_guarded(fn, inputs, outputs, device=None, mutated=(), may_hold_canary=()
 
     Afterwards: all guards intact (inputs' too: a kernel must not write around its inputs either); no input changed, except
     those named in `mutated`; no NaN and no surviving canary anywhere in the outputs (names in `may_hold_canary` are exempt
-    from the canary check: an integer output whose legitimate values include it).  -> {name: output view}."""
+    from the canary check: an integer output whose legitimate values include it).  nan_expected {name: bool array of the
+    output's shape}: where a case plants NaNs in its inputs, the elements whose reference is NaN -- a NaN anywhere else still
+    fails.  -> {name: output view}."""
     ins, outs, arenas = {}, {}, []
     for name, t in inputs.items():
         big, view = guarded_input(t, device)
@@ -145,6 +147,8 @@ def run_guarded(fn, inputs, outputs, device=None, mutated=(), may_hold_canary=()
             continue
         if view.dtype.is_floating_point:
             nan = torch.isnan(view)
+            if nan_expected is not None and name in nan_expected:
+                nan &= ~torch.as_tensor(nan_expected[name], device=view.device).reshape(view.shape)
             assert not bool(nan.any()), (f"{what}: {int(nan.sum())} NaN, first at flat element {int(torch.nonzero(nan.flatten())[0])}"
                                          " -- a value from an input's NaN guard (a read outside an input tensor) reached the output")
         if name not in may_hold_canary:

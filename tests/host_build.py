@@ -40,10 +40,12 @@ class Program:
 
 
 def build(tmp_dir, name, main, *, sources=(), stage=(), shim=False, threads=False, strict=False, sanitize=True,
-          without_compiler="fail"):
+          without_compiler="fail", staged_text=None):
     """Compiles tests/native/<main> plus `sources` (csrc files) into <tmp_dir>/<name> -> Program.
     stage: csrc files copied into tmp_dir, for the drivers that #include a .hip or .cc and for `sources` that must find the shim;
     shim: tests/native/host_shim.h goes beside them as common.h, which is what the staged kernels include;
+    staged_text: {csrc file name: text} -- a staged file whose text is given here is written from it instead of being copied
+        (tests/test_track_mutants_native.py builds mutated kernels this way: the text exists in tmp_dir only);
     without_compiler: "fail", "skip" or "none" (-> None) where there is no g++."""
     gxx = shutil.which("g++")
     if gxx is None:
@@ -52,8 +54,14 @@ def build(tmp_dir, name, main, *, sources=(), stage=(), shim=False, threads=Fals
         assert without_compiler == "none", f"g++ is needed to build tests/native/{main} for the host"
         return None
     d = str(tmp_dir)
+    staged_text = dict(staged_text or {})
+    assert set(staged_text) <= set(stage), "staged_text names a file that is not staged"
     for f in stage:
-        shutil.copy(os.path.join(CSRC, f), os.path.join(d, f))
+        if f in staged_text:
+            with open(os.path.join(d, f), "w") as out:
+                out.write(staged_text[f])
+        else:
+            shutil.copy(os.path.join(CSRC, f), os.path.join(d, f))
     if shim:
         shutil.copy(os.path.join(NATIVE, "host_shim.h"), os.path.join(d, "common.h"))
     exe = os.path.join(d, name)

@@ -1,7 +1,10 @@
 """The contract of pr_smooth_tracks (include/poserisk_hip.h, section s1) restated in float64 numpy: what the kernel's outputs
 are compared with.  Vectorised over rows, looping over window offsets in ascending order, so every sum is accumulated in the
-order the contract names (adding 0.0 for a row that is no member leaves a sum's bits alone).  A row whose stage-2 window holds
-nobody else comes back as stage 1 left it, bit for bit.
+order the contract names.  Membership is a SELECTION, never a zero weight: what a row that is no member holds -- another
+track's NaN, an inf beyond a gap -- is not multiplied by anything and enters no sum (0.0 * nan would be nan); adding the
+selected 0.0 leaves a sum's bits alone.  A row whose stage-2 window holds nobody else comes back as stage 1 left it, bit for
+bit.  Non-finite members behave as the header says: a NaN cost is never smaller than anything (a window whose every cost is
+NaN yields its first member), a joint whose c is not a number falls back, cam and betas propagate.
 
     smooth(rotmat, frame_no, track_start, m, sigma, betas=None, cam=None) -> dict
         rotmat, betas, cam   with sigma > 0 float64 (the values before the one rounding to f32), else float32 (an input row's bits)
@@ -55,9 +58,10 @@ def medoid(x, frame_no, lo, hi, r):
 
     def dist(ka, kb):                                   # ||x_ka - x_kb|| per group, the squares summed in element order
         ss = np.zeros((N, G))
-        for e in range(D):
-            d = X[ka, :, e] - X[kb, :, e]
-            ss = ss + d * d
+        with np.errstate(invalid="ignore"):             # (inf - inf where a row holds an inf)
+            for e in range(D):
+                d = X[ka, :, e] - X[kb, :, e]
+                ss = ss + d * d
         return np.sqrt(ss)
     best = np.full((N, G), -1, np.int64)
     best_cost = np.full((N, G), np.inf)
@@ -136,9 +140,10 @@ def smooth(rotmat, frame_no, track_start, m, sigma, betas=None, cam=None):
             Y = y.astype(np.float64)
             acc, wsum = np.zeros(Y.shape), np.zeros(N)
             for o in range(2 * g + 1):
-                wo = np.where(mem[:, o], w[:, o], 0.0)
-                acc = acc + wo[:, None, None] * Y[kc[:, o]]
-                wsum = wsum + wo
+                is_mem = mem[:, o]
+                with np.errstate(invalid="ignore"):                          # (0 * inf where a member holds an inf)
+                    acc = acc + np.where(is_mem[:, None, None], w[:, o, None, None] * Y[kc[:, o]], 0.0)
+                wsum = wsum + np.where(is_mem, w[:, o], 0.0)
             if name == "rotmat":
                 A = acc.reshape(N, 24, 3, 3)
                 c = fallback_measure(A)
@@ -149,7 +154,8 @@ def smooth(rotmat, frame_no, track_start, m, sigma, betas=None, cam=None):
                     out["status"] |= fell[:, j].astype(np.int32) << j
                 out["c"] = c
             else:
-                res = acc / wsum[:, None, None]
+                with np.errstate(invalid="ignore"):
+                    res = acc / wsum[:, None, None]
             alone = mem.sum(1) == 1                                          # an isolated row comes back as it is
             res = np.where(alone[:, None, None], Y, res)
         else:

@@ -29,7 +29,8 @@ H, R, G, E = ac.H0, ac.R0, ac.G0, ac.E0
 def test_the_case_list_covers_what_the_kernel_can_get_wrong():
     sizes = {n: len(ac.case(n)["frame_no"]) for n in ac.NAMES}
     assert max(sizes.values()) <= 3000 and sizes["empty"] == 0 and len(ac.case("empty")["track_start"]) == 1
-    assert all(ac.case(n)["H"] <= 40 for n in ac.NAMES if n != "big") and ac.case("big")["H"] == 700 and sizes["big"] == 1500
+    assert all(ac.case(n)["H"] <= (110 if n in ac.LATTICE_NAMES else 40) for n in ac.NAMES if n != "big")
+    assert ac.case("big")["H"] == 700 and sizes["big"] == 1500
     assert ac.case("big")["H"] > 10 * ac.CHUNK and sizes["big"] > 10 * ac.TILE                  # many chunks, many tiles
     lengths = np.diff(ac.case("lengths")["track_start"]).tolist()
     assert {0, 1, H, H + 1, H + G} <= set(lengths)
@@ -128,6 +129,147 @@ def test_rows_holding_nan_fail_every_comparison():
     assert not ref["stage_b"][50:50 + H + 1, 0].any() and (ref["stage_b"][50 + H + 1:80, 0] == ALL).all()      # the all-NaN row 50
     assert not ref["flags"][30, 3] & torso and not ref["flags"][30, 2] & torso
     assert ref["stage_b"][50, 0] == 0 and ref["flags"][50, 2] == 0 and ref["flags"][50, 3] == 0
+
+
+# ---- the cases that pin the chunk loop, the span, the spread and the bounds ---------------------------------------------------
+def _first_row(c, i):
+    ts = c["track_start"]
+    return int(ts[np.searchsorted(ts, i, side="right") - 1])
+
+
+def _has_hole(c, i):
+    """Two rows that follow each other in W_i(H) are not 1..G frames apart."""
+    f = c["frame_no"].astype(np.int64)
+    steps = np.diff(f[activity_ref.window(f, i, _first_row(c, i), c["H"])])
+    return bool(((steps < 1) | (steps > c["G"])).any())
+
+
+def _nearest_witness(c, x, i, b):
+    """The largest k in W_i(R) with dot_b(k, i) < dot_rapid, or None."""
+    f = c["frame_no"].astype(np.int64)
+    mem = activity_ref.window(f, i, _first_row(c, i), c["R"])
+    with np.errstate(invalid="ignore"):
+        hit = mem[activity_ref.dots(x[mem, b], x[i, b][None]) < c["dot_rapid"]]
+    return int(hit.max()) if hit.size else None
+
+
+def test_the_lattice_reaches_an_older_chunk_for_rapid_alone():
+    assert [(ac.case(n)["H"], ac.case(n)["R"]) for n in ac.LATTICE_NAMES] == [(31, 31), (32, 1), (33, 33), (63, 40), (64, 64), (65, 33), (96, 96), (100, 50)]
+    fired = np.zeros(4, np.int64)
+    far = {}
+    for name in ac.LATTICE_NAMES:
+        c, ref = ac.case(name), ac.reference(name)
+        ts, f = c["track_start"], c["frame_no"].astype(np.int64)
+        assert np.diff(ts).tolist() == [200, 130, 70] and f.min() == -2 ** 31 and f.max() == 2 ** 31 - 1
+        steps = np.diff(f[:330])
+        assert (steps == c["G"]).any() and (steps == c["G"] + 1).any() and (steps == 0).any()      # gaps <= G, > G, a repeated frame
+        assert f[128] == f[127] and f[256] == f[255] and 128 % ac.TILE == 0 == 256 % ac.TILE       # the holes, on tile edges
+        fired += np.count_nonzero(ref["flags"], axis=0)
+        x = activity_ref.scored(c["rotmat"])
+        far[name] = 0
+        for i in np.nonzero(ref["flags"][:, 2])[0]:
+            if not _has_hole(c, i):
+                continue
+            for b in range(12):
+                if ref["flags"][i, 2] >> b & 1:
+                    far[name] += int(i - _nearest_witness(c, x, i, b) >= ac.CHUNK)
+    assert (fired > 0).all(), fired                              # held, repeated, rapid and moved each fire somewhere
+    # rows that are rapid only through a row CHUNK or more back, in a window with a hole: wherever R allows it
+    assert all((far[n] > 0) == (ac.case(n)["R"] > ac.CHUNK) for n in ac.LATTICE_NAMES), far
+
+
+def test_a_span_of_exactly_h_minus_g_is_not_whole_and_one_more_is():
+    c, ref = ac.case("span_edge"), ac.reference("span_edge")
+    f, ts, p = c["frame_no"].astype(np.int64), c["track_start"], c["planted"]
+    assert len(p["not_whole"]) == len(p["whole"]) == 4
+    for rows, whole in ((p["not_whole"], False), (p["whole"], True)):
+        for i in rows:
+            first = _first_row(c, i)
+            mem = activity_ref.window(f, i, first, H)
+            assert i + 1 in ts and not _has_hole(c, i)                          # the track's last row, its window without a hole
+            assert (f[i] - f[mem[0]] == H - G) if not whole else (f[i] - f[mem[0]] in (H - G + 1, H - G + 2))
+            assert ref["stage_b"][i, 0] == (ALL if whole else 0)                 # the reference's stage-B mask ...
+            assert (ref["flags"][mem, 0] == (ALL if whole else 0)).all()         # ... and what the spread makes of it
+            assert not ref["stage_b"][first:i, 0].any()                          # no earlier window of the track is whole
+    assert [int(f[i] - f[activity_ref.window(f, i, _first_row(c, i), H)[0]]) for i in p["whole"]] == [H - G + 1] * 3 + [H - G + 2]
+    assert not ref["flags"][p["untouched"], 0].any()                             # the rows before the long step are out of reach
+    assert np.count_nonzero(ref["stage_b"][:, 0]) == 4
+
+
+def test_a_gap_bound_above_the_hold_makes_every_covered_window_whole():
+    for name in ("G_huge", "G_gt_H"):
+        c, ref = ac.case(name), ac.reference(name)
+        assert c["G"] > c["H"] and (c["G"] == 2 ** 31 - 1) == (name == "G_huge")
+        lengths = np.diff(c["track_start"])
+        one = int(c["track_start"][np.nonzero(lengths == 1)[0][0]])
+        assert ref["stage_b"][one, 0] == ALL == ref["flags"][one, 0]           # a one-row window is whole, and still
+        for i in range(len(c["frame_no"])):
+            if not _has_hole(c, i):
+                assert ref["stage_b"][i, 0] != 0 or np.count_nonzero(ref["flags"][i, 2:]) or c["rotmat"][i].std() > 0, i
+        still_rows = np.arange(c["track_start"][0], c["track_start"][1]) if name == "G_huge" else np.arange(3, 43)
+        holes = np.array([_has_hole(c, int(i)) for i in still_rows])
+        assert np.array_equal(ref["stage_b"][still_rows, 0] == ALL, ~holes)       # in a still track: held exactly where there is no hole
+    f = ac.case("G_huge")["frame_no"].astype(np.int64)
+    assert (np.diff(f[:72]) > 2 ** 29).any() and not np.array([_has_hole(ac.case("G_huge"), i) for i in range(72)]).any()
+    assert np.array([_has_hole(ac.case("G_huge"), i) for i in range(123, 130)]).any()      # a repeated and a backward frame still are holes
+    # (with G > H a step above G never lies inside a window: the row behind it is more than H frames away)
+    assert not np.array([_has_hole(ac.case("G_gt_H"), i) for i in range(3, 43)]).any()
+
+
+def test_more_tracks_than_a_launch_with_the_second_launch_inside_a_tile():
+    c = ac.case("many_unaligned")
+    ts = c["track_start"]
+    lengths = np.diff(ts)
+    assert len(lengths) >= 300 and lengths.min() == 0 and lengths.max() == 10 and (c["H"], c["R"]) == (5, 2)
+    assert len(ts) - 1 > 256 and ts[256] % ac.TILE != 0 and ts[256] < ts[-1]
+    assert (np.count_nonzero(ac.reference("many_unaligned")["flags"][:, [0, 1, 3]], axis=0) > 0).all()
+
+
+def test_a_held_bit_does_not_spread_to_a_row_that_lies_later_in_frames():
+    c, ref = ac.case("spread_back"), ac.reference("spread_back")
+    f = c["frame_no"].astype(np.int64)
+    i, e = c["planted"]["i"], c["planted"]["e"]
+    assert 0 < e - i <= H and f[e] < f[i] and ref["stage_b"][e, 0] == ALL and not ref["stage_b"][:e, 0].any()
+    assert ref["flags"][i, 0] == 0 and not ref["flags"][:i + 1, 0].any() and (ref["flags"][i + 1:, 0] == ALL).all()
+    # stage C without its `0 <=` on the frame difference would change this case's flags
+    n = len(f)
+    dropped = np.zeros(n, np.int32)
+    for r in range(n):
+        es = np.arange(r, min(r + H, n - 1) + 1)
+        dropped[r] = np.bitwise_or.reduce(ref["stage_b"][es[f[es] - f[r] <= H], 0])
+    assert dropped[i] == ALL and not np.array_equal(dropped, ref["flags"][:, 0])
+
+
+def test_thresholds_at_the_ends_of_their_range():
+    c, ref = ac.case("thresholds_at_bounds"), ac.reference("thresholds_at_bounds")
+    assert (c["dot_static"], c["dot_move"], c["dot_rapid"]) == (3.0, 3.0, -1.0)
+    b, u, fb, fl = ac.BOUNDS["ulp_bit"], ac.BOUNDS["ulp_row"], ac.BOUNDS["flip_bit"], ac.BOUNDS["flip_row"]
+    assert activity_ref.dot_pair(c["rotmat"], 0, 1, b) == 3.0                           # bit-equal rows: exactly 3
+    assert 3.0 - 2.0 ** -23 < activity_ref.dot_pair(c["rotmat"], u, u + 1, b) < 3.0      # one ulp of one element
+    assert activity_ref.dot_pair(c["rotmat"], u, u, b) < 3.0                             # ... and the row against itself
+    assert activity_ref.dot_pair(c["rotmat"], fl, fl + 1, fb) == -1.0                    # a half turn: exactly -1, not below
+    assert not ref["flags"][:, 2].any()                                                  # rapid never
+    want = np.zeros(80, np.int32)
+    want[[u, u + 1]] = 1 << b
+    want[[fl, fl + 1]] |= 1 << fb
+    assert np.array_equal(ref["flags"][:, 3], want)                                      # an event there and on the way back
+    held = np.full(80, ALL, np.int32)
+    held[u:u + H + 1] &= ~(1 << b)
+    held[fl:fl + H + 1] &= ~(1 << fb)
+    held[:H - G + 1] = 0                                                                 # (the first windows span H - G frames or fewer)
+    assert np.array_equal(ref["stage_b"][:, 0], held)                                    # held only where every member is bit-equal
+
+
+def test_the_sweep_draws_every_kind_of_problem():
+    fired, wild, holds = np.zeros(4, np.int64), 0, set()
+    for name in ac.SWEEP_NAMES:
+        c, ref = ac.case(name), ac.reference(name)
+        assert 1 <= c["R"] <= c["H"] <= 110 and 1 <= c["G"] <= 5 and 0 <= c["E"] <= 4 and 1 <= len(c["track_start"]) - 1 <= 3
+        assert np.diff(c["track_start"]).max() <= 160 and len(c["frame_no"]) >= 1
+        fired += np.count_nonzero(ref["flags"], axis=0)
+        wild += int((c["frame_no"] == -2 ** 31).any())
+        holds.add(c["H"] // ac.CHUNK)
+    assert (fired > 0).all() and wild >= 5 and holds == {0, 1, 2, 3} and len(ac.SWEEP_NAMES) == 60
 
 
 # ---- the Python helpers ------------------------------------------------------------------------------------------------------

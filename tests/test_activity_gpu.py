@@ -33,11 +33,8 @@ def _call(c, i, o):
 
 
 # ---- the contract, through the C ABI, between guard bands -------------------------------------------------------------------
-@pytest.mark.parametrize("name", ac.NAMES)
-def test_every_case_equals_the_reference_inside_its_guard_bands(gpu_device, name):
-    """Inputs between NaN / 0x7fffffff guards, flags, adds and the workspace between canary guards (tests/guard_band.py): a chunk
-    that left its track's rows at a tile's or a tensor's edge would read a guard (a NaN fails every comparison, a frame number
-    of 0x7fffffff is no member), a store outside a tensor lands in one."""
+def _run_guarded(gpu_device, name):
+    """One case or sweep problem through the C entry between guard bands, held to its reference."""
     lib = _lib.load()
     assert lib.pr_activity_tile_rows() == ac.TILE and lib.pr_activity_chunk_rows() == ac.CHUNK
     c = ac.case(name)
@@ -50,6 +47,63 @@ def test_every_case_equals_the_reference_inside_its_guard_bands(gpu_device, name
     # the workspace's size is rounded up to 256 bytes: its tail is never written
     got = gb.run_guarded(lambda i, o: _call(c, i, o), ins, outs, may_hold_canary=("workspace",))
     ac.check(name, {k: got[k].cpu().numpy() for k in ("flags", "adds")})
+
+
+@pytest.mark.parametrize("name", ac.NAMES)
+def test_every_case_equals_the_reference_inside_its_guard_bands(gpu_device, name):
+    """Inputs between NaN / 0x7fffffff guards, flags, adds and the workspace between canary guards (tests/guard_band.py): a chunk
+    that left its track's rows at a tile's or a tensor's edge would read a guard (a NaN fails every comparison, a frame number
+    of 0x7fffffff is no member), a store outside a tensor lands in one."""
+    _run_guarded(gpu_device, name)
+
+
+SWEEP_BLOCK = 10
+
+
+@pytest.mark.parametrize("block", range(0, ac.SWEEP, SWEEP_BLOCK))
+def test_the_seeded_sweep_equals_the_reference_inside_its_guard_bands(gpu_device, block):
+    """Ten problems of activity_cases.sweep_problem a test id, each as the cases above."""
+    for q in range(block, min(block + SWEEP_BLOCK, ac.SWEEP)):
+        _run_guarded(gpu_device, ac.sweep_name(q))
+
+
+def test_activity_tracks_is_capturable(gpu_device):
+    """The three launches captured once on a side stream (one stream, no branches) and replayed twice with both inputs
+    overwritten in place in between: each replay gives the eager call's bits for the inputs it found."""
+    c = ac.case("edges")
+    N = len(c["frame_no"])
+    lib = _lib.load()
+    second = dict(rotmat=np.roll(c["rotmat"], 11, axis=0), frame_no=np.array(c["frame_no"]))
+    second["frame_no"][70:90] += ac.G0 + 1                                 # a hole in the second track
+    sets = [{k: torch.from_numpy(np.ascontiguousarray(src[k])).to(gpu_device) for k in ("rotmat", "frame_no")} for src in (c, second)]
+    ins = {k: torch.empty_like(v) for k, v in sets[0].items()}
+    new = lambda: {"flags": torch.full((N, 4), -1, dtype=torch.int32, device=gpu_device), "adds": torch.full((N, 4), -1, dtype=torch.int32, device=gpu_device),
+                   "workspace": torch.zeros((lib.pr_activity_workspace_bytes(N) // 4,), dtype=torch.int32, device=gpu_device)}
+    eager = []
+    for given in sets:
+        for k in ins:
+            ins[k].copy_(given[k])
+        outs = new()
+        _call(c, ins, outs)
+        eager.append({k: outs[k].clone() for k in ("flags", "adds")})
+    ac.check("edges", {k: eager[0][k].cpu().numpy() for k in ("flags", "adds")})
+    assert not torch.equal(eager[0]["flags"], eager[1]["flags"])
+    outs = new()
+    for k in ins:
+        ins[k].copy_(sets[0][k])
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        _call(c, ins, outs)
+    for given, want in zip(sets, eager):
+        for k in ins:
+            ins[k].copy_(given[k])
+        for k in want:
+            outs[k].fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        for k in want:
+            assert torch.equal(outs[k], want[k]), k
 
 
 def test_a_track_alone_and_among_others_gives_the_same_bits(gpu_device):

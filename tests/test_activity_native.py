@@ -32,3 +32,8 @@ def test_every_argument_error_is_refused_before_any_work(activity_host):
 @pytest.mark.parametrize("name", ac.NAMES)
 def test_kernel_source_on_the_host_equals_the_reference(activity_host, name):
     ac.check(name, activity_host(name))
+
+
+@pytest.mark.parametrize("name", ac.SWEEP_NAMES)
+def test_the_seeded_sweep_on_the_host_equals_the_reference(activity_host, name):
+    ac.check(name, activity_host(name))

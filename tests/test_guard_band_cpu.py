@@ -80,6 +80,18 @@ def test_a_store_around_an_input_is_caught_too():
     gb.run_guarded(overwrites_input, {"x": torch.ones(SHAPE)}, {"y": (SHAPE, torch.float32)}, device="cpu", mutated=("x",))
 
 
+def test_a_planted_nan_passes_only_where_it_is_expected():
+    x = torch.arange(60, dtype=torch.float32).reshape(SHAPE) + 1
+    x[1, 2, 3] = float("nan")
+    run = lambda fn, mask: gb.run_guarded(fn, {"x": x}, {"y": (SHAPE, torch.float32)}, device="cpu", nan_expected={"y": mask})["y"]
+    y = run(_scale_correct, torch.isnan(x).numpy())
+    assert torch.equal(torch.isnan(y), torch.isnan(x))
+    with pytest.raises(AssertionError, match="1 NaN, first at flat element 31"):      # the planted one, with no mask for it
+        run(_scale_correct, torch.zeros(SHAPE, dtype=torch.bool).numpy())
+    with pytest.raises(AssertionError, match="1 NaN, first at flat element 59"):      # the guard's NaN is not excused by the mask
+        run(_reads_one_past_the_input, torch.isnan(x).numpy())
+
+
 def test_guard_sizes_and_fills():
     # one frame, at least 4 KiB, in multiples of 256 bytes
     assert gb.guard_bytes((2, 9, 9, 64), torch.float32) == 9 * 9 * 64 * 4

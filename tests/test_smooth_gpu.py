@@ -34,11 +34,9 @@ def _call(c, i, o):
 
 
 # ---- the contract, through the C ABI, between guard bands -------------------------------------------------------------------
-@pytest.mark.parametrize("name", sc.NAMES)
-def test_every_case_matches_the_reference_inside_its_guard_bands(gpu_device, name):
-    """Inputs between NaN / 0x7fffffff guards, outputs, status, replaced and the workspace between canary guards
-    (tests/guard_band.py): a window that left its track's rows at a tile's or a tensor's edge would read a guard (a NaN
-    reaches the output, a frame number of 0x7fffffff is no member), a store outside a tensor lands in one."""
+def _run_guarded(gpu_device, name):
+    """One case or sweep problem through the C entry between guard bands, checked against its reference -> the worst
+    rotation error."""
     lib = _lib.load()
     assert lib.pr_smooth_tile_rows() == sc.TILE
     c = sc.case(name)
@@ -52,13 +50,84 @@ def test_every_case_matches_the_reference_inside_its_guard_bands(gpu_device, nam
     if c["m"] > 0 and c["sigma"] > 0:
         outs["workspace"] = ((lib.pr_smooth_workspace_bytes(N, c["betas"] is not None, c["cam"] is not None) // 4,), torch.float32)
     # the workspace's size is rounded up to 256 bytes: its tail is never written
-    got = gb.run_guarded(lambda i, o: _call(c, i, o), ins, outs, may_hold_canary=("workspace",))
+    # a case that plants NaNs says where its reference holds one (stage 1's output for the workspace); nowhere else may one be
+    nans = None
+    if not c["rotations"]:
+        ref = sc.reference(name)
+        nans = {k: np.isnan(np.asarray(ref[k])) for k in ("rotmat", "betas", "cam")}
+        if "workspace" in outs:
+            ws = np.concatenate([np.isnan(ref["stage1"][k]).reshape(-1) for k in ("rotmat", "cam", "betas")])
+            nans["workspace"] = np.concatenate([ws, np.zeros(outs["workspace"][0][0] - ws.size, bool)])
+    got = gb.run_guarded(lambda i, o: _call(c, i, o), ins, outs, may_hold_canary=("workspace",), nan_expected=nans)
     host = {k: (got[k].cpu().numpy() if k in got else None) for k in ("rotmat", "betas", "cam", "status", "replaced")}
     worst = sc.check(name, host)
-    measured(f"smooth_rot_err[{name}]", worst, sc.ROT_TOL)
-    # orthonormal enough for the next stage: pose_to_euler's isRotationMatrix and round-trip checks pass on every row
-    _, _, st = ops.pose_to_euler(got["rotmat"])
-    assert not st.cpu().numpy().any()
+    # orthonormal enough for the next stage: pose_to_euler's isRotationMatrix and round-trip checks pass on every row -- of
+    # every case that holds rotations throughout (all but those that plant NaNs and infinities)
+    if c["rotations"]:
+        _, _, st = ops.pose_to_euler(got["rotmat"])
+        assert not st.cpu().numpy().any()
+    else:
+        assert name.startswith("nonfinite_")
+    return worst
+
+
+@pytest.mark.parametrize("name", sc.NAMES)
+def test_every_case_matches_the_reference_inside_its_guard_bands(gpu_device, name):
+    """Inputs between NaN / 0x7fffffff guards, outputs, status, replaced and the workspace between canary guards
+    (tests/guard_band.py): a window that left its track's rows at a tile's or a tensor's edge would read a guard (a NaN
+    reaches the output, a frame number of 0x7fffffff is no member), a store outside a tensor lands in one."""
+    measured(f"smooth_rot_err[{name}]", _run_guarded(gpu_device, name), sc.ROT_TOL)
+
+
+SWEEP_BLOCK = 10
+
+
+@pytest.mark.parametrize("block", range(0, sc.SWEEP, SWEEP_BLOCK))
+def test_the_seeded_sweep_matches_the_reference_inside_its_guard_bands(gpu_device, block):
+    """Ten problems of smooth_cases.sweep_problem a test id, each as the cases above."""
+    worst = max(_run_guarded(gpu_device, sc.sweep_name(q)) for q in range(block, min(block + SWEEP_BLOCK, sc.SWEEP)))
+    measured(f"smooth_rot_err[sweep_{block}]", worst, sc.ROT_TOL)
+
+
+def test_smooth_tracks_is_capturable(gpu_device):
+    """Both stages with the workspace, captured once on a side stream (one stream, no branches) and replayed twice with every
+    input overwritten in place in between: each replay gives the eager call's bits for the inputs it found."""
+    c = sc.case("mixed_m2_s1.5")
+    N = len(c["frame_no"])
+    lib = _lib.load()
+    second = {k: np.roll(c[k], 7, axis=0) for k in ("rotmat", "betas", "cam")}
+    second["frame_no"] = c["frame_no"].copy()
+    second["frame_no"][50:90] += 2                                        # (rows 50 .. 89 of the first track: a new gap)
+    sets = [{k: torch.from_numpy(np.ascontiguousarray(src[k])).to(gpu_device) for k in ("rotmat", "betas", "cam", "frame_no")} for src in (c, second)]
+    ins = {k: torch.empty_like(v) for k, v in sets[0].items()}
+    new = lambda: {"rotmat": torch.zeros((N, 24, 3, 3), device=gpu_device), "betas": torch.zeros((N, 10), device=gpu_device),
+                   "cam": torch.zeros((N, 3), device=gpu_device), "status": torch.full((N,), -1, dtype=torch.int32, device=gpu_device),
+                   "replaced": torch.full((N,), -1, dtype=torch.int32, device=gpu_device),
+                   "workspace": torch.zeros((lib.pr_smooth_workspace_bytes(N, 1, 1) // 4,), device=gpu_device)}
+    eager = []
+    for given in sets:
+        for k in ins:
+            ins[k].copy_(given[k])
+        outs = new()
+        _call(c, ins, outs)
+        eager.append({k: outs[k].clone() for k in ("rotmat", "betas", "cam", "status", "replaced")})
+    assert not torch.equal(eager[0]["rotmat"], eager[1]["rotmat"]) and not torch.equal(eager[0]["replaced"], eager[1]["replaced"])
+    outs = new()
+    for k in ins:
+        ins[k].copy_(sets[0][k])
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        _call(c, ins, outs)
+    for given, want in zip(sets, eager):
+        for k in ins:
+            ins[k].copy_(given[k])
+        for k in want:
+            outs[k].fill_(-1)
+        g.replay()
+        torch.cuda.synchronize()
+        for k in want:
+            assert torch.equal(outs[k].view(torch.int32), want[k].view(torch.int32)), k
 
 
 def test_a_track_smoothed_alone_and_among_others_gives_the_same_bits(gpu_device):

@@ -32,3 +32,8 @@ def test_every_argument_error_is_refused_before_any_work(smooth_host):
 @pytest.mark.parametrize("name", sc.NAMES)
 def test_kernel_source_on_the_host_matches_the_reference(smooth_host, name):
     sc.check(name, smooth_host(name))
+
+
+@pytest.mark.parametrize("name", sc.SWEEP_NAMES)
+def test_the_seeded_sweep_on_the_host_matches_the_reference(smooth_host, name):
+    sc.check(name, smooth_host(name))
