@@ -328,7 +328,13 @@ int pr_rot6d_to_rotmat(const float* pose6d_dev, int N, float* rotmat_dev, void* 
  * rotmat_dev f32[N,24,3,3] -> axis_angle_dev f32[N,24,3] (OpenCV Rodrigues semantics,
  * double arithmetic, float32 result) and euler_deg_dev f64[N,24,3] (x,y,z degrees).
  * status_dev int32[N] (may be NULL): bit0 = isRotationMatrix failed (coord_utils.py:70),
- * bit1 = Euler round-trip check failed (coord_utils.py:90-91); the reference aborts there. */
+ * bit1 = Euler round-trip check failed (coord_utils.py:90-91); the reference aborts there.
+ * Bit 0 is set by a non-finite axis-angle component (NaN or +-inf: theta, so the rebuilt matrix, is NaN), never by finite
+ * input: the matrix tested is rebuilt from the axis-angle, and its float32 norm stays under 2.4e-7 against the threshold
+ * of 1e-6.  Through this entry the axis-angle is always finite (a matrix entry that is NaN or >= 100 in magnitude gives
+ * the zero vector, OpenCV's checkRange), so status is 0 here; pr_axis_angle_to_euler reads the caller's vector and can
+ * set it.  Bit 1 has no reachable input (the round trip reproduces a matrix that came out of Rodrigues' formula to
+ * float32 rounding, 1e-5 against 0.1); it is kept for parity with the reference's dead assert. */
 int pr_pose_to_euler(const float* rotmat_dev, int N, float* axis_angle_dev, double* euler_deg_dev,
                      int32_t* status_dev, void* stream);
 /* replaces: axis_angle_to_euler_angle called on its own   lib/utils/coord_utils.py:83-95

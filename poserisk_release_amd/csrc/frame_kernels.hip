@@ -468,7 +468,12 @@ __device__ inline float add_f32(float a, float b) {
   return a + b;
 }
 
+// OpenCV's doubles: R = c I + c1 (r r^T) + s [r]x with the products of r formed first and every operation rounded on its
+// own.  A fused multiply-add, or c1 * rx taken first, changes the last ulp of a double, which is another float32 where an
+// entry cancels to 1e-6 (next to the gimbal lock, about one such entry in 600).  The sum under theta keeps its order too:
+// at |v| = 1e30 an ulp of theta is another rotation altogether.
 __device__ inline void rodrigues_vec2mat(const float* v, float* Rf) {
+#pragma clang fp contract(off)
   double rx = (double)v[0], ry = (double)v[1], rz = (double)v[2];
   const double theta = sqrt(rx * rx + ry * ry + rz * rz);
   if (theta < DBL_EPSILON) {
@@ -477,9 +482,10 @@ __device__ inline void rodrigues_vec2mat(const float* v, float* Rf) {
   }
   const double c = cos(theta), s = sin(theta), c1 = 1.0 - c, it = 1.0 / theta;
   rx *= it; ry *= it; rz *= it;
-  Rf[0] = (float)(c + c1 * rx * rx);        Rf[1] = (float)(c1 * rx * ry - s * rz);   Rf[2] = (float)(c1 * rx * rz + s * ry);
-  Rf[3] = (float)(c1 * rx * ry + s * rz);   Rf[4] = (float)(c + c1 * ry * ry);        Rf[5] = (float)(c1 * ry * rz - s * rx);
-  Rf[6] = (float)(c1 * rx * rz - s * ry);   Rf[7] = (float)(c1 * ry * rz + s * rx);   Rf[8] = (float)(c + c1 * rz * rz);
+  const double xx = rx * rx, xy = rx * ry, xz = rx * rz, yy = ry * ry, yz = ry * rz, zz = rz * rz;
+  Rf[0] = (float)(c + c1 * xx);        Rf[1] = (float)(c1 * xy - s * rz);   Rf[2] = (float)(c1 * xz + s * ry);
+  Rf[3] = (float)(c1 * xy + s * rz);   Rf[4] = (float)(c + c1 * yy);        Rf[5] = (float)(c1 * yz - s * rx);
+  Rf[6] = (float)(c1 * xz - s * ry);   Rf[7] = (float)(c1 * yz + s * rx);   Rf[8] = (float)(c + c1 * zz);
 }
 
 constexpr int kEulerFramesPerBlock = 8;

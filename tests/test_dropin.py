@@ -119,6 +119,36 @@ def test_coord_utils_surface(gpu_device):
 
 
 @pytest.mark.gpu
+def test_coord_utils_euler_raises_where_the_reference_asserts(gpu_device):
+    """axis_angle_to_euler_angle raises AssertionError from the kernel's status exactly where the oracle raises
+    RotationAssertion (a pose with a NaN or an infinity; tests/euler_cases.py), not on the finite pose, and returns the
+    oracle's angles for the two exact gimbal-lock vectors (0, +-fl32(pi/2), 0).  A drop-in that stopped reading the status,
+    or read another frame's, passes every other test."""
+    import euler_cases as ec
+    from oracle import coord_ref
+    base = ec.nonfinite_base(1)[0]
+    assert coord_utils.axis_angle_to_euler_angle(base).shape == (24, 3)
+    for j, c, v in ((0, 0, ec.NONFINITE_VALUES[0]), (23, 2, ec.NONFINITE_VALUES[1]), (11, 1, ec.NONFINITE_VALUES[2]),
+                    (5, 0, ec.NONFINITE_VALUES[3])):
+        pose = base.copy()
+        pose[j, c] = v
+        with pytest.raises(coord_ref.RotationAssertion):
+            ec.oracle_euler(pose[None])
+        with pytest.raises(AssertionError):
+            coord_utils.axis_angle_to_euler_angle(pose)
+    aa, labels, _ = ec.gimbal()
+    lab = labels.reshape(-1)
+    pose = aa.reshape(-1, 3)[[int(np.nonzero(lab == n)[0][0]) for n in ("exact_y+", "exact_y-")]]
+    assert pose.tolist() == [[0.0, float(ec.PI_2_F32), 0.0], [0.0, -float(ec.PI_2_F32), 0.0]]
+    want = coord_ref.axis_angle_to_euler_angle(pose)
+    e = coord_utils.axis_angle_to_euler_angle(pose)
+    assert e.shape == (2, 3) and e.dtype == np.float64
+    assert not ec.compare(e, want, ec.detail(pose)["R"])[3].any(), (e, want)
+    np.testing.assert_allclose(e[:, 1], [89.9999975, -89.9999975], atol=1e-7)
+    assert np.all(e[:, 2] == 0) and not np.signbit(e[:, 2]).any()
+
+
+@pytest.mark.gpu
 def test_predictor_score_crops(gpu_device):
     import types
     sd = synth.hmr_state_dict(seed=1)

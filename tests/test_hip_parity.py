@@ -931,6 +931,12 @@ def test_pose_to_euler_flags_non_rotation(gpu_device):
     ref = coord_ref.rot_to_angle(rot[1])
     np.testing.assert_allclose(aa.cpu().numpy()[1], ref, atol=1e-6)
     assert np.all(aa.cpu().numpy()[2, 3] == 0)
+    # the flags do stay clear, on all three frames: bit 0 is taken from the matrix rebuilt from the axis-angle, never from
+    # the input; the zero vector is the identity, whose angles are exactly (0, -0, 0)
+    assert st.cpu().tolist() == [0, 0, 0]
+    assert np.array_equal(aa.cpu().numpy()[2, 3].view(np.int32), np.zeros(3, np.int32))
+    e = eul.cpu().numpy()[2, 3]
+    assert np.all(e == 0) and np.signbit(e).tolist() == [False, True, False]
 
 
 # ------------------------------------------------------------------------------------------------
