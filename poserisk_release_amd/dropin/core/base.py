@@ -8,12 +8,10 @@
 `get_pose_estimation_results` is the reference's loop (base.py:211-240) with the per-frame Python
 removed: every batch is one `pr_frames_forward` call on the GPU, results stay on the device until the
 end of the loop, and with `torch.distributed` initialised every rank takes a contiguous frame shard and
-the per-frame records are all-gathered once.  Tracking and the decoding of videos other than Motion-JPEG AVI
-(base.py:47-74) are outside the accelerated path: `__call__` takes decoded frames + the tracker's
-dict, finds them in a directory, reads a Motion-JPEG AVI on the GPU (poserisk_release_amd/frontend.py), or runs the
-reference's own front end when cv2 and multi_person_tracker are importable; it writes the
-result text files, the score plots, the debug CSVs and the annotated video (drawn by OpenCV where cv2 is importable, or
-composed on the GPU with the gpu_video knob).
+the per-frame records are all-gathered once.  This file holds the Predictor's construction, its knobs and
+its scoring.  Where `__call__`'s frames and tracking come from (base.py:47-74, outside the accelerated path:
+DESIGN.md section 7) is core/front_end.py, what it writes once the scores are there is core/outputs.py; the
+Predictor's methods of those names are their functions.
 """
 import json
 import os
@@ -23,9 +21,10 @@ import numpy as np
 import torch
 
 from poserisk_release_amd import pipeline as pl
-from poserisk_release_amd import sinks, synth
+from poserisk_release_amd import synth
 from poserisk_release_amd.hmr import hmr
 
+from core import front_end, outputs
 from core.config import cfg
 from reba import REBA
 from rula import RULA
@@ -124,19 +123,48 @@ def _knob(args, name, key, default):
     return knob if knob is not None else cfg.DATASET.get(key, default) or default
 
 
-def _jpeg_options():                                   # what every jpeg.decode_files call of the front end takes from cfg.DATASET
-    return dict(entropy=cfg.DATASET.get('jpeg_entropy', 'auto'), progressive=bool(cfg.DATASET.get('jpeg_progressive', True)))
+def _video_output_knobs(args):
+    """-> (gpu_video_codec, video_encoder, video_encoder_ext, video_chroma, gpu_video_quality), cross-checked: an encoder command
+    needs its {output}, is fed YUV4MPEG2 and so implies the 'y4m' codec."""
+    codec = outputs.known_codec(str(_knob(args, 'video_codec', 'gpu_video_codec', '')))
+    encoder = str(_knob(args, 'video_encoder', 'video_encoder', ''))
+    if encoder:
+        if '{output}' not in encoder:
+            raise ValueError(f"video_encoder {encoder!r} must be a command line containing {{output}}")
+        if codec not in ('', 'y4m'):
+            raise ValueError(f"video_encoder is fed YUV4MPEG2: it goes with gpu_video_codec 'y4m' (or ''), not {codec!r}")
+        codec = 'y4m'
+    return (codec, encoder, str(_knob(args, 'video_encoder_ext', 'video_encoder_ext', '.mp4')),
+            str(cfg.DATASET.get('video_chroma', '420mpeg2') or '420mpeg2'), int(cfg.DATASET.get('gpu_video_quality', 90)))
 
 
-def _front_limits():                                   # the front end's downscale rule (frontend.target_size) from cfg.DATASET
-    return dict(max_w=cfg.DATASET.get('front_max_w', 800), max_h=cfg.DATASET.get('front_max_h', 450))
+def track_start(people):
+    """people [(id, bboxes, frame indices)] -> i64[len + 1]: where each person's rows start in the concatenation (and its end)."""
+    return np.cumsum([0] + [len(f) for _, _, f in people]).astype(np.int64)
 
 
-def _yuv_matrix():                                     # the Y'CbCr matrix the YUV4MPEG2 reader and sink take from cfg.DATASET
-    return str(cfg.DATASET.get('yuv_matrix', '601'))
+def _valid_rotations(status, where):
+    """A non-zero rotation status (device i32[n]) raises, naming its rows: the reference aborts on these (coord_utils.py:70,91)."""
+    status = status.cpu().numpy()
+    if np.any(status != 0):
+        raise AssertionError(f"invalid rotation {where} {np.nonzero(status)[0].tolist()}")
 
 
 class Predictor:
+    # what a Predictor that never ran __init__ (the CPU tests build such) answers for the knobs its methods read; __init__ sets them from
+    # args and cfg, except `visualize`: main/run.py's --visualize is ignored, as the reference ignores it
+    persons = 'target'
+    people_mesh = False
+    render_mesh = False
+    gpu_video = False
+    smooth_median_radius = 0
+    smooth_sigma = 0.0
+    activity = None
+    visualize = True
+    _detector = None                    # front_end.track_frames' detector ...
+    _detector_key = None                # ... and the cfg.TRACKER values it was built from
+    _warned_no_cv2 = False
+
     def __init__(self, args, spin_model=None, smpl_model=None, batch_size=None, spin_checkpoint=None,
                  smpl_mean_params=None):
         """`Predictor(args)` as main/run.py:31 calls it (args fields gpu,type,input,info,output,visualize,debug,
@@ -152,7 +180,6 @@ class Predictor:
             spin_model = load_spin_model(smpl_mean_params, spin_checkpoint, precision=self.precision)
         self.spin_model = spin_model.to(self.device)
         self.batch_size = int(batch_size if batch_size is not None else cfg.DATASET.get('hip_batch_size', 64))
-        # whole batches in flight (pipeline.FramePipeline): args.lanes, else cfg.DATASET.hip_lanes
         self.lanes = int(getattr(args, 'lanes', None) or cfg.DATASET.get('hip_lanes', 2))
         self._pipe = None
         debug = bool(getattr(args, 'debug', False))
@@ -162,56 +189,22 @@ class Predictor:
         self.run_rula = 'RULA' in scores
         self.debugging = debug
         self.debug_frame = getattr(args, 'debug_frame', -1)
-        # the mesh overlay (render_overlay): args.render_mesh, else cfg.DATASET.render_mesh (False; $POSERISK_CFG can set it)
+        # the knobs of the MI355X path: args.<name>, else cfg's (core/config.py's docstring says what each one does)
         self.render_mesh = bool(_knob(args, 'render_mesh', 'render_mesh', False))
-        # the annotated score video composed on the GPU (write_gpu_video): args.gpu_video, else cfg.DATASET.gpu_video (False)
         self.gpu_video = bool(_knob(args, 'gpu_video', 'gpu_video', False))
-        # whom __call__ scores: args.persons, else cfg.DATASET.persons.  'target' (default): the reference's one person; 'all':
-        # every kept track in one pass (score_people), with person_<id>/, people.json and <TITLE>_people beside the target's outputs
         self.persons = str(_knob(args, 'persons', 'persons', 'target'))
         if self.persons not in ('target', 'all'):
             raise ValueError(f"persons {self.persons!r} is not known: 'target' or 'all' (cfg.DATASET.persons / args.persons)")
-        # the mesh of EVERY scored person over every frame, depth-tested against each other (render_people, pr_render_people):
-        # args.people_mesh, else cfg.DATASET.people_mesh (False).  A knob of its own: render_mesh stays the target's overlay
         self.people_mesh = bool(_knob(args, 'people_mesh', 'people_mesh', False))
         if self.people_mesh and self.persons != 'all':
             raise ValueError(f"people_mesh draws the people that persons 'all' scores, but persons is {self.persons!r} "
                              "(cfg.DATASET.people_mesh / args.people_mesh, cfg.DATASET.persons / args.persons)")
-        # temporal smoothing of each track's poses before scoring (poserisk_release_amd/smooth.py, pr_smooth_tracks), both in
-        # FRAMES: args.smooth_median_radius, else cfg.DATASET.smooth_median_radius (0); args.smooth_sigma, else
-        # cfg.DATASET.smooth_sigma (0.0).  Both 0 = off: _score_tracks takes the path it always took
         from poserisk_release_amd.smooth import check_parameters
         self.smooth_median_radius, self.smooth_sigma = check_parameters(_knob(args, 'smooth_median_radius', 'smooth_median_radius', 0),
                                                                         _knob(args, 'smooth_sigma', 'smooth_sigma', 0.0))
-        # REBA's activity score and RULA's muscle use derived from each track's motion (poserisk_release_amd/activity.py,
-        # pr_activity_tracks): args.derive_activity, else cfg.ACTIVITY.derive (False).  Off = None: _score_tracks takes the path it
-        # always took.  On: cfg.ACTIVITY's other keys, refused by name here where they make no sense at any frame rate
-        self.activity = self._activity_knob(args)
-        # how write_gpu_video and the mesh overlay store their frames (poserisk_release_amd/sinks.py): args.video_codec, else
-        # cfg.DATASET.gpu_video_codec.  '' (default) = mp4 through cv2 where importable, else one PNG per frame; 'mjpeg' = encoded
-        # to JPEG on the GPU into <TITLE>_video.avi / <TITLE>_mesh.avi, with or without cv2; 'png' = lossless, encoded on the GPU
-        # into <TITLE>_video/%09d.png / <TITLE>_mesh/%09d.png, with or without cv2; 'y4m' = converted to Y'CbCr on the GPU into
-        # <TITLE>_video.y4m / <TITLE>_mesh.y4m, or, with the video_encoder knob, piped to that command, which writes
-        # <TITLE>_video.mp4 / <TITLE>_mesh.mp4 in the codec it names
-        self.gpu_video_codec = str(_knob(args, 'video_codec', 'gpu_video_codec', ''))
-        if self.gpu_video_codec not in sinks.CODECS:
-            raise ValueError(f"gpu_video_codec {self.gpu_video_codec!r} is not known: '' (mp4 through cv2, else PNG frames), 'mjpeg', "
-                             "'png' or 'y4m' (any other codec: 'y4m' with the video_encoder knob)")
-        # args.video_encoder, else cfg.DATASET.video_encoder ('' = off): a command line with {output} that reads YUV4MPEG2 on its
-        # standard input; it implies the 'y4m' codec.  video_encoder_ext ('.mp4') ends the file's name, video_chroma the layout
-        self.video_encoder = str(_knob(args, 'video_encoder', 'video_encoder', ''))
-        self.video_encoder_ext = str(_knob(args, 'video_encoder_ext', 'video_encoder_ext', '.mp4'))
-        self.video_chroma = str(cfg.DATASET.get('video_chroma', '420mpeg2') or '420mpeg2')
-        if self.video_encoder:
-            if '{output}' not in self.video_encoder:
-                raise ValueError(f"video_encoder {self.video_encoder!r} must be a command line containing {{output}}")
-            if self.gpu_video_codec not in ('', 'y4m'):
-                raise ValueError(f"video_encoder is fed YUV4MPEG2: it goes with gpu_video_codec 'y4m' (or ''), not "
-                                 f"{self.gpu_video_codec!r}")
-            self.gpu_video_codec = 'y4m'
-        self.gpu_video_quality = int(cfg.DATASET.get('gpu_video_quality', 90))
-        # load_front_end's case 3c: args.video_decoder, else cfg.DATASET.video_decoder ('' = off): a command line with {input}
-        # whose standard output is read as YUV4MPEG2
+        self.activity = self._activity_knob(args)           # None (off), or cfg.ACTIVITY's parameters
+        (self.gpu_video_codec, self.video_encoder, self.video_encoder_ext, self.video_chroma,
+         self.gpu_video_quality) = _video_output_knobs(args)
         self.video_decoder = str(_knob(args, 'video_decoder', 'video_decoder', ''))
         dj = str(getattr(args, 'debug_joints', '')).replace(' ', '').split(',')
         if dj == ['']:
@@ -336,9 +329,7 @@ class Predictor:
                 params = {k: pl.gather_padded(t, n_total) for k, t in params.items()}
         if params is not None:
             smpl_params.update({k: t.cpu().numpy() for k, t in params.items()})
-        status = st.cpu().numpy()
-        if np.any(status != 0):     # coord_utils.py:70,91: the reference aborts on these
-            raise AssertionError(f"invalid rotation in frames {np.nonzero(status)[0].tolist()}")
+        _valid_rotations(st, "in frames")
         result = eul.cpu().numpy()
         joint_cam = jc.cpu().numpy()
         debug_result = aa.cpu().numpy()
@@ -400,17 +391,15 @@ class Predictor:
         from poserisk_release_amd import ops, smooth
         layer = self.smpl_model.layer['neutral']
         dev = layer.device
-        track_start = np.cumsum([0] + [len(f) for _, _, f in people]).astype(np.int64)
-        sm = smooth.smooth_tracks(torch.as_tensor(smpl['rotmat'], device=dev), np.asarray(fidx, np.int64), track_start, median_radius,
-                                  sigma, betas=torch.as_tensor(smpl['betas'], device=dev), cam=torch.as_tensor(smpl['cam'], device=dev))
+        sm = smooth.smooth_tracks(torch.as_tensor(smpl['rotmat'], device=dev), np.asarray(fidx, np.int64), track_start(people),
+                                  median_radius, sigma, betas=torch.as_tensor(smpl['betas'], device=dev),
+                                  cam=torch.as_tensor(smpl['cam'], device=dev))
         aa, eul, st = ops.pose_to_euler(sm['rotmat'])
         n = aa.shape[0]
         joint_cam = torch.empty((n, 24, 3), dtype=torch.float32, device=dev)
         for lo in range(0, n, self.batch_size):                     # the SMPL layer takes batch_size rows a call
             layer.joint_cam(aa[lo:lo + self.batch_size], out=joint_cam[lo:lo + self.batch_size])
-        status = st.cpu().numpy()
-        if np.any(status != 0):     # as get_pose_estimation_results: the reference aborts on these
-            raise AssertionError(f"invalid rotation after smoothing in rows {np.nonzero(status)[0].tolist()}")
+        _valid_rotations(st, "after smoothing in rows")
         smpl.update({k: sm[k].cpu().numpy() for k in ('rotmat', 'betas', 'cam')})
         flags = {k: sm[k].cpu().numpy() for k in ('status', 'replaced')}
         return eul.cpu().numpy(), joint_cam.cpu().numpy(), aa.cpu().numpy(), flags
@@ -421,8 +410,8 @@ class Predictor:
         adds i32[n,4], the parameters in seconds and frames), host arrays."""
         from poserisk_release_amd import activity
         dev = self.smpl_model.layer['neutral'].device
-        track_start = np.cumsum([0] + [len(f) for _, _, f in people]).astype(np.int64)
-        act = activity.activity_tracks(torch.as_tensor(rotmat, device=dev), np.asarray(fidx, np.int64), track_start, fps, **parameters)
+        act = activity.activity_tracks(torch.as_tensor(rotmat, device=dev), np.asarray(fidx, np.int64), track_start(people), fps,
+                                       **parameters)
         return act['flags'].cpu().numpy(), act['adds'].cpu().numpy(), act['parameters']
 
     def _score_tracks(self, frames, people, add_info, bgr, bbox_scale, shard=None, with_smpl_params=False, fps=None):
@@ -438,7 +427,7 @@ class Predictor:
         _activity_rows once, each person's derived addends reach the scorers as `rows`, and each dict holds 'activity'
         (parameters, flags, adds); `fps` is then needed (ValueError without).  Off, nothing here differs."""
         from poserisk_release_amd import ops
-        deriving = getattr(self, 'activity', None)
+        deriving = self.activity
         if deriving is not None and fps is None:
             raise ValueError("the activity knob (cfg.ACTIVITY.derive / args.derive_activity) needs fps to turn its seconds into "
                              "frames: pass fps= to score_frames / score_people (Predictor.__call__ does)")
@@ -457,7 +446,7 @@ class Predictor:
             for i in range(lo, hi, self.batch_size):
                 j = min(i + self.batch_size, hi)
                 yield ops.crop_frames(frames, bboxes[i:j], fidx[i:j].astype(np.int32), scale=bbox_scale, bgr=bgr)
-        smooth_m, smooth_sigma = getattr(self, 'smooth_median_radius', 0), getattr(self, 'smooth_sigma', 0.0)
+        smooth_m, smooth_sigma = self.smooth_median_radius, self.smooth_sigma
         smoothing = smooth_m > 0 or smooth_sigma > 0
         smpl = {} if with_smpl_params or smoothing or deriving is not None else None
         result, joint_cam, _, debug_result = self.get_pose_estimation_results(batches(), keep_images=False, n_total=n_total,
@@ -544,534 +533,25 @@ class Predictor:
         n_frames = len(frames)
         people = tracks.people_tracks(tracking_results, n_frames, cfg.DATASET.min_frame_ratio)
         if with_smpl_params is None:
-            with_smpl_params = getattr(self, 'people_mesh', False)
+            with_smpl_params = self.people_mesh
         outs, pose_logs = self._score_tracks(frames, people, add_info, bgr, bbox_scale, with_smpl_params=bool(with_smpl_params), fps=fps)
         people_out = {'people': outs, 'ids': [pid for pid, _, _ in people], 'frames_total': n_frames}
         return dict(people_out, pose_logs=pose_logs) if self.debugging else people_out
 
-    # ---- the mesh overlay (extends the --debug_frame mesh of base.py:273-282 to every track frame) -----------------
-    def render_overlay(self, out, frames, title='REBA', bgr=False, alpha=0.6):
-        """Yield (track frame numbers int[b], overlaid frames u8[b,H,W,3] CUDA) batch by batch: the fitted mesh of every
-        track frame drawn over its video frame (poserisk_release_amd.render), parts coloured by the `title` scheme's
-        risk levels ('REBA' / 'RULA'; None: one neutral colour).  `out` is what score_frames returned with the SMPL
-        parameters.  The pose is rebuilt from the returned rotmat (ops.pose_to_euler's axis-angle: the root keeps the
-        network's rotation, it is NOT overwritten as the scores' pose is), betas from the prediction, vertices from
-        smpl_model.layer['neutral']; `frames` and the output share one channel order (`bgr`)."""
-        from poserisk_release_amd import ops, render
-        if 'rotmat' not in out:
-            raise ValueError("render_overlay needs score_frames(..., with_smpl_params=True) (or the render_mesh knob)")
-        scheme, faces, face_part, frames, dev, faces_dev = self._mesh_setup(frames, title)
-        fidx, n = np.asarray(out['frames']), len(out['frames'])
-        info = out.get('add_info') or default_information()
-        for i in range(0, n, self.batch_size):
-            j = min(i + self.batch_size, n)
-            verts, rgb = self._posed_meshes(out['rotmat'][i:j], out['betas'][i:j], info, scheme, dev)
-            img = render.overlay(frames, verts, faces_dev, out['cam'][i:j], out['bboxes'][i:j],
-                                 scale=out.get('bbox_scale', cfg.DATASET.bbox_scale), frame_idx=fidx[i:j].astype(np.int32),
-                                 face_part=face_part, part_rgb=rgb, alpha=alpha, bgr=bgr)
-            yield fidx[i:j], img
-
-    def _mesh_setup(self, frames, title):
-        """What render_overlay and render_people share before their loops -> (scheme, the model's faces, face_part by the
-        scheme, frames on the device, that device, the faces on it)."""
-        from poserisk_release_amd import render
-        faces = np.asarray(self.smpl_model.face)
-        if faces.ndim != 2 or faces.shape[0] == 0:
-            raise ValueError("the SMPL model has no faces to draw")
-        scheme = None if title is None else str(title).upper()
-        face_part = render.face_parts(self.smpl_model.layer['neutral'].th_weights.numpy(), faces, scheme)
-        frames = self._on_device(frames)
-        return scheme, faces, face_part, frames, frames.device, torch.as_tensor(faces.astype(np.int32), device=frames.device)
-
-    def _posed_meshes(self, rotmat, betas, info, scheme, dev):
-        """rotmat f32[n,24,3,3] + betas f32[n,10] (n <= batch_size) -> (vertices f32[n,V,3] on `dev`, part_rgb u8[n,P,3]): the
-        meshes render_overlay and render_people draw and their parts' colours by the scheme's risk levels of each row."""
-        from poserisk_release_amd import ops, render
-        n = len(rotmat)
-        aa, eul, _ = ops.pose_to_euler(torch.as_tensor(rotmat, device=dev))
-        verts, _ = self.smpl_model.layer['neutral'](aa.reshape(n, 72), torch.as_tensor(betas, device=dev))
-        if scheme is None:
-            return verts, render.part_colours(np.zeros((n, 1)), None)
-        packed = (ops.reba if scheme == 'REBA' else ops.rula)(eul, info[scheme]).cpu().numpy()
-        return verts, render.part_colours(packed, scheme)
-
-    def render_people(self, people_out, frames, title='REBA', bgr=False, alpha=0.6):
-        """Yield (video frame numbers int[b], frames u8[b,H,W,3] CUDA) over ALL frames of the video, batch_size frames at a
-        time: the fitted mesh of every scored person who is in the frame drawn over it, the people depth-tested against each
-        other (poserisk_release_amd.render.overlay_people, pr_render_people); a frame nobody is in comes back as it is.
-        `people_out` is what score_people returned with the SMPL parameters.  Meshes as in render_overlay, each person's parts
-        coloured by that person's own risk levels of that frame; the meshes of a frame are ordered as tracks.people_tracks
-        orders the people, and their depth steps come from render.people_z_step, the cameras' size on the screen."""
-        from poserisk_release_amd import render
-        outs = people_out['people']
-        if any('rotmat' not in o for o in outs):
-            raise ValueError("render_people needs score_people(..., with_smpl_params=True) (or the people_mesh knob)")
-        scheme, faces, face_part, frames, dev, faces_dev = self._mesh_setup(frames, title)
-        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        if not outs:
-            raise ValueError("render_people: nobody was scored")
-        scale = outs[0].get('bbox_scale', cfg.DATASET.bbox_scale)
-        info = outs[0].get('add_info') or default_information()
-        # every (person, track frame) row is a mesh, person after person: a selection of rows keeps the people's order
-        cat = lambda key: np.concatenate([np.asarray(o[key]) for o in outs])
-        fidx, cam, bboxes, rotmat, betas = cat('frames'), cat('cam'), cat('bboxes'), cat('rotmat'), cat('betas')
-        z_step = render.people_z_step(cam, bboxes, scale, H, W)
-        for lo in range(0, n_frames, self.batch_size):
-            hi = min(lo + self.batch_size, n_frames)
-            sel = np.nonzero((fidx >= lo) & (fidx < hi))[0]
-            verts, rgb = [], []
-            for i in range(0, len(sel), self.batch_size):               # the SMPL layer takes batch_size rows a call
-                v, c = self._posed_meshes(rotmat[sel[i:i + self.batch_size]], betas[sel[i:i + self.batch_size]], info, scheme, dev)
-                verts.append(v)
-                rgb.append(c)
-            verts = torch.cat(verts) if verts else torch.zeros((0, int(faces.max()) + 1, 3), device=dev)
-            img = render.overlay_people(frames, verts, faces_dev, cam[sel], bboxes[sel], (fidx[sel] - lo).astype(np.int32),
-                                        np.arange(lo, hi, dtype=np.int32), z_step[sel], scale=scale, face_part=face_part,
-                                        part_rgb=np.concatenate(rgb) if rgb else None, alpha=alpha, bgr=bgr)
-            yield np.arange(lo, hi), img
-
-    def _open_sink(self, output_path, name, frame_size, fps, bgr):
-        """<output>/<name>: the sink of the gpu_video_codec knob (poserisk_release_amd/sinks.py) for frames of (height, width) =
-        `frame_size`, with this Predictor's other knobs."""
-        return sinks.open_sink(self.gpu_video_codec, osp.join(output_path, name), int(frame_size[1]), int(frame_size[0]), fps, bgr,
-                               quality=self.gpu_video_quality, chroma=self.video_chroma, encoder=self.video_encoder,
-                               encoder_ext=self.video_encoder_ext, matrix=_yuv_matrix())
-
-    def write_mesh_overlay(self, out, frames, output_path, title='REBA', bgr=False, fps=30.0):
-        """<output>/<TITLE>_mesh.mp4 where cv2 is importable, else <output>/<TITLE>_mesh/%09d.png (frame number) per track
-        frame.  Returns the path written."""
-        sink = self._open_sink(output_path, f"{title if title is not None else 'MESH'}_mesh", frames.shape[1:3], fps, bgr)
-        return sinks.write_all(sink, self.render_overlay(out, frames, title, bgr))
-
-    def _write_canvases(self, canvases, frames, output_path, name, bgr, fps):
-        """<output>/<name> through the sink of the gpu_video_codec knob: `canvases` yields the canvases of `frames`' video batch
-        by batch, one per video frame, numbered 0 .. n_frames - 1.  Returns the path written."""
-        from poserisk_release_amd import video
-        canvas_h, resize_w, panel_w = video.canvas_size(int(frames.shape[1]), int(frames.shape[2]))
-
-        def batches():
-            i = 0
-            for batch in canvases:
-                yield range(i, i + int(batch.shape[0])), batch
-                i += int(batch.shape[0])
-        return sinks.write_all(self._open_sink(output_path, name, (canvas_h, resize_w + panel_w), fps, bgr), batches())
-
-    # ---- base.py:284-327 on the GPU (the gpu_video knob) ---------------------------------------------------------
-    def write_gpu_video(self, out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
-        """`<TITLE>_video`: every frame of the video at 720 px wide with the target's box, beside the score panel, composed by
-        poserisk_release_amd.video (pr_compose_video) from the arrays score_frames returned.  <output>/<TITLE>_video.mp4 where
-        cv2 is importable (it only writes the container), else <output>/<TITLE>_video/%09d.png, one per video frame; with
-        gpu_video_codec 'mjpeg' <output>/<TITLE>_video.avi, the canvases encoded on the GPU, whether or not cv2 is there; with
-        'png' <output>/<TITLE>_video/%09d.png, encoded on the GPU (lossless), whether or not cv2 is there; with 'y4m'
-        <output>/<TITLE>_video.y4m, or through the video_encoder knob's command <TITLE>_video.mp4 (sinks.Y4mSink).  With
-        the render_mesh knob the track frames are the mesh-overlaid ones, the box over the mesh (`out` must then hold the SMPL
-        parameters: render_overlay says so by name), and `mesh_sink(frame numbers, images)` receives every overlaid batch, so
-        that the mesh output is written from the same rendering.  Returns the path written."""
-        from poserisk_release_amd import video
-        frames = self._on_device(frames)
-        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        _, scores, logs, _ = out[title.lower()]
-        items = (self.reba if title.upper() == 'REBA' else self.rula).eval_items
-        fidx = np.asarray(out['frames'])
-        draw = video.draw_list(title, n_frames, out['bboxes'], (0, fidx, n_frames), scores, items, logs, video.canvas_size(H, W)[0])
-        overlay = None
-        if self.render_mesh:
-            def overlay(lo, hi):
-                sel = np.nonzero((fidx >= lo) & (fidx < hi))[0]
-                if not sel.size:
-                    return [], None
-                some = dict(out, frames=fidx[sel], bboxes=out['bboxes'][sel])
-                some.update({k: out[k][sel] for k in ('rotmat', 'betas', 'cam') if k in out})
-                parts = list(self.render_overlay(some, frames, title, bgr))      # raises by name without the SMPL parameters
-                numbers, images = np.concatenate([f for f, _ in parts]), torch.cat([img for _, img in parts])
-                if mesh_sink is not None:
-                    mesh_sink(numbers, images)
-                return numbers, images
-        return self._write_canvases(video.annotated_frames(frames, draw, self.batch_size, overlay=overlay), frames, output_path,
-                                    title + '_video', bgr, fps)
-
-    # ---- the persons='all' outputs (no counterpart in the reference, which describes one person) -----------------------------
-    def write_people_video(self, people_out, frames, output_path, title, bgr=False, fps=30.0, mesh_sink=None):
-        """`<TITLE>_people`: every frame of the video at 720 px wide with every scored person's box and `#<id> <score>` tag in
-        the colour of that frame's action level, beside a panel that lists the people of the frame
-        (poserisk_release_amd.video.people_draw_list, pr_compose_people), from what score_people returned.  Written through
-        the sink of the gpu_video_codec knob, as write_gpu_video's.  With the people_mesh knob the image region is
-        render_people's frame, boxes and tags over the meshes (`people_out` must then hold the SMPL parameters), and
-        `mesh_sink(frame numbers, images)` receives every rendered batch, so that <TITLE>_people_mesh is written from the same
-        rendering.  Returns the path written."""
-        from poserisk_release_amd import video
-        frames = self._on_device(frames)
-        n_frames, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        scorer = self.reba if title.upper() == 'REBA' else self.rula
-        people = []
-        for pid, out in zip(people_out['ids'], people_out['people']):
-            scores = out[title.lower()][1]
-            acts = [scorer.action_level(s) for s in scores]
-            people.append(dict(id=pid, frames=out['frames'], bboxes=out['bboxes'], scores=scores, levels=[a[0] for a in acts],
-                               names=[a[1] for a in acts]))
-        canvas_h, resize_w, _ = video.canvas_size(H, W)
-        draw = video.people_draw_list(title, n_frames, people, canvas_h, resize_w, H, W, bgr=bgr)
-        overlay = None
-        if getattr(self, 'people_mesh', False):
-            meshed = self.render_people(people_out, frames, title, bgr)       # batch_size frames a step, as people_frames asks
-
-            def overlay(lo, hi):
-                numbers, images = next(meshed)
-                if numbers[0] != lo or numbers[-1] != hi - 1:
-                    raise RuntimeError(f"render_people yielded frames {numbers[0]}..{numbers[-1]} where {lo}..{hi - 1} are composed")
-                if mesh_sink is not None:
-                    mesh_sink(numbers, images)
-                return numbers, images
-        return self._write_canvases(video.people_frames(frames, draw, self.batch_size, overlay=overlay), frames, output_path,
-                                    title + '_people', bgr, fps)
-
-    def _write_reports(self, out, folder, debug_folder, n_frames, pose_logs, after_plot=lambda title: None, after_txt=lambda title: None):
-        """One scored person's files.  Into `folder`, per title scored: <TITLE>_score.png, then <title>_result.txt.  With args.debug
-        into `debug_folder`: pose_log.csv (the debug_joints) first, and per title, last, <TITLE>_score_log.csv and <TITLE>_eval_pose_log.csv
-        from pose_logs[<title>], rows of the scorer's angle log.  after_plot / after_txt: what __call__ writes in between (videos, mesh)."""
-        from poserisk_release_amd import reports
-        timestamp = (0, np.asarray(out['frames']), n_frames)           # base.py:130
-        if self.debugging and self.debug_joints is not None:
-            reports.save_pose_log_csv(debug_folder, timestamp, reports.pose_to_str(out['result']), self.debug_joints,
-                                      self.smpl_model.joints_name_upper)
-        for title, scorer in (('REBA', self.reba), ('RULA', self.rula)):
-            if title.lower() not in out:
-                continue
-            final, scores, logs, (level, name) = out[title.lower()]
-            reports.save_score_plot(folder, title, timestamp, scores)      # base.py:254-262
-            after_plot(title)
-            reports.write_result_txt(folder, title, final, level, name)
-            after_txt(title)
-            if self.debugging:
-                reports.save_score_csv(debug_folder, title, timestamp, scores, scorer.eval_items, logs, pose_logs[title.lower()])
-
-    def write_people_reports(self, people_out, output_path):
-        """<output>/person_<id>/ per scored person -- reba_result.txt / rula_result.txt and <TITLE>_score.png, with args.debug the
-        score, pose-evaluation and pose logs too, all by the method that writes the target's (_write_reports) -- and
-        <output>/people.json.  Returns the list people.json holds."""
-        plain = lambda v: v.item() if isinstance(v, np.generic) else v
-        num = lambda v: None if v is None or np.isnan(v) else float(v)        # top-10 % of fewer than 10 frames is NaN: null
-        n_frames, summary = people_out['frames_total'], []
-        for p, (pid, out) in enumerate(zip(people_out['ids'], people_out['people'])):
-            folder = osp.join(output_path, f'person_{pid}')
-            os.makedirs(folder, exist_ok=True)
-            self._write_reports(out, folder, folder, n_frames, people_out['pose_logs'][p] if self.debugging else None)
-            fidx, boxes = np.asarray(out['frames']), np.asarray(out['bboxes'])
-            entry = dict(id=plain(pid), first_frame=int(fidx.min()) if fidx.size else None, last_frame=int(fidx.max()) if fidx.size else None,
-                         n_frames=int(fidx.size), mean_box_area=float((boxes[:, 2] * boxes[:, 3]).mean()) if fidx.size else None)
-            for title in ('REBA', 'RULA'):
-                if title.lower() in out:
-                    final, _, _, (level, name) = out[title.lower()]
-                    entry[title] = dict(avg=num(final[0]), top50=num(final[1]), top10=num(final[2]), max=num(final[3]), mode=num(final[4]),
-                                        action_level=plain(level), action=name)
-            summary.append(entry)
-        with open(osp.join(output_path, 'people.json'), 'w') as f:
-            json.dump({'frames_total': n_frames, 'people': summary}, f, indent=1)
-        return summary
-
-    def write_smooth_report(self, out, people_out, output_path):
-        """<output>/smooth.json, written only when a smoothing knob is on: the parameters (in frames) and per scored person
-        (the target alone, id null, without persons 'all') how many (row, joint) items stage 1 replaced by another frame's
-        rotation and how many fell back in stage 2 (pr_smooth_tracks' replaced and status bits).  Returns what it holds."""
-        from poserisk_release_amd import smooth
-        plain = lambda v: v.item() if isinstance(v, np.generic) else v
-        scored = list(zip(people_out['ids'], people_out['people'])) if people_out is not None else [(None, out)]
-        people = []
-        for pid, o in scored:
-            replaced, fallbacks = smooth.counts(o['smooth']['status'], o['smooth']['replaced'])
-            people.append(dict(id=plain(pid), n_frames=int(len(o['smooth']['status'])), replaced=replaced, fallbacks=fallbacks))
-        report = dict(median_radius=int(out['smooth']['median_radius']), sigma=float(out['smooth']['sigma']), unit='frames',
-                      gaussian_radius=smooth.gaussian_radius(float(out['smooth']['sigma'])), people=people)
-        with open(osp.join(output_path, 'smooth.json'), 'w') as f:
-            json.dump(report, f, indent=1)
-        return report
-
-    def write_activity_report(self, out, people_out, output_path):
-        """<output>/activity.json, written only with the activity knob on: the parameters in seconds, degrees and frames, and
-        per scored person (the target alone, id null, without persons 'all') the rows flagged per kind -- held, repeated,
-        rapid, moved -- in all and per joint name, and the sum of each derived addend.  Returns what it holds."""
-        from poserisk_release_amd import activity
-        plain = lambda v: v.item() if isinstance(v, np.generic) else v
-        scored = list(zip(people_out['ids'], people_out['people'])) if people_out is not None else [(None, out)]
-        people = []
-        for pid, o in scored:
-            adds = np.asarray(o['activity']['adds']).reshape(-1, 4)
-            people.append(dict(id=plain(pid), n_frames=int(len(adds)), **activity.counts(o['activity']['flags']),
-                               adds={name: int(adds[:, c].sum()) for c, name in enumerate(activity.ADDS)}))
-        report = dict(parameters={k: plain(v) for k, v in out['activity']['parameters'].items()}, joints=list(activity.JOINT_NAMES),
-                      people=people)
-        with open(osp.join(output_path, 'activity.json'), 'w') as f:
-            json.dump(report, f, indent=1)
-        return report
-
-    # ---- base.py:273-282 ------------------------------------------------------------------------------------
-    def visualize_joint_cam_mesh(self, debug_result, joint_cam, frames, output_path):
-        """The --debug --debug_frame N outputs: `smpl_model.obj` (the frame's mesh in mm, zero betas, from the axis-angle
-        with the root already overwritten, Q5) and `joint_3d.png`."""
-        from poserisk_release_amd import reports
-        idx = int(np.where(np.asarray(frames) == self.debug_frame)[0][0])
-        pose = torch.as_tensor(debug_result[idx]).reshape(1, -1).float()
-        verts, _ = self.smpl_model.layer['neutral'](pose, torch.zeros((1, 10)))
-        mesh = verts.detach().cpu().numpy().astype(np.float32).reshape(-1, 3) * 1000
-        reports.save_obj(mesh, self.smpl_model.face, osp.join(output_path, 'smpl_model.obj'))
-        reports.save_joint_3d_plot(joint_cam[idx], self.smpl_model.skeleton, osp.join(output_path, 'joint_3d.png'),
-                                   frame=self.debug_frame)
+    # ---- the public names of what core/front_end.py and core/outputs.py hold: their functions take the predictor first ----------
+    load_front_end = front_end.load_front_end
+    track_frames = front_end.track_frames
+    render_overlay = outputs.render_overlay
+    render_people = outputs.render_people
+    write_mesh_overlay = outputs.write_mesh_overlay
+    write_gpu_video = outputs.write_gpu_video
+    write_people_video = outputs.write_people_video
+    write_people_reports = outputs.write_people_reports
+    write_smooth_report = outputs.write_smooth_report
+    write_activity_report = outputs.write_activity_report
+    visualize_joint_cam_mesh = outputs.visualize_joint_cam_mesh
 
     # ---- main/run.py:31  predictor(args.input, args.info, args.output) -----------------------------------
-    def _folder_sidecars(self, folder, frames=None):
-        """What every frame folder carries beside its frames -> (fps, tracking): `fps.txt` (optional, 30.0 without it) and
-        `tracking.pkl`; without that file and with cfg.TRACKER.weights set, the built-in tracker's dict for `frames`."""
-        import pickle
-        if frames is not None and self._tracker_weights() and not osp.isfile(osp.join(folder, 'tracking.pkl')):
-            tracking = self.track_frames(frames, bgr=False)
-        else:
-            with open(osp.join(folder, 'tracking.pkl'), 'rb') as f:
-                tracking = pickle.load(f)
-        fps_file = osp.join(folder, 'fps.txt')
-        fps = float(open(fps_file).read()) if osp.isfile(fps_file) else 30.0
-        return fps, tracking
-
-    def load_front_end(self, input_path, output_path, tracking_results=None):
-        """Decoded frames + tracker output for `input_path` -> (frames u8[F,H,W,3], bgr, fps, tracking dict).
-
-        Video decoding and multi-person tracking are outside the accelerated path; this only finds them:
-          1. a directory with `frames.npy` (uint8 [F,H,W,3] RGB) and `tracking.pkl` (multi_person_tracker's
-             dict {id: {'bbox': [n,4] (cx,cy,w,h), 'frames': [n]}}), optional `fps.txt`;
-          2. a directory without `frames.npy` but with JPEG frames (`*.jpg` / `*.jpeg`, sorted by name: what the reference's
-             front end leaves under <output>/tmp, what `ffmpeg -i video %09d.jpg` or a camera writes) and `tracking.pkl`,
-             optional `fps.txt`: the files are decoded on the GPU, bit-exact with cv2.imread's pixels
-             (poserisk_release_amd/jpeg.py), and the frames come back as a device tensor, RGB.  A frame that is not
-             baseline JPEG, has another size than the first or is damaged raises, naming the file and the reason;
-          2b. a directory without `frames.npy`, with `tracking.pkl`, at least one `*.png` name and no `*.jpg` / `*.jpeg` name
-             (what `ffmpeg -i video %09d.png`, screen recorders and this package's own report path write): the files are
-             decoded on the GPU, exact with zlib and libpng (poserisk_release_amd/png.py), RGB on the device, gray replicated
-             and alpha dropped; optional `fps.txt`.  A file that is not an 8-bit non-interlaced PNG, has another size than
-             the first or is damaged raises, naming the file and the reason.  A folder that mixes the two kinds of names
-             goes to 2 and is refused there;
-          3. a Motion-JPEG AVI file (a camera's, `ffmpeg -c:v mjpeg`'s, this package's own <TITLE>_video.avi): demuxed in
-             Python, decoded and downscaled on the GPU by the reference's rule (poserisk_release_amd/frontend.py;
-             cfg.DATASET.front_max_w / front_max_h), no OpenCV anywhere.  Its tracking is, in this order, the
-             `tracking_results` given to __call__, `<stem>.tracking.pkl` beside the video (boxes in the downscaled frames'
-             coordinates), or multi_person_tracker where importable, run on a folder of JPEGs encoded on the GPU; the frames
-             are then the pixels decoded back from those files, as the reference's CropDataset would read them.  An AVI of
-             another codec, or a damaged one, goes on to 3c and 4;
-          3b. a YUV4MPEG2 file (one that starts with `YUV4MPEG2 `: what `ffmpeg -f yuv4mpegpipe`, mpv, x264 and the AV1 tools
-             write): read in chunks into pinned memory, converted to RGB (cfg.DATASET.yuv_matrix, '601') and downscaled by the
-             same rule in one kernel on the GPU (poserisk_release_amd/y4m.py).  Its tracking comes from the same sources as 3's,
-             in the same order;
-          3c. with cfg.DATASET.video_decoder / args.video_decoder set (off, '', by default), any other regular file: the knob
-             is a command line containing `{input}`, e.g. `ffmpeg -v error -i {input} -f yuv4mpegpipe -pix_fmt yuv420p -`; it
-             is started as a fresh child process (shlex.split, no shell), its standard output is read as YUV4MPEG2 exactly as
-             3b reads a file, and it is always reaped.  A child that exits non-zero or writes no stream header raises
-             RuntimeError naming the command, the exit status and the tail of its standard error;
-          With cfg.TRACKER.weights set (off, '', by default) the tracking of cases 3, 3b and 3c comes from this package's own
-          detector and tracker (`track_frames`: YOLOv3 on the GPU + SORT) after the dict given and the sidecar and before
-          multi_person_tracker, and the folders of cases 1, 2 and 2b are accepted without `tracking.pkl`;
-          4. otherwise the reference's own front end when `cv2` and `multi_person_tracker` are importable:
-             frames are decoded and resized as funcs_utils.get_images does (width <= 800, else height <= 450),
-             written as JPEGs under <output>/tmp for the tracker (base.py:47-56) and read back, so the crops see
-             the same JPEG-decoded pixels as the reference's CropDataset."""
-        if osp.isdir(input_path) and osp.isfile(osp.join(input_path, 'frames.npy')):
-            frames = np.load(osp.join(input_path, 'frames.npy'))
-            return (frames, False) + self._folder_sidecars(input_path, frames)
-        if osp.isdir(input_path) and (osp.isfile(osp.join(input_path, 'tracking.pkl')) or self._tracker_weights()):
-            from poserisk_release_amd import jpeg, png
-            module, opts = jpeg, _jpeg_options()
-            if png.list_frames(input_path) and not any(n.lower().endswith(('.jpg', '.jpeg')) for n in os.listdir(input_path)):
-                module, opts = png, {}
-            names = module.list_frames(input_path)
-            if names:
-                frames = self._decode_frames(module, [osp.join(input_path, n) for n in names], **opts)
-                return (frames, False) + self._folder_sidecars(input_path, frames)
-        not_mjpeg = None
-        if osp.isfile(input_path):
-            from poserisk_release_amd import mjpeg, y4m
-            if mjpeg.is_avi(input_path):
-                try:
-                    reader = mjpeg.AviReader(input_path)
-                except ValueError as e:
-                    not_mjpeg = e                              # an AVI, but not one to read here: cv2 may still open it
-                else:
-                    return self._video_front_end(reader, input_path, output_path, tracking_results, **_jpeg_options())
-            if y4m.is_y4m(input_path):
-                with y4m.Reader(input_path) as reader:
-                    return self._video_front_end(reader, input_path, output_path, tracking_results,
-                                                 matrix=_yuv_matrix())
-            if self.video_decoder:
-                return self._decoder_front_end(input_path, output_path, tracking_results)
-        try:
-            import cv2
-            from multi_person_tracker import MPT
-        except ImportError as e:
-            raise RuntimeError(
-                f"{input_path!r} is neither a directory with frames.npy + tracking.pkl nor one with JPEG frames "
-                f"(*.jpg, decoded on the GPU) or PNG frames (*.png, decoded on the GPU) + tracking.pkl, and the reference's front end "
-                f"(cv2 video decoding, multi_person_tracker) is not importable here ({e}); decode and track outside, "
-                "then call Predictor.score_frames(frames, tracking_results, info)"
-                + (f" [as a Motion-JPEG AVI it was refused: {not_mjpeg}]" if not_mjpeg is not None else "")) from e
-        import shutil
-        image_path = osp.join(output_path, 'tmp')
-        shutil.rmtree(image_path, ignore_errors=True)
-        os.makedirs(image_path, exist_ok=True)
-        cap = cv2.VideoCapture(input_path)
-        fps = cap.get(cv2.CAP_PROP_FPS)
-        width, height = cap.get(cv2.CAP_PROP_FRAME_WIDTH), cap.get(cv2.CAP_PROP_FRAME_HEIGHT)
-        if width > 800:
-            width, height = 800, int(height * 800 / width)
-        elif height > 450:
-            width, height = int(width * 450 / height), 450
-        n = 0
-        while cap.isOpened():
-            ok, frame = cap.read()
-            if not ok:
-                break
-            cv2.imwrite(osp.join(image_path, '{0:09d}.jpg'.format(n)), cv2.resize(frame, (int(width), int(height))))
-            n += 1
-        cap.release()
-        tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
-                      output_format='dict', yolo_img_size=416)
-        tracking = tracker(image_path)
-        frames = np.stack([cv2.imread(osp.join(image_path, '{0:09d}.jpg'.format(i))) for i in range(n)])
-        shutil.rmtree(image_path, ignore_errors=True)
-        return frames, True, fps, tracking
-
-    def _decode_frames(self, module, paths, written_to=None, **opts):
-        """`paths` (files, or their bytes) decoded by `module` (jpeg | png: decode_files with `opts`) -> the frames on the device.  The
-        first bad frame raises RuntimeError naming its file -- for bytes written to a tracker's folder `written_to`, its number there."""
-        frames, status = module.decode_files(paths, self.device, **opts)
-        bad = module.bad_frames(paths, status, **{k: opts[k] for k in ('progressive',) if k in opts})
-        if bad and written_to is not None:
-            raise RuntimeError(f"{written_to!r}: frame {bad[0][0]} written for the tracker cannot be decoded: {bad[0][1]}")
-        if bad:
-            raise RuntimeError(f"{paths[bad[0][0]]!r} cannot be decoded: {bad[0][1]}"
-                               + (f" (and {len(bad) - 1} more frames)" if len(bad) > 1 else ""))
-        return frames
-
-    def _video_front_end(self, reader, input_path, output_path, tracking_results=None, **opts):
-        """load_front_end's cases 3, 3b and 3c: `reader` is the mjpeg.AviReader of `input_path` (`opts`: the JPEG options), or the
-        y4m.Reader of `input_path` or of a decoder's standard output (`opts`: the colour matrix)."""
-        from poserisk_release_amd import frontend
-        frames, fps = frontend.read_video(reader, self.device, **_front_limits(), **opts)
-        return self._tracking_for(frames, fps, input_path, output_path, tracking_results)
-
-    def _decoder_front_end(self, input_path, output_path, tracking_results=None):
-        """load_front_end's case 3c: self.video_decoder, with {input} replaced, runs as a child process whose standard output
-        is read as YUV4MPEG2.  Never a shell and never this process's own program; the child is reaped whatever happens."""
-        import shlex
-        from poserisk_release_amd import _child, y4m
-        if '{input}' not in self.video_decoder:
-            raise ValueError(f"video_decoder {self.video_decoder!r} must be a command line containing {{input}}")
-        child = _child.Child([a.replace('{input}', input_path) for a in shlex.split(self.video_decoder)],
-                             f"{input_path!r}: the video decoder", feed=False)
-        failure, read_to_the_end = None, False
-        try:
-            try:
-                reader = y4m.Reader(child.pipe)
-            except ValueError as e:
-                failure = f"it wrote no YUV4MPEG2 stream header ({e})"
-            else:
-                try:
-                    return_value = self._video_front_end(reader, input_path, output_path, tracking_results,
-                                                         matrix=_yuv_matrix())
-                    read_to_the_end = True
-                except ValueError as e:                         # the stream broke off: the child's status says why
-                    failure = str(e)
-        finally:
-            child.pipe.close()                  # a child still writing gets EPIPE and ends by itself; its status raises nothing
-            child.finish(60 if read_to_the_end else 5, failure, raising=read_to_the_end or failure is not None)    # over another error
-        return return_value
-
-    # ---- the built-in tracker (cfg.TRACKER; off while its weights are '') --------------------------------------------------
-    @staticmethod
-    def _tracker_weights():
-        return str(cfg.get('TRACKER', {}).get('weights', '') or '')
-
-    def track_frames(self, frames, bgr=False):
-        """frames u8[F,H,W,3] (device tensor or numpy) -> multi_person_tracker's dict, by this package's own detector
-        (poserisk_release_amd.detector, YOLOv3 on the GPU) and tracker (poserisk_release_amd.sort).  No person found anywhere
-        raises RuntimeError naming the threshold used."""
-        from poserisk_release_amd import detector, sort
-        t = cfg.TRACKER
-        det = getattr(self, '_detector', None)
-        key = (self._tracker_weights(), tuple(t.img_size), int(t.batch), str(t.get('precision', 'fp32')))
-        detector.check_precision(key[3])        # 'fp32' | 'bf16', anything else raises naming the two
-        if det is None or getattr(self, '_detector_key', None) != key:
-            det = detector.Detector(key[0], img_size=key[1], device=self.device, max_batch=key[2], precision=key[3])
-            self._detector, self._detector_key = det, key
-        dets = det.detect(frames, bgr=bgr, conf_thres=float(t.conf_thres), nms_thres=float(t.nms_thres))
-        tracking = sort.track_frames(dets, max_age=int(t.max_age), min_hits=int(t.min_hits), iou_thres=float(t.iou_thres))
-        if not tracking:
-            raise RuntimeError(f"the built-in tracker found no person track in {len(dets)} frames ({sum(len(d) for d in dets)} "
-                               f"detections at conf_thres {float(t.conf_thres):g}, nms_thres {float(t.nms_thres):g}; a track needs "
-                               f"{int(t.min_hits)} consecutive hits)")
-        return tracking
-
-    def _tracking_for(self, frames, fps, input_path, output_path, tracking_results=None):
-        """The second half of cases 3, 3b and 3c: the tracking of a video file's decoded, downscaled `frames`, in this order: the
-        `tracking_results` given, `<stem>.tracking.pkl`, the built-in tracker where cfg.TRACKER.weights names a weight file,
-        multi_person_tracker where importable, else the named error."""
-        import pickle
-        import shutil
-        from poserisk_release_amd import frontend, jpeg
-        if tracking_results is not None:
-            return frames, False, fps, tracking_results
-        sidecar = osp.splitext(input_path)[0] + '.tracking.pkl'
-        if osp.isfile(sidecar):
-            with open(sidecar, 'rb') as f:
-                return frames, False, fps, pickle.load(f)
-        if self._tracker_weights():
-            return frames, False, fps, self.track_frames(frames, bgr=False)
-        try:
-            from multi_person_tracker import MPT
-        except ImportError as e:
-            raise RuntimeError(
-                f"{input_path!r}: {frames.shape[0]} frames of {frames.shape[2]} x {frames.shape[1]} were decoded, but there is no "
-                f"tracking for them: {sidecar!r} (multi_person_tracker's dict, boxes in the downscaled frames' coordinates) does not "
-                f"exist, no tracking_results were given and multi_person_tracker is not importable here ({e}).  Write the frames for "
-                f"a tracker with `python -m poserisk_release_amd.frontend prepare {input_path} <dir>`, add its tracking.pkl to <dir> "
-                "and pass <dir>") from e
-        image_path = osp.join(output_path, 'tmp')
-        shutil.rmtree(image_path, ignore_errors=True)
-        try:
-            files = frontend.write_frame_folder(frames, image_path, quality=95)      # cv2.imwrite's default quality
-            tracker = MPT(device=self.device, batch_size=8, display=False, detection_threshold=0.1, detector_type='yolo',
-                          output_format='dict', yolo_img_size=416)
-            tracking = tracker(image_path)
-            frames = self._decode_frames(jpeg, files, written_to=image_path, **_jpeg_options())
-        finally:
-            shutil.rmtree(image_path, ignore_errors=True)
-        return frames, False, fps, tracking
-
-    def _front_end_on_rank0(self, input_path, output_path, world, rank, **given):
-        """Several ranks (one per GPU): the front end writes, runs the tracker in and deletes <output>/tmp, so it runs on
-        rank 0 ONLY and its output is broadcast -- every rank then shards the SAME track (a tracker run per rank may select
-        different tracks; one rank's rmtree would delete JPEGs another rank is still reading).  The metadata goes as one
-        pickled object, the frames as one uint8 tensor (on this rank's GPU with RCCL, on the host with gloo)."""
-        import torch.distributed as dist
-        meta, err = [None], None
-        frames = None
-        if rank == 0:
-            try:
-                frames, bgr, fps, tracking = self.load_front_end(input_path, output_path, **given)
-                # a device tensor (the JPEG folder case) stays where it is; arrays become one contiguous host tensor
-                frames = frames.contiguous() if isinstance(frames, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(frames))
-                meta = [dict(shape=tuple(frames.shape), bgr=bool(bgr), fps=float(fps), tracking=tracking)]
-            except Exception as e:               # the other ranks are waiting in the broadcast: tell them, then raise
-                meta, err = [dict(error=f"{type(e).__name__}: {e}")], e
-        dist.broadcast_object_list(meta, src=0)
-        m = meta[0]
-        if 'error' in m:
-            raise err if err is not None else RuntimeError(f"rank 0's front end failed: {m['error']}")
-        on_gpu = dist.get_backend() == 'nccl'
-        if rank != 0:
-            frames = torch.empty(m['shape'], dtype=torch.uint8, device=self.device if on_gpu else 'cpu')
-        elif on_gpu:
-            frames = frames.to(self.device)
-        else:
-            frames = frames.cpu()                    # gloo broadcasts host memory
-        dist.broadcast(frames, src=0)
-        return frames, m['bgr'], m['fps'], m['tracking']
-
     def __call__(self, input_path, info_path, output_path, frames=None, tracking_results=None, fps=30.0, bgr=False):
         """The reference's entry point (base.py:126-209) around the accelerated path: front end (given, found or
         the reference's own: `load_front_end`) -> crops, pose, scores on the GPU -> `reba_result.txt` /
@@ -1080,7 +560,6 @@ class Predictor:
         With the persons knob at 'all' all of that is written for the target from score_people's element 0 (the model runs
         once), then <output>/person_<id>/, <output>/people.json and, with gpu_video, <TITLE>_people (write_people_reports,
         write_people_video); the dict returned also holds 'people', what score_people returned."""
-        from poserisk_release_amd import reports
         os.makedirs(output_path, exist_ok=True)
         world, rank = pl.world_and_rank()
         if frames is None or tracking_results is None:
@@ -1088,12 +567,12 @@ class Predictor:
             # brings its own, as before
             given = {'tracking_results': tracking_results} if frames is None and tracking_results is not None else {}
             if world > 1:
-                frames, bgr, fps, tracking_results = self._front_end_on_rank0(input_path, output_path, world, rank, **given)
+                frames, bgr, fps, tracking_results = front_end.load_on_rank0(self, input_path, output_path, rank, **given)
             else:
                 frames, bgr, fps, tracking_results = self.load_front_end(input_path, output_path, **given)
         add_info = _information(info_path if info_path and osp.isfile(str(info_path)) else None)      # base.py:140-142
         people_out = None
-        if getattr(self, 'persons', 'target') == 'all':
+        if self.persons == 'all':
             # everybody in one pass; the target is element 0, bit for bit what score_frames returns, so the model runs once
             people_out = self.score_people(frames, tracking_results, add_info, bgr=bgr, fps=fps)
             out = dict(people_out['people'][0])
@@ -1105,76 +584,5 @@ class Predictor:
             # every rank holds all frames' results after the gather; the reports (result txt, plots, mp4, debug CSVs and
             # OBJ) are ONE set of files in <output>: rank 0 writes them, the others would race it on the same names
             return out
-        if 'smooth' in out:                                        # only with a smoothing knob on
-            self.write_smooth_report(out, people_out, output_path)
-        if 'activity' in out:                                      # only with the activity knob on
-            self.write_activity_report(out, people_out, output_path)
-        fidx = out['frames']
-        timestamp = (0, fidx, int(frames.shape[0]))                # base.py:130 (torch tensor or numpy: both have .shape)
-        debug_path = osp.join(output_path, 'debug')
-        if self.debugging:
-            os.makedirs(debug_path, exist_ok=True)
-        if self.debugging and self.debug_frame is not None and self.debug_frame >= 0:
-            # base.py:128-135: the --debug_frame branch dumps that frame's mesh and 3-D skeleton and stops there
-            self.visualize_joint_cam_mesh(out['debug_result'], out['joint_cam'], fidx, debug_path)
-            if self.render_mesh:
-                idx = int(np.where(np.asarray(fidx) == self.debug_frame)[0][0])
-                one = dict(out, frames=fidx[idx:idx + 1], bboxes=out['bboxes'][idx:idx + 1], rotmat=out['rotmat'][idx:idx + 1],
-                           betas=out['betas'][idx:idx + 1], cam=out['cam'][idx:idx + 1])
-                title = 'REBA' if 'reba' in out else ('RULA' if 'rula' in out else None)
-                for _, img in self.render_overlay(one, frames, title, bgr):
-                    im = img[0].cpu().numpy()
-                    sinks.save_png(osp.join(debug_path, 'mesh_overlay.png'), im[..., ::-1] if bgr else im)
-            print("\n Debug files are saved in : ", debug_path)
-            return out
-        show = getattr(self, 'visualize', True)
-        on_gpu = show and self.gpu_video
-        if on_gpu:
-            frames = torch.as_tensor(frames).to(self.device)       # one upload for both titles' videos (and the mesh)
-
-        def with_mesh_sink(name, write):                           # one rendering of the meshes feeds the video and <output>/<name>
-            mesh = self._open_sink(output_path, name, frames.shape[1:3], fps, bgr)
-            try:
-                write(mesh.put)
-            except BaseException:
-                mesh.abort()                    # the video's error stands; a mesh encoder child is reaped all the same
-                raise
-            mesh.close()
-
-        def videos(title):                                         # base.py:156,173: behind the title's plot
-            if on_gpu:
-                if self.render_mesh:                # one rendering of the mesh feeds both outputs
-                    with_mesh_sink(title + '_mesh', lambda put: self.write_gpu_video(out, frames, output_path, title, bgr, fps, mesh_sink=put))
-                else:
-                    self.write_gpu_video(out, frames, output_path, title, bgr, fps)
-            elif show:                                             # ... (OpenCV only)
-                _, scores, logs, _ = out[title.lower()]
-                fr = frames.cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)   # once, host side
-                video = reports.write_annotated_video(output_path, title, fr if bgr else fr[..., ::-1], out['bboxes'], timestamp, fps,
-                                                      scores, (self.reba if title == 'REBA' else self.rula).eval_items, logs)
-                if video is None and not getattr(self, '_warned_no_cv2', False):
-                    print("OpenCV (cv2) is not importable: the annotated mp4 is skipped, all other outputs are written")
-                    self._warned_no_cv2 = True
-
-        def mesh_alone(title):                                     # behind the title's result txt
-            if self.render_mesh and not on_gpu:                    # with both knobs videos() has written the mesh
-                self.write_mesh_overlay(out, frames, output_path, title, bgr, fps)
-        # the scorers' whole angle logs, as the reference writes them (Q19: they are never cleared)
-        self._write_reports(out, output_path, debug_path, timestamp[2], {'reba': self.reba.log, 'rula': self.rula.log}, videos, mesh_alone)
-        if people_out is not None:
-            self.write_people_reports(people_out, output_path)
-            people_mesh = getattr(self, 'people_mesh', False)
-            if on_gpu:
-                for title in ('REBA', 'RULA'):
-                    if title.lower() not in out:
-                        continue
-                    if people_mesh:                     # one rendering of the meshes feeds both outputs, as in videos()
-                        with_mesh_sink(title + '_people_mesh',
-                                       lambda put: self.write_people_video(people_out, frames, output_path, title, bgr, fps, mesh_sink=put))
-                    else:
-                        self.write_people_video(people_out, frames, output_path, title, bgr, fps)
-            elif show:
-                print("The people video (<TITLE>_people) is composed on the GPU only: it needs the gpu_video knob and is skipped")
-                if people_mesh:
-                    print("The people mesh (<TITLE>_people_mesh) is drawn beside it: it needs the gpu_video knob too and is skipped")
+        outputs.write_outputs(self, out, people_out, frames, output_path, bgr, fps)
         return out

@@ -48,7 +48,7 @@ def refusal_name(code):
 def list_frames(directory):
     """The frame files of `directory`: names ending in .png (any case), sorted -- position in that order is the frame index, as
     in sorted(os.listdir).  Other files (tracking.pkl, fps.txt) are ignored; a folder that also holds .jpg / .jpeg frames is
-    for the caller to refuse (dropin/core/base.py does)."""
+    for the caller to refuse (dropin/core/front_end.py does)."""
     return [n for n in sorted(os.listdir(directory)) if n.lower().endswith(_EXT)]
 
 

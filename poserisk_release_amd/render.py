@@ -2,7 +2,7 @@
 level (include/poserisk_hip.h, pr_render_overlay; the kernels are csrc/render.hip).
 
 `overlay` is the torch wrapper of the kernel.  `face_parts` and `part_colours` turn SMPL's skinning weights and the REBA /
-RULA logs into the kernel's face_part and part_rgb tables.  The Predictor's `render_overlay` (dropin/core/base.py) chains
+RULA logs into the kernel's face_part and part_rgb tables.  The Predictor's `render_overlay` (dropin/core/outputs.py) chains
 them on the arrays `score_frames` returns.
 
 `overlay_people` is the wrapper of pr_render_people (header section r4): the meshes of everybody in a frame on one canvas,

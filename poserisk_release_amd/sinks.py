@@ -1,5 +1,5 @@
 """What a batch of frames is written to: the five destinations of the Predictor's annotated video and mesh overlay
-(dropin/core/base.py: write_gpu_video, write_mesh_overlay), each a small class with the same three methods; `open_sink` is the one
+(dropin/core/outputs.py: write_gpu_video, write_mesh_overlay), each a small class with the same three methods; `open_sink` is the one
 place that chooses among them, `write_all` the one loop that fills them.
 
     put(numbers, images)   frame numbers int[b], images u8[b,H,W,3] on the device

@@ -5,7 +5,7 @@ vis_utils.py:278-294) composed on the GPU (include/poserisk_hip.h, pr_compose_vi
 `draw_list` is the host half: the strings, origins, sizes, colours and box corners `reports.write_annotated_video` hands to
 OpenCV, per video frame.  `font_atlas` is the panel's font: a monospace coverage atlas in three sizes.  `compose` is the torch
 wrapper of the kernel, `annotated_frames` chains them batch by batch.  The Predictor's `write_gpu_video`
-(dropin/core/base.py) writes what it yields.
+(dropin/core/outputs.py) writes what it yields.
 
 The people video (`<TITLE>_people`, the persons knob; no counterpart in the reference) is the second half of this file:
 `people_draw_list`, `compose_people` (pr_compose_people: the same kernel in csrc/compose.hip, of which pr_compose_video is the

@@ -129,10 +129,12 @@ from core.base import Predictor
 predictor = Predictor(args)
 out = predictor(args.input, args.info, args.output)
 # ---- end of main/run.py; what follows checks the run
-import core.base, core.config, funcs_utils
+import core.base, core.config, core.front_end, core.outputs, funcs_utils
 assert osp.realpath(funcs_utils.__file__).startswith(osp.realpath(osp.join(os.getcwd(), 'lib', 'utils'))), funcs_utils.__file__   # the checkout's own module
 assert funcs_utils.cfg is cfg and core.config.__file__.startswith(osp.dirname(dropin.__file__)), core.config.__file__
 assert core.base.__file__.startswith(osp.dirname(dropin.__file__)), core.base.__file__
+assert core.front_end.__file__.startswith(osp.dirname(dropin.__file__)), core.front_end.__file__
+assert core.outputs.__file__.startswith(osp.dirname(dropin.__file__)), core.outputs.__file__
 assert cfg.root_dir == os.getcwd(), (cfg.root_dir, os.getcwd())
 import json, pickle
 import numpy as np
